@@ -14,7 +14,10 @@ stay in HBM (nothing crosses PCIe inside it).  Each rank owns an independent IQ 
 (stream id = rank): weak scaling, no data-path collective; RCCL only reduces the packet
 counters and the elapsed time at the end.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (`value`,
+`ms_per_step`, `crc_pass_rate`).  --full adds what takes work of its own: per-kernel HIP-event times and the roofline
+(with a few extra steps run in sequence when steps overlap), the sensing figures, the bit-exact check of the delivered
+payloads and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -134,6 +137,54 @@ def cpu_baseline(cfg, sigma, lead, tail, size, npkt):
             "gpu_rx_matches_on_sample": bool(same)}
 
 
+def _sample(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of at most k of range(n): one index in each of k equal strata."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    stride = n // k
+    return np.arange(k, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, k)
+
+
+def dump_outputs(dirname, npk, off, ln, ok, d_out, size, npkt_sent, d_iq, nsamples, sense_res):
+    """What the last timed step handed its caller, as float32 / float64 .npy files (under 64 MB in all; larger outputs
+    as a fixed, seeded sample whose indices {packet,payload,iq,sense}_rows.npy hold).  packet_ok / packet_len: CRC
+    verdict and length of the delivered packets in stream order (all of them up to 2^19); payload_sample: the bytes of
+    sampled packets (-1 past a packet's end or for a packet not delivered); iq_sample: sampled (re, im) of the TX +
+    channel stream the receiver read; sense_bits: sampled decisions of the fused spectrum sensor (BASELINE config 5)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+    rows = _sample(npk, 1 << 19, 1)
+    save("packet_rows", rows.astype(np.float64))
+    save("packet_ok", ok[rows].astype(np.float32))
+    save("packet_len", ln[rows].astype(np.float32))
+    prow = _sample(npkt_sent, max(1, (6 << 20) // size), 2)
+    got = np.full((len(prow), size), -1.0, np.float32)
+    have = prow < npk
+    if have.any():
+        dev = d_out.device
+        starts = torch.from_numpy(off[prow[have]].astype(np.int64)).to(dev)
+        lens = torch.from_numpy(np.minimum(ln[prow[have]], size).astype(np.int64)).to(dev)
+        col = torch.arange(size, device=dev)
+        idx = (starts[:, None] + col[None, :]).clamp_(max=d_out.numel() - 1)
+        vals = d_out[idx].float().masked_fill_(col[None, :] >= lens[:, None], -1.0)
+        got[have] = vals.cpu().numpy()
+    save("payload_rows", prow.astype(np.float64))
+    save("payload_sample", got)
+    srow = _sample(nsamples, 1 << 19, 3)
+    iq = d_iq[:nsamples * 2].view(-1, 2)
+    save("iq_rows", srow.astype(np.float64))
+    save("iq_sample", iq[torch.from_numpy(srow).to(iq.device)].cpu().numpy())
+    if sense_res is not None:
+        bits = sense_res["bits"]
+        drow = _sample(len(bits), 512, 4)
+        save("sense_rows", drow.astype(np.float64))
+        save("sense_bits", bits[drow].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,7 +193,12 @@ def main():
     ap.add_argument("--packets", type=int, default=None, help="packets per stream per step (default: per config)")
     ap.add_argument("--size", type=int, default=None, help="payload bytes (default: per config)")
     ap.add_argument("--snr", type=float, default=None)
-    ap.add_argument("--cpu-packets", type=int, default=4096, help="sample size of the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-packets", type=int, default=4096, help="sample size of the CPU baseline (--full; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel times, roofline, sensing "
+                         "figures, bit-exact payload check, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     ap.add_argument("--sense", default="auto", choices=("auto", "on", "off"),
                     help="fuse the predictive_sense.py spectrum sensor into every RX call (auto: on for c5)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -161,6 +217,8 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS),
                     help="BASELINE.json config to run (default c2 = configs[1], the one the metric is quoted on)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import torch
 
@@ -231,6 +289,7 @@ def main():
     sc = None
     sense_tot = {"messages": 0, "decisions": 0}
     last_hex = [None]
+    last = {}                      # the last step's IQ buffer, sample count and sensing result (--dump-outputs)
     if sense_on:
         sc = config.make_sense_cfg(N, max(0, int(round(1e-3 * 6.25e6 / N))), max(1, int(round(10e-3 * 6.25e6 / N))),
                                    10, 1, 0.00010)
@@ -259,6 +318,7 @@ def main():
                 eng.rx_submit_device(d_iq.data_ptr(), n)
                 nxt = tx(i + 1) if i + 1 < nsteps else None
             npk, off, ln, ok = eng.rx_device(d_iq.data_ptr(), n, d_out.data_ptr(), d_out.numel(), max_pkts)
+            last["iq"], last["n"] = d_iq, n
             rx_stats = dict(eng.last_stats)
             if sense_on:
                 if world > 1:
@@ -271,6 +331,7 @@ def main():
                 sense_tot["messages"] += nm
                 sense_tot["decisions"] += len(res["hex"])
                 last_hex[0] = res["hex"][-1] if res["hex"] else None
+                last["sense"] = res
             if tot is not None:
                 tot["symbols"] += tx_stats["symbols"]
                 tot["samples"] += rx_stats["samples"]
@@ -287,8 +348,9 @@ def main():
 
     run_steps(args.warmup, None)
     sense_tot["messages"] = sense_tot["decisions"] = 0
-    eng.prof_enable(True)
-    eng.prof_reset()
+    if args.full:
+        eng.prof_enable(True)
+        eng.prof_reset()
     parallel.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -297,38 +359,68 @@ def main():
     torch.cuda.synchronize()
     parallel.barrier()
     elapsed = time.perf_counter() - t0
-    prof = eng.prof()
-    # Per-kernel durations.  While steps overlap, a HIP-event span around a kernel also counts the time it shared the
-    # GPU with the other stream's kernels; the durations the roofline is priced on are therefore measured on a few
-    # extra steps run strictly in sequence right after the timed region (same buffers, same work; not part of `value`).
-    prof_overlapped = None
-    if pipelined:
-        prof_overlapped = prof
-        eng.prof_reset()
-        nseq = max(2, min(4, args.steps))
-        run_steps(nseq, None, pipelined=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, npk, off, ln, ok, d_out, size, P, last["iq"], last["n"], last.get("sense"))
+    if args.full:
         prof = eng.prof()
-        prof_steps = nseq
-    else:
-        prof_steps = max(args.steps, 1)
-    eng.prof_enable(False)
+        # Per-kernel durations.  While steps overlap, a HIP-event span around a kernel also counts the time it shared
+        # the GPU with the other stream's kernels; the durations the roofline is priced on are therefore measured on a
+        # few extra steps run strictly in sequence right after the timed region (same buffers, same work; not part of
+        # `value`).
+        prof_overlapped = None
+        if pipelined:
+            prof_overlapped = prof
+            eng.prof_reset()
+            nseq = max(2, min(4, args.steps))
+            run_steps(nseq, None, pipelined=False)
+            prof = eng.prof()
+            prof_steps = nseq
+        else:
+            prof_steps = max(args.steps, 1)
+        eng.prof_enable(False)
 
-    # correctness of the last step: every delivered payload whose CRC passed is bit-exact what was sent
-    # (the reference's own timing jitter loses about one packet in 10^4 at 30 dB; the oracle shows the same)
-    delivered_ok = bool(npk == P and bool((ln == size).all()))
-    if delivered_ok:
-        got = d_out[:P * size].view(P, size)
-        sent = d_blob.view(P, size)
-        row_eq = (got == sent).all(dim=1).cpu().numpy()
-        delivered_ok = bool(np.all(row_eq[ok.astype(bool)]))
+        # correctness of the last step: every delivered payload whose CRC passed is bit-exact what was sent
+        # (the reference's own timing jitter loses about one packet in 10^4 at 30 dB; the oracle shows the same)
+        delivered_ok = bool(npk == P and bool((ln == size).all()))
+        if delivered_ok:
+            got = d_out[:P * size].view(P, size)
+            sent = d_blob.view(P, size)
+            row_eq = (got == sent).all(dim=1).cpu().numpy()
+            delivered_ok = bool(np.all(row_eq[ok.astype(bool)]))
     elapsed = parallel.reduce_max(elapsed, device=dev)
     g = parallel.reduce_counters(tot, device=dev)
-    all_exact = parallel.reduce_counters({"packets": int(delivered_ok)}, device=dev)["packets"] == world
+    if args.full:
+        all_exact = parallel.reduce_counters({"packets": int(delivered_ok)}, device=dev)["packets"] == world
 
-    result_line = None
     if rank == 0:
         sym_per_s = g["symbols"] / elapsed
         ms_per_step = 1e3 * elapsed / max(args.steps, 1)
+        out = {
+            "metric": "OFDM symbols/sec (TX+loopback RX) @ N_fft=512; packet CRC pass rate",
+            "value": sym_per_s,
+            "unit": "OFDM symbols/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": cfgd["name"] + ("" if args.sync == "pn" else " -- SYNC='fixed' test mode (no filter / metric)"),
+                       "packets_per_stream_per_step": P, "payload_bytes": size, "symbols_per_packet": nsym // P,
+                       "snr_db": args.snr, "streams": world, "iq_buffers": args.iq_buffers, "parallelism": "independent streams, 1 per GPU",
+                       "pipelining": (("TX of step i+1 queued on the handle's transmit stream behind the input stage of "
+                                       "step i's RX" if not reads_to_end else
+                                       "TX of step i+1 into the other of two IQ buffers, beside step i's RX (which reads its "
+                                       "buffer to the end of the call)") if pipelined else "none (steps in sequence)")},
+            "crc_pass_rate": g["crc_ok"] / float(max(world * P * args.steps, 1)),
+            # (the synthetic channel's Gaussian is a 16-bit-radius Box-Muller, truncated at 4.85 sigma: pass rates at
+            #  high SNR are marginally optimistic against an untruncated Gaussian; DESIGN.md section 2)
+            "channel": "AWGN %.1f dB fused into the TX store; Philox-2x32-7, Box-Muller with 16-bit radius (|n| <= 4.85 sigma)" % args.snr,
+        }
+    if rank == 0 and args.full:
         # dominant kernel by HIP-event time (events recorded on the engine's own stream)
         kern = max(prof.items(), key=lambda kv: kv[1][0])
         kname, (kms, klaunch) = kern
@@ -364,31 +456,8 @@ def main():
         except (ImportError, IOError, OSError, ValueError, KeyError):
             pass
         path_achieved = sym_per_s / world * path_bytes / 1e9
-        out = {
-            "metric": "OFDM symbols/sec (TX+loopback RX) @ N_fft=512; packet CRC pass rate",
-            "value": sym_per_s,
-            "unit": "OFDM symbols/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": cfgd["name"] + ("" if args.sync == "pn" else " -- SYNC='fixed' test mode (no filter / metric)"),
-                       "packets_per_stream_per_step": P, "payload_bytes": size, "symbols_per_packet": nsym // P,
-                       "snr_db": args.snr, "streams": world, "iq_buffers": args.iq_buffers, "parallelism": "independent streams, 1 per GPU",
-                       "pipelining": (("TX of step i+1 queued on the handle's transmit stream behind the input stage of "
-                                       "step i's RX" if not reads_to_end else
-                                       "TX of step i+1 into the other of two IQ buffers, beside step i's RX (which reads its "
-                                       "buffer to the end of the call)") if pipelined else "none (steps in sequence)")},
-            "crc_pass_rate": g["crc_ok"] / float(max(world * P * args.steps, 1)),
+        out.update({
             "crc_ok_payloads_bit_exact": all_exact,
-            # (the synthetic channel's Gaussian is a 16-bit-radius Box-Muller, truncated at 4.85 sigma: pass rates at
-            #  high SNR are marginally optimistic against an untruncated Gaussian; DESIGN.md section 2)
-            "channel": "AWGN %.1f dB fused into the TX store; Philox-2x32-7, Box-Muller with 16-bit radius (|n| <= 4.85 sigma)" % args.snr,
             # `achieved` / `frac`: the PATH figure the north star's 40 % is defined on -- SURVEY 8(d)'s algorithmic bytes per
             # symbol (TX writes the stream once, RX reads it once, payload bits in and out) x symbols per second per GPU.
             # kernel_*: the dominant kernel on its own compulsory bytes over its own HIP-event duration.
@@ -403,7 +472,7 @@ def main():
                                           else "HIP events on the kernel's stream over the timed region",
                          "path_achieved": path_achieved, "path_frac": path_achieved / HBM_PEAK_GBPS},
             "kernels_ms_per_step": {k: v[0] / prof_steps for k, v in prof.items()},
-        }
+        })
         if prof_overlapped is not None:
             out["kernels_ms_per_step_overlapped"] = {k: v[0] / max(args.steps, 1) for k, v in prof_overlapped.items()}
         if sense_on:
@@ -423,7 +492,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(cfg_host, sigma, lead, tail, size, args.cpu_packets)
         else:
             out["cpu_baseline"] = None
-        result_line = json.dumps(out)
+    result_line = json.dumps(out) if rank == 0 else None
     eng.close()
     try:
         import torch.distributed as dist

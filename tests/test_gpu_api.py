@@ -137,7 +137,7 @@ def test_bench_under_torchrun_one_rank():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--packets", "4096", "--cpu-packets", "0"]
+    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--packets", "4096", "--cpu-packets", "0", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     a = subprocess.run([sys.executable] + args, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert a.returncode == 0, a.stderr[-2000:]
@@ -175,7 +175,7 @@ def test_bench_modes_contract(extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["bench.py", "--steps", "2", "--warmup", "1", "--cpu-packets", "64"] + extra
+    args = ["bench.py", "--steps", "2", "--warmup", "1", "--cpu-packets", "64", "--full"] + extra
     p = subprocess.run([sys.executable] + args, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = p.stdout.strip().splitlines()
@@ -191,3 +191,50 @@ def test_bench_modes_contract(extra):
     c = j["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["gpu_rx_matches_on_sample"]
     assert j["crc_ok_payloads_bit_exact"] and j["crc_pass_rate"] > 0.9
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run prints the headline alone (per-kernel, roofline and CPU figures are --full's), times exactly
+    --steps steps, and --dump-outputs writes the last step's outputs: float32 / float64, under 64 MB, the same from run
+    to run, and every CRC-ok payload in the sample is the payload that was sent."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    P, size = 2048, 1026
+    runs = []
+    for d in ("a", "b"):
+        args = ["bench.py", "--steps", "3", "--warmup", "1", "--packets", str(P), "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run([sys.executable] + args, cwd=root, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        runs.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    for j in runs:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "crc_pass_rate"):
+            assert k in j, k
+        for k in ("roofline", "kernels_ms_per_step", "cpu_baseline", "crc_ok_payloads_bit_exact"):
+            assert k not in j, k
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["crc_pass_rate"] > 0.9
+        assert abs(j["value"] * j["ms_per_step"] * 1e-3 - j["config"]["symbols_per_packet"] * P) < 1e-6 * j["value"]
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b")))
+    assert {"packet_ok.npy", "packet_len.npy", "payload_sample.npy", "iq_sample.npy"} <= set(names)
+    total = 0
+    out = {}
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), n
+        total += os.path.getsize(str(tmp_path / "a" / n))
+        out[n[:-4]] = a
+    assert total <= 64 << 20
+    sent = bench.make_payload_blob(P, size, 0).reshape(P, size).astype(np.float32)
+    rows = out["payload_rows"].astype(np.int64)
+    have = rows < len(out["packet_ok"])       # (P packets: the per-packet arrays are not sampled)
+    ok = np.zeros(len(rows), bool)
+    ok[have] = out["packet_ok"][rows[have]] == 1
+    assert ok.sum() > 0.9 * len(rows)
+    got = out["payload_sample"][ok]
+    pktno = (got[:, 0] * 256 + got[:, 1]).astype(np.int64)   # a lost packet shifts the rest: match by packet number
+    assert np.array_equal(got, sent[pktno])

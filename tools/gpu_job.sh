@@ -11,7 +11,7 @@
 #   bash tools/gpu_job.sh cache                           Infinity-Cache microbenchmark + C2 bench against the batch size
 CMD=$1; shift
 show() { python tools/show_bench.py "$1" 2>/dev/null || tail -c 1500 "${1%.json}.err"; }
-bench() { timeout -k 10 300 python bench.py --cpu-packets 0 "$@"; }
+bench() { timeout -k 10 300 python bench.py --full --cpu-packets 0 "$@"; }
 case $CMD in
 test)
   TAG=${1:-x}; shift; ARGS=${@:-tests -m gpu -x -q}; O=gpurun_out/r3_$TAG; mkdir -p $O
