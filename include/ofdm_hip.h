@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OFDM_ABI_VERSION 5
+#define OFDM_ABI_VERSION 6
 
 #define OFDM_MAX_FFT 4096
 #define OFDM_MAX_CARRIER_HEX 1024 /* hex digits of a carrier map: OFDM_MAX_FFT / 4 */
@@ -205,7 +205,42 @@ int ofdm_rx(ofdm_handle *h, const ofdm_c32 *iq, uint64_t nsamples, uint8_t *payl
 /* digital_ofdm_frame_acquisition::snr() (digital_swig.py:4231-4239, "Return an estimate of the SNR of the channel").
  * In GNU Radio 3.6.0 the block initialises d_snr_est to 0 in its constructor and no code path ever updates it
  * [GR-3.6.0, recalled; the reference never calls it]: the accessor returns that constant, and so does this. */
-int ofdm_rx_snr(const ofdm_handle *h, float *snr_est);
+int ofdm_rx_snr(const ofdm_handle *h, float *snr_est); /* still the stub: per-packet figures come from ofdm_rx_quality */
+
+/* --- link quality: per-packet SNR, EVM and carrier offset (no reference counterpart) -----------------------------
+ * Off by default; ofdm_set_rx_quality(h, 1) holds for the following ofdm_rx calls.  A call with it on runs the
+ * demodulator's instrumented kernel and one gather kernel more; a call with it off runs exactly what it ran before.
+ * Definitions (occ = occupied_tones, zl = (N - occ) / 2, ks = the known preamble symbol over the occupied block):
+ *   pilot / null bins  occupied index i in [0, occ) is read at Ysh[i + zl + coarse] of the packet's own preamble
+ *                      (FFT output, DC in the middle; 0 outside [0, N), as frame acquisition reads it): a pilot bin
+ *                      where ks[i] != 0, a null bin where ks[i] == 0 (every odd absolute bin).  The means divide by
+ *                      the two bin counts.
+ *   decision energies  every carrier the frame sink demapped for the packet (header symbols included, and a later
+ *                      preamble the packet's chain consumed as data): the rows of OFDM_TAP_RX_SINK.  sigrot is the
+ *                      slicer's input, decision the constellation point it picked.
+ *   cfo_bins           coarse + fine, fine = -step * N / (2 pi) with step the NCO's per-sample phase step at the
+ *                      packet's flag (SYNC "fixed": the one fixed_freq_offset gives).  Same sign as
+ *                      ofdm_chan.cfo * N / (2 pi).
+ * Sums are per-thread sequential, then the demodulator's fixed reduction tree: the records are bit-reproducible. */
+typedef struct ofdm_pkt_quality {
+  uint64_t flag;          /* flag sample of the packet's preamble (= its ofdm_rx_packet_pos entry)             */
+  uint32_t first_symbol;  /* ordinal of that preamble among the call's sampled symbols (row of TAP_RX_FFT)     */
+  uint32_t nsym;          /* symbols the frame sink demapped for this packet (rows of TAP_RX_SINK)             */
+  uint32_t ncarriers;     /* carriers demapped = nsym * (data carriers of the sink's map)                      */
+  int32_t coarse;         /* frame acquisition's integer bin shift                                             */
+  float cfo_bins;         /* carrier offset estimate, subcarrier spacings                                      */
+  float pilot_power;      /* mean |Y|^2 over the preamble's known (non-zero) carriers, FFT-output units        */
+  float null_power;       /* mean |Y|^2 over its zeroed carriers inside the occupied band                      */
+  float err_energy;       /* sum over demapped carriers of |sigrot - decision|^2                               */
+  float ref_energy;       /* sum over demapped carriers of |decision|^2                                        */
+  float snr_preamble_db;  /* 10 log10(max(pilot_power / null_power - 1, 1e-6))                                 */
+  float snr_decision_db;  /* 10 log10(ref_energy / max(err_energy, 1e-30)) = -20 log10(EVM_rms)                */
+} ofdm_pkt_quality;
+
+int ofdm_set_rx_quality(ofdm_handle *h, int enable); /* off by default; holds for the following ofdm_rx calls */
+/* one record per packet of the last ofdm_rx, in the order of its payloads (CRC failures included); out == NULL:
+ * size query.  OFDM_E_INVAL if the last call ran without link quality; OFDM_E_CAPACITY (with *n set) if cap < *n. */
+int ofdm_rx_quality(ofdm_handle *h, ofdm_pkt_quality *out, int cap, int *n);
 
 /* --- spectrum sensing: the `sensor` flowgraph + sense_loop + hex_conv
  *     (predictive_sense.py:72-123,150-268; same code in sensing_and_tramsmitting*.py) ---

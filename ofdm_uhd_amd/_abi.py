@@ -7,7 +7,7 @@ __graft_entry__ as g; g.build()"`` or ``make -C ofdm_uhd_amd/csrc``).
 import ctypes as C
 import os
 
-OFDM_ABI_VERSION = 5
+OFDM_ABI_VERSION = 6
 OFDM_MAX_FFT = 4096
 OFDM_MAX_TAPS = 512
 OFDM_MAX_ARITY = 256
@@ -104,6 +104,23 @@ class ofdm_sense_cfg(C.Structure):
     ]
 
 
+class ofdm_pkt_quality(C.Structure):
+    _fields_ = [
+        ("flag", C.c_uint64),
+        ("first_symbol", C.c_uint32),
+        ("nsym", C.c_uint32),
+        ("ncarriers", C.c_uint32),
+        ("coarse", C.c_int32),
+        ("cfo_bins", C.c_float),
+        ("pilot_power", C.c_float),
+        ("null_power", C.c_float),
+        ("err_energy", C.c_float),
+        ("ref_energy", C.c_float),
+        ("snr_preamble_db", C.c_float),
+        ("snr_decision_db", C.c_float),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -113,6 +130,7 @@ EXPORTS = (
     "ofdm_kernel_name", "ofdm_sense_count", "ofdm_sense", "ofdm_sense_decide", "ofdm_set_rx_sense",
     "ofdm_rx_sense_result", "ofdm_sense_device_msgs", "ofdm_sense_redecide",
     "ofdm_rx_packet_pos", "ofdm_rx_nco_state", "ofdm_rx_set_flag_history", "ofdm_rx_set_origin", "ofdm_rx_submit", "ofdm_rx_snr",
+    "ofdm_set_rx_quality", "ofdm_rx_quality",
 )
 
 _LIB = None
@@ -161,6 +179,8 @@ def _declare(lib):
     lib.ofdm_rx_nco_state.argtypes = [H, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_rx_set_origin.argtypes = [H, C.c_uint64]
     lib.ofdm_rx_snr.argtypes = [H, C.POINTER(C.c_float)]
+    lib.ofdm_set_rx_quality.argtypes = [H, C.c_int]
+    lib.ofdm_rx_quality.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_rx_submit.argtypes = [H, C.c_void_p, C.c_uint64]
     lib.ofdm_rx_set_flag_history.argtypes = [H, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.c_double]
     lib.ofdm_sense_device_msgs.argtypes = [H, C.POINTER(C.c_void_p), u64p, u32p]

@@ -20,7 +20,7 @@ class rx_accounting(object):
         self.packet_file = packet_file
         self.verbose = verbose
 
-    def rx_callback(self, ok, payload):
+    def rx_callback(self, ok, payload, quality=None):
         if len(payload) < 4:
             return  # the reference would raise struct.error on a short payload
         (preamble,) = struct.unpack('!H', payload[2:4])
@@ -32,7 +32,11 @@ class rx_accounting(object):
             if ok:
                 self.n_right += 1
             if self.verbose:
-                print("ok: %r \t pktno: %d \t n_rcvd: %d \t n_right: %d" % (ok, pktno, self.n_rcvd, self.n_right))
+                line = "ok: %r \t pktno: %d \t n_rcvd: %d \t n_right: %d" % (ok, pktno, self.n_rcvd, self.n_right)
+                if quality is not None:   # --link-quality
+                    line += " \t snr_pre: %.1f \t snr_dd: %.1f \t cfo: %+.3f" % (
+                        quality["snr_preamble_db"], quality["snr_decision_db"], quality["cfo_bins"])
+                print(line)
 
 
 def main(argv=None):
@@ -44,6 +48,9 @@ def main(argv=None):
     parser.add_option("", "--chunk-samples", type="eng_float", default=0,
                       help="stream the capture through the demodulator in chunks of this many samples "
                            "(0 = one call on the whole file) [default=%default]")
+    parser.add_option("", "--link-quality", action="store_true", default=False,
+                      help="append the packet's link quality (preamble SNR, decision SNR in dB, carrier offset in "
+                           "subcarrier spacings) to each packet line [default=%default]")
     receive_path.receive_path.add_options(parser, expert_grp)
     ofdm.ofdm_demod.add_options(parser, expert_grp)
     (options, args) = parser.parse_args(argv)
@@ -53,7 +60,10 @@ def main(argv=None):
 
     packet_file = open(options.to_file, 'wb')
     acct = rx_accounting(packet_file)
-    rxpath = receive_path.receive_path(acct.rx_callback, options)
+    if options.link_quality:
+        rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback)
+    else:
+        rxpath = receive_path.receive_path(acct.rx_callback, options)
     rxpath.run(iqio.file_source(options.from_file), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     return acct

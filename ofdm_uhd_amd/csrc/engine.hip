@@ -77,6 +77,7 @@ struct ofdm_handle {
   int sign_kind = 0;      // two-level constellations: sign slicer (DemodParams::sign_kind)
   unsigned char sign_idx[4] = {0, 0, 0, 0};
   float sign_eps = 0.f, sign_bound = 0.f;
+  int q_npilot = 0, q_nnull = 0;  // bins of the preamble with a known (non-zero) / zeroed carrier (link quality)
   int filtF = 0;  // transform length of the channel filter (sync_filter_F)
 
   // TX workspaces
@@ -469,6 +470,13 @@ static int create_impl(const ofdm_cfg* cfg, ofdm_handle* h) {
   HIPCHK(h, upload(h->d_Hf, Hf.data(), Hf.size()));
   HIPCHK(h, upload(h->d_twF, twF.data(), twF.size()));
   HIPCHK(h, upload(h->d_ks, reinterpret_cast<const c32*>(cfg->known_symbol), (size_t)occ));
+  h->q_npilot = h->q_nnull = 0;  // the link-quality denominators: known and zeroed bins of the preamble
+  for (int i = 0; i < occ; i++) {
+    if (cfg->known_symbol[i].re != 0.f || cfg->known_symbol[i].im != 0.f)
+      h->q_npilot++;
+    else
+      h->q_nnull++;
+  }
   HIPCHK(h, upload(h->d_kd, kd.data(), kd.size()));
   return OFDM_OK;
 }

@@ -27,11 +27,11 @@ static int launch_demod_t(ofdm_handle* h, const DemodParams& q, size_t shmem) {
   HIPCHK(h, hipGetLastError());
   return OFDM_OK;
 }
-// (a call without symbol taps runs the kernel compiled without them: rx_demod.h)
+// (a call without symbol taps and without link quality runs the kernel compiled without them: rx_demod.h)
 template <int N, bool TWL>
 static int launch_demod_v(ofdm_handle* h, const DemodParams& q, size_t shmem) {
-  const bool taps = q.tap_mode != 0 || q.tap_sampler || q.tap_fft || q.tap_acq || q.tap_sink || q.tap_demapped;
-  return taps ? launch_demod_t<N, TWL, true>(h, q, shmem) : launch_demod_t<N, TWL, false>(h, q, shmem);
+  const bool instr = q.tap_mode != 0 || q.tap_sampler || q.tap_fft || q.tap_acq || q.tap_sink || q.tap_demapped || q.qual;
+  return instr ? launch_demod_t<N, TWL, true>(h, q, shmem) : launch_demod_t<N, TWL, false>(h, q, shmem);
 }
 
 // LDS extras of the demodulator (twiddle table for long transforms, the sink's carrier map): taken when they do not
@@ -580,6 +580,8 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   rx.npeaks = rx.nframes = rx.j0 = rx.nsym_total = rx.raw_tap_bytes = 0;
   rx.last_pos.clear();
   rx.last_swallowed.clear();
+  rx.last_quality.clear();
+  rx.quality_valid = rx.quality_on;
   if (stats) stats->samples = nsamples;
   if (nsamples == 0) return OFDM_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -781,6 +783,10 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   dq.invalid = rx.invalid.as<uint8_t>();
   dq.res = rx.res.as<FrameResult>();
   dq.raw = rx.raw.as<uint8_t>();
+  if (rx.quality_on) {
+    HIPCHK(h, rx.qual_frame.ensure(nframes * sizeof(FrameQuality)));
+    dq.qual = rx.qual_frame.as<FrameQuality>();
+  }
   h->prof.begin(OFDM_K_DEMOD, h->stream);
   rc = run_demod(h, dq);
 #ifdef SYNC_STAMPS
@@ -838,6 +844,7 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   if (tapm & ((1u << OFDM_TAP_RX_FFT) | (1u << OFDM_TAP_RX_ACQ) | (1u << OFDM_TAP_RX_SINK) | (1u << OFDM_TAP_RX_SAMPLER))) {
     DemodParams tq = dq;
     tq.tap_mode = 1;
+    tq.qual = nullptr;  // (the records come from the optimistic pass)
     if (tapm & (1u << OFDM_TAP_RX_SAMPLER)) {
       HIPCHK(h, rx.tap_sampler.ensure(nsym * (uint64_t)N * sizeof(c32)));
       tq.tap_sampler = rx.tap_sampler.as<c32>();
@@ -929,6 +936,19 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     fq.max_pkts = (uint32_t)npk_ub;
     hipLaunchKernelGGL(k_deframe_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq);
     HIPCHK(h, hipGetLastError());
+    if (rx.quality_on) {
+      HIPCHK(h, rx.qual_out.ensure(npk_ub * sizeof(ofdm_pkt_quality)));
+      QualityParams qw;
+      qw.fq = rx.qual_frame.as<FrameQuality>();
+      qw.step = rx.step.as<double>();
+      qw.out = rx.qual_out.as<ofdm_pkt_quality>();
+      qw.inv_npilot = h->q_npilot ? 1.0f / (float)h->q_npilot : 0.0f;
+      qw.inv_nnull = h->q_nnull ? 1.0f / (float)h->q_nnull : 0.0f;
+      qw.N = N;
+      qw.nmap = h->nmap;
+      hipLaunchKernelGGL(k_quality_write, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, qw);
+      HIPCHK(h, hipGetLastError());
+    }
     if (tapm & (1u << OFDM_TAP_RX_PACKETS)) {
       rx.raw_tap_bytes = hc[CT_RAWTOT];
       HIPCHK(h, rx.raw_tap.ensure(std::max<uint64_t>(rx.raw_tap_bytes, 1)));
@@ -942,6 +962,11 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     HIPCHK(h, hipMemcpyAsync(crc_ok, rx.out_ok.p, npk_ub, hipMemcpyDeviceToHost, h->stream));
     rx.last_pos.resize(npk_ub);
     HIPCHK(h, hipMemcpyAsync(rx.last_pos.data(), rx.out_pos.p, npk_ub * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if (rx.quality_on) {
+      rx.last_quality.resize(npk_ub);
+      HIPCHK(h, hipMemcpyAsync(rx.last_quality.data(), rx.qual_out.p, npk_ub * sizeof(ofdm_pkt_quality), hipMemcpyDeviceToHost,
+                               h->stream));
+    }
     if (!dyn && !h->dev_ptrs && nbytes)
       HIPCHK(h, hipMemcpyAsync(payload_out, d_pay, nbytes, hipMemcpyDeviceToHost, h->stream));
   }
@@ -964,6 +989,7 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
       stats->chained_frames = hc[CT_DEFR + 3];
     }
     rx.last_pos.resize(std::min<uint64_t>(npk, npk_ub));
+    if (rx.quality_on) rx.last_quality.resize(std::min<uint64_t>(npk, npk_ub));
     if (npk > (uint64_t)max_pkts || nbytes > payload_cap) {
       *npkt = (int)std::min<uint64_t>(npk, 0x7FFFFFFF);
       FAIL(h, OFDM_E_CAPACITY, "payload_out / max_pkts too small for the packets found");
@@ -1146,6 +1172,24 @@ extern "C" int ofdm_rx_nco_state(ofdm_handle* h, uint64_t* peaks, uint64_t* phi,
 extern "C" int ofdm_rx_snr(const ofdm_handle* h, float* snr_est) {
   if (!h || !snr_est) return OFDM_E_INVAL;
   *snr_est = 0.0f;  // d_snr_est of digital_ofdm_frame_acquisition: set to 0 by the constructor, never updated (GR 3.6.0)
+  return OFDM_OK;
+}
+
+extern "C" int ofdm_set_rx_quality(ofdm_handle* h, int enable) {
+  if (!h) return OFDM_E_INVAL;
+  h->rx.quality_on = enable != 0;
+  return OFDM_OK;
+}
+
+extern "C" int ofdm_rx_quality(ofdm_handle* h, ofdm_pkt_quality* out, int cap, int* n) {
+  if (!h) return OFDM_E_INVAL;
+  const RxState& rx = h->rx;
+  if (!rx.quality_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without link quality (ofdm_set_rx_quality)");
+  const size_t np = rx.last_quality.size();
+  if (n) *n = (int)np;
+  if (np == 0 || !out) return OFDM_OK;  // out == NULL: size query
+  if ((size_t)cap < np) FAIL(h, OFDM_E_CAPACITY, "quality array too small");
+  memcpy(out, rx.last_quality.data(), np * sizeof(ofdm_pkt_quality));
   return OFDM_OK;
 }
 

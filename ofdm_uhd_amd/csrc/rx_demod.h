@@ -33,6 +33,17 @@ struct FrameResult {
   uint32_t header_ok;
 };
 
+// Link quality of one frame (ofdm_set_rx_quality), written next to its FrameResult by the optimistic pass: the sums of
+// the chain's own preamble and of every carrier the chain demapped.  k_quality_write turns the records of the frames
+// that became packets into ofdm_pkt_quality.
+struct FrameQuality {
+  float pilot, null_;  // sums of |Y|^2 over the preamble's known / zeroed bins of the occupied band
+  float err, ref;      // sums of |sigrot - decision|^2 and |decision|^2 over the demapped carriers
+  uint32_t nsym;       // symbols demapped
+  int32_t coarse;      // the preamble's integer bin shift
+  uint64_t first_symbol;
+};
+
 struct FramesParams {
   uint64_t npeaks, nsamples;
   int N, L;
@@ -188,6 +199,7 @@ struct DemodParams {
   int ref_on;
   int64_t ref_peak;
   double ref_phi, ref_step;
+  FrameQuality* qual;      // optional [nframes]: link quality (instrumented kernel, optimistic pass)
 };
 
 // LDS of one frame's workgroup: fft (2 buffers; the first doubles as the shifted spectrum, the second as
@@ -413,19 +425,20 @@ __device__ __forceinline__ void frame_sync() {
     __syncthreads();
   }
 }
-// TAPS = false: the kernel of a call that asked for no symbol tap (no tap pointer set, no tap pass).  The five pointers and
-// the tap-pass flag are then compile-time nothing: 15 vector registers and 20 spilled scalar registers less at N = 512
-// (110 -> 95 VGPRs), k_rx_demod 2.55 -> 2.46 ms at C2, 2.09 -> 2.01 at C3.
-template <int N, bool TWL, bool TAPS>
+// INSTR = false: the lean kernel of a call that asked for no symbol tap and no link quality (no tap pointer set, no tap
+// pass, no quality record).  The six pointers and the tap-pass flag are then compile-time nothing: 15 vector registers and
+// 20 spilled scalar registers less at N = 512 (110 -> 95 VGPRs), k_rx_demod 2.55 -> 2.46 ms at C2, 2.09 -> 2.01 at C3.
+template <int N, bool TWL, bool INSTR>
 __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), demod_waves_per_simd(N)) k_rx_demod(DemodParams q_in) {
   DemodParams q = q_in;
-  if constexpr (!TAPS) {
+  if constexpr (!INSTR) {
     q.tap_sampler = nullptr;
     q.tap_fft = nullptr;
     q.tap_acq = nullptr;
     q.tap_sink = nullptr;
     q.tap_demapped = nullptr;
     q.tap_mode = 0;
+    q.qual = nullptr;
   }
   static_assert(TWL || fft_onebuf(N), "up to N = 1024 the twiddles are always in LDS");
   constexpr int T = N / 8;
@@ -487,6 +500,12 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
   uint32_t end_frame = f;
   int coarse = 0;
   unsigned phase_count = 1;
+  // link quality (q.qual: uniform across the frame's threads): per-thread sequential sums, reduced once at the end.
+  // (Every use sits under `if constexpr (INSTR)`: the lean kernel compiles to the code it had before the feature.)
+  const bool qon = INSTR && q.qual != nullptr && !q.tap_mode;
+  float q_pil = 0.f, q_nul = 0.f, q_err = 0.f, q_ref = 0.f;
+  uint32_t q_nsym = 0;
+  int q_coarse = 0;
   uint8_t* rawslot = q.raw + (uint64_t)f * RAW_SLOT;
 
   for (int i = t; i < sbw; i += T) sbits[i] = 0;
@@ -673,6 +692,21 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
           if (t == 0 && !(q.occ & 1)) hinv[q.occ - 1] = hinv[q.occ - 2];
           frame_sync<FPW>();
         }
+        if constexpr (INSTR) if (qon && cf == f) {
+          // the chain's own preamble: |Y|^2 over its known (pilot) and zeroed (null) bins, read where the equaliser reads
+          for (int i = t; i < q.occ; i += T) {
+            const int yi = i + q.zl + coarse;
+            const c32 Y = (yi >= 0 && yi < N) ? Ysh[yi] : mk(0.f, 0.f);
+            const c32 kv = q.ks[i];
+            const float p2 = cnorm(Y);
+            if (kv.re != 0.f || kv.im != 0.f)
+              q_pil = q_pil + p2;
+            else
+              q_nul = q_nul + p2;
+          }
+          block_sum2_f<T>(q_pil, q_nul, red);
+          q_coarse = coarse;
+        }
       }
       c32 comp;
       {
@@ -774,6 +808,10 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
           }
         }
         const c32 closest = cst[best];
+        if constexpr (INSTR) if (qon) {
+          q_err = q_err + cnorm(csub(sigrot, closest));
+          q_ref = q_ref + cnorm(closest);
+        }
         const c32 er = cmul_conj(sigrot, closest);
         are = are + er.re;
         aim = aim + er.im;
@@ -796,6 +834,7 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
       }
       DSTAMP(5);  // demapper: equalise, rotate, slice, DFE update, bit packing
       if (q.tap_demapped && t == 0) q.tap_demapped[symb + k] = 1;
+      if constexpr (INSTR) q_nsym++;
       block_sum2_f<T>(are, aim, red);
       const float angle = det_atan2f(aim, are);  // arg(accumulated error), bit-reproducible form
       pll_freq = pll_freq - q.freq_gain * angle;
@@ -853,6 +892,8 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
     cf++;  // the next preamble arrives while the sink is not searching: it is consumed as data
   }
   if (!done) end_frame = q_nframes - 1;
+  // (every thread of the frame gets here: the chain's exits above are uniform)
+  if constexpr (INSTR) if (qon) block_sum2_f<T>(q_err, q_ref, red);
 
 #ifdef SYNC_STAMPS
   if (threadIdx.x == 0)
@@ -865,6 +906,17 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
     r.end_frame = end_frame;
     r.header_ok = header_ok;
     q.res[f] = r;
+    if constexpr (INSTR) if (qon) {
+      FrameQuality fq;
+      fq.pilot = q_pil;
+      fq.null_ = q_nul;
+      fq.err = q_err;
+      fq.ref = q_ref;
+      fq.nsym = q_nsym;
+      fq.coarse = q_coarse;
+      fq.first_symbol = q.sym_base[q_j0 + f];
+      q.qual[f] = fq;
+    }
   }
 }
 
@@ -1060,6 +1112,45 @@ __global__ void __launch_bounds__(256) k_deframe_write(DeframeParams q) {
   }
 }
 
+// Link quality of the delivered packets: one thread per frame, keeping exactly the frames k_deframe_write keeps, record
+// `ord` of the call's packet list.
+struct QualityParams {
+  const FrameQuality* fq;  // [nframes]
+  const double* step;      // [npeaks] NCO step per flag
+  ofdm_pkt_quality* out;   // [max_pkts]
+  float inv_npilot, inv_nnull;
+  int N, nmap;
+};
+__global__ void __launch_bounds__(256) k_quality_write(DeframeParams q, QualityParams w) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= dyn_nframes(q.dyn, q.nframes)) return;
+  if (q.invalid[f]) return;
+  const FrameResult r = q.res[f];
+  if (r.status != FR_COMPLETE) return;
+  const uint64_t pos = q.pos[f];
+  const uint64_t ord = pos >> 40, boff = pos & ((1ull << 40) - 1);
+  const uint32_t plen = r.packetlen >= 4 ? r.packetlen - 4 : 0;
+  if (ord >= q.max_pkts || boff + plen > q.payload_cap) return;
+  const uint32_t j = dyn_j0(q.dyn, q.j0) + f;
+  const FrameQuality a = w.fq[f];
+  ofdm_pkt_quality o;
+  o.flag = q.peaks[j];
+  o.first_symbol = (uint32_t)a.first_symbol;
+  o.nsym = a.nsym;
+  o.ncarriers = a.nsym * (uint32_t)w.nmap;
+  o.coarse = a.coarse;
+  // the NCO turns by step per sample: it removes an offset of -step * N / (2 pi) subcarrier spacings
+  o.cfo_bins = (float)((double)a.coarse - w.step[j] * (double)w.N * 0.15915494309189533577);
+  o.pilot_power = a.pilot * w.inv_npilot;
+  o.null_power = a.null_ * w.inv_nnull;
+  o.err_energy = a.err;
+  o.ref_energy = a.ref;
+  const double ratio = (double)o.pilot_power / (double)fmaxf(o.null_power, 1e-30f) - 1.0;
+  o.snr_preamble_db = (float)(10.0 * log10(fmax(ratio, 1e-6)));
+  o.snr_decision_db = (float)(10.0 * log10((double)a.ref / (double)fmaxf(a.err, 1e-30f)));
+  w.out[ord] = o;
+}
+
 // raw (pre-dewhitening) messages, concatenated in stream order, for the PACKETS tap
 __global__ void __launch_bounds__(256) k_raw_tap(DeframeParams q, const uint64_t* __restrict__ rawpos, uint8_t* __restrict__ dst) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1123,7 +1214,7 @@ __global__ void __launch_bounds__(256) k_sigmix_tap(const c32* __restrict__ y, u
 struct RxState {
   DevBuf recs, x_stage, y, metric, presel, tile_B, tile_np, tile_first, tile_pieces, avg_in, cand_u, cand_P, counters, counts, offsets,
       partial, peaks, peak_P, angle, step, inc, Phi, K, nsym, sym_base, res, raw, invalid, chain_list, key, pos,
-      out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco;
+      out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco, qual_frame, qual_out;
   uint64_t nsamples = 0, npeaks = 0, nframes = 0, j0 = 0, nsym_total = 0, raw_tap_bytes = 0;
   const c32* y_ptr = nullptr;  // chan_filt's output of the last call: rx.y, or the input itself (SYNC "fixed")
   // ofdm_rx_submit: the input stage of the next ofdm_rx call is already queued for this buffer
@@ -1145,12 +1236,15 @@ struct RxState {
   std::vector<double> hist_steps;
   std::vector<uint8_t> hist_swallowed;
   std::vector<uint8_t> last_swallowed;  // per flag of the last call: its frame was swallowed by an earlier packet
+  // link quality (ofdm_set_rx_quality): on for the following calls; whether the last call ran with it, its records
+  bool quality_on = false, quality_valid = false;
+  std::vector<ofdm_pkt_quality> last_quality;
   void release() {
     DevBuf* all[] = {&recs, &x_stage, &y,      &metric,  &presel, &tile_B,   &tile_np,  &tile_first, &tile_pieces, &avg_in,     &cand_u,
                      &cand_P,  &counters, &counts, &offsets,  &partial,  &peaks,       &peak_P,     &angle,
                      &step,    &inc,    &Phi,     &K,        &nsym,     &sym_base,    &res,        &raw,
                      &invalid, &chain_list, &key, &pos,      &out_payload, &out_off,  &out_len,    &out_ok,
-                     &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco};
+                     &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco, &qual_frame, &qual_out};
     for (DevBuf* b : all) b->release();
   }
 };

@@ -15,6 +15,19 @@ import numpy as np
 from . import _abi, config
 
 
+def _quality_dtype():
+    st = _abi.ofdm_pkt_quality
+    conv = {C.c_uint64: np.uint64, C.c_uint32: np.uint32, C.c_int32: np.int32, C.c_float: np.float32}
+    return np.dtype({"names": [f for f, _ in st._fields_],
+                     "formats": [conv[t] for _, t in st._fields_],
+                     "offsets": [getattr(st, f).offset for f, _ in st._fields_],
+                     "itemsize": C.sizeof(st)})
+
+
+# one ofdm_pkt_quality record (include/ofdm_hip.h) as a NumPy structured dtype
+QUALITY_DTYPE = _quality_dtype()
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "libofdm_hip: %s (code %d)" % (msg, code))
@@ -220,6 +233,21 @@ class Engine(object):
         v = C.c_float(-1.0)
         self._check(self._lib.ofdm_rx_snr(self._h, C.byref(v)))
         return float(v.value)
+
+    def set_rx_quality(self, on=True):
+        """Per-packet link quality (SNR, EVM, carrier offset) for the following rx() / rx_device() calls."""
+        self._check(self._lib.ofdm_set_rx_quality(self._h, 1 if on else 0))
+
+    def rx_quality(self):
+        """Link quality of the packets the last rx() / rx_device() call returned, one record per packet in the same
+        order: a NumPy structured array of QUALITY_DTYPE (the fields of ofdm_pkt_quality).  ValueError if that call
+        ran without set_rx_quality(True)."""
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_rx_quality(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), QUALITY_DTYPE)
+        if n.value:
+            self._check(self._lib.ofdm_rx_quality(self._h, _ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
 
     def rx_submit_device(self, iq_ptr, nsamples):
         """Queue the receiver's input stage for this buffer and return at once (ofdm_rx_submit): a tx_device(...,

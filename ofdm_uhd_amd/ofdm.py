@@ -163,11 +163,14 @@ class ofdm_demod(object):
     app via the callback.
     """
 
-    def __init__(self, options, callback=None, device_id=0):
+    def __init__(self, options, callback=None, device_id=0, quality_callback=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
         @type callback: ok: bool; payload: bytes
+        @param quality_callback: optional function of three args: ok, payload, quality -- turns on the per-packet
+            link quality (a record of engine.QUALITY_DTYPE: SNR, EVM, carrier offset) and is fired per packet next to
+            ``callback``
         """
         self._modulation = options.modulation
         self._fft_length = options.fft_length
@@ -175,10 +178,15 @@ class ofdm_demod(object):
         self._cp_length = options.cp_length
         self._snr = getattr(options, "snr", 30)
         self._callback = callback
+        self._quality_callback = quality_callback
 
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
         self._engine = engine.Engine(options, device_id=device_id)
+        if quality_callback is not None:
+            self._engine.set_rx_quality(True)
+        # link-quality records of the packets the last work() / feed() returned (quality_callback only)
+        self.last_quality = np.zeros(0, engine.QUALITY_DTYPE)
         self._log = bool(getattr(options, "log", False))
         if self._log:
             self._engine.set_taps(engine._abi.TAP_RX_FFT, engine._abi.TAP_RX_ACQ, engine._abi.TAP_RX_SINK,
@@ -204,15 +212,22 @@ class ofdm_demod(object):
         if self._streaming:
             self.reset_stream()  # a one-shot call ends any chunked stream (and drops its carried history)
         pkts = self._engine.rx(iq)
+        if self._quality_callback is not None:
+            self.last_quality = self._engine.rx_quality()
         if self._log:
             self._write_logs()
-        for ok, payload in pkts:
+        self._deliver(pkts)
+        return pkts
+
+    def _deliver(self, pkts):
+        for i, (ok, payload) in enumerate(pkts):
             self.n_packets += 1
             if ok:
                 self.n_ok += 1
             if self._callback:
                 self._callback(ok, payload)  # _queue_watcher_thread.run (ofdm.py:300-305)
-        return pkts
+            if self._quality_callback is not None:
+                self._quality_callback(ok, payload, self.last_quality[i])
 
     def run(self, source):
         return self.work(source.read_all())
@@ -249,10 +264,26 @@ class ofdm_demod(object):
         # settled flags still of interest: (abs flag, phase in 2^-64 turn, step, swallowed); before any flag
         # the NCO idles at phase 0
         self._s_hist = [(0, 0, 0.0, 0)]
+        self._s_sym = None                         # (abs flag, symbol ordinal) of the last final flag (link quality)
         self._engine.set_flag_history(None)
         self._engine.set_origin(0)
         self._streaming = False
         self._log_samples = 0
+
+    def _stream_symbol(self, p):
+        """Ordinal, among the sampled symbols of the whole capture, of the preamble of the next final flag p (absolute):
+        the sampler's bookkeeping (k_frames) restated over the final flags -- the frame of the flag before takes
+        min(timeout + 1, (p - q - 2) // L) data symbols plus its preamble, if it was accepted (q >= N)."""
+        cfg = self._engine.cfg
+        N, L = cfg.fft_length, cfg.fft_length + cfg.cp_length
+        ordinal = 0
+        if self._s_sym is not None:
+            q, oq = self._s_sym
+            ordinal = oq
+            if q >= N:
+                ordinal += 1 + (min(cfg.sampler_timeout + 1, (p - q - 2) // L) if p >= q + 2 else 0)
+        self._s_sym = (p, ordinal)
+        return ordinal
 
     def feed(self, iq, flush=False):
         """Demodulate the next chunk of a continuous capture; returns the packets that became final.
@@ -269,6 +300,7 @@ class ofdm_demod(object):
         prev_final = self._s_final
         ran = False
         out = []
+        qual = []
         if len(buf) and horizon > self._s_final:
             eng = self._engine
             # the settled past: flags inside this buffer keep their known steps (whatever the call re-detects
@@ -282,13 +314,22 @@ class ofdm_demod(object):
             pkts = eng.rx(buf)
             ran = True
             pos = eng.rx_packet_pos().astype(np.int64) + base
-            for (ok, payload), p in zip(pkts, pos):
-                if self._s_final < p <= horizon:
-                    out.append((ok, payload))
             fl, phi, st, sw = eng.rx_nco_state()
             fl = fl.astype(np.int64) + base
+            first_sym = {}
             for j in np.flatnonzero((fl > self._s_final) & (fl <= horizon)):
                 self._s_hist.append((int(fl[j]), int(phi[j]), float(st[j]), int(sw[j])))
+                first_sym[int(fl[j])] = self._stream_symbol(int(fl[j]))
+            recs = eng.rx_quality() if self._quality_callback is not None else None
+            for i, ((ok, payload), p) in enumerate(zip(pkts, pos)):
+                if self._s_final < p <= horizon:
+                    out.append((ok, payload))
+                    if recs is not None:
+                        # the record as one call on the whole capture gives it: flag and symbol ordinal in the capture
+                        r = recs[i].copy()
+                        r["flag"] = p
+                        r["first_symbol"] = first_sym[int(p)]
+                        qual.append(r)
             self._s_final = max(self._s_final, horizon)
         if self._log and ran:
             self._write_logs(base=base, prev_final=prev_final, horizon=horizon, end=total if flush else None)
@@ -304,12 +345,9 @@ class ofdm_demod(object):
             keep = [f for f in self._s_hist if f[0] >= max(start, 1)]
             older = [f for f in self._s_hist if f[0] < max(start, 1)]
             self._s_hist = older[-1:] + keep
-        for ok, payload in out:
-            self.n_packets += 1
-            if ok:
-                self.n_ok += 1
-            if self._callback:
-                self._callback(ok, payload)
+        if self._quality_callback is not None:
+            self.last_quality = np.array(qual, engine.QUALITY_DTYPE)
+        self._deliver(out)
         return out
 
     def flush(self):
