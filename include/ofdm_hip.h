@@ -242,6 +242,44 @@ int ofdm_set_rx_quality(ofdm_handle *h, int enable); /* off by default; holds fo
  * size query.  OFDM_E_INVAL if the last call ran without link quality; OFDM_E_CAPACITY (with *n set) if cap < *n. */
 int ofdm_rx_quality(ofdm_handle *h, ofdm_pkt_quality *out, int cap, int *n);
 
+/* --- per-subcarrier channel state (CSI) per packet, and its per-carrier summary (no reference counterpart) ---------
+ * Off by default; ofdm_set_rx_csi(h, 1) holds for the following ofdm_rx calls.  A call with it on runs the
+ * demodulator's CSI instantiation and one gather kernel more; a call with it off runs exactly what it ran before.
+ * Independent of link quality.  Notation: occ = occupied_tones, zl = (N - occ + 1) / 2, coarse = frame acquisition's
+ * integer bin shift for the packet's preamble, Y[i] = Ysh[i + zl + coarse] of that preamble (FFT output, DC in the
+ * middle; 0 outside [0, N)), read exactly where the equaliser and the link-quality sums read it.  Pilot bin: ks[i] != 0;
+ * null bin: ks[i] == 0, every odd absolute bin.
+ * Per delivered packet (CRC failures included), one row per array, occ entries each, in payload order:
+ *   eq         hinv[i] of the packet's OWN preamble, bit for bit what the demodulator multiplies with:
+ *              ks[i] / (comp Y[i]) at even i, the mean of the two neighbours at interior odd i, a copy of occ-2 at occ-1
+ *              when occ is even (the equaliser works on occupied-index parity, not on ks).  A later preamble the
+ *              packet's chain consumes as data re-estimates hinv; the row keeps the first one.  Non-finite values are
+ *              stored as computed.
+ *   pre_power  |Y[i]|^2 of the packet's own preamble
+ *   err        sum over the symbols the frame sink demapped for the packet (those link quality counts), in symbol
+ *              order, of |sigrot - decision|^2 on the carrier whose sink-map entry is i (smap[c] == i); 0 where i is
+ *              not in the sink's map
+ *   ref        the same sum of |decision|^2
+ * One thread owns each carrier for the whole chain: every entry is a sequential float32 sum, bit-reproducible.
+ * Summary over the last call's packets (all, or the CRC-ok ones), per carrier, float64: npkt, sum pre_power, sum err,
+ * sum ref, and sum |1/eq|^2 over the finite non-zero eq with the count of those entries.  Summation order is fixed
+ * (chunks of consecutive packets, then the chunks in order; no float atomics): repeated calls give the same bits.
+ * Derived report (host side, ofdm_uhd_amd/csi.py):
+ *   P[i] = sum pre_power[i] / npkt
+ *   Nh[i] = P[i] at a null bin; at a pilot bin the mean of P at the nearest null bin on each side (one at the edge)
+ *   Sh[i] = max(P[i] - Nh[i], 0) at a pilot bin; at a null bin the mean of Sh at the neighbouring pilot bins
+ *   snr_preamble_db[i] = 10 log10(max(Sh / Nh, 1e-6))   (every occupied carrier, used by the current map or not)
+ *   snr_decision_db[i] = 10 log10(sum ref / max(sum err, 1e-30))   (NaN outside the sink's map)
+ *   gain_db[i] = 10 log10(mean |1/eq|^2)
+ * Rows take about 20 occ bytes of device memory per frame and per packet, allocated only while CSI is on. */
+int ofdm_set_rx_csi(ofdm_handle *h, int enable); /* off by default; holds for the following ofdm_rx calls */
+/* rows [first, first+count) of the last call's packets, HOST memory, any array may be NULL; *n = packets of that
+ * call (count == 0: size query).  OFDM_E_INVAL if that call ran without CSI or first+count > *n. */
+int ofdm_rx_csi(ofdm_handle *h, int first, int count, ofdm_c32 *eq, float *pre_power, float *err, float *ref, int *n);
+/* per-carrier float64 sums of the definitions above, each array occ entries, HOST memory (any may be NULL) */
+int ofdm_rx_csi_summary(ofdm_handle *h, int crc_ok_only, uint32_t *npkt, double *pre_power, double *err, double *ref,
+                        double *inv_gain, uint32_t *ninv);
+
 /* --- spectrum sensing: the `sensor` flowgraph + sense_loop + hex_conv
  *     (predictive_sense.py:72-123,150-268; same code in sensing_and_tramsmitting*.py) ---
  * stream_to_vector(fft_size) -> fft_vcc(fft_size, True, window) -> complex_to_mag_squared

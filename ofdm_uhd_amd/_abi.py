@@ -130,7 +130,7 @@ EXPORTS = (
     "ofdm_kernel_name", "ofdm_sense_count", "ofdm_sense", "ofdm_sense_decide", "ofdm_set_rx_sense",
     "ofdm_rx_sense_result", "ofdm_sense_device_msgs", "ofdm_sense_redecide",
     "ofdm_rx_packet_pos", "ofdm_rx_nco_state", "ofdm_rx_set_flag_history", "ofdm_rx_set_origin", "ofdm_rx_submit", "ofdm_rx_snr",
-    "ofdm_set_rx_quality", "ofdm_rx_quality",
+    "ofdm_set_rx_quality", "ofdm_rx_quality", "ofdm_set_rx_csi", "ofdm_rx_csi", "ofdm_rx_csi_summary",
 )
 
 _LIB = None
@@ -181,6 +181,9 @@ def _declare(lib):
     lib.ofdm_rx_snr.argtypes = [H, C.POINTER(C.c_float)]
     lib.ofdm_set_rx_quality.argtypes = [H, C.c_int]
     lib.ofdm_rx_quality.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_set_rx_csi.argtypes = [H, C.c_int]
+    lib.ofdm_rx_csi.argtypes = [H, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.ofdm_rx_csi_summary.argtypes = [H, C.c_int, u32p, vp, vp, vp, vp, vp]
     lib.ofdm_rx_submit.argtypes = [H, C.c_void_p, C.c_uint64]
     lib.ofdm_rx_set_flag_history.argtypes = [H, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.c_double]
     lib.ofdm_sense_device_msgs.argtypes = [H, C.POINTER(C.c_void_p), u64p, u32p]

@@ -10,7 +10,7 @@ import struct
 import sys
 from optparse import OptionParser
 
-from . import iqio, ofdm, options as _options, receive_path
+from . import config, iqio, ofdm, options as _options, receive_path
 
 
 class rx_accounting(object):
@@ -51,6 +51,11 @@ def main(argv=None):
     parser.add_option("", "--link-quality", action="store_true", default=False,
                       help="append the packet's link quality (preamble SNR, decision SNR in dB, carrier offset in "
                            "subcarrier spacings) to each packet line [default=%default]")
+    parser.add_option("", "--csi-report", default=None,
+                      help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
+                           "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
+    parser.add_option("", "--suggest-map", type="eng_float", default=None,
+                      help="print the hex carrier map of the carriers whose SNR reaches this many dB [default=off]")
     receive_path.receive_path.add_options(parser, expert_grp)
     ofdm.ofdm_demod.add_options(parser, expert_grp)
     (options, args) = parser.parse_args(argv)
@@ -60,12 +65,23 @@ def main(argv=None):
 
     packet_file = open(options.to_file, 'wb')
     acct = rx_accounting(packet_file)
+    want_csi = options.csi_report is not None or options.suggest_map is not None
     if options.link_quality:
-        rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback)
+        rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
-        rxpath = receive_path.receive_path(acct.rx_callback, options)
+        rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
     rxpath.run(iqio.file_source(options.from_file), chunk_samples=int(options.chunk_samples))
     packet_file.close()
+    if options.csi_report is not None:
+        rep = rxpath.ofdm_rx.carrier_report()
+        zl = config.zeros_on_left(options.fft_length, options.occupied_tones)
+        with open(options.csi_report, "w") as f:
+            f.write("# carrier fft_bin snr_preamble_db snr_decision_db gain_db\n")
+            for i in range(options.occupied_tones):
+                f.write("%d %d %.2f %.2f %.2f\n" % (i, i + zl, rep["snr_preamble_db"][i], rep["snr_decision_db"][i],
+                                                     rep["gain_db"][i]))
+    if options.suggest_map is not None:
+        print("suggested carrier map: %s" % rxpath.ofdm_rx.suggest_carrier_map(float(options.suggest_map)))
     return acct
 
 

@@ -120,6 +120,87 @@ def carrier_map(occupied_tones, container, carriers="FE7F", sink=None):
     return out
 
 
+def _grown(occupied_tones, ndigits):
+    """carrier_map's growth of an ndigits-long string: (full 'f' digits added per side, dl, dr) -- dl / dr are the
+    carriers of the partial nibbles on the left / right (0: none)."""
+    diff = occupied_tones - 4 * ndigits
+    g = 0
+    while diff > 7:
+        g += 1
+        diff -= 8
+    dl = int(math.ceil(diff / 2.0)) if diff > 0 else 0
+    return g, dl, (diff - dl if diff > 0 else 0)
+
+
+def carrier_map_hex(occupied_tones, fft_length, carriers):
+    """The exact inverse of carrier_map: an upper-case hex string (hex_conv's form) for which the frame sink's rule selects
+    exactly ``carriers`` (indices into the occupied block) and the mapper's rule exactly [i + zl for i in carriers].
+
+    carrier_map grows a short string with forced-on carriers and centres the mapper's copy in units of four bins, so not
+    every length puts both copies in the same place (N = 512 / occ = 204: a 51-digit string puts the mapper's block at
+    bin 152 and the sink's at 154).  The longest string whose placement agrees is used; ValueError if every such length
+    has the growth rule force on a carrier the set excludes (the message names it), or if the set is empty or outside
+    the occupied block.  The result is checked against both forward rules before it is returned."""
+    occ, N = int(occupied_tones), int(fft_length)
+    want = sorted(set(int(c) for c in carriers))
+    if not want:
+        raise ValueError("carrier set is empty")
+    if want[0] < 0 or want[-1] >= occ:
+        raise ValueError("carrier %d lies outside the occupied block [0, %d)" % (want[0] if want[0] < 0 else want[-1], occ))
+    zl = zeros_on_left(N, occ)
+    wset = set(want)
+    forced_bad = None
+    for nd in range(min(occ // 4 + 2, _abi.OFDM_MAX_CARRIER_HEX), 0, -1):
+        g, dl, dr = _grown(occ, nd)
+        part = occ - 4 * nd - 8 * g > 0  # partial nibbles on both sides
+        tot = nd + 2 * g + (2 if part else 0)
+        if 4 * int((N // 4 - tot) / 2) + dl != zl:
+            continue  # the mapper's copy would not sit at zl
+        # digits of the grown string: [g (+1) forced] [nd free] [g (+1) forced]; carrier = 4 * digit + bit - dl
+        lo = g + (1 if part else 0)
+        forced = set()
+        for d in range(tot):
+            if lo <= d < lo + nd:
+                continue
+            if part and d == 0:
+                v = (1 << dl) - 1
+            elif part and d == tot - 1:
+                v = 0xF ^ ((1 << dr) - 1)
+            else:
+                v = 0xF
+            for j in range(4):
+                if (v >> (3 - j)) & 1:
+                    forced.add(4 * d + j - dl)
+        if any(c < 0 or c >= occ for c in forced):
+            continue  # a forced carrier the sink never reads: the two rules could not agree
+        excl = sorted(forced - wset)
+        if excl:
+            if forced_bad is None:
+                forced_bad = excl[0]
+            continue
+        digits = [0] * nd
+        ok = True
+        for c in want:
+            d, j = divmod(c + dl, 4)
+            if lo <= d < lo + nd:
+                digits[d - lo] |= 1 << (3 - j)
+            elif c not in forced:
+                ok = False
+                break
+        if not ok:
+            continue
+        s = "".join("0123456789ABCDEF"[v] for v in digits)
+        try:
+            if carrier_map(occ, occ, s, sink=True) != want or carrier_map(occ, N, s, sink=False) != [c + zl for c in want]:
+                continue
+        except ValueError:
+            continue
+        return s
+    if forced_bad is not None:
+        raise ValueError("the carrier map's growth rule forces carrier %d on, which the set excludes" % forced_bad)
+    raise ValueError("no hex carrier map selects exactly this carrier set at fft_length %d / occupied_tones %d" % (N, occ))
+
+
 def make_cfg(options, pad_for_usrp=False, device_ptrs=False, device_id=0, pad_seed=0x0FD30000, carriers=None):
     """Build the engine configuration from an options object carrying the
     reference's attribute names (modulation, fft_length, occupied_tones, cp_length,

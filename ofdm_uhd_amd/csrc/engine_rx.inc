@@ -17,19 +17,22 @@ static int dev_excl_scan(ofdm_handle* h, const T* d_in, uint64_t n, T* d_out, T*
   return OFDM_OK;
 }
 
-template <int N, bool TWL, bool TAPS>
+template <int N, bool TWL, bool TAPS, bool CSI = false>
 static int launch_demod_t(ofdm_handle* h, const DemodParams& q, size_t shmem) {
   constexpr int T = N / 8, FPW = demod_fpw(N);
   if (shmem > 64 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rx_demod<N, TWL, TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shmem));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rx_demod<N, TWL, TAPS>), dim3((q.nframes + FPW - 1) / FPW), dim3(T * FPW), shmem, h->stream, q);
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rx_demod<N, TWL, TAPS, CSI>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rx_demod<N, TWL, TAPS, CSI>), dim3((q.nframes + FPW - 1) / FPW), dim3(T * FPW), shmem,
+                     h->stream, q);
   HIPCHK(h, hipGetLastError());
   return OFDM_OK;
 }
-// (a call without symbol taps and without link quality runs the kernel compiled without them: rx_demod.h)
+// (a call without symbol taps and without link quality runs the kernel compiled without them: rx_demod.h; a call with
+// per-subcarrier channel state runs the CSI instantiation for its optimistic pass)
 template <int N, bool TWL>
 static int launch_demod_v(ofdm_handle* h, const DemodParams& q, size_t shmem) {
+  if (q.csi_eq) return launch_demod_t<N, TWL, true, true>(h, q, shmem);
   const bool instr = q.tap_mode != 0 || q.tap_sampler || q.tap_fft || q.tap_acq || q.tap_sink || q.tap_demapped || q.qual;
   return instr ? launch_demod_t<N, TWL, true>(h, q, shmem) : launch_demod_t<N, TWL, false>(h, q, shmem);
 }
@@ -42,7 +45,10 @@ static int launch_demod(ofdm_handle* h, const DemodParams& q0) {
   DemodParams q = q0;
   constexpr int T = N / 8, WAVES = demod_fpw(N) * ((T + WAVE - 1) / WAVE);
   const bool grid = q.grid != nullptr;
-  auto bytes = [&](bool twl, bool sm) { return (size_t)demod_lds_bytes(N, twl, sm, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid); };
+  const bool csi = q.csi_eq != nullptr;
+  auto bytes = [&](bool twl, bool sm) {
+    return (size_t)demod_lds_bytes(N, twl, sm, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid, csi);
+  };
   constexpr int CU_WAVES = 4 * demod_waves_per_simd(N);  // waves a CU holds at the kernel's register budget
   auto wgs = [&](size_t b) { return std::max<size_t>(1, std::min<size_t>(std::max(1, CU_WAVES / WAVES), (160 * 1024) / b)); };
   constexpr bool base_twl = !fft_onebuf(N);
@@ -582,6 +588,9 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   rx.last_swallowed.clear();
   rx.last_quality.clear();
   rx.quality_valid = rx.quality_on;
+  rx.csi_valid = rx.csi_on;
+  rx.csi_n = 0;
+  rx.csi_ok.clear();
   if (stats) stats->samples = nsamples;
   if (nsamples == 0) return OFDM_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -787,6 +796,22 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     HIPCHK(h, rx.qual_frame.ensure(nframes * sizeof(FrameQuality)));
     dq.qual = rx.qual_frame.as<FrameQuality>();
   }
+  CsiRows csi_fr = {nullptr, nullptr, nullptr, nullptr};
+  if (rx.csi_on) {
+    // per-frame rows, structure of arrays: eq | pre | err | ref, [nframes][stride] each
+    const uint64_t st = (uint64_t)((h->occ + 3) & ~3), cell = nframes * st;
+    HIPCHK(h, rx.csi_frame.ensure(cell * (sizeof(c32) + 3 * sizeof(float))));
+    csi_fr.eq = rx.csi_frame.as<c32>();
+    csi_fr.pre = reinterpret_cast<float*>(csi_fr.eq + cell);
+    csi_fr.err = csi_fr.pre + cell;
+    csi_fr.ref = csi_fr.err + cell;
+    rx.csi_stride = (int)st;
+    dq.csi_eq = csi_fr.eq;
+    dq.csi_pre = csi_fr.pre;
+    dq.csi_err = csi_fr.err;
+    dq.csi_ref = csi_fr.ref;
+    dq.csi_stride = (int)st;
+  }
   h->prof.begin(OFDM_K_DEMOD, h->stream);
   rc = run_demod(h, dq);
 #ifdef SYNC_STAMPS
@@ -845,6 +870,8 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     DemodParams tq = dq;
     tq.tap_mode = 1;
     tq.qual = nullptr;  // (the records come from the optimistic pass)
+    tq.csi_eq = nullptr;  // (so do the channel-state rows)
+    tq.csi_pre = tq.csi_err = tq.csi_ref = nullptr;
     if (tapm & (1u << OFDM_TAP_RX_SAMPLER)) {
       HIPCHK(h, rx.tap_sampler.ensure(nsym * (uint64_t)N * sizeof(c32)));
       tq.tap_sampler = rx.tap_sampler.as<c32>();
@@ -949,6 +976,18 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
       hipLaunchKernelGGL(k_quality_write, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, qw);
       HIPCHK(h, hipGetLastError());
     }
+    if (rx.csi_on) {
+      const uint64_t st = (uint64_t)rx.csi_stride, cell = npk_ub * st;
+      HIPCHK(h, rx.csi_rows.ensure(cell * (sizeof(c32) + 3 * sizeof(float))));
+      CsiRows pk;
+      pk.eq = rx.csi_rows.as<c32>();
+      pk.pre = reinterpret_cast<float*>(pk.eq + cell);
+      pk.err = pk.pre + cell;
+      pk.ref = pk.err + cell;
+      rx.csi_rows_cap = npk_ub;
+      hipLaunchKernelGGL(k_csi_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq, csi_fr, pk, rx.csi_stride);
+      HIPCHK(h, hipGetLastError());
+    }
     if (tapm & (1u << OFDM_TAP_RX_PACKETS)) {
       rx.raw_tap_bytes = hc[CT_RAWTOT];
       HIPCHK(h, rx.raw_tap.ensure(std::max<uint64_t>(rx.raw_tap_bytes, 1)));
@@ -1004,6 +1043,10 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   }
   if (npk > 0) payload_off[npk] = nbytes;
   *npkt = (int)npk;
+  if (rx.csi_on) {
+    rx.csi_n = npk;
+    rx.csi_ok.assign(crc_ok, crc_ok + npk);
+  }
   if (stats) {
     uint64_t nok = 0;
     for (uint64_t i = 0; i < npk; i++) nok += crc_ok[i] ? 1 : 0;
@@ -1190,6 +1233,92 @@ extern "C" int ofdm_rx_quality(ofdm_handle* h, ofdm_pkt_quality* out, int cap, i
   if (np == 0 || !out) return OFDM_OK;  // out == NULL: size query
   if ((size_t)cap < np) FAIL(h, OFDM_E_CAPACITY, "quality array too small");
   memcpy(out, rx.last_quality.data(), np * sizeof(ofdm_pkt_quality));
+  return OFDM_OK;
+}
+
+extern "C" int ofdm_set_rx_csi(ofdm_handle* h, int enable) {
+  if (!h) return OFDM_E_INVAL;
+  h->rx.csi_on = enable != 0;
+  return OFDM_OK;
+}
+
+// the four packet-row arrays of the last call in csi_rows: eq | pre | err | ref, [csi_rows_cap][stride] each
+static CsiRows csi_packet_rows(const RxState& rx) {
+  const uint64_t cell = rx.csi_rows_cap * (uint64_t)rx.csi_stride;
+  CsiRows pk;
+  pk.eq = rx.csi_rows.as<c32>();
+  pk.pre = reinterpret_cast<float*>(pk.eq + cell);
+  pk.err = pk.pre + cell;
+  pk.ref = pk.err + cell;
+  return pk;
+}
+
+extern "C" int ofdm_rx_csi(ofdm_handle* h, int first, int count, ofdm_c32* eq, float* pre_power, float* err, float* ref, int* n) {
+  if (!h) return OFDM_E_INVAL;
+  if (!n) FAIL(h, OFDM_E_INVAL, "null argument");
+  const RxState& rx = h->rx;
+  if (!rx.csi_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without channel state (ofdm_set_rx_csi)");
+  *n = (int)rx.csi_n;
+  if (count == 0) return OFDM_OK;  // size query
+  if (first < 0 || count < 0 || (uint64_t)first + (uint64_t)count > rx.csi_n) FAIL(h, OFDM_E_INVAL, "rows out of range");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  const CsiRows pk = csi_packet_rows(rx);
+  const size_t st = (size_t)rx.csi_stride, occ = (size_t)h->occ, r0 = (size_t)first * st;
+  if (eq)
+    HIPCHK(h, hipMemcpy2DAsync(eq, occ * sizeof(c32), pk.eq + r0, st * sizeof(c32), occ * sizeof(c32), (size_t)count,
+                               hipMemcpyDeviceToHost, h->stream));
+  float* dst[3] = {pre_power, err, ref};
+  const float* src[3] = {pk.pre, pk.err, pk.ref};
+  for (int a = 0; a < 3; a++)
+    if (dst[a])
+      HIPCHK(h, hipMemcpy2DAsync(dst[a], occ * sizeof(float), src[a] + r0, st * sizeof(float), occ * sizeof(float), (size_t)count,
+                                 hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return OFDM_OK;
+}
+
+extern "C" int ofdm_rx_csi_summary(ofdm_handle* h, int crc_ok_only, uint32_t* npkt, double* pre_power, double* err, double* ref,
+                                   double* inv_gain, uint32_t* ninv) {
+  if (!h) return OFDM_E_INVAL;
+  RxState& rx = h->rx;
+  if (!rx.csi_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without channel state (ofdm_set_rx_csi)");
+  const int occ = h->occ;
+  uint64_t np = 0;
+  for (uint64_t p = 0; p < rx.csi_n; p++) np += (!crc_ok_only || rx.csi_ok[p]) ? 1 : 0;
+  if (npkt) *npkt = (uint32_t)np;
+  double* dst[CSI_S_COUNT] = {pre_power, err, ref, inv_gain};
+  if (np == 0) {
+    for (int k = 0; k < CSI_S_COUNT; k++)
+      if (dst[k]) std::fill(dst[k], dst[k] + occ, 0.0);
+    if (ninv) std::fill(ninv, ninv + occ, 0u);
+    return OFDM_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  CsiSumParams s;
+  s.rows = csi_packet_rows(rx);
+  s.ok = rx.out_ok.as<uint8_t>();  // (the device copy of the verdicts: intact until the next ofdm_rx)
+  s.npk = (uint32_t)rx.csi_n;
+  s.occ = occ;
+  s.stride = rx.csi_stride;
+  s.crc_ok_only = crc_ok_only ? 1 : 0;
+  s.nchunks = (uint32_t)((rx.csi_n + CSI_SUM_CHUNK - 1) / CSI_SUM_CHUNK);
+  const uint64_t part = (uint64_t)s.nchunks * (uint64_t)occ;
+  HIPCHK(h, rx.csi_part.ensure(part * (CSI_S_COUNT * sizeof(double) + sizeof(uint32_t))));
+  HIPCHK(h, rx.csi_sum.ensure((uint64_t)occ * (CSI_S_COUNT * sizeof(double) + sizeof(uint32_t))));
+  s.part = rx.csi_part.as<double>();
+  s.part_n = reinterpret_cast<uint32_t*>(s.part + CSI_S_COUNT * part);
+  s.out = rx.csi_sum.as<double>();
+  s.out_n = reinterpret_cast<uint32_t*>(s.out + CSI_S_COUNT * occ);
+  const unsigned gx = (unsigned)((occ + 255) / 256);
+  hipLaunchKernelGGL(k_csi_summary, dim3(gx, s.nchunks), dim3(256), 0, h->stream, s);
+  HIPCHK(h, hipGetLastError());
+  hipLaunchKernelGGL(k_csi_summary_combine, dim3(gx), dim3(256), 0, h->stream, s);
+  HIPCHK(h, hipGetLastError());
+  for (int k = 0; k < CSI_S_COUNT; k++)
+    if (dst[k])
+      HIPCHK(h, hipMemcpyAsync(dst[k], s.out + (size_t)k * occ, occ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (ninv) HIPCHK(h, hipMemcpyAsync(ninv, s.out_n, occ * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return OFDM_OK;
 }
 

@@ -200,6 +200,13 @@ struct DemodParams {
   int64_t ref_peak;
   double ref_phi, ref_step;
   FrameQuality* qual;      // optional [nframes]: link quality (instrumented kernel, optimistic pass)
+  // per-subcarrier channel state (ofdm_set_rx_csi): the CSI instantiation's per-frame rows, [nframes][csi_stride] each,
+  // indexed by occupied carrier (set exactly when the CSI instantiation runs: optimistic pass only)
+  c32* csi_eq;      // hinv of the frame's own preamble
+  float* csi_pre;   // |Y|^2 of that preamble
+  float* csi_err;   // per carrier: sum of |sigrot - decision|^2 over the demapped symbols
+  float* csi_ref;   // per carrier: sum of |decision|^2
+  int csi_stride;   // occ rounded up to a multiple of 4 (16-byte rows)
 };
 
 // LDS of one frame's workgroup: fft (2 buffers; the first doubles as the shifted spectrum, the second as
@@ -231,15 +238,17 @@ __host__ __device__ inline int demod_lds_shared(int n, bool twl, bool smap_lds, 
                 (grid ? (int)sizeof(SlicerGrid) : 0) + (smap_lds ? ((nmap * 2 + 3) & ~3) : 0);
   return (b + 15) & ~15;
 }
-// one frame's own: transform buffer | hinv | dfe | reduction scratch | the bits of one symbol
-__host__ __device__ inline int demod_lds_frame(int n, int occ, int nmap, int nbits, int shift) {
+// one frame's own: transform buffer | hinv | dfe | reduction scratch | the bits of one symbol (| CSI instantiation: the
+// per-carrier err / ref sums, 2 * occ floats indexed by occupied carrier)
+__host__ __device__ inline int demod_lds_frame(int n, int occ, int nmap, int nbits, int shift, bool csi = false) {
   const int b = fft_lds_points(n) * (int)sizeof(c32) + (demod_hinv_len(n, occ, shift) + occ) * (int)sizeof(c32) +
-                demod_red_floats(n) * (int)sizeof(float) + ((demod_symbits_words(nmap, nbits) + 3) & ~3) * 4;
+                demod_red_floats(n) * (int)sizeof(float) + ((demod_symbits_words(nmap, nbits) + 3) & ~3) * 4 +
+                (csi ? 2 * occ * (int)sizeof(float) : 0);
   return (b + 15) & ~15;
 }
 __host__ __device__ inline int demod_lds_bytes(int n, bool twl, bool smap_lds, int occ, int arity, int nmap, int nbits, int shift,
-                                               bool grid) {
-  return demod_lds_shared(n, twl, smap_lds, arity, nmap, grid) + demod_fpw(n) * demod_lds_frame(n, occ, nmap, nbits, shift);
+                                               bool grid, bool csi = false) {
+  return demod_lds_shared(n, twl, smap_lds, arity, nmap, grid) + demod_fpw(n) * demod_lds_frame(n, occ, nmap, nbits, shift, csi);
 }
 
 // Two wave-wide sums in the normative order (oracle: lane_tree_sum -- partner = lane ^ d for d = 32, 16, ... 1, each
@@ -428,8 +437,11 @@ __device__ __forceinline__ void frame_sync() {
 // INSTR = false: the lean kernel of a call that asked for no symbol tap and no link quality (no tap pointer set, no tap
 // pass, no quality record).  The six pointers and the tap-pass flag are then compile-time nothing: 15 vector registers and
 // 20 spilled scalar registers less at N = 512 (110 -> 95 VGPRs), k_rx_demod 2.55 -> 2.46 ms at C2, 2.09 -> 2.01 at C3.
-template <int N, bool TWL, bool INSTR>
+// CSI = true (INSTR as well): the kernel of a call with per-subcarrier channel state on (ofdm_set_rx_csi).  Every CSI
+// line sits under `if constexpr (CSI)`: the other two instantiations compile to what they compiled to before it.
+template <int N, bool TWL, bool INSTR, bool CSI = false>
 __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), demod_waves_per_simd(N)) k_rx_demod(DemodParams q_in) {
+  static_assert(INSTR || !CSI, "the CSI instantiation is an instrumented one");
   DemodParams q = q_in;
   if constexpr (!INSTR) {
     q.tap_sampler = nullptr;
@@ -457,7 +469,7 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
   // (a frame's threads fill one wave: the slot is wave-uniform -- say so, and its LDS base lives in a scalar register)
   const int slot = FPW > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / T)) : 0;
   unsigned char* mine = smem + demod_lds_shared(N, TWL, q.smap_lds != 0, q.arity, q.nmap, use_grid) +
-                        slot * demod_lds_frame(N, q.occ, q.nmap, q.nbits, q.shift);
+                        slot * demod_lds_frame(N, q.occ, q.nmap, q.nbits, q.shift, CSI);
   c32* fftbuf = reinterpret_cast<c32*>(mine);
   c32* Ysh = fftbuf;  // the FFT buffer is free again after the last pass: shifted spectrum, linear
   c32* hinv = fftbuf + fft_lds_points(N);
@@ -468,6 +480,8 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
   float* red = reinterpret_cast<float*>(dfe + q.occ);
   uint32_t* sbits = reinterpret_cast<uint32_t*>(red + demod_red_floats(N));
   const int sbw = demod_symbits_words(q.nmap, q.nbits);
+  // CSI: err sums at [i], ref sums at [occ + i] for occupied carrier i; the thread that demaps carrier c owns i = smap[c]
+  float* csi_acc = reinterpret_cast<float*>(sbits + ((sbw + 3) & ~3));
 
   const int t = FPW > 1 ? (int)(threadIdx.x % T) : (int)threadIdx.x;
   const uint32_t f = blockIdx.x * FPW + (uint32_t)slot;
@@ -513,6 +527,8 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
     hinv[i] = mk(0.f, 0.f);
     dfe[i] = mk(1.f, 0.f);
   }
+  if constexpr (CSI)
+    for (int i = t; i < 2 * q.occ; i += T) csi_acc[i] = 0.f;
   frame_sync<FPW>();
 
 #ifdef SYNC_STAMPS
@@ -707,6 +723,18 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
           block_sum2_f<T>(q_pil, q_nul, red);
           q_coarse = coarse;
         }
+        if constexpr (CSI) if (cf == f) {
+          // The chain's own preamble: its equaliser and |Y|^2, stored here -- the one point of the frame where both are
+          // still in LDS and the symbol has no demapper work behind which a wait for these stores would hide less (the
+          // next symbol's prefetch, issued before them, is waited for with them at the top of the next symbol).
+          const uint64_t row = (uint64_t)f * (uint64_t)q.csi_stride;
+          for (int i = t; i < q.occ; i += T) {
+            const int yi = i + q.zl + coarse;
+            const c32 Y = (yi >= 0 && yi < N) ? Ysh[yi] : mk(0.f, 0.f);
+            q.csi_eq[row + i] = hinv[i];
+            q.csi_pre[row + i] = cnorm(Y);
+          }
+        }
       }
       c32 comp;
       {
@@ -812,6 +840,10 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
           q_err = q_err + cnorm(csub(sigrot, closest));
           q_ref = q_ref + cnorm(closest);
         }
+        if constexpr (CSI) {
+          csi_acc[i] = csi_acc[i] + cnorm(csub(sigrot, closest));
+          csi_acc[q.occ + i] = csi_acc[q.occ + i] + cnorm(closest);
+        }
         const c32 er = cmul_conj(sigrot, closest);
         are = are + er.re;
         aim = aim + er.im;
@@ -894,6 +926,15 @@ __global__ void __launch_bounds__(((N / 8 < 64) ? 64 : N / 8) * demod_fpw(N), de
   if (!done) end_frame = q_nframes - 1;
   // (every thread of the frame gets here: the chain's exits above are uniform)
   if constexpr (INSTR) if (qon) block_sum2_f<T>(q_err, q_ref, red);
+  if constexpr (CSI) {
+    // the per-carrier sums, after the chain: the symbol loop's only global traffic stays the next symbol's prefetch
+    frame_sync<FPW>();
+    const uint64_t row = (uint64_t)f * (uint64_t)q.csi_stride;
+    for (int i = t; i < q.occ; i += T) {
+      q.csi_err[row + i] = csi_acc[i];
+      q.csi_ref[row + i] = csi_acc[q.occ + i];
+    }
+  }
 
 #ifdef SYNC_STAMPS
   if (threadIdx.x == 0)
@@ -1151,6 +1192,97 @@ __global__ void __launch_bounds__(256) k_quality_write(DeframeParams q, QualityP
   w.out[ord] = o;
 }
 
+// Per-subcarrier channel state of the delivered packets: one WAVE per frame, keeping exactly the frames k_deframe_write
+// keeps, copies the frame's four rows (k_rx_demod's CSI instantiation) to packet row `ord` with coalesced 16-byte moves.
+struct CsiRows {
+  c32* eq;  // [rows][stride]
+  float* pre;
+  float* err;
+  float* ref;
+};
+__device__ __forceinline__ void csi_copy16(const void* src, void* dst, uint32_t n16, int lane) {
+  const uint4* s = reinterpret_cast<const uint4*>(src);
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  for (uint32_t k = (uint32_t)lane; k < n16; k += WAVE) d[k] = s[k];
+}
+__global__ void __launch_bounds__(256) k_csi_write(DeframeParams q, CsiRows fr, CsiRows pk, int stride) {
+  const int lane = lane_id();
+  const uint32_t f = blockIdx.x * 4 + (uint32_t)wave_id();
+  if (f >= dyn_nframes(q.dyn, q.nframes)) return;
+  if (q.invalid[f]) return;
+  const FrameResult r = q.res[f];
+  if (r.status != FR_COMPLETE) return;
+  const uint64_t pos = q.pos[f];
+  const uint64_t ord = pos >> 40, boff = pos & ((1ull << 40) - 1);
+  const uint32_t plen = r.packetlen >= 4 ? r.packetlen - 4 : 0;
+  if (ord >= q.max_pkts || boff + plen > q.payload_cap) return;
+  const uint64_t fo = (uint64_t)f * (uint64_t)stride, po = ord * (uint64_t)stride;
+  const uint32_t n16 = (uint32_t)stride / 4;  // (stride: a multiple of 4)
+  csi_copy16(fr.eq + fo, pk.eq + po, 2 * n16, lane);
+  csi_copy16(fr.pre + fo, pk.pre + po, n16, lane);
+  csi_copy16(fr.err + fo, pk.err + po, n16, lane);
+  csi_copy16(fr.ref + fo, pk.ref + po, n16, lane);
+}
+
+// Per-carrier summary of the packet rows (ofdm_rx_csi_summary), float64, in a fixed order: k_csi_summary sums the
+// packets of chunk blockIdx.y (CSI_SUM_CHUNK consecutive rows) in row order, one thread per carrier; k_csi_summary_combine
+// adds the chunks' partials in chunk order.  No atomics: the same rows give the same bits.
+#define CSI_SUM_CHUNK 128
+enum { CSI_S_PRE = 0, CSI_S_ERR = 1, CSI_S_REF = 2, CSI_S_INV = 3, CSI_S_COUNT = 4 };
+struct CsiSumParams {
+  CsiRows rows;
+  const uint8_t* ok;   // [npk] CRC verdicts
+  uint32_t npk;
+  int occ, stride, crc_ok_only;
+  double* part;        // [nchunks][CSI_S_COUNT][occ]
+  uint32_t* part_n;    // [nchunks][occ] finite non-zero eq entries
+  double* out;         // [CSI_S_COUNT][occ]
+  uint32_t* out_n;     // [occ]
+  uint32_t nchunks;
+};
+__global__ void __launch_bounds__(256) k_csi_summary(CsiSumParams s) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= s.occ) return;
+  const uint32_t b = blockIdx.y;
+  const uint32_t p0 = b * CSI_SUM_CHUNK, p1 = min(s.npk, p0 + CSI_SUM_CHUNK);
+  double a_pre = 0.0, a_err = 0.0, a_ref = 0.0, a_inv = 0.0;
+  uint32_t n_inv = 0;
+  for (uint32_t p = p0; p < p1; p++) {
+    if (s.crc_ok_only && !s.ok[p]) continue;
+    const uint64_t o = (uint64_t)p * (uint64_t)s.stride + (uint64_t)i;
+    a_pre += (double)s.rows.pre[o];
+    a_err += (double)s.rows.err[o];
+    a_ref += (double)s.rows.ref[o];
+    const c32 e = s.rows.eq[o];
+    const double re = (double)e.re, im = (double)e.im, m = re * re + im * im;
+    if (isfinite(re) && isfinite(im) && m != 0.0) {
+      a_inv += 1.0 / m;  // |1/eq|^2
+      n_inv++;
+    }
+  }
+  double* pp = s.part + (uint64_t)b * CSI_S_COUNT * (uint64_t)s.occ;
+  pp[CSI_S_PRE * s.occ + i] = a_pre;
+  pp[CSI_S_ERR * s.occ + i] = a_err;
+  pp[CSI_S_REF * s.occ + i] = a_ref;
+  pp[CSI_S_INV * s.occ + i] = a_inv;
+  s.part_n[(uint64_t)b * (uint64_t)s.occ + i] = n_inv;
+}
+__global__ void __launch_bounds__(256) k_csi_summary_combine(CsiSumParams s) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= s.occ) return;
+  double a[CSI_S_COUNT] = {0.0, 0.0, 0.0, 0.0};
+  uint32_t n = 0;
+  for (uint32_t b = 0; b < s.nchunks; b++) {
+    const double* pp = s.part + (uint64_t)b * CSI_S_COUNT * (uint64_t)s.occ;
+#pragma unroll
+    for (int k = 0; k < CSI_S_COUNT; k++) a[k] += pp[k * s.occ + i];
+    n += s.part_n[(uint64_t)b * (uint64_t)s.occ + i];
+  }
+#pragma unroll
+  for (int k = 0; k < CSI_S_COUNT; k++) s.out[k * s.occ + i] = a[k];
+  s.out_n[i] = n;
+}
+
 // raw (pre-dewhitening) messages, concatenated in stream order, for the PACKETS tap
 __global__ void __launch_bounds__(256) k_raw_tap(DeframeParams q, const uint64_t* __restrict__ rawpos, uint8_t* __restrict__ dst) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1214,7 +1346,8 @@ __global__ void __launch_bounds__(256) k_sigmix_tap(const c32* __restrict__ y, u
 struct RxState {
   DevBuf recs, x_stage, y, metric, presel, tile_B, tile_np, tile_first, tile_pieces, avg_in, cand_u, cand_P, counters, counts, offsets,
       partial, peaks, peak_P, angle, step, inc, Phi, K, nsym, sym_base, res, raw, invalid, chain_list, key, pos,
-      out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco, qual_frame, qual_out;
+      out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco, qual_frame, qual_out,
+      csi_frame, csi_rows, csi_part, csi_sum;
   uint64_t nsamples = 0, npeaks = 0, nframes = 0, j0 = 0, nsym_total = 0, raw_tap_bytes = 0;
   const c32* y_ptr = nullptr;  // chan_filt's output of the last call: rx.y, or the input itself (SYNC "fixed")
   // ofdm_rx_submit: the input stage of the next ofdm_rx call is already queued for this buffer
@@ -1239,12 +1372,19 @@ struct RxState {
   // link quality (ofdm_set_rx_quality): on for the following calls; whether the last call ran with it, its records
   bool quality_on = false, quality_valid = false;
   std::vector<ofdm_pkt_quality> last_quality;
+  // per-subcarrier channel state (ofdm_set_rx_csi): on for the following calls; whether the last call ran with it, its
+  // packet count and CRC verdicts.  The rows themselves stay in csi_rows (device) until the next call.
+  bool csi_on = false, csi_valid = false;
+  uint64_t csi_n = 0, csi_rows_cap = 0;
+  int csi_stride = 0;
+  std::vector<uint8_t> csi_ok;
   void release() {
     DevBuf* all[] = {&recs, &x_stage, &y,      &metric,  &presel, &tile_B,   &tile_np,  &tile_first, &tile_pieces, &avg_in,     &cand_u,
                      &cand_P,  &counters, &counts, &offsets,  &partial,  &peaks,       &peak_P,     &angle,
                      &step,    &inc,    &Phi,     &K,        &nsym,     &sym_base,    &res,        &raw,
                      &invalid, &chain_list, &key, &pos,      &out_payload, &out_off,  &out_len,    &out_ok,
-                     &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco, &qual_frame, &qual_out};
+                     &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco, &qual_frame, &qual_out,
+                     &csi_frame, &csi_rows, &csi_part, &csi_sum};
     for (DevBuf* b : all) b->release();
   }
 };

@@ -249,6 +249,42 @@ class Engine(object):
             self._check(self._lib.ofdm_rx_quality(self._h, _ptr(out), n.value, C.byref(n)))
         return out[:n.value]
 
+    def set_rx_csi(self, on=True):
+        """Per-subcarrier channel state (equaliser, preamble power, decision error / reference energy per carrier) for
+        the following rx() / rx_device() calls."""
+        self._check(self._lib.ofdm_set_rx_csi(self._h, 1 if on else 0))
+
+    def rx_csi(self, first=0, count=None):
+        """Channel-state rows of the packets the last rx() / rx_device() call returned, in the same order, packets
+        [first, first + count) (count None: to the end): a dict of ``eq`` complex64 and ``pre_power``, ``err``,
+        ``ref`` float32, each [count, occupied_tones] (definitions: include/ofdm_hip.h).  ValueError if that call ran
+        without set_rx_csi(True) or the range lies outside its packets."""
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_rx_csi(self._h, 0, 0, None, None, None, None, C.byref(n)))
+        count = max(n.value - int(first), 0) if count is None else int(count)
+        occ = int(self.cfg.occupied_tones)
+        out = {"eq": np.zeros((count, occ), np.complex64)}
+        for k in ("pre_power", "err", "ref"):
+            out[k] = np.zeros((count, occ), np.float32)
+        if count:
+            self._check(self._lib.ofdm_rx_csi(self._h, int(first), count, _ptr(out["eq"]), _ptr(out["pre_power"]),
+                                              _ptr(out["err"]), _ptr(out["ref"]), C.byref(n)))
+        return out
+
+    def rx_csi_summary(self, crc_ok_only=True):
+        """Per-carrier float64 sums over the last call's packets (the CRC-ok ones only by default), reduced on the
+        device in a fixed order: ``npkt``, ``pre_power``, ``err``, ``ref``, ``inv_gain`` (sum |1/eq|^2 over the finite
+        non-zero eq) and ``ninv`` (their count, uint32).  csi.carrier_report turns it into per-carrier dB figures."""
+        occ = int(self.cfg.occupied_tones)
+        out = {k: np.zeros(occ, np.float64) for k in ("pre_power", "err", "ref", "inv_gain")}
+        out["ninv"] = np.zeros(occ, np.uint32)
+        npk = C.c_uint32(0)
+        self._check(self._lib.ofdm_rx_csi_summary(self._h, 1 if crc_ok_only else 0, C.byref(npk), _ptr(out["pre_power"]),
+                                                  _ptr(out["err"]), _ptr(out["ref"]), _ptr(out["inv_gain"]),
+                                                  _ptr(out["ninv"])))
+        out["npkt"] = int(npk.value)
+        return out
+
     def rx_submit_device(self, iq_ptr, nsamples):
         """Queue the receiver's input stage for this buffer and return at once (ofdm_rx_submit): a tx_device(...,
         wait=False) issued next is held back only until that stage has read the buffer, and runs beside the

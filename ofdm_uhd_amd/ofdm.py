@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -163,7 +163,7 @@ class ofdm_demod(object):
     app via the callback.
     """
 
-    def __init__(self, options, callback=None, device_id=0, quality_callback=None):
+    def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -171,6 +171,8 @@ class ofdm_demod(object):
         @param quality_callback: optional function of three args: ok, payload, quality -- turns on the per-packet
             link quality (a record of engine.QUALITY_DTYPE: SNR, EVM, carrier offset) and is fired per packet next to
             ``callback``
+        @param csi: per-subcarrier channel state: ``last_csi`` holds the rows of the packets the last work() / feed()
+            returned, carrier_report() / suggest_carrier_map() aggregate the CRC-ok ones (csi.py)
         """
         self._modulation = options.modulation
         self._fft_length = options.fft_length
@@ -187,6 +189,12 @@ class ofdm_demod(object):
             self._engine.set_rx_quality(True)
         # link-quality records of the packets the last work() / feed() returned (quality_callback only)
         self.last_quality = np.zeros(0, engine.QUALITY_DTYPE)
+        # channel-state rows of the packets the last work() / feed() returned (csi only), and their running sums
+        self._csi = bool(csi)
+        if self._csi:
+            self._engine.set_rx_csi(True)
+        self.last_csi = self._csi_rows(None, [])
+        self.reset_carrier_report()
         self._log = bool(getattr(options, "log", False))
         if self._log:
             self._engine.set_taps(engine._abi.TAP_RX_FFT, engine._abi.TAP_RX_ACQ, engine._abi.TAP_RX_SINK,
@@ -214,6 +222,9 @@ class ofdm_demod(object):
         pkts = self._engine.rx(iq)
         if self._quality_callback is not None:
             self.last_quality = self._engine.rx_quality()
+        if self._csi:
+            self.last_csi = self._engine.rx_csi()
+            self._csi_accumulate(pkts)
         if self._log:
             self._write_logs()
         self._deliver(pkts)
@@ -301,6 +312,7 @@ class ofdm_demod(object):
         ran = False
         out = []
         qual = []
+        sel, rows = [], None    # packets of this call that are delivered now (rows of its channel state)
         if len(buf) and horizon > self._s_final:
             eng = self._engine
             # the settled past: flags inside this buffer keep their known steps (whatever the call re-detects
@@ -321,9 +333,11 @@ class ofdm_demod(object):
                 self._s_hist.append((int(fl[j]), int(phi[j]), float(st[j]), int(sw[j])))
                 first_sym[int(fl[j])] = self._stream_symbol(int(fl[j]))
             recs = eng.rx_quality() if self._quality_callback is not None else None
+            rows = eng.rx_csi() if self._csi else None
             for i, ((ok, payload), p) in enumerate(zip(pkts, pos)):
                 if self._s_final < p <= horizon:
                     out.append((ok, payload))
+                    sel.append(i)
                     if recs is not None:
                         # the record as one call on the whole capture gives it: flag and symbol ordinal in the capture
                         r = recs[i].copy()
@@ -347,8 +361,53 @@ class ofdm_demod(object):
             self._s_hist = older[-1:] + keep
         if self._quality_callback is not None:
             self.last_quality = np.array(qual, engine.QUALITY_DTYPE)
+        if self._csi:
+            self.last_csi = self._csi_rows(rows, sel)
+            self._csi_accumulate(out)
         self._deliver(out)
         return out
+
+    # -- per-subcarrier channel state (csi=True) ------------------------------------------------------------------
+    def _csi_rows(self, rows, sel):
+        occ = int(self._engine.cfg.occupied_tones)
+        if rows is None:
+            return {"eq": np.zeros((0, occ), np.complex64),
+                    **{k: np.zeros((0, occ), np.float32) for k in ("pre_power", "err", "ref")}}
+        return {k: v[np.asarray(sel, np.int64)] for k, v in rows.items()}
+
+    def _csi_accumulate(self, pkts):
+        """Adds the CRC-ok packets of last_csi to the running per-carrier sums, one packet after the other in delivery
+        order (float64): a chunked stream sums exactly what one call on the whole capture sums."""
+        acc = self._csi_acc
+        for i, (ok, _) in enumerate(pkts):
+            if not ok:
+                continue
+            acc["npkt"] += 1
+            for k in ("pre_power", "err", "ref"):
+                acc[k] += self.last_csi[k][i].astype(np.float64)
+            eq = self.last_csi["eq"][i].astype(np.complex128)
+            m = eq.real ** 2 + eq.imag ** 2
+            good = np.isfinite(eq.real) & np.isfinite(eq.imag) & (m != 0)
+            acc["inv_gain"][good] += 1.0 / m[good]
+            acc["ninv"][good] += 1
+
+    def reset_carrier_report(self):
+        """Starts the per-carrier sums behind carrier_report() afresh."""
+        occ = int(self._engine.cfg.occupied_tones)
+        self._csi_acc = {"npkt": 0, "ninv": np.zeros(occ, np.uint32),
+                         **{k: np.zeros(occ, np.float64) for k in ("pre_power", "err", "ref", "inv_gain")}}
+
+    def carrier_report(self):
+        """Per-carrier SNR (preamble, decision) and gain in dB over the CRC-ok packets delivered since construction or
+        reset_carrier_report() (csi.carrier_report; needs csi=True)."""
+        if not self._csi:
+            raise ValueError("carrier_report() needs ofdm_demod(..., csi=True)")
+        return _csi.carrier_report(self._csi_acc, self._engine.cfg)
+
+    def suggest_carrier_map(self, min_snr_db, respect_current=True):
+        """Hex carrier map of the carriers whose SNR reaches min_snr_db (csi.suggest_carrier_map): for
+        reset_carrier_map() here and the transmitter's set_carrier_map()."""
+        return _csi.suggest_carrier_map(self.carrier_report(), self._engine.cfg, min_snr_db, respect_current)
 
     def flush(self):
         return self.feed(np.zeros(0, np.complex64), flush=True)

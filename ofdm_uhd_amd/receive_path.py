@@ -5,7 +5,7 @@ from . import ofdm
 
 
 class receive_path(object):
-    def __init__(self, rx_callback, options, device_id=0, quality_callback=None):
+    def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False):
         options = copy.copy(options)    # make a copy so we can destructively modify
 
         self._verbose = getattr(options, "verbose", False)
@@ -13,7 +13,7 @@ class receive_path(object):
         self._rx_callback = rx_callback      # this callback is fired when there's a packet available
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
-                                       quality_callback=quality_callback)
+                                       quality_callback=quality_callback, csi=csi)
 
         if self._verbose:
             self._print_verbage()
