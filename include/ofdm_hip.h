@@ -84,7 +84,8 @@ typedef struct ofdm_cfg {
 
   float peak_rise;  /* gr_peak_detector_fb threshold_factor_rise 0.20 (ofdm_sync_pn) */
   float peak_fall;  /* gr_peak_detector_fb threshold_factor_fall 0.20 */
-  float peak_alpha; /* gr_peak_detector_fb alpha 0.001; accepted range (0, 0.25] */
+  float peak_alpha; /* gr_peak_detector_fb alpha 0.001; accepted range (0, 0.005]: above it the Q40 part of the
+                     * detector's closed-form average can lose more than 1e-6 at a run start */
 
   uint32_t ntaps;             /* len(chan_coeffs), odd (ofdm_receiver.py~:71-75) */
   float taps[OFDM_MAX_TAPS];  /* gr.firdes.low_pass(1, 1, bw+tb, tb, WIN_HAMMING) as float32 */
@@ -397,7 +398,10 @@ enum {
                               * detector's running average outside them); no reference probe point */
   OFDM_TAP_RX_DEMAPPED = 17, /* u8[nsym]: 1 where the frame sink demapped the symbol (row of RX_FFT / RX_ACQ / RX_SAMPLER): the rows
                               * OFDM_TAP_RX_SINK holds, in order.  Needs OFDM_TAP_RX_SINK enabled. */
-  OFDM_TAP_COUNT = 18
+  OFDM_TAP_RX_RUN_AVG = 18,  /* f64[nruns][2]: (first sample, detector average there) of every run of candidates the peak
+                              * detector walks, by first sample; the average is the float32 value its state machine starts
+                              * from (engine-internal stage); no reference probe point */
+  OFDM_TAP_COUNT = 19
 };
 /* SIGMIX / NCO evaluate the NCO's closed form sample by sample over the whole stream; inside the symbols the
  * sampler picks, the receiver itself advances the same phasor by a float64 recurrence: RX_SAMPLER is

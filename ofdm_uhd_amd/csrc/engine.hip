@@ -277,9 +277,9 @@ static int create_impl(const ofdm_cfg* cfg, ofdm_handle* h) {
       FAIL(h, OFDM_E_INVAL, "constellation points must be finite");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "ntaps must be in [1, 512]");
   if (cfg->whitener_offset > 15) FAIL(h, OFDM_E_INVAL, "whitener_offset must be between 0 and 15, inclusive");
-  // (alpha <= 0.25: the closed form of the detector's running average carries weights decay^-2048 in float64)
-  if (!(cfg->peak_rise > 0.f) || !(cfg->peak_fall > 0.f) || !(cfg->peak_alpha > 0.f) || !(cfg->peak_alpha <= 0.25f))
-    FAIL(h, OFDM_E_INVAL, "peak detector factors must be positive, alpha in (0, 0.25]");
+  // (alpha <= 0.005: the Q40 error of the average at a run start is <= decay^-2048 * 2^-41 / (e * alpha) ~ 1e-6 there)
+  if (!(cfg->peak_rise > 0.f) || !(cfg->peak_fall > 0.f) || !(cfg->peak_alpha > 0.f) || !(cfg->peak_alpha <= 0.005f))
+    FAIL(h, OFDM_E_INVAL, "peak detector factors must be positive, alpha in (0, 0.005]");
   if (cfg->max_fft_shift_len > 64) FAIL(h, OFDM_E_INVAL, "max_fft_shift_len too large");
   if (cfg->sync_mode != OFDM_SYNC_PN && cfg->sync_mode != OFDM_SYNC_FIXED)
     FAIL(h, OFDM_E_INVAL, "sync_mode must be OFDM_SYNC_PN or OFDM_SYNC_FIXED (\"ml\" / \"pnac\" need blocks the reference does not ship)");

@@ -470,6 +470,14 @@ retry_sync:
   pp.stash_peaks = rx.stash_peaks.as<uint64_t>();
   pp.stash_P = rx.stash_P.as<c32>();
   pp.stash_overflow = reinterpret_cast<unsigned int*>(ctr + CT_STASH);
+  // OFDM_TAP_RX_RUN_AVG: one row per piece slot; slots no interval starts in stay NaN (compacted when read)
+  uint64_t run_cap = 0;
+  if (h->tap_mask & (1u << OFDM_TAP_RX_RUN_AVG)) {
+    run_cap = sp.piece_cap;
+    HIPCHK(h, rx.run_rows.ensure(run_cap * 2 * sizeof(double)));
+    HIPCHK(h, hipMemsetAsync(rx.run_rows.p, 0xFF, run_cap * 2 * sizeof(double), h->stream));  // NaN
+    pp.run_rows = rx.run_rows.as<double>();
+  }
   const uint64_t nslots = ntiles;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_peak<false>), dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, h->stream, pp);
   HIPCHK(h, hipGetLastError());
@@ -489,6 +497,7 @@ retry_sync:
     h->prof.collect();
     FAIL(h, OFDM_E_OVERFLOW, "candidate / piece buffer exhausted");
   }
+  rx.run_slots = std::min<uint64_t>(hc[CT_PIECES], run_cap);
   uint64_t npeaks = hc[CT_NPEAKS] & 0xFFFFFFFFull;
   rx.npeaks = npeaks;
   if (stats) stats->peaks = npeaks;
@@ -583,7 +592,7 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   if (stats) memset(stats, 0, sizeof(*stats));
   RxState& rx = h->rx;
   rx.nsamples = nsamples;
-  rx.npeaks = rx.nframes = rx.j0 = rx.nsym_total = rx.raw_tap_bytes = 0;
+  rx.npeaks = rx.nframes = rx.j0 = rx.nsym_total = rx.raw_tap_bytes = rx.run_slots = 0;
   rx.last_pos.clear();
   rx.last_swallowed.clear();
   rx.last_quality.clear();
@@ -1132,6 +1141,27 @@ extern "C" int ofdm_tap(ofdm_handle* h, int tap, void* out, uint64_t cap, uint64
       if (!en) FAIL(h, OFDM_E_INVAL, "tap not enabled (ofdm_set_taps)");
       if (h->cfg.sync_mode == OFDM_SYNC_FIXED) FAIL(h, OFDM_E_INVAL, "SYNC \"fixed\" computes no timing metric");
       return copy_tap(h, rx.presel.p, rx.nsamples * sizeof(float), out, cap, nbytes);
+    case OFDM_TAP_RX_RUN_AVG: {
+      // rows of the piece slots the count pass wrote (their order follows the chunked allocation), by first sample
+      if (!en) FAIL(h, OFDM_E_INVAL, "tap not enabled (ofdm_set_taps)");
+      if (h->cfg.sync_mode == OFDM_SYNC_FIXED) FAIL(h, OFDM_E_INVAL, "SYNC \"fixed\" runs no peak detector");
+      std::vector<double> all(rx.run_slots * 2);
+      if (rx.run_slots) HIPCHK(h, hipMemcpy(all.data(), rx.run_rows.p, all.size() * sizeof(double), hipMemcpyDeviceToHost));
+      std::vector<std::pair<double, double>> rows;
+      for (uint64_t i = 0; i < rx.run_slots; i++)
+        if (all[2 * i] == all[2 * i]) rows.emplace_back(all[2 * i], all[2 * i + 1]);
+      std::sort(rows.begin(), rows.end());
+      const uint64_t nb = rows.size() * 2 * sizeof(double);
+      if (nbytes) *nbytes = nb;
+      if (!out || nb == 0) return OFDM_OK;
+      if (cap < nb) FAIL(h, OFDM_E_CAPACITY, "tap buffer too small");
+      double* o = static_cast<double*>(out);
+      for (size_t i = 0; i < rows.size(); i++) {
+        o[2 * i] = rows[i].first;
+        o[2 * i + 1] = rows[i].second;
+      }
+      return OFDM_OK;
+    }
     case OFDM_TAP_RX_PEAKS:
       return copy_tap(h, rx.peaks.p, rx.npeaks * sizeof(uint64_t), out, cap, nbytes);
     case OFDM_TAP_RX_ANGLES:

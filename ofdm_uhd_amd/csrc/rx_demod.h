@@ -1347,8 +1347,9 @@ struct RxState {
   DevBuf recs, x_stage, y, metric, presel, tile_B, tile_np, tile_first, tile_pieces, avg_in, cand_u, cand_P, counters, counts, offsets,
       partial, peaks, peak_P, angle, step, inc, Phi, K, nsym, sym_base, res, raw, invalid, chain_list, key, pos,
       out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco, qual_frame, qual_out,
-      csi_frame, csi_rows, csi_part, csi_sum;
+      csi_frame, csi_rows, csi_part, csi_sum, run_rows;
   uint64_t nsamples = 0, npeaks = 0, nframes = 0, j0 = 0, nsym_total = 0, raw_tap_bytes = 0;
+  uint64_t run_slots = 0;  // OFDM_TAP_RX_RUN_AVG: piece slots of the last call (unwritten ones hold NaN)
   const c32* y_ptr = nullptr;  // chan_filt's output of the last call: rx.y, or the input itself (SYNC "fixed")
   // ofdm_rx_submit: the input stage of the next ofdm_rx call is already queued for this buffer
   bool sub_valid = false, in_event_at_end = false;
@@ -1384,7 +1385,7 @@ struct RxState {
                      &step,    &inc,    &Phi,     &K,        &nsym,     &sym_base,    &res,        &raw,
                      &invalid, &chain_list, &key, &pos,      &out_payload, &out_off,  &out_len,    &out_ok,
                      &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco, &qual_frame, &qual_out,
-                     &csi_frame, &csi_rows, &csi_part, &csi_sum};
+                     &csi_frame, &csi_rows, &csi_part, &csi_sum, &run_rows};
     for (DevBuf* b : all) b->release();
   }
 };

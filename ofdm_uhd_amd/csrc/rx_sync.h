@@ -1403,6 +1403,9 @@ struct PeakParams {
   uint64_t* stash_peaks;    // [ntiles][PEAK_STASH]
   c32* stash_P;             // [ntiles][PEAK_STASH]
   unsigned int* stash_overflow;
+  // OFDM_TAP_RX_RUN_AVG (count pass; null when the tap is off): [slot of the interval's first piece][2] = (its first
+  // sample, the average it starts from)
+  double* run_rows;
 };
 #define PEAK_STASH 4
 
@@ -1423,6 +1426,11 @@ __global__ void __launch_bounds__(256) k_peak(PeakParams p) {
       if (npp > 0 && p.pieces[p.tile_first[g - 1] + npp - 1].end + 1 == pc.start) continue;
     }
     float avg = (float)(p.avg_in[g] * p.dpow[pc.start - g * (uint64_t)SYNC_TILE] + pc.bloc);
+    if (!WRITE && p.run_rows) {
+      double* row = p.run_rows + 2 * (p.tile_first[g0] + slot);
+      row[0] = (double)pc.start;
+      row[1] = (double)avg;
+    }
     int state = 0;
     float peak_val = -INFINITY;
     uint64_t peak_ind = 0;

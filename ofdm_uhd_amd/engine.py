@@ -439,6 +439,7 @@ class Engine(object):
         _abi.TAP_RX_SINK: np.complex64, _abi.TAP_RX_PACKETS: np.uint8, _abi.TAP_TX_MAPPER: np.complex64,
         _abi.TAP_TX_IFFT: np.complex64, _abi.TAP_RX_SAMPLER: np.complex64, _abi.TAP_RX_SIGMIX: np.complex64,
         _abi.TAP_RX_NCO: np.complex64, _abi.TAP_RX_PRESEL: np.float32, _abi.TAP_RX_DEMAPPED: np.uint8,
+        _abi.TAP_RX_RUN_AVG: np.float64,
     }
 
     def tap(self, tap):
@@ -448,7 +449,7 @@ class Engine(object):
         out = np.zeros(nb.value // dt.itemsize, dt)
         if nb.value:
             self._check(self._lib.ofdm_tap(self._h, tap, _ptr(out), nb.value, C.byref(nb)))
-        if tap == _abi.TAP_RX_FRAMES:
+        if tap in (_abi.TAP_RX_FRAMES, _abi.TAP_RX_RUN_AVG):
             out = out.reshape(-1, 2)
         elif tap in (_abi.TAP_TX_FREQ, _abi.TAP_RX_FFT, _abi.TAP_TX_MAPPER, _abi.TAP_TX_IFFT, _abi.TAP_RX_SAMPLER):
             out = out.reshape(-1, self.N)

@@ -766,6 +766,7 @@ struct orc_rx_result {
   vec peaks_gr; /* u64: flags of the literal float32 recurrence (cross-check, ORC_TAP_PEAKS_GR) */
   vec presel;   /* f32 [nsamples]: float32 pre-selection metric (OFDM_TAP_RX_PRESEL) */
   vec ranges;   /* i32 [ntiles][2]: exact-evaluation range of every 2048-sample tile, -1 -1 = none (ORC_TAP_RANGES) */
+  vec run_avg;  /* f64 [nruns][2]: first sample and detector average there of every run walked (OFDM_TAP_RX_RUN_AVG) */
   uint64_t presel_miss; /* samples with exact u > theta outside every range (must be 0: see orc_rx_presel_miss) */
   vec angles;   /* f32 */
   vec frames;   /* u64 x2 */
@@ -1024,7 +1025,7 @@ typedef struct {
 } sy_tile;
 
 static void peak_detect(const ofdm_cfg *cfg, const ofdm_c32 *y, const float *ux, uint64_t n, vec *peaks, float *u32_tap,
-                        int32_t *range_tap, uint64_t *presel_miss) {
+                        int32_t *range_tap, uint64_t *presel_miss, vec *run_avg) {
   const int T = SY_T, D = (int)cfg->fft_length / 2, CP = (int)cfg->cp_length;
   const float rise = cfg->peak_rise, fall = cfg->peak_fall, alpha = cfg->peak_alpha;
   const float one_m_alpha = 1.0f - alpha, decay_f = one_m_alpha;
@@ -1285,6 +1286,11 @@ static void peak_detect(const ofdm_cfg *cfg, const ofdm_c32 *y, const float *ux,
       }
       const double bloc = ((double)tl[g].gpre + (double)X * QINV) * (1.0 / dpow[Tl - k]);
       float avg = (float)(avg_in[g] * dpow[k] + bloc);
+      if (run_avg) {
+        double *row = (double *)vec_push(run_avg, 2);
+        row[0] = (double)(t0 + (uint64_t)k);
+        row[1] = (double)avg;
+      }
       int state = 0;
       float peak_val = -INFINITY;
       uint64_t peak_ind = 0;
@@ -1466,6 +1472,8 @@ static void rx_post_message(orc_rx_result *r, const ofdm_cfg *cfg, const uint8_t
 orc_rx_result *orc_rx(const ofdm_cfg *cfg, const ofdm_c32 *iq, uint64_t n, uint32_t tap_mask) {
   int N = (int)cfg->fft_length, CP = (int)cfg->cp_length, occ = (int)cfg->occupied_tones;
   int L = N + CP;
+  /* the engine's range (create_impl): above 0.005 the closed form's Q40 part loses the average at a run start */
+  if (!(cfg->peak_alpha > 0.0f) || !(cfg->peak_alpha <= 0.005f)) return NULL;
   orc_rx_result *r = (orc_rx_result *)calloc(1, sizeof(*r));
   r->tap_mask = tap_mask;
   r->N = N;
@@ -1476,6 +1484,7 @@ orc_rx_result *orc_rx(const ofdm_cfg *cfg, const ofdm_c32 *iq, uint64_t n, uint3
   vec_init(&r->peaks_gr, sizeof(uint64_t));
   vec_init(&r->presel, sizeof(float));
   vec_init(&r->ranges, sizeof(int32_t));
+  vec_init(&r->run_avg, sizeof(double));
   vec_init(&r->angles, sizeof(float));
   vec_init(&r->frames, sizeof(uint64_t));
   vec_init(&r->fft, sizeof(ofdm_c32));
@@ -1508,7 +1517,8 @@ orc_rx_result *orc_rx(const ofdm_cfg *cfg, const ofdm_c32 *iq, uint64_t n, uint3
     sync_metric(cfg, y, n, u, P);
     float *u32_tap = (tap_mask & (1u << OFDM_TAP_RX_PRESEL)) ? (float *)vec_push(&r->presel, n) : NULL;
     int32_t *range_tap = (int32_t *)vec_push(&r->ranges, 2 * (size_t)((n + SY_T - 1) / SY_T));
-    peak_detect(cfg, y, u, n, &r->peaks, u32_tap, range_tap, &r->presel_miss);
+    peak_detect(cfg, y, u, n, &r->peaks, u32_tap, range_tap, &r->presel_miss,
+                (tap_mask & (1u << OFDM_TAP_RX_RUN_AVG)) ? &r->run_avg : NULL);
     peak_detect_gr(cfg, u, n, &r->peaks_gr);
   } else {
     /* SYNC = "fixed" (ofdm_receiver.py~:108-119, "for testing only"): chan_filt = gr.multiply_const_cc(1.0);
@@ -1843,6 +1853,7 @@ uint64_t orc_rx_tap(const orc_rx_result *r, int tap, void *out, uint64_t cap_byt
     case ORC_TAP_PEAKS_GR: v = &r->peaks_gr; break;
     case OFDM_TAP_RX_PRESEL: v = &r->presel; break;
     case ORC_TAP_RANGES: v = &r->ranges; break;
+    case OFDM_TAP_RX_RUN_AVG: v = &r->run_avg; break;
     case OFDM_TAP_RX_ANGLES: v = &r->angles; break;
     case OFDM_TAP_RX_FRAMES: v = &r->frames; break;
     case OFDM_TAP_RX_FFT: v = &r->fft; break;
@@ -1886,6 +1897,7 @@ void orc_rx_free(orc_rx_result *r) {
   vec_free(&r->peaks_gr);
   vec_free(&r->presel);
   vec_free(&r->ranges);
+  vec_free(&r->run_avg);
   vec_free(&r->angles);
   vec_free(&r->frames);
   vec_free(&r->fft);

@@ -202,7 +202,7 @@ _TAP_DTYPES = {
     _abi.TAP_RX_ANGLES: np.float32, _abi.TAP_RX_FRAMES: np.uint64, _abi.TAP_RX_FFT: np.complex64,
     _abi.TAP_RX_ACQ: np.complex64, _abi.TAP_RX_SINK: np.complex64, _abi.TAP_RX_PACKETS: np.uint8,
     _abi.TAP_RX_SAMPLER: np.complex64, _abi.TAP_RX_SIGMIX: np.complex64, _abi.TAP_RX_NCO: np.complex64,
-    _abi.TAP_RX_PRESEL: np.float32,
+    _abi.TAP_RX_PRESEL: np.float32, _abi.TAP_RX_RUN_AVG: np.float64,
 }
 # oracle-only taps: the literal float32-recurrence detector's flags (cross-check of the normative evaluation) and the
 # exact-evaluation range of every 2048-sample tile
@@ -216,6 +216,8 @@ class RxResult(object):
         iq = np.ascontiguousarray(iq, np.complex64)
         self._cfg = cfg
         self._h = lib().orc_rx(C.byref(cfg), _ptr(iq) if len(iq) else None, len(iq), tap_mask)
+        if not self._h:
+            raise ValueError("peak_alpha must be in (0, 0.005] (got %r)" % cfg.peak_alpha)
         st = _abi.ofdm_stats()
         lib().orc_rx_stats(self._h, C.byref(st))
         self.stats = st.as_dict()
@@ -237,7 +239,7 @@ class RxResult(object):
         out = np.zeros(nb // dt.itemsize, dt)
         if nb:
             lib().orc_rx_tap(self._h, tap, _ptr(out), nb)
-        if tap in (_abi.TAP_RX_FRAMES, TAP_RANGES):
+        if tap in (_abi.TAP_RX_FRAMES, TAP_RANGES, _abi.TAP_RX_RUN_AVG):
             out = out.reshape(-1, 2)
         elif tap in (_abi.TAP_RX_FFT, _abi.TAP_RX_SAMPLER):
             out = out.reshape(-1, self._cfg.fft_length)

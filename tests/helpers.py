@@ -72,3 +72,44 @@ def marginal_capture(orc, d):
     return cfg, x
 
 
+# The peak detector's average at run starts (OFDM_TAP_RX_RUN_AVG): the grid of tests/test_detector_average.py, a subset
+# of which tests/test_gpu_detector.py runs on the engine.
+DETECTOR_ALPHAS = (0.0003, 0.001, 0.002, 0.005)
+DETECTOR_RISE_FALL = ((0.2, 0.2), (0.5, 0.2), (0.8, 0.6), (0.3, 0.1))
+DETECTOR_GEOMS = ((512, 200, 128), (2048, 1200, 512))
+# float32 roundings one value of the closed form goes through outside the exact ranges, with margin: a lane's chain of 8
+# fmaf, its table weight, the 64-lane scan (6), the four groups (3), the final conversion -- each relative to sums
+# of |alpha * decay^j * u32| <= 1 (u32 lies in [-1, theta - 1e-3] there), the earlier tiles' summaries included
+F32_ULPS = 24
+
+
+def q40_bound(alpha, tile=2048):
+    """Largest error the Q40 rounding of X(s) can put into the average at a run start: s - amin products, each rounded
+    to 2^-40 (error <= 2^-41), carried back by 1 / decay^(Tl - s); the worst s for amin = 0, Tl = 2048.  About
+    decay^-2048 * 2^-41 / (e * alpha): 1e-6 at alpha = 0.005, 1.4e-2 at 0.01."""
+    d = float(np.float32(1.0) - np.float32(alpha))
+    dp = np.ones(tile + 1)
+    for j in range(1, tile + 1):
+        dp[j] = dp[j - 1] * d
+    x = np.arange(tile + 1)
+    return float(np.max(x * 2.0 ** -41 / dp[tile - x]))
+
+
+def run_avg_tolerance(alpha):
+    """|tap - float64| <= tol * (1 + |ref|) at every run start: the Q40 bound plus the float32 roundings (F32_ULPS)."""
+    return q40_bound(alpha) + F32_ULPS * 2.0 ** -24
+
+
+def detector_capture(orc, N, occ, CP, snr, lead=None, npkt=4, seed=3):
+    """QPSK bursts of 1026-byte packets at 0.05 bins carrier offset (the shape the issue's table was measured on)."""
+    cfg = make_cfg("qpsk", N, occ, CP)
+    pay = make_payloads(npkt, 1026, seed=seed)
+    return loopback_stream(orc, cfg, pay, snr_db=snr, cfo_bins=0.05, lead=lead)
+
+
+def noise_capture(orc, ntiles=16, seed=11):
+    """Several tiles of complex white noise for N = 64: M = |P|^2 / R^2 fluctuates around 1/D there, so with
+    rise / fall 0.8 / 0.6 (theta = -0.8) runs of u > theta come from the noise alone."""
+    x = np.zeros(ntiles * 2048 + 333, np.complex64)
+    orc.channel(x, sigma=0.05, seed=seed)
+    return x

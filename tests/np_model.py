@@ -335,3 +335,77 @@ def rx(cfg, iq):
     packets = [ofdm_packet_utils.unmake_packet(m) for m in msgs]
     return dict(y=y, u=u, peaks=peaks, angles=angles, frames=frames, fft=syms, acq=acq, sink=derots,
                 msgs=msgs, packets=packets)
+
+
+# --- the peak detector's running average at run starts (OFDM_TAP_RX_RUN_AVG) ------------------------------------
+def detector_avg(v, alpha):
+    """gr_peak_detector_fb's running average as a float64 recurrence with the block's float32 coefficients alpha and
+    1 - alpha: avg[i] is the value BEFORE sample i (avg[0] = 0), len(v) + 1 entries."""
+    a = float(np.float32(alpha))
+    d = float(np.float32(1.0) - np.float32(alpha))
+    out = [0.0]
+    acc = 0.0
+    for x in np.asarray(v, np.float64).tolist():
+        acc = a * x + d * acc
+        out.append(acc)
+    return np.array(out)
+
+
+def detector_input(u_exact, u_presel, ranges, tile=2048):
+    """The samples the normative closed form of the average weights: the exact metric inside each
+    tile's range (ORC_TAP_RANGES rows, -1 -1 = none), the float32 pre-selection everywhere else."""
+    v = np.asarray(u_presel, np.float64).copy()
+    u = np.asarray(u_exact, np.float64)
+    for g, (a, b) in enumerate(np.asarray(ranges).reshape(-1, 2)):
+        if b >= 0:
+            v[g * tile + a:g * tile + b + 1] = u[g * tile + a:g * tile + b + 1]
+    return v
+
+
+def run_start_avg(u_exact, u_presel, ranges, alpha, starts):
+    """Float64 reference of the average each run starts from: the recurrence over detector_input, read just before
+    every given first sample."""
+    avg = detector_avg(detector_input(u_exact, u_presel, ranges), alpha)
+    return avg[np.asarray(starts, np.int64)]
+
+
+def peak_detect_margins(u, rise, fall, alpha, avg=None):
+    """gr_peak_detector_fb run literally in float64 over u, and how narrowly each run was decided.
+
+    Runs are the maximal intervals u > theta = -max(rise, fall): outside them no comparison can succeed (avg >= -1),
+    so every run starts in the searching state.  Returns (flags, runs [nruns][2] first and last sample, margin[nruns]):
+    margin = the smallest |u - avg*factor| / (1 + |avg|) over the threshold comparisons the machine makes in the run."""
+    u = np.asarray(u, np.float64)
+    n = len(u)
+    if avg is None:
+        avg = detector_avg(u, alpha)
+    theta = -max(float(np.float32(rise)), float(np.float32(fall)))
+    rise, fall = float(np.float32(rise)), float(np.float32(fall))
+    above = np.concatenate([[False], u > theta, [False]])
+    edges = np.flatnonzero(above[1:] != above[:-1])
+    runs = edges.reshape(-1, 2) - np.array([0, 1])
+    flags, margin = [], []
+    for r0, r1 in runs.tolist():
+        state, pv, pi, m = 0, -np.inf, 0, np.inf
+        for i in range(r0, r1 + 1):
+            x, a = u[i], avg[i]
+            w = 1.0 + abs(a)
+            if state == 0:
+                m = min(m, abs(x - a * rise) / w)
+                state = 1 if x > a * rise else 0
+            if state == 1:
+                if x > pv:
+                    pv, pi = x, i
+                else:
+                    m = min(m, abs(x - a * fall) / w)
+                    if not x > a * fall:
+                        flags.append(pi)
+                        pv = -np.inf
+                        m = min(m, abs(x - a * rise) / w)
+                        state = 1 if x > a * rise else 0
+                        if state == 1:
+                            pv, pi = x, i
+        if state == 1 and r1 + 1 < n:        # the sample after the run (u <= theta) closes it
+            flags.append(pi)
+        margin.append(m)
+    return np.array(flags, np.int64), runs.reshape(-1, 2), np.array(margin)

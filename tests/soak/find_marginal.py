@@ -49,7 +49,7 @@ while ncase < ncases:
     if rng.random() < 0.25:
         cfg.peak_rise, cfg.peak_fall = float(rng.choice([0.1, 0.3, 0.5])), float(rng.choice([0.1, 0.2, 0.4]))
     if rng.random() < 0.2:
-        cfg.peak_alpha = float(rng.choice([0.01, 0.0003]))
+        cfg.peak_alpha = float(rng.choice([0.0003, 0.001, 0.002, 0.005]))
     if rng.random() < 0.2:
         cfg.max_fft_shift_len = int(rng.choice([1, 2, 8]))
     npkt = int(rng.integers(1, 12))
