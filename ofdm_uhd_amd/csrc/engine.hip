@@ -16,6 +16,7 @@
 #include "tx.h"
 #include "rx_sync.h"
 #include "rx_demod.h"
+#include "rx_state.h"
 #include "sense.h"
 
 static std::string g_create_error;
@@ -96,7 +97,7 @@ struct ofdm_handle {
   uint32_t tap_mask = 0;
   Profiler prof;
 
-  RxState rx;  // receive-side workspaces (rx_demod.h)
+  RxState rx;  // receive-side workspaces (rx_state.h)
   SenseState sense;
 };
 

@@ -171,8 +171,17 @@ static int sync_params(ofdm_handle* h, uint64_t nsamples, bool cap_full, SyncPar
   return OFDM_OK;
 }
 
+static uint64_t sync_nseg(const SyncParams& sp) { return (sp.ntiles + (uint64_t)sp.tiles_per_seg - 1) / (uint64_t)sp.tiles_per_seg; }
+
 #ifdef SYNC_STAMPS
 static DevBuf g_stamp_buf;
+// cleared stamp slots for the nseg workgroups of one k_sync launch
+static int stamps_prepare(ofdm_handle* h, SyncParams& sp, uint64_t nseg) {
+  HIPCHK(h, g_stamp_buf.ensure(nseg * 16 * sizeof(unsigned long long)));
+  HIPCHK(h, hipMemsetAsync(g_stamp_buf.p, 0, nseg * 16 * sizeof(unsigned long long), h->stream));
+  sp.stamps = g_stamp_buf.as<unsigned long long>();
+  return OFDM_OK;
+}
 static int sync_stamps_report(ofdm_handle* h, const unsigned long long* d_stamps, uint64_t nseg, int tiles_per_seg) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   std::vector<unsigned long long> st(nseg * 16);
@@ -207,27 +216,19 @@ static bool front_fused(const ofdm_handle* h) {
   return front_lds_layout(sync_ring_samples(HY), h->CP, B, F).total <= 160 * 1024 / 3;
 }
 
-// ------------------------------------------------------------------------------------
-// The receiver's input stage: wait for the transmit batch that fills the buffer (if one is queued), stage a host
-// buffer, run the channel filter x -> y.  With SYNC "pn" and no fused sensing nothing reads the input afterwards:
-// ev_rx_in is recorded right here and the NEXT transmit batch (queued on the transmit stream while this call's
-// kernels and host round trips are still under way) may overwrite it.
-// ------------------------------------------------------------------------------------
 // k_sync over the whole filtered stream (the float32 pre-selection; the counters are cleared first)
 static int launch_sync(ofdm_handle* h, SyncParams& sp) {
   RxState& rx = h->rx;
   const int T = SYNC_TILE;
-  const uint64_t nseg = (sp.ntiles + (uint64_t)sp.tiles_per_seg - 1) / (uint64_t)sp.tiles_per_seg;
+  const uint64_t nseg = sync_nseg(sp);
   HIPCHK(h, hipMemsetAsync(rx.counters.p, 0, CT_COUNT * sizeof(uint64_t), h->stream));
 #ifdef SYNC_STAMPS
-  HIPCHK(h, g_stamp_buf.ensure(nseg * 16 * sizeof(unsigned long long)));
-  HIPCHK(h, hipMemsetAsync(g_stamp_buf.p, 0, nseg * 16 * sizeof(unsigned long long), h->stream));
-  sp.stamps = g_stamp_buf.as<unsigned long long>();
+  if (int rs = stamps_prepare(h, sp, nseg)) return rs;
 #endif
   const size_t sync_shmem = sync_lds_layout(sp.R, sp.HM).total;
   if (sync_shmem > 160 * 1024) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_sync");
-  h->prof.begin(OFDM_K_SYNC, h->stream);
   {
+    ProfScope span(h->prof, OFDM_K_SYNC, h->stream);
     // register budget for as many workgroups per CU as the LDS footprint admits (5 at C2, fewer for long symbols)
     int wg = (int)std::min<size_t>(SYNC_MAX_WG, (160 * 1024) / sync_shmem);
     if (const char* w = getenv("OFDM_SYNC_W")) wg = std::min(wg, atoi(w));  // tuning knob: a larger register budget
@@ -247,7 +248,6 @@ static int launch_sync(ofdm_handle* h, SyncParams& sp) {
     void* args[] = {&sp, &nofp};
     HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)nseg), dim3(SYNC_THREADS), args, sync_shmem, h->stream));
   }
-  h->prof.end(h->stream);
   HIPCHK(h, hipGetLastError());
   return OFDM_OK;
 }
@@ -262,6 +262,65 @@ static void rx_note_input(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples)
   h->rx_in_hi[0] = (uintptr_t)iq + nsamples * sizeof(c32);
 }
 
+// fused front end: channel filter + Schmidl-Cox pre-selection in one pass over x (k_sync<W, true, F>)
+static int launch_front(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
+  const int F = h->filtF;
+  SyncParams sp;
+  int rcs = sync_params(h, nsamples, false, &sp);
+  if (rcs != OFDM_OK) return rcs;
+  HIPCHK(h, hipMemsetAsync(h->rx.counters.p, 0, CT_COUNT * sizeof(uint64_t), h->stream));
+  const size_t shm = front_lds_layout(sp.R, sp.HM, fp.B, F).total;
+  const uint64_t nseg = sync_nseg(sp);
+  const void* fn = F == 64    ? reinterpret_cast<const void*>(&k_sync<3, true, 64>)
+                   : F == 128 ? reinterpret_cast<const void*>(&k_sync<3, true, 128>)
+                   : F == 256 ? reinterpret_cast<const void*>(&k_sync<3, true, 256>)
+                              : reinterpret_cast<const void*>(&k_sync<3, true, 512>);
+  HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+#ifdef SYNC_STAMPS
+  if (int rs = stamps_prepare(h, sp, nseg)) return rs;
+#endif
+  void* args[] = {&sp, &fp};
+  {
+    ProfScope span(h->prof, OFDM_K_FRONT, h->stream);
+    HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)nseg), dim3(SYNC_THREADS), args, shm, h->stream));
+  }
+  HIPCHK(h, hipGetLastError());
+#ifdef SYNC_STAMPS
+  if (int rs = sync_stamps_report(h, sp.stamps, nseg, sp.tiles_per_seg)) return rs;
+#endif
+  h->rx.front_done = true;
+  return OFDM_OK;
+}
+
+// channel filter: x -> y (streaming)
+static int launch_filter(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
+  const int F = h->filtF;
+  const uint64_t bpr = 256 / (F / 8);
+  const uint64_t nblk = (nsamples + (uint64_t)fp.goff + (uint64_t)fp.B - 1) / (uint64_t)fp.B;
+  fp.nrounds = (nblk + bpr - 1) / bpr;
+  const size_t fsh = (size_t)256 * 9 * sizeof(c32);  // 256/(F/8) transforms x (F + F/8) points
+  const unsigned fgrid = (unsigned)std::min<uint64_t>(fp.nrounds, 256ull * 8ull * 4ull);
+  {
+    ProfScope span(h->prof, OFDM_K_FILTER, h->stream);
+    switch (F) {
+      case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<64>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 128: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<128>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 256: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<256>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 512: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<512>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 1024: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<1024>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      default: FAIL(h, OFDM_E_INVAL, "unsupported channel filter transform length");
+    }
+  }
+  HIPCHK(h, hipGetLastError());
+  return OFDM_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// The receiver's input stage: wait for the transmit batch that fills the buffer (if one is queued), stage a host
+// buffer, run the channel filter x -> y.  With SYNC "pn" and no fused sensing nothing reads the input afterwards:
+// ev_rx_in is recorded right here and the NEXT transmit batch (queued on the transmit stream while this call's
+// kernels and host round trips are still under way) may overwrite it.
+// ------------------------------------------------------------------------------------
 static int rx_submit_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, const c32** d_x_out) {
   RxState& rx = h->rx;
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -279,8 +338,7 @@ static int rx_submit_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples,
   HIPCHK(h, rx.y.ensure(nsamples * sizeof(c32)));
   FilterParams fp;
   memset(&fp, 0, sizeof(fp));
-  const int F = h->filtF;
-  fp.B = F - (int)h->cfg.ntaps + 1;
+  fp.B = h->filtF - (int)h->cfg.ntaps + 1;
   fp.ntm1 = (int)h->cfg.ntaps - 1;
   fp.goff = (int)(rx.origin % (uint64_t)fp.B);
   fp.nsamples = nsamples;
@@ -289,52 +347,7 @@ static int rx_submit_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples,
   fp.Hf = h->d_Hf.as<c32>();
   fp.twF = h->d_twF.as<c32>();
   rx.front_done = false;
-  if (front_fused(h)) {
-    // ---- fused front end: channel filter + Schmidl-Cox pre-selection in one pass over x (k_sync<W, true, F>) ----
-    SyncParams sp;
-    int rcs = sync_params(h, nsamples, false, &sp);
-    if (rcs != OFDM_OK) return rcs;
-    HIPCHK(h, hipMemsetAsync(rx.counters.p, 0, CT_COUNT * sizeof(uint64_t), h->stream));
-    const size_t shm = front_lds_layout(sp.R, sp.HM, fp.B, F).total;
-    const uint64_t nseg = (sp.ntiles + (uint64_t)sp.tiles_per_seg - 1) / (uint64_t)sp.tiles_per_seg;
-    const void* fn = F == 64    ? reinterpret_cast<const void*>(&k_sync<3, true, 64>)
-                     : F == 128 ? reinterpret_cast<const void*>(&k_sync<3, true, 128>)
-                     : F == 256 ? reinterpret_cast<const void*>(&k_sync<3, true, 256>)
-                                : reinterpret_cast<const void*>(&k_sync<3, true, 512>);
-    HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-#ifdef SYNC_STAMPS
-    HIPCHK(h, g_stamp_buf.ensure(nseg * 16 * sizeof(unsigned long long)));
-    HIPCHK(h, hipMemsetAsync(g_stamp_buf.p, 0, nseg * 16 * sizeof(unsigned long long), h->stream));
-    sp.stamps = g_stamp_buf.as<unsigned long long>();
-#endif
-    void* args[] = {&sp, &fp};
-    h->prof.begin(OFDM_K_FRONT, h->stream);
-    HIPCHK(h, hipLaunchKernel(fn, dim3((unsigned)nseg), dim3(SYNC_THREADS), args, shm, h->stream));
-    h->prof.end(h->stream);
-    HIPCHK(h, hipGetLastError());
-#ifdef SYNC_STAMPS
-    { int rs_ = sync_stamps_report(h, sp.stamps, nseg, sp.tiles_per_seg); if (rs_) return rs_; }
-#endif
-    rx.front_done = true;
-  } else {
-    // ---- channel filter: x -> y (streaming) ------------------------------------------------------
-    const uint64_t bpr = 256 / (F / 8);
-    const uint64_t nblk = (nsamples + (uint64_t)fp.goff + (uint64_t)fp.B - 1) / (uint64_t)fp.B;
-    fp.nrounds = (nblk + bpr - 1) / bpr;
-    const size_t fsh = (size_t)256 * 9 * sizeof(c32);  // 256/(F/8) transforms x (F + F/8) points
-    const unsigned fgrid = (unsigned)std::min<uint64_t>(fp.nrounds, 256ull * 8ull * 4ull);
-    h->prof.begin(OFDM_K_FILTER, h->stream);
-    switch (F) {
-      case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<64>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 128: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<128>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 256: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<256>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 512: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<512>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 1024: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<1024>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      default: FAIL(h, OFDM_E_INVAL, "unsupported channel filter transform length");
-    }
-    h->prof.end(h->stream);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int rc = front_fused(h) ? launch_front(h, fp, nsamples) : launch_filter(h, fp, nsamples)) return rc;
   if (!h->sense.rx_on) {
     rx_note_input(h, iq, nsamples);
     HIPCHK(h, hipEventRecord(h->ev_rx_in, h->stream));
@@ -364,95 +377,145 @@ extern "C" int ofdm_rx_submit(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamp
 }
 
 // ------------------------------------------------------------------------------------
-// SYNC = "pn" (ofdm_receiver.py~:97-101): channel filter, Schmidl-Cox metric, peak detector.  Leaves the timing
-// flags and P at the flags in rx.peaks / rx.peak_P.  *done: the call is complete (no flag and no carried history).
+// One ofdm_rx call: the caller's arguments and what its stages hand to each other.
 // ------------------------------------------------------------------------------------
-static int rx_flags_pn(ofdm_handle* h, const c32* d_x, uint64_t nsamples, ofdm_stats* stats, uint64_t* npeaks_out, bool* done) {
+struct RxCall {
+  ofdm_handle* h;
+  const ofdm_c32* iq;  // the arguments of ofdm_rx, in its order
+  uint64_t nsamples;
+  uint8_t* payload_out;
+  uint64_t payload_cap;
+  uint64_t* payload_off;
+  uint32_t* payload_len;
+  uint8_t* crc_ok;
+  int max_pkts;
+  int* npkt;
+  ofdm_stats* stats;
+  const c32* d_x = nullptr;  // the input on the device
+  bool fixed = false;        // SYNC "fixed"
+  bool done = false;         // a stage found nothing left to do (no flag, no frame)
+  // Count path.  dyn: the frame count (flags the sampler accepts) and the packet count stay on the device (DynFrames),
+  // dependent launches are sized by their upper bound npeaks and leave early, and the call has two host round trips
+  // (flag count, final) instead of four.  Probes and the chunked-stream splice need the counts on the host as they go.
+  bool dyn = false;
+  uint64_t npeaks = 0, nforced = 0;  // timing flags; those of them a chunked stream's history supplied
+  // the counter block as rx_read_counts decoded it last (dyn: n_lo = 0, nframes = npeaks are bounds until the final one)
+  uint64_t n_lo = 0, nframes = 0, nsym = 0, npk = 0, nbytes = 0, rawtot = 0;
+  uint64_t npk_ub = 0;  // packets the outputs are sized for
+  DynFrames dynf;
+  DemodParams dq;  // (zero from the call's start; rx_frames puts the NCO's reference line in, make_demod_params the rest)
+  DeframeParams fq;
+  CsiRows csi_fr = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_pay = nullptr;  // where the deframer writes: the caller's device buffer, or the staging buffer
+};
+
+static uint64_t* rx_ctr(ofdm_handle* h) { return h->rx.counters.as<uint64_t>(); }
+
+// The one read-back and decoding of the counter block (slots no kernel has written yet read zero): frames the sampler
+// accepted, their symbols, packets and payload bytes the deframer counted.  A host round trip.
+static int rx_read_counts(RxCall& c) {
+  ofdm_handle* h = c.h;
   RxState& rx = h->rx;
-  const int T = SYNC_TILE;
-  *done = false;
-  // ---- sync pass ---------------------------------------------------------------------
-  const uint64_t ntiles = (nsamples + T - 1) / T;
-  bool cap_full = false;
-  bool sense_queued = false;
-  SyncParams sp;
-  {
-    int rcs = sync_params(h, nsamples, false, &sp);
-    if (rcs != OFDM_OK) return rcs;
+  uint64_t hc[CT_COUNT];
+  HIPCHK(h, hipMemcpyAsync(hc, rx.counters.p, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  c.n_lo = hc[CT_NLO] & 0xFFFFFFFFull;
+  c.nframes = c.npeaks - c.n_lo - (hc[CT_NHI] & 0xFFFFFFFFull);
+  c.nsym = hc[CT_NSYM];
+  c.npk = hc[CT_KEYTOT] >> 40;
+  c.nbytes = hc[CT_KEYTOT] & ((1ull << 40) - 1);
+  c.rawtot = hc[CT_RAWTOT];
+  rx.nframes = c.nframes;
+  rx.j0 = c.n_lo;
+  rx.nsym_total = c.nsym;
+  if (c.stats) {
+    c.stats->frames = c.nframes;
+    c.stats->symbols = c.nsym;
+    c.stats->headers_ok = hc[CT_DEFR + 0];
+    c.stats->chained_frames = hc[CT_DEFR + 3];
+    c.stats->overflow = hc[CT_OVERFLOW] & 0xFFFFFFFFull;
   }
-  const int tiles_per_seg = sp.tiles_per_seg;
-  const uint64_t nseg = (ntiles + tiles_per_seg - 1) / tiles_per_seg;
-  uint64_t* ctr = rx.counters.as<uint64_t>();
-  float* d_metric = sp.metric_tap;
-  if (!rx.front_done) {  // (else the input stage -- rx_submit_impl -- has queued it already)
-    int rcs = launch_sync(h, sp);
-    if (rcs != OFDM_OK) return rcs;
-  }
-  (void)nseg;
-  const uint64_t egrid = std::min<uint64_t>(ntiles, 256ull * 8ull), egrid_small = std::min<uint64_t>(ntiles, 256ull * 16ull);
-retry_sync:
+  return OFDM_OK;
+}
+
+// the one capacity check, on decoded counts: *npkt tells the caller how many packets there are
+static int rx_check_capacity(RxCall& c) {
+  if (c.npk <= (uint64_t)c.max_pkts && c.nbytes <= c.payload_cap) return OFDM_OK;
+  *c.npkt = (int)std::min<uint64_t>(c.npk, 0x7FFFFFFF);
+  FAIL(c.h, OFDM_E_CAPACITY, "payload_out / max_pkts too small for the packets found");
+}
+
+// ------------------------------------------------------------------------------------
+// SYNC = "pn" (ofdm_receiver.py~:97-101): channel filter, Schmidl-Cox metric, peak detector.  Leaves the timing
+// flags and P at the flags in rx.peaks / rx.peak_P.
+// ------------------------------------------------------------------------------------
+static hipError_t launch_sync_exact(const void* fn, unsigned grid, size_t shmem, SyncParams sp, hipStream_t s) {
+  void* args[] = {&sp};
+  return hipLaunchKernel(fn, dim3(grid), dim3(SYNC_THREADS), args, shmem, s);
+}
+
+// the tiles the pre-selection fired in: fixed-point metric, candidate pieces, detector summary
+static int rx_sync_exact(RxCall& c, SyncParams& sp, bool cap_full) {
+  ofdm_handle* h = c.h;
   if (cap_full) {
     // Second attempt after a candidate / piece overflow: storage for every sample.  The pre-selection's results (the
     // records, the summaries of the tiles without a range) stand; only k_sync_exact and the detector run again.
-    int rcs = sync_params(h, nsamples, true, &sp);
+    int rcs = sync_params(h, c.nsamples, true, &sp);
     if (rcs != OFDM_OK) return rcs;
-    ctr = rx.counters.as<uint64_t>();
+    uint64_t* ctr = rx_ctr(h);
     HIPCHK(h, hipMemsetAsync(ctr + CT_CAND, 0, 2 * sizeof(uint64_t), h->stream));     // CT_CAND, CT_OVERFLOW
     HIPCHK(h, hipMemsetAsync(ctr + CT_NPEAKS, 0, sizeof(uint64_t), h->stream));
     HIPCHK(h, hipMemsetAsync(ctr + CT_PIECES, 0, 2 * sizeof(uint64_t), h->stream));   // CT_PIECES, CT_STASH
   }
-  // the tiles the pre-selection fired in: fixed-point metric, candidate pieces, detector summary
-  h->prof.begin(OFDM_K_EXACT, h->stream);
+  const unsigned egrid = (unsigned)std::min<uint64_t>(sp.ntiles, 256ull * 8ull);
+  const unsigned egrid_small = (unsigned)std::min<uint64_t>(sp.ntiles, 256ull * 16ull);
   {
-    const size_t esh = exact_lds_layout(sp.CP, T).total, esh_small = exact_lds_layout(sp.CP, sp.exact_small).total;
-    const bool keep = sp.D >= 2048;  // (deltas kept in registers between the two passes: pays for long symbols only)
-    const void* fbig = keep ? reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, true>)
-                            : reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, false>);
+    ProfScope span(h->prof, OFDM_K_EXACT, h->stream);
+    const size_t esh = exact_lds_layout(sp.CP, SYNC_TILE).total, esh_small = exact_lds_layout(sp.CP, sp.exact_small).total;
+    // (deltas kept in registers between the two passes: pays for long symbols only)
+    const void* fbig = sp.D >= 2048 ? reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, true>)
+                                    : reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, false>);
     if (esh > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(fbig, hipFuncAttributeMaxDynamicSharedMemorySize, (int)esh));
     if (sp.exact_small > 0)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<WAVE, false>), dim3((unsigned)egrid_small), dim3(WAVE), esh_small, h->stream, sp);
-    if (keep)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<SYNC_THREADS, true>), dim3((unsigned)egrid), dim3(SYNC_THREADS), esh, h->stream, sp);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<SYNC_THREADS, false>), dim3((unsigned)egrid), dim3(SYNC_THREADS), esh, h->stream, sp);
-    if (d_metric) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<WAVE, false>), dim3(egrid_small), dim3(WAVE), esh_small, h->stream, sp);
+    HIPCHK(h, launch_sync_exact(fbig, egrid, esh, sp, h->stream));
+    if (sp.metric_tap) {
       // the metric tap: the normative metric of EVERY sample, in a pass of its own that writes nothing else -- the
       // detector works from exactly what it works from without the tap
       SyncParams tp = sp;
       tp.tap_only = 1;
-      if (keep)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<SYNC_THREADS, true>), dim3((unsigned)egrid), dim3(SYNC_THREADS), esh, h->stream, tp);
-      else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sync_exact<SYNC_THREADS, false>), dim3((unsigned)egrid), dim3(SYNC_THREADS), esh, h->stream, tp);
+      HIPCHK(h, launch_sync_exact(fbig, egrid, esh, tp, h->stream));
     }
   }
-  h->prof.end(h->stream);
   HIPCHK(h, hipGetLastError());
 #ifdef SYNC_STAMPS
-  if (!rx.front_done) { int rs_ = sync_stamps_report(h, sp.stamps, nseg, tiles_per_seg); if (rs_) return rs_; }
+  if (!h->rx.front_done)
+    if (int rs = sync_stamps_report(h, sp.stamps, sync_nseg(sp), sp.tiles_per_seg)) return rs;
 #endif
+  return OFDM_OK;
+}
 
-  // ---- fused spectrum sensing (BASELINE config 5): same IQ buffer, second stream.  It starts
-  //      when k_sync has drained (both are VALU/LDS-bound: run side by side they only slow
-  //      each other) and runs beside the peak pass and the demodulator; joined at the end of ofdm_rx
-  if (h->sense.rx_on && !sense_queued) {
-    sense_queued = true;
-    SenseState& ss = h->sense;
-    HIPCHK(h, hipEventRecord(ss.ev_in, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(ss.side, ss.ev_in, 0));
-    int src = sense_enqueue(h, &ss.rx_cfg, d_x, nsamples, ss.side);
-    if (src != OFDM_OK) return src;
-    HIPCHK(h, hipEventRecord(ss.ev_out, ss.side));
-  }
+// fused spectrum sensing (BASELINE config 5): same IQ buffer, second stream.  It starts when k_sync has drained (both
+// are VALU/LDS-bound: run side by side they only slow each other) and runs beside the peak pass and the demodulator;
+// joined at the end of ofdm_rx
+static int rx_sense_fork(RxCall& c) {
+  ofdm_handle* h = c.h;
+  SenseState& ss = h->sense;
+  HIPCHK(h, hipEventRecord(ss.ev_in, h->stream));
+  HIPCHK(h, hipStreamWaitEvent(ss.side, ss.ev_in, 0));
+  int src = sense_enqueue(h, &ss.rx_cfg, c.d_x, c.nsamples, ss.side);
+  if (src != OFDM_OK) return src;
+  HIPCHK(h, hipEventRecord(ss.ev_out, ss.side));
+  return OFDM_OK;
+}
 
-  // ---- peak detector ----------------------------------------------------------------------
-  h->prof.begin(OFDM_K_PEAK, h->stream);
-  hipLaunchKernelGGL(k_avg_carry, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, h->stream, rx.tile_B.as<double>(),
-                     ntiles, nsamples, sp.dpow, rx.avg_in.as<double>());
+// (the stash and, with OFDM_TAP_RX_RUN_AVG, the run rows are sized by the caller)
+static PeakParams make_peak_params(ofdm_handle* h, const SyncParams& sp) {
+  RxState& rx = h->rx;
   PeakParams pp;
   memset(&pp, 0, sizeof(pp));
-  pp.ntiles = ntiles;
-  pp.nsamples = nsamples;
+  pp.ntiles = sp.ntiles;
+  pp.nsamples = sp.nsamples;
   pp.rise = h->cfg.peak_rise;
   pp.fall = h->cfg.peak_fall;
   pp.alpha = h->cfg.peak_alpha;
@@ -465,47 +528,45 @@ retry_sync:
   pp.cand_P = rx.cand_P.as<c32>();
   pp.counts = rx.counts.as<uint32_t>();
   pp.offsets = rx.offsets.as<uint32_t>();
-  HIPCHK(h, rx.stash_peaks.ensure(ntiles * PEAK_STASH * sizeof(uint64_t)));
-  HIPCHK(h, rx.stash_P.ensure(ntiles * PEAK_STASH * sizeof(c32)));
   pp.stash_peaks = rx.stash_peaks.as<uint64_t>();
   pp.stash_P = rx.stash_P.as<c32>();
-  pp.stash_overflow = reinterpret_cast<unsigned int*>(ctr + CT_STASH);
+  pp.stash_overflow = reinterpret_cast<unsigned int*>(rx_ctr(h) + CT_STASH);
+  if (h->tap_mask & (1u << OFDM_TAP_RX_RUN_AVG)) pp.run_rows = rx.run_rows.as<double>();
+  return pp;
+}
+
+// The peak detector over the candidates of this attempt; the flag count is the call's first host round trip.
+// *overflow: non-zero when the candidate / piece storage did not suffice.  c.done: no flag and no carried history.
+static int rx_flags_pn(RxCall& c, const SyncParams& sp, uint64_t* overflow) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  const uint64_t ntiles = sp.ntiles;
+  const unsigned grid = (unsigned)((ntiles + 255) / 256);
+  uint64_t* ctr = rx_ctr(h);
   // OFDM_TAP_RX_RUN_AVG: one row per piece slot; slots no interval starts in stay NaN (compacted when read)
-  uint64_t run_cap = 0;
-  if (h->tap_mask & (1u << OFDM_TAP_RX_RUN_AVG)) {
-    run_cap = sp.piece_cap;
-    HIPCHK(h, rx.run_rows.ensure(run_cap * 2 * sizeof(double)));
-    HIPCHK(h, hipMemsetAsync(rx.run_rows.p, 0xFF, run_cap * 2 * sizeof(double), h->stream));  // NaN
-    pp.run_rows = rx.run_rows.as<double>();
-  }
-  const uint64_t nslots = ntiles;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_peak<false>), dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, h->stream, pp);
+  const uint64_t run_cap = (h->tap_mask & (1u << OFDM_TAP_RX_RUN_AVG)) ? sp.piece_cap : 0;
+  HIPCHK(h, rx.stash_peaks.ensure(ntiles * PEAK_STASH * sizeof(uint64_t)));
+  HIPCHK(h, rx.stash_P.ensure(ntiles * PEAK_STASH * sizeof(c32)));
+  if (run_cap) HIPCHK(h, rx.run_rows.ensure(run_cap * 2 * sizeof(double)));
+  PeakParams pp = make_peak_params(h, sp);
+  hipLaunchKernelGGL(k_avg_carry, dim3(grid), dim3(256), 0, h->stream, rx.tile_B.as<double>(), ntiles, c.nsamples, sp.dpow,
+                     rx.avg_in.as<double>());
+  if (run_cap) HIPCHK(h, hipMemsetAsync(rx.run_rows.p, 0xFF, run_cap * 2 * sizeof(double), h->stream));  // NaN
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_peak<false>), dim3(grid), dim3(256), 0, h->stream, pp);
   HIPCHK(h, hipGetLastError());
-  int rc = dev_excl_scan<uint32_t>(h, rx.counts.as<uint32_t>(), nslots, rx.offsets.as<uint32_t>(),
+  int rc = dev_excl_scan<uint32_t>(h, rx.counts.as<uint32_t>(), ntiles, rx.offsets.as<uint32_t>(),
                                    reinterpret_cast<uint32_t*>(ctr + CT_NPEAKS));
   if (rc) return rc;
   uint64_t hc[CT_COUNT];
   HIPCHK(h, hipMemcpyAsync(hc, ctr, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (hc[CT_OVERFLOW] & 0xFFFFFFFFull) {
-    h->prof.end(h->stream);
-    if (!cap_full) {
-      cap_full = true;  // once more with room for every sample
-      goto retry_sync;
-    }
-    if (stats) stats->overflow = hc[CT_OVERFLOW] & 0xFFFFFFFFull;
-    h->prof.collect();
-    FAIL(h, OFDM_E_OVERFLOW, "candidate / piece buffer exhausted");
-  }
+  if ((*overflow = hc[CT_OVERFLOW] & 0xFFFFFFFFull)) return OFDM_OK;
   rx.run_slots = std::min<uint64_t>(hc[CT_PIECES], run_cap);
-  uint64_t npeaks = hc[CT_NPEAKS] & 0xFFFFFFFFull;
-  rx.npeaks = npeaks;
-  if (stats) stats->peaks = npeaks;
+  const uint64_t npeaks = hc[CT_NPEAKS] & 0xFFFFFFFFull;
+  c.npeaks = rx.npeaks = npeaks;
+  if (c.stats) c.stats->peaks = npeaks;
   if (npeaks == 0 && !(rx.nco_ref_on && !rx.hist_flags.empty())) {
-    h->prof.end(h->stream);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->prof.collect();
-    *done = true;
+    c.done = true;
     return OFDM_OK;
   }
   HIPCHK(h, rx.peaks.ensure(std::max<uint64_t>(npeaks, 1) * sizeof(uint64_t)));
@@ -514,12 +575,11 @@ retry_sync:
   pp.peak_P = rx.peak_P.as<c32>();
   if (npeaks > 0) {
     if (hc[CT_STASH] & 0xFFFFFFFFull)  // some tile raised more flags than the count pass stashes: run the machine again
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_peak<true>), dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, h->stream, pp);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_peak<true>), dim3(grid), dim3(256), 0, h->stream, pp);
     else
-      hipLaunchKernelGGL(k_peak_compact, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, h->stream, pp);
+      hipLaunchKernelGGL(k_peak_compact, dim3(grid), dim3(256), 0, h->stream, pp);
     HIPCHK(h, hipGetLastError());
   }
-  *npeaks_out = npeaks;
   return OFDM_OK;
 }
 
@@ -533,119 +593,48 @@ __global__ void __launch_bounds__(256) k_fixed_flags(uint64_t npeaks, uint64_t f
   peak_P[k] = mk(0.f, 0.f);
 }
 
-static int rx_flags_fixed(ofdm_handle* h, uint64_t nsamples, ofdm_stats* stats, uint64_t* npeaks_out, bool* done) {
+// the flag count of SYNC "fixed" (known without the device) and cleared counters; c.done: the capture holds no symbol
+static int rx_fixed_count(RxCall& c) {
+  ofdm_handle* h = c.h;
   RxState& rx = h->rx;
-  *done = false;
-  const uint64_t L = (uint64_t)h->L, period = (uint64_t)h->cfg.fixed_nsymbols * L;
-  const uint64_t npeaks = nsamples >= L ? (nsamples - L) / period + 1 : 0;
-  rx.npeaks = npeaks;
-  if (stats) stats->peaks = npeaks;
+  const uint64_t L = (uint64_t)h->L;
+  c.npeaks = rx.npeaks = c.nsamples >= L ? (c.nsamples - L) / ((uint64_t)h->cfg.fixed_nsymbols * L) + 1 : 0;
+  if (c.stats) c.stats->peaks = c.npeaks;
   HIPCHK(h, rx.counters.ensure(CT_COUNT * sizeof(uint64_t)));
   HIPCHK(h, hipMemsetAsync(rx.counters.p, 0, CT_COUNT * sizeof(uint64_t), h->stream));
-  if (npeaks == 0) {
+  if (c.npeaks == 0) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    *done = true;
-    return OFDM_OK;
+    c.done = true;
   }
-  HIPCHK(h, rx.peaks.ensure(npeaks * sizeof(uint64_t)));
-  HIPCHK(h, rx.peak_P.ensure(npeaks * sizeof(c32)));
-  h->prof.begin(OFDM_K_PEAK, h->stream);  // (the bookkeeping kernels that follow close the span)
-  hipLaunchKernelGGL(k_fixed_flags, dim3((unsigned)((npeaks + 255) / 256)), dim3(256), 0, h->stream, npeaks, L - 1, period,
-                     rx.peaks.as<uint64_t>(), rx.peak_P.as<c32>());
-  HIPCHK(h, hipGetLastError());
-  *npeaks_out = npeaks;
   return OFDM_OK;
 }
 
-static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_t* payload_out, uint64_t payload_cap,
-                   uint64_t* payload_off, uint32_t* payload_len, uint8_t* crc_ok, int max_pkts, int* npkt, ofdm_stats* stats);
-
-extern "C" int ofdm_rx(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_t* payload_out, uint64_t payload_cap,
-                       uint64_t* payload_off, uint32_t* payload_len, uint8_t* crc_ok, int max_pkts, int* npkt,
-                       ofdm_stats* stats) {
-  if (!h) return OFDM_E_INVAL;
-  h->rx.in_event_at_end = false;
-  const int rc = rx_impl(h, iq, nsamples, payload_out, payload_cap, payload_off, payload_len, crc_ok, max_pkts, npkt, stats);
-  h->rx.sub_valid = false;
-  h->rx.sub_hold = false;
-  // the fused sensor works on its own stream beside the peak pass and the demodulator: joined here, before the caller
-  // gets its input buffer back
-  if (h->sense.rx_on && h->sense.side) {
-    (void)hipStreamSynchronize(h->sense.side);
-    h->prof.collect();
-  }
-  if (h->rx.in_event_at_end) {  // the input was read to the end of the call (SYNC "fixed", fused sensing)
-    h->rx.in_event_at_end = false;
-    rx_note_input(h, iq, nsamples);
-    if (hipEventRecord(h->ev_rx_in, h->stream) == hipSuccess) h->rx_in_pending = true;
-  }
-  return rc;
+static int rx_flags_fixed(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  HIPCHK(h, rx.peaks.ensure(c.npeaks * sizeof(uint64_t)));
+  HIPCHK(h, rx.peak_P.ensure(c.npeaks * sizeof(c32)));
+  hipLaunchKernelGGL(k_fixed_flags, dim3((unsigned)((c.npeaks + 255) / 256)), dim3(256), 0, h->stream, c.npeaks, (uint64_t)h->L - 1,
+                     (uint64_t)h->cfg.fixed_nsymbols * (uint64_t)h->L, rx.peaks.as<uint64_t>(), rx.peak_P.as<c32>());
+  HIPCHK(h, hipGetLastError());
+  return OFDM_OK;
 }
 
-static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_t* payload_out, uint64_t payload_cap,
-                   uint64_t* payload_off, uint32_t* payload_len, uint8_t* crc_ok, int max_pkts, int* npkt, ofdm_stats* stats) {
-  if (!h) return OFDM_E_INVAL;
-  if (!npkt || max_pkts < 0 || (nsamples && !iq)) FAIL(h, OFDM_E_INVAL, "null argument");
-  if (max_pkts > 0 && (!payload_off || !payload_len || !crc_ok)) FAIL(h, OFDM_E_INVAL, "null metadata array");
-  *npkt = 0;
-  if (payload_off) payload_off[0] = 0;
-  if (stats) memset(stats, 0, sizeof(*stats));
+// Chunked stream: flags up to trust_after are the ones earlier calls settled, not what this call detects in its
+// unsettled overlap.  Splice on the host (a few hundred flags; this path is not timed).  c.done: no flag either way.
+static int rx_splice(RxCall& c) {
+  ofdm_handle* h = c.h;
   RxState& rx = h->rx;
-  rx.nsamples = nsamples;
-  rx.npeaks = rx.nframes = rx.j0 = rx.nsym_total = rx.raw_tap_bytes = rx.run_slots = 0;
-  rx.last_pos.clear();
-  rx.last_swallowed.clear();
-  rx.last_quality.clear();
-  rx.quality_valid = rx.quality_on;
-  rx.csi_valid = rx.csi_on;
-  rx.csi_n = 0;
-  rx.csi_ok.clear();
-  if (stats) stats->samples = nsamples;
-  if (nsamples == 0) return OFDM_OK;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  const int N = h->N, CP = h->CP, L = h->L;
-
-  // ---- input stage (already queued when the caller went through ofdm_rx_submit) -------------------
-  const c32* d_x = nullptr;
-  if (rx.sub_valid && rx.sub_iq == iq && rx.sub_n == nsamples) {
-    d_x = rx.sub_dx;
-    rx.in_event_at_end = h->cfg.sync_mode != OFDM_SYNC_PN || h->sense.rx_on;
-  } else {
-    int rcs = rx_submit_impl(h, iq, nsamples, &d_x);
-    if (rcs != OFDM_OK) return rcs;
-  }
-  rx.sub_valid = false;
-
-  // ---- timing flags ---------------------------------------------------------------------
-  const bool fixed = h->cfg.sync_mode == OFDM_SYNC_FIXED;
-  // chan_filt: the filtered stream, or -- SYNC "fixed": gr.multiply_const_cc(1.0) -- the input itself
-  rx.y_ptr = fixed ? d_x : rx.y.as<c32>();
-  uint64_t npeaks = 0;
-  {
-    bool done = false;
-    int rcf = fixed ? rx_flags_fixed(h, nsamples, stats, &npeaks, &done) : rx_flags_pn(h, d_x, nsamples, stats, &npeaks, &done);
-    if (rcf != OFDM_OK || done) return rcf;
-  }
-  uint64_t* ctr = rx.counters.as<uint64_t>();
-  uint64_t hc[CT_COUNT];
-  int rc = OFDM_OK;
-  uint64_t nforced = 0;
-  if (rx.nco_ref_on) {
-    // chunked stream: flags up to trust_after are the ones earlier calls settled, not what this call
-    // detects in its unsettled overlap.  Splice on the host (a few hundred flags; this path is not timed).
-    std::vector<uint64_t> hp(npeaks);
-    if (npeaks) HIPCHK(h, hipMemcpyAsync(hp.data(), rx.peaks.p, npeaks * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    uint64_t kdrop = 0;
-    while (kdrop < npeaks && (int64_t)hp[kdrop] <= rx.nco_trust_after) kdrop++;
-    const uint64_t m = rx.hist_flags.size(), np2 = m + npeaks - kdrop;
-    if (np2 == 0) {
-      rx.npeaks = 0;
-      if (stats) stats->peaks = 0;
-      h->prof.end(h->stream);
-      h->prof.collect();
-      return OFDM_OK;
-    }
+  if (!rx.nco_ref_on) return OFDM_OK;
+  const uint64_t npeaks = c.npeaks;
+  std::vector<uint64_t> hp(npeaks);
+  if (npeaks) HIPCHK(h, hipMemcpyAsync(hp.data(), rx.peaks.p, npeaks * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  uint64_t kdrop = 0;
+  while (kdrop < npeaks && (int64_t)hp[kdrop] <= rx.nco_trust_after) kdrop++;
+  const uint64_t m = rx.hist_flags.size(), np2 = m + npeaks - kdrop;
+  c.done = np2 == 0;
+  if (!c.done) {
     HIPCHK(h, rx.peaks2.ensure(np2 * sizeof(uint64_t)));
     HIPCHK(h, rx.peak_P2.ensure(np2 * sizeof(c32)));
     HIPCHK(h, rx.fstep.ensure(std::max<uint64_t>(m, 1) * sizeof(double)));
@@ -663,30 +652,25 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors may change after this call
     std::swap(rx.peaks, rx.peaks2);
     std::swap(rx.peak_P, rx.peak_P2);
-    nforced = m;
-    npeaks = np2;
-    rx.npeaks = npeaks;
-    if (stats) stats->peaks = npeaks;
+    c.nforced = m;
   }
-  HIPCHK(h, rx.angle.ensure(npeaks * sizeof(float)));
-  HIPCHK(h, rx.step.ensure(npeaks * sizeof(double)));
-  HIPCHK(h, rx.inc.ensure(npeaks * sizeof(uint64_t)));
-  HIPCHK(h, rx.inc_acc.ensure(npeaks * sizeof(uint64_t)));
-  HIPCHK(h, rx.Phi_u.ensure(npeaks * sizeof(uint64_t)));
-  HIPCHK(h, rx.Phi.ensure(npeaks * sizeof(double)));
-  HIPCHK(h, rx.K.ensure(npeaks * sizeof(uint32_t)));
-  HIPCHK(h, rx.nsym.ensure(npeaks * sizeof(uint64_t)));
-  HIPCHK(h, rx.sym_base.ensure(npeaks * sizeof(uint64_t)));
+  c.npeaks = rx.npeaks = np2;
+  if (c.stats) c.stats->peaks = np2;
+  return OFDM_OK;
+}
 
-  // ---- sample & hold, NCO, sampler ----------------------------------------------------------
+static FramesParams make_frames_params(const RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  uint64_t* ctr = rx_ctr(h);
   FramesParams fp;
   memset(&fp, 0, sizeof(fp));
-  fp.npeaks = npeaks;
-  fp.nsamples = nsamples;
-  fp.N = N;
-  fp.L = L;
+  fp.npeaks = c.npeaks;
+  fp.nsamples = c.nsamples;
+  fp.N = h->N;
+  fp.L = h->L;
   fp.timeout = h->cfg.sampler_timeout;
-  fp.sens = (float)(-2.0 / (double)N);  // nco_sensitivity, ofdm_receiver.py~:98
+  fp.sens = (float)(-2.0 / (double)h->N);  // nco_sensitivity, ofdm_receiver.py~:98
   fp.peaks = rx.peaks.as<uint64_t>();
   fp.peak_P = rx.peak_P.as<c32>();
   fp.angle = rx.angle.as<float>();
@@ -696,74 +680,96 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   fp.nsym = rx.nsym.as<uint64_t>();
   fp.n_lo = reinterpret_cast<unsigned int*>(ctr + CT_NLO);
   fp.n_hi = reinterpret_cast<unsigned int*>(ctr + CT_NHI);
-  fp.nforced = nforced;
+  fp.nforced = c.nforced;
   fp.forced_step = rx.fstep.as<double>();
-  fp.fixed_on = fixed ? 1 : 0;
+  fp.fixed_on = c.fixed ? 1 : 0;
   fp.fixed_angle = h->cfg.fixed_freq_offset;
+  return fp;
+}
+
+// sample & hold, NCO, sampler: per flag the frequency step, the NCO phase, the symbols its frame takes
+static int rx_frames(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  const uint64_t npeaks = c.npeaks;
+  const unsigned grid = (unsigned)((npeaks + 255) / 256);
+  HIPCHK(h, rx.angle.ensure(npeaks * sizeof(float)));
+  HIPCHK(h, rx.step.ensure(npeaks * sizeof(double)));
+  HIPCHK(h, rx.inc.ensure(npeaks * sizeof(uint64_t)));
+  HIPCHK(h, rx.inc_acc.ensure(npeaks * sizeof(uint64_t)));
+  HIPCHK(h, rx.Phi_u.ensure(npeaks * sizeof(uint64_t)));
+  HIPCHK(h, rx.Phi.ensure(npeaks * sizeof(double)));
+  HIPCHK(h, rx.K.ensure(npeaks * sizeof(uint32_t)));
+  HIPCHK(h, rx.nsym.ensure(npeaks * sizeof(uint64_t)));
+  HIPCHK(h, rx.sym_base.ensure(npeaks * sizeof(uint64_t)));
+  const FramesParams fp = make_frames_params(c);
   // the NCO line in force before the first flag: none (phase 0), the one a chunked stream carries in, or -- SYNC
   // "fixed", whose frequency input is constant from the first sample on -- the line through (sample 0, phase 0)
-  const bool ref_on = rx.nco_ref_on || (fixed && h->cfg.fixed_freq_offset != 0.0f);
-  const int64_t ref_peak = rx.nco_ref_on ? rx.nco_ref_peak : 0;
   const uint64_t ref_u = rx.nco_ref_on ? rx.nco_ref_u : 0ull;
-  const double ref_step = rx.nco_ref_on ? rx.nco_ref_step : (double)(fp.sens * h->cfg.fixed_freq_offset);
-  hipLaunchKernelGGL(k_frames, dim3((unsigned)((npeaks + 255) / 256)), dim3(256), 0, h->stream, fp);
+  c.dq.ref_on = (rx.nco_ref_on || (c.fixed && h->cfg.fixed_freq_offset != 0.0f)) ? 1 : 0;
+  c.dq.ref_peak = rx.nco_ref_on ? rx.nco_ref_peak : 0;
+  c.dq.ref_phi = nco_radians(ref_u);
+  c.dq.ref_step = rx.nco_ref_on ? rx.nco_ref_step : (double)(fp.sens * h->cfg.fixed_freq_offset);
+  hipLaunchKernelGGL(k_frames, dim3(grid), dim3(256), 0, h->stream, fp);
   HIPCHK(h, hipGetLastError());
-  rc = dev_excl_scan<uint64_t>(h, rx.inc.as<uint64_t>(), npeaks, rx.inc_acc.as<uint64_t>(), (uint64_t*)nullptr);
+  int rc = dev_excl_scan<uint64_t>(h, rx.inc.as<uint64_t>(), npeaks, rx.inc_acc.as<uint64_t>(), (uint64_t*)nullptr);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_nco_phase, dim3((unsigned)((npeaks + 255) / 256)), dim3(256), 0, h->stream, rx.peaks.as<uint64_t>(),
-                     rx.inc_acc.as<uint64_t>(), npeaks, ref_on ? 1 : 0, ref_peak, ref_u, ref_step,
-                     rx.Phi_u.as<uint64_t>(), rx.Phi.as<double>());
+  hipLaunchKernelGGL(k_nco_phase, dim3(grid), dim3(256), 0, h->stream, rx.peaks.as<uint64_t>(), rx.inc_acc.as<uint64_t>(), npeaks,
+                     c.dq.ref_on, c.dq.ref_peak, ref_u, c.dq.ref_step, rx.Phi_u.as<uint64_t>(), rx.Phi.as<double>());
   HIPCHK(h, hipGetLastError());
-  rc = dev_excl_scan<uint64_t>(h, rx.nsym.as<uint64_t>(), npeaks, rx.sym_base.as<uint64_t>(), ctr + CT_NSYM);
-  if (rc) return rc;
-  h->prof.end(h->stream);
-  // From here on nothing the HOST needs is known before the end of the call -- unless a probe or the chunked-stream
-  // splice asks for it: the frame count (flags the sampler accepts) and the packet count then stay on the device
-  // (DynFrames), dependent launches are sized by their upper bound npeaks and leave early, and the call has two host
-  // round trips (flag count, final) instead of four.
-  const uint32_t tapm = h->tap_mask;
-  const bool dyn = !rx.nco_ref_on && !(tapm & ((1u << OFDM_TAP_RX_SIGMIX) | (1u << OFDM_TAP_RX_NCO) | (1u << OFDM_TAP_RX_FFT) |
-                                               (1u << OFDM_TAP_RX_ACQ) | (1u << OFDM_TAP_RX_SINK) | (1u << OFDM_TAP_RX_SAMPLER) |
-                                               (1u << OFDM_TAP_RX_PACKETS))) && !getenv("OFDM_RX_SYNCS");
-  uint64_t n_lo = 0, nframes = npeaks, nsym = 0;  // (dyn: upper bounds until the final read-back)
-  if (!dyn) {
-    HIPCHK(h, hipMemcpyAsync(hc, ctr, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    n_lo = hc[CT_NLO] & 0xFFFFFFFFull;
-    const uint64_t n_hi = hc[CT_NHI] & 0xFFFFFFFFull;
-    nframes = npeaks - n_lo - n_hi;
-    nsym = hc[CT_NSYM];
-    rx.nframes = nframes;
-    rx.j0 = n_lo;
-    rx.nsym_total = nsym;
-    if (stats) {
-      stats->frames = nframes;
-      stats->symbols = nsym;
-    }
-    if (nframes == 0) {
-      h->prof.collect();
+  return dev_excl_scan<uint64_t>(h, rx.nsym.as<uint64_t>(), npeaks, rx.sym_base.as<uint64_t>(), rx_ctr(h) + CT_NSYM);
+}
+
+// Timing: flags -> chunked-stream splice -> frames / NCO / sampler, the last three under one detector span.  SYNC "pn"
+// runs k_sync_exact and the detector a second time, with room for every sample, when the sparse candidate storage
+// overflows (a carrier, a periodic sequence: legitimate input in which the reference simply finds no frame).
+static int rx_timing(RxCall& c) {
+  ofdm_handle* h = c.h;
+  SyncParams sp;
+  uint64_t overflow = 0;
+  int rc = c.fixed ? rx_fixed_count(c) : sync_params(h, c.nsamples, false, &sp);
+  if (rc || c.done) return rc;
+  // (a fused front end has queued the pre-selection already: the input stage, rx_submit_impl)
+  if (!c.fixed && !h->rx.front_done && (rc = launch_sync(h, sp))) return rc;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if (!c.fixed && (rc = rx_sync_exact(c, sp, attempt == 1))) return rc;
+    if (!c.fixed && attempt == 0 && h->sense.rx_on && (rc = rx_sense_fork(c))) return rc;
+    ProfScope span(h->prof, OFDM_K_PEAK, h->stream);
+    if ((rc = c.fixed ? rx_flags_fixed(c) : rx_flags_pn(c, sp, &overflow))) return rc;
+    if (overflow) continue;
+    if (c.done) {  // no flag: the span ends before the stream drains, so that the call's one collect() sees it complete
+      span.end();
+      HIPCHK(h, hipStreamSynchronize(h->stream));
       return OFDM_OK;
     }
+    if ((rc = rx_splice(c)) || c.done) return rc;
+    return rx_frames(c);
   }
-  DynFrames dynf;
-  dynf.lo = dyn ? reinterpret_cast<const unsigned int*>(ctr + CT_NLO) : nullptr;
-  dynf.hi = dyn ? reinterpret_cast<const unsigned int*>(ctr + CT_NHI) : nullptr;
-  dynf.npeaks = (uint32_t)npeaks;
+  if (c.stats) c.stats->overflow = overflow;
+  FAIL(h, OFDM_E_OVERFLOW, "candidate / piece buffer exhausted");
+}
 
-  // ---- demodulate every frame ------------------------------------------------------------------
-  HIPCHK(h, rx.res.ensure(nframes * sizeof(FrameResult)));
-  HIPCHK(h, rx.raw.ensure(nframes * (uint64_t)RAW_SLOT));
-  HIPCHK(h, rx.invalid.ensure(nframes));
-  HIPCHK(h, rx.chain_list.ensure(4096 * sizeof(uint32_t)));
-  HIPCHK(h, rx.key.ensure(nframes * sizeof(uint64_t)));
-  HIPCHK(h, rx.pos.ensure(nframes * sizeof(uint64_t)));
-  HIPCHK(h, hipMemsetAsync(rx.invalid.p, 0, nframes, h->stream));
-  DemodParams dq;
-  memset(&dq, 0, sizeof(dq));
-  dq.dyn = dynf;
-  dq.N = N;
-  dq.CP = CP;
-  dq.L = L;
+// four row arrays carved from one buffer, structure of arrays: eq | pre | err | ref, [rows][stride] each
+static size_t csi_bytes(uint64_t rows, uint64_t stride) { return rows * stride * (sizeof(c32) + 3 * sizeof(float)); }
+static CsiRows csi_carve(const DevBuf& b, uint64_t rows, uint64_t stride) {
+  const uint64_t cell = rows * stride;
+  CsiRows r;
+  r.eq = b.as<c32>();
+  r.pre = reinterpret_cast<float*>(r.eq + cell);
+  r.err = r.pre + cell;
+  r.ref = r.err + cell;
+  return r;
+}
+
+// parameters of the optimistic demodulator pass; link quality and channel state bring their per-frame workspaces
+static int make_demod_params(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  DemodParams& dq = c.dq;
+  dq.dyn = c.dynf;
+  dq.N = h->N;
+  dq.CP = h->CP;
+  dq.L = h->L;
   dq.occ = h->occ;
   dq.zl = h->zl;
   dq.nmap = h->nmap;
@@ -777,15 +783,10 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   memcpy(dq.sign_idx, h->sign_idx, 4);
   dq.sign_eps = h->sign_eps;
   dq.sign_bound = h->sign_bound;
-  dq.nsamples = nsamples;
-  dq.j0 = (uint32_t)n_lo;
-  dq.nframes = (uint32_t)nframes;
-  dq.npeaks = (uint32_t)npeaks;
-  dq.tap_mode = 0;
-  dq.ref_on = ref_on ? 1 : 0;
-  dq.ref_peak = ref_peak;
-  dq.ref_phi = nco_radians(ref_u);
-  dq.ref_step = ref_step;
+  dq.nsamples = c.nsamples;
+  dq.j0 = (uint32_t)c.n_lo;
+  dq.nframes = (uint32_t)c.nframes;
+  dq.npeaks = (uint32_t)c.npeaks;
   dq.y = rx.y_ptr;
   dq.peaks = rx.peaks.as<uint64_t>();
   dq.Phi = rx.Phi.as<double>();
@@ -802,113 +803,144 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   dq.res = rx.res.as<FrameResult>();
   dq.raw = rx.raw.as<uint8_t>();
   if (rx.quality_on) {
-    HIPCHK(h, rx.qual_frame.ensure(nframes * sizeof(FrameQuality)));
+    HIPCHK(h, rx.qual_frame.ensure(c.nframes * sizeof(FrameQuality)));
     dq.qual = rx.qual_frame.as<FrameQuality>();
   }
-  CsiRows csi_fr = {nullptr, nullptr, nullptr, nullptr};
   if (rx.csi_on) {
-    // per-frame rows, structure of arrays: eq | pre | err | ref, [nframes][stride] each
-    const uint64_t st = (uint64_t)((h->occ + 3) & ~3), cell = nframes * st;
-    HIPCHK(h, rx.csi_frame.ensure(cell * (sizeof(c32) + 3 * sizeof(float))));
-    csi_fr.eq = rx.csi_frame.as<c32>();
-    csi_fr.pre = reinterpret_cast<float*>(csi_fr.eq + cell);
-    csi_fr.err = csi_fr.pre + cell;
-    csi_fr.ref = csi_fr.err + cell;
-    rx.csi_stride = (int)st;
-    dq.csi_eq = csi_fr.eq;
-    dq.csi_pre = csi_fr.pre;
-    dq.csi_err = csi_fr.err;
-    dq.csi_ref = csi_fr.ref;
-    dq.csi_stride = (int)st;
+    rx.csi_stride = (h->occ + 3) & ~3;
+    HIPCHK(h, rx.csi_frame.ensure(csi_bytes(c.nframes, (uint64_t)rx.csi_stride)));
+    c.csi_fr = csi_carve(rx.csi_frame, c.nframes, (uint64_t)rx.csi_stride);  // per-frame rows
+    dq.csi_eq = c.csi_fr.eq;
+    dq.csi_pre = c.csi_fr.pre;
+    dq.csi_err = c.csi_fr.err;
+    dq.csi_ref = c.csi_fr.ref;
+    dq.csi_stride = rx.csi_stride;
   }
-  h->prof.begin(OFDM_K_DEMOD, h->stream);
-  rc = run_demod(h, dq);
-#ifdef SYNC_STAMPS
-  if (rc == OFDM_OK) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    unsigned long long st[16];
-    HIPCHK(h, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_demod_stamps), sizeof(st)));
-    const unsigned long long zero[16] = {0};
-    HIPCHK(h, hipMemcpyToSymbol(HIP_SYMBOL(g_demod_stamps), zero, sizeof(zero)));
-    const char* nm[8] = {"frame prologue", "derotation (+ sample wait)", "transform", "prefetch issue + spectrum to LDS", "frame acquisition",
-                         "demapper", "loop bookkeeping", "PLL, header, bytes"};
-    double tot = 0;
-    for (int k = 0; k < 8; k++) tot += (double)st[k];
-    fprintf(stderr, "[k_rx_demod stamps] s_memtime ticks summed over the workgroups' thread 0 (%.3e in all):\n", tot);
-    for (int k = 0; k < 8; k++) fprintf(stderr, "  %-34s %12.4e  %5.1f%%\n", nm[k], (double)st[k], 100.0 * (double)st[k] / (tot > 0 ? tot : 1));
-  }
-#endif
-  h->prof.end(h->stream);
-  if (rc) return rc;
+  return OFDM_OK;
+}
 
-  // ---- chains, deframing ---------------------------------------------------------------------------
-  h->prof.begin(OFDM_K_DEFRAME, h->stream);
-  hipLaunchKernelGGL(k_chain_collect, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, rx.res.as<FrameResult>(),
-                     (uint32_t)nframes, dynf, rx.chain_list.as<uint32_t>(), 4096u, reinterpret_cast<unsigned int*>(ctr + CT_CHAIN));
+#ifdef SYNC_STAMPS
+static int demod_stamps_report(ofdm_handle* h) {
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned long long st[16];
+  HIPCHK(h, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_demod_stamps), sizeof(st)));
+  const unsigned long long zero[16] = {0};
+  HIPCHK(h, hipMemcpyToSymbol(HIP_SYMBOL(g_demod_stamps), zero, sizeof(zero)));
+  const char* nm[8] = {"frame prologue", "derotation (+ sample wait)", "transform", "prefetch issue + spectrum to LDS", "frame acquisition",
+                       "demapper", "loop bookkeeping", "PLL, header, bytes"};
+  double tot = 0;
+  for (int k = 0; k < 8; k++) tot += (double)st[k];
+  fprintf(stderr, "[k_rx_demod stamps] s_memtime ticks summed over the workgroups' thread 0 (%.3e in all):\n", tot);
+  for (int k = 0; k < 8; k++) fprintf(stderr, "  %-34s %12.4e  %5.1f%%\n", nm[k], (double)st[k], 100.0 * (double)st[k] / (tot > 0 ? tot : 1));
+  return OFDM_OK;
+}
+#endif
+
+// demodulate every frame (dyn: every flag; the frames the sampler refused leave early)
+static int rx_demodulate(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  const uint64_t nframes = c.nframes;
+  HIPCHK(h, rx.res.ensure(nframes * sizeof(FrameResult)));
+  HIPCHK(h, rx.raw.ensure(nframes * (uint64_t)RAW_SLOT));
+  HIPCHK(h, rx.invalid.ensure(nframes));
+  HIPCHK(h, rx.chain_list.ensure(4096 * sizeof(uint32_t)));
+  HIPCHK(h, rx.key.ensure(nframes * sizeof(uint64_t)));
+  HIPCHK(h, rx.pos.ensure(nframes * sizeof(uint64_t)));
+  HIPCHK(h, hipMemsetAsync(rx.invalid.p, 0, nframes, h->stream));
+  int rc = make_demod_params(c);
+  if (rc) return rc;
+  ProfScope span(h->prof, OFDM_K_DEMOD, h->stream);
+  rc = run_demod(h, c.dq);
+#ifdef SYNC_STAMPS
+  if (rc == OFDM_OK) rc = demod_stamps_report(h);
+#endif
+  return rc;
+}
+
+// chains: frames swallowed by the packet of an earlier flag are marked invalid (a chunked stream brings the verdicts
+// of its settled frames: frame f is flag j0 + f of the spliced list)
+static int rx_chains(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  uint64_t* ctr = rx_ctr(h);
+  const uint32_t nframes = (uint32_t)c.nframes;
+  hipLaunchKernelGGL(k_chain_collect, dim3((nframes + 255) / 256), dim3(256), 0, h->stream, rx.res.as<FrameResult>(), nframes, c.dynf,
+                     rx.chain_list.as<uint32_t>(), 4096u, reinterpret_cast<unsigned int*>(ctr + CT_CHAIN));
   uint32_t npre = 0;
   std::vector<uint8_t> pre_host;
-  if (rx.nco_ref_on && nforced > rx.j0) {
-    // settled frames: frame f is flag j0 + f of the spliced list
-    npre = (uint32_t)std::min<uint64_t>(nforced - rx.j0, nframes);
-    pre_host.assign(rx.hist_swallowed.begin() + rx.j0, rx.hist_swallowed.begin() + rx.j0 + npre);
+  if (rx.nco_ref_on && c.nforced > c.n_lo) {
+    npre = (uint32_t)std::min<uint64_t>(c.nforced - c.n_lo, c.nframes);
+    pre_host.assign(rx.hist_swallowed.begin() + c.n_lo, rx.hist_swallowed.begin() + c.n_lo + npre);
     HIPCHK(h, rx.pre_inv.ensure(npre));
     HIPCHK(h, hipMemcpyAsync(rx.pre_inv.p, pre_host.data(), npre, hipMemcpyHostToDevice, h->stream));
   }
-  hipLaunchKernelGGL(k_chain_resolve, dim3(1), dim3(64), 0, h->stream, rx.res.as<FrameResult>(), (uint32_t)nframes, dynf,
+  hipLaunchKernelGGL(k_chain_resolve, dim3(1), dim3(64), 0, h->stream, rx.res.as<FrameResult>(), nframes, c.dynf,
                      rx.chain_list.as<uint32_t>(), 4096u, reinterpret_cast<const unsigned int*>(ctr + CT_CHAIN),
                      rx.invalid.as<uint8_t>(), reinterpret_cast<unsigned int*>(ctr + CT_OVERFLOW), rx.pre_inv.as<uint8_t>(), npre);
   HIPCHK(h, hipGetLastError());
   if (npre) HIPCHK(h, hipStreamSynchronize(h->stream));  // pre_host is read by the copy above
+  return OFDM_OK;
+}
 
-  if (tapm & ((1u << OFDM_TAP_RX_SIGMIX) | (1u << OFDM_TAP_RX_NCO))) {
+// debug taps of the mixer and of the demodulator's stages: the latter from a second, instrumented pass over the frames
+static int rx_tap_pass(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  const uint32_t tapm = h->tap_mask;
+  auto on = [&](int tap) { return (tapm >> tap) & 1u; };
+  const uint64_t nsamples = c.nsamples, nsym = c.nsym;
+  if (on(OFDM_TAP_RX_SIGMIX) || on(OFDM_TAP_RX_NCO)) {
     c32 *d_sm = nullptr, *d_nco = nullptr;
-    if (tapm & (1u << OFDM_TAP_RX_SIGMIX)) {
+    if (on(OFDM_TAP_RX_SIGMIX)) {
       HIPCHK(h, rx.tap_sigmix.ensure(nsamples * sizeof(c32)));
       d_sm = rx.tap_sigmix.as<c32>();
     }
-    if (tapm & (1u << OFDM_TAP_RX_NCO)) {
+    if (on(OFDM_TAP_RX_NCO)) {
       HIPCHK(h, rx.tap_nco.ensure(nsamples * sizeof(c32)));
       d_nco = rx.tap_nco.as<c32>();
     }
     hipLaunchKernelGGL(k_sigmix_tap, dim3((unsigned)((nsamples + 255) / 256)), dim3(256), 0, h->stream, rx.y_ptr, nsamples,
-                       rx.peaks.as<uint64_t>(), rx.Phi.as<double>(), rx.step.as<double>(), npeaks, dq.ref_on, dq.ref_peak,
-                       dq.ref_phi, dq.ref_step, d_sm, d_nco);
+                       rx.peaks.as<uint64_t>(), rx.Phi.as<double>(), rx.step.as<double>(), c.npeaks, c.dq.ref_on, c.dq.ref_peak,
+                       c.dq.ref_phi, c.dq.ref_step, d_sm, d_nco);
     HIPCHK(h, hipGetLastError());
   }
-  if (tapm & ((1u << OFDM_TAP_RX_FFT) | (1u << OFDM_TAP_RX_ACQ) | (1u << OFDM_TAP_RX_SINK) | (1u << OFDM_TAP_RX_SAMPLER))) {
-    DemodParams tq = dq;
-    tq.tap_mode = 1;
-    tq.qual = nullptr;  // (the records come from the optimistic pass)
-    tq.csi_eq = nullptr;  // (so do the channel-state rows)
-    tq.csi_pre = tq.csi_err = tq.csi_ref = nullptr;
-    if (tapm & (1u << OFDM_TAP_RX_SAMPLER)) {
-      HIPCHK(h, rx.tap_sampler.ensure(nsym * (uint64_t)N * sizeof(c32)));
-      tq.tap_sampler = rx.tap_sampler.as<c32>();
-    }
-    if (tapm & (1u << OFDM_TAP_RX_FFT)) {
-      HIPCHK(h, rx.tap_fft.ensure(nsym * (uint64_t)N * sizeof(c32)));
-      tq.tap_fft = rx.tap_fft.as<c32>();
-    }
-    if (tapm & (1u << OFDM_TAP_RX_ACQ)) {
-      HIPCHK(h, rx.tap_acq.ensure(nsym * (uint64_t)h->occ * sizeof(c32)));
-      tq.tap_acq = rx.tap_acq.as<c32>();
-    }
-    if (tapm & (1u << OFDM_TAP_RX_SINK)) {
-      HIPCHK(h, rx.tap_sink.ensure(nsym * (uint64_t)h->occ * sizeof(c32)));
-      HIPCHK(h, rx.tap_demapped.ensure(nsym));
-      HIPCHK(h, hipMemsetAsync(rx.tap_sink.p, 0, nsym * (uint64_t)h->occ * sizeof(c32), h->stream));
-      HIPCHK(h, hipMemsetAsync(rx.tap_demapped.p, 0, nsym, h->stream));
-      tq.tap_sink = rx.tap_sink.as<c32>();
-      tq.tap_demapped = rx.tap_demapped.as<uint8_t>();
-    }
-    rc = run_demod(h, tq);
-    if (rc) return rc;
+  if (!(on(OFDM_TAP_RX_FFT) || on(OFDM_TAP_RX_ACQ) || on(OFDM_TAP_RX_SINK) || on(OFDM_TAP_RX_SAMPLER))) return OFDM_OK;
+  DemodParams tq = c.dq;
+  tq.tap_mode = 1;
+  tq.qual = nullptr;  // (the records come from the optimistic pass)
+  tq.csi_eq = nullptr;  // (so do the channel-state rows)
+  tq.csi_pre = tq.csi_err = tq.csi_ref = nullptr;
+  if (on(OFDM_TAP_RX_SAMPLER)) {
+    HIPCHK(h, rx.tap_sampler.ensure(nsym * (uint64_t)h->N * sizeof(c32)));
+    tq.tap_sampler = rx.tap_sampler.as<c32>();
   }
+  if (on(OFDM_TAP_RX_FFT)) {
+    HIPCHK(h, rx.tap_fft.ensure(nsym * (uint64_t)h->N * sizeof(c32)));
+    tq.tap_fft = rx.tap_fft.as<c32>();
+  }
+  if (on(OFDM_TAP_RX_ACQ)) {
+    HIPCHK(h, rx.tap_acq.ensure(nsym * (uint64_t)h->occ * sizeof(c32)));
+    tq.tap_acq = rx.tap_acq.as<c32>();
+  }
+  if (on(OFDM_TAP_RX_SINK)) {
+    HIPCHK(h, rx.tap_sink.ensure(nsym * (uint64_t)h->occ * sizeof(c32)));
+    HIPCHK(h, rx.tap_demapped.ensure(nsym));
+    HIPCHK(h, hipMemsetAsync(rx.tap_sink.p, 0, nsym * (uint64_t)h->occ * sizeof(c32), h->stream));
+    HIPCHK(h, hipMemsetAsync(rx.tap_demapped.p, 0, nsym, h->stream));
+    tq.tap_sink = rx.tap_sink.as<c32>();
+    tq.tap_demapped = rx.tap_demapped.as<uint8_t>();
+  }
+  return run_demod(h, tq);
+}
 
+static DeframeParams make_deframe_params(const RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
   DeframeParams fq;
   memset(&fq, 0, sizeof(fq));
-  fq.dyn = dynf;
-  fq.nframes = (uint32_t)nframes;
+  fq.dyn = c.dynf;
+  fq.nframes = (uint32_t)c.nframes;
   fq.res = rx.res.as<FrameResult>();
   fq.invalid = rx.invalid.as<uint8_t>();
   fq.raw = rx.raw.as<uint8_t>();
@@ -917,132 +949,122 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
   fq.xp8 = h->d_xp8.as<uint32_t>();
   fq.key = rx.key.as<uint64_t>();
   fq.pos = rx.pos.as<uint64_t>();
-  fq.counters = ctr + CT_DEFR;
-  hipLaunchKernelGGL(k_deframe_count, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq);
+  fq.counters = rx_ctr(h) + CT_DEFR;
+  return fq;
+}
+
+// the deframer's count pass: which frames deliver a packet, where each goes in the call's packet list and payload
+static int rx_deframe_count(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  const uint64_t nframes = c.nframes;
+  const unsigned grid = (unsigned)((nframes + 255) / 256);
+  c.fq = make_deframe_params(c);
+  hipLaunchKernelGGL(k_deframe_count, dim3(grid), dim3(256), 0, h->stream, c.fq);
   HIPCHK(h, hipGetLastError());
-  rc = dev_excl_scan<uint64_t>(h, rx.key.as<uint64_t>(), nframes, rx.pos.as<uint64_t>(), ctr + CT_KEYTOT);
+  int rc = dev_excl_scan<uint64_t>(h, rx.key.as<uint64_t>(), nframes, rx.pos.as<uint64_t>(), rx_ctr(h) + CT_KEYTOT);
   if (rc) return rc;
-  if (tapm & (1u << OFDM_TAP_RX_PACKETS)) {
+  if (h->tap_mask & (1u << OFDM_TAP_RX_PACKETS)) {
     HIPCHK(h, rx.raw_lens.ensure(nframes * sizeof(uint64_t)));
     HIPCHK(h, rx.raw_pos.ensure(nframes * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_raw_len, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, rx.raw_lens.as<uint64_t>());
-    rc = dev_excl_scan<uint64_t>(h, rx.raw_lens.as<uint64_t>(), nframes, rx.raw_pos.as<uint64_t>(), ctr + CT_RAWTOT);
-    if (rc) return rc;
+    hipLaunchKernelGGL(k_raw_len, dim3(grid), dim3(256), 0, h->stream, c.fq, rx.raw_lens.as<uint64_t>());
+    rc = dev_excl_scan<uint64_t>(h, rx.raw_lens.as<uint64_t>(), nframes, rx.raw_pos.as<uint64_t>(), rx_ctr(h) + CT_RAWTOT);
   }
-  uint64_t npk = 0, nbytes = 0;
-  if (!dyn) {
-    HIPCHK(h, hipMemcpyAsync(hc, ctr, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    npk = hc[CT_KEYTOT] >> 40;
-    nbytes = hc[CT_KEYTOT] & ((1ull << 40) - 1);
-    if (stats) {
-      stats->headers_ok = hc[CT_DEFR + 0];
-      stats->chained_frames = hc[CT_DEFR + 3];
-      stats->overflow = hc[CT_OVERFLOW] & 0xFFFFFFFFull;
-    }
-    if (npk > (uint64_t)max_pkts || nbytes > payload_cap) {
-      h->prof.end(h->stream);
-      h->prof.collect();
-      *npkt = (int)std::min<uint64_t>(npk, 0x7FFFFFFF);
-      FAIL(h, OFDM_E_CAPACITY, "payload_out / max_pkts too small for the packets found");
-    }
+  return rc;
+}
+
+static QualityParams make_quality_params(ofdm_handle* h) {
+  RxState& rx = h->rx;
+  QualityParams qw;
+  qw.fq = rx.qual_frame.as<FrameQuality>();
+  qw.step = rx.step.as<double>();
+  qw.out = rx.qual_out.as<ofdm_pkt_quality>();
+  qw.inv_npilot = h->q_npilot ? 1.0f / (float)h->q_npilot : 0.0f;
+  qw.inv_nnull = h->q_nnull ? 1.0f / (float)h->q_nnull : 0.0f;
+  qw.N = h->N;
+  qw.nmap = h->nmap;
+  return qw;
+}
+
+// Outputs: payload bytes and packet metadata (k_deframe_write), link quality, channel state, the raw-packet tap, and
+// the copies of the metadata to the caller.  dyn: the packet count is not known here -- at most one per frame, and no
+// more than the caller has room for; the entries behind the real count are scratch.
+static int rx_outputs(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  DeframeParams& fq = c.fq;
+  const uint64_t nframes = c.nframes;
+  const uint64_t npk_ub = c.npk_ub = c.dyn ? std::min<uint64_t>(nframes, (uint64_t)c.max_pkts) : c.npk;
+  c.d_pay = c.payload_out;
+  if (npk_ub == 0) return OFDM_OK;
+  HIPCHK(h, rx.out_off.ensure((npk_ub + 1) * sizeof(uint64_t)));
+  HIPCHK(h, rx.out_len.ensure(npk_ub * sizeof(uint32_t)));
+  HIPCHK(h, rx.out_ok.ensure(npk_ub));
+  HIPCHK(h, rx.out_pos.ensure(npk_ub * sizeof(uint64_t)));
+  if (!h->dev_ptrs) {
+    // (dyn: every frame could carry a maximum-length message -- but never more than the caller's buffer takes)
+    const uint64_t stage = c.dyn ? std::min<uint64_t>(c.payload_cap, nframes * (uint64_t)OFDM_MAX_PKT_LEN) : c.nbytes;
+    HIPCHK(h, rx.out_payload.ensure(std::max<uint64_t>(stage, 1)));
+    c.d_pay = rx.out_payload.as<uint8_t>();
   }
-  // dyn: the packet count is not known here -- at most one per frame, and no more than the caller has room for
-  const uint64_t npk_ub = dyn ? std::min<uint64_t>(nframes, (uint64_t)max_pkts) : npk;
-  uint8_t* d_pay = payload_out;
-  if (npk_ub > 0) {
-    HIPCHK(h, rx.out_off.ensure((npk_ub + 1) * sizeof(uint64_t)));
-    HIPCHK(h, rx.out_len.ensure(npk_ub * sizeof(uint32_t)));
-    HIPCHK(h, rx.out_ok.ensure(npk_ub));
-    HIPCHK(h, rx.out_pos.ensure(npk_ub * sizeof(uint64_t)));
-    if (!h->dev_ptrs) {
-      // (dyn: every frame could carry a maximum-length message -- but never more than the caller's buffer takes)
-      const uint64_t stage = dyn ? std::min<uint64_t>(payload_cap, nframes * (uint64_t)OFDM_MAX_PKT_LEN) : nbytes;
-      HIPCHK(h, rx.out_payload.ensure(std::max<uint64_t>(stage, 1)));
-      d_pay = rx.out_payload.as<uint8_t>();
-    }
-    fq.payload_out = d_pay;
-    fq.payload_cap = dyn ? payload_cap : nbytes;
-    fq.out_off = rx.out_off.as<uint64_t>();
-    fq.out_len = rx.out_len.as<uint32_t>();
-    fq.out_ok = rx.out_ok.as<uint8_t>();
-    fq.out_pos = rx.out_pos.as<uint64_t>();
-    fq.peaks = rx.peaks.as<uint64_t>();
-    fq.j0 = (uint32_t)rx.j0;
-    fq.max_pkts = (uint32_t)npk_ub;
-    hipLaunchKernelGGL(k_deframe_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq);
+  fq.payload_out = c.d_pay;
+  fq.payload_cap = c.dyn ? c.payload_cap : c.nbytes;
+  fq.out_off = rx.out_off.as<uint64_t>();
+  fq.out_len = rx.out_len.as<uint32_t>();
+  fq.out_ok = rx.out_ok.as<uint8_t>();
+  fq.out_pos = rx.out_pos.as<uint64_t>();
+  fq.peaks = rx.peaks.as<uint64_t>();
+  fq.j0 = (uint32_t)c.n_lo;
+  fq.max_pkts = (uint32_t)npk_ub;
+  hipLaunchKernelGGL(k_deframe_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq);
+  HIPCHK(h, hipGetLastError());
+  if (rx.quality_on) {
+    HIPCHK(h, rx.qual_out.ensure(npk_ub * sizeof(ofdm_pkt_quality)));
+    hipLaunchKernelGGL(k_quality_write, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, make_quality_params(h));
     HIPCHK(h, hipGetLastError());
-    if (rx.quality_on) {
-      HIPCHK(h, rx.qual_out.ensure(npk_ub * sizeof(ofdm_pkt_quality)));
-      QualityParams qw;
-      qw.fq = rx.qual_frame.as<FrameQuality>();
-      qw.step = rx.step.as<double>();
-      qw.out = rx.qual_out.as<ofdm_pkt_quality>();
-      qw.inv_npilot = h->q_npilot ? 1.0f / (float)h->q_npilot : 0.0f;
-      qw.inv_nnull = h->q_nnull ? 1.0f / (float)h->q_nnull : 0.0f;
-      qw.N = N;
-      qw.nmap = h->nmap;
-      hipLaunchKernelGGL(k_quality_write, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, qw);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (rx.csi_on) {
-      const uint64_t st = (uint64_t)rx.csi_stride, cell = npk_ub * st;
-      HIPCHK(h, rx.csi_rows.ensure(cell * (sizeof(c32) + 3 * sizeof(float))));
-      CsiRows pk;
-      pk.eq = rx.csi_rows.as<c32>();
-      pk.pre = reinterpret_cast<float*>(pk.eq + cell);
-      pk.err = pk.pre + cell;
-      pk.ref = pk.err + cell;
-      rx.csi_rows_cap = npk_ub;
-      hipLaunchKernelGGL(k_csi_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq, csi_fr, pk, rx.csi_stride);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (tapm & (1u << OFDM_TAP_RX_PACKETS)) {
-      rx.raw_tap_bytes = hc[CT_RAWTOT];
-      HIPCHK(h, rx.raw_tap.ensure(std::max<uint64_t>(rx.raw_tap_bytes, 1)));
-      hipLaunchKernelGGL(k_raw_tap, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, rx.raw_pos.as<uint64_t>(),
-                         rx.raw_tap.as<uint8_t>());
-      HIPCHK(h, hipGetLastError());
-    }
-    // (dyn: the metadata of npk_ub packets is fetched; the entries behind the real count are scratch)
-    HIPCHK(h, hipMemcpyAsync(payload_off, rx.out_off.p, npk_ub * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(payload_len, rx.out_len.p, npk_ub * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(crc_ok, rx.out_ok.p, npk_ub, hipMemcpyDeviceToHost, h->stream));
-    rx.last_pos.resize(npk_ub);
-    HIPCHK(h, hipMemcpyAsync(rx.last_pos.data(), rx.out_pos.p, npk_ub * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (rx.quality_on) {
-      rx.last_quality.resize(npk_ub);
-      HIPCHK(h, hipMemcpyAsync(rx.last_quality.data(), rx.qual_out.p, npk_ub * sizeof(ofdm_pkt_quality), hipMemcpyDeviceToHost,
-                               h->stream));
-    }
-    if (!dyn && !h->dev_ptrs && nbytes)
-      HIPCHK(h, hipMemcpyAsync(payload_out, d_pay, nbytes, hipMemcpyDeviceToHost, h->stream));
   }
-  h->prof.end(h->stream);
-  HIPCHK(h, hipMemcpyAsync(hc, ctr, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->prof.collect();
-  if (dyn) {
-    n_lo = hc[CT_NLO] & 0xFFFFFFFFull;
-    nframes = npeaks - n_lo - (hc[CT_NHI] & 0xFFFFFFFFull);
-    rx.nframes = nframes;
-    rx.j0 = n_lo;
-    rx.nsym_total = hc[CT_NSYM];
-    npk = hc[CT_KEYTOT] >> 40;
-    nbytes = hc[CT_KEYTOT] & ((1ull << 40) - 1);
-    if (stats) {
-      stats->frames = nframes;
-      stats->symbols = hc[CT_NSYM];
-      stats->headers_ok = hc[CT_DEFR + 0];
-      stats->chained_frames = hc[CT_DEFR + 3];
-    }
-    rx.last_pos.resize(std::min<uint64_t>(npk, npk_ub));
-    if (rx.quality_on) rx.last_quality.resize(std::min<uint64_t>(npk, npk_ub));
-    if (npk > (uint64_t)max_pkts || nbytes > payload_cap) {
-      *npkt = (int)std::min<uint64_t>(npk, 0x7FFFFFFF);
-      FAIL(h, OFDM_E_CAPACITY, "payload_out / max_pkts too small for the packets found");
-    }
-    if (!h->dev_ptrs && nbytes) HIPCHK(h, hipMemcpy(payload_out, d_pay, nbytes, hipMemcpyDeviceToHost));
+  if (rx.csi_on) {
+    HIPCHK(h, rx.csi_rows.ensure(csi_bytes(npk_ub, (uint64_t)rx.csi_stride)));
+    rx.csi_rows_cap = npk_ub;
+    hipLaunchKernelGGL(k_csi_write, dim3((unsigned)((nframes + 3) / 4)), dim3(256), 0, h->stream, fq, c.csi_fr,
+                       csi_carve(rx.csi_rows, npk_ub, (uint64_t)rx.csi_stride), rx.csi_stride);
+    HIPCHK(h, hipGetLastError());
+  }
+  if (h->tap_mask & (1u << OFDM_TAP_RX_PACKETS)) {
+    rx.raw_tap_bytes = c.rawtot;
+    HIPCHK(h, rx.raw_tap.ensure(std::max<uint64_t>(rx.raw_tap_bytes, 1)));
+    hipLaunchKernelGGL(k_raw_tap, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, h->stream, fq, rx.raw_pos.as<uint64_t>(),
+                       rx.raw_tap.as<uint8_t>());
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipMemcpyAsync(c.payload_off, rx.out_off.p, npk_ub * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(c.payload_len, rx.out_len.p, npk_ub * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(c.crc_ok, rx.out_ok.p, npk_ub, hipMemcpyDeviceToHost, h->stream));
+  rx.last_pos.resize(npk_ub);
+  HIPCHK(h, hipMemcpyAsync(rx.last_pos.data(), rx.out_pos.p, npk_ub * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  if (rx.quality_on) {
+    rx.last_quality.resize(npk_ub);
+    HIPCHK(h, hipMemcpyAsync(rx.last_quality.data(), rx.qual_out.p, npk_ub * sizeof(ofdm_pkt_quality), hipMemcpyDeviceToHost,
+                             h->stream));
+  }
+  if (!c.dyn && !h->dev_ptrs && c.nbytes)
+    HIPCHK(h, hipMemcpyAsync(c.payload_out, c.d_pay, c.nbytes, hipMemcpyDeviceToHost, h->stream));
+  return OFDM_OK;
+}
+
+// The final read-back (dyn: the first time the host learns the frame and packet counts, hence the capacity check and
+// the payload copy here) and what the call leaves for its accessors.
+static int rx_finish(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  int rc = rx_read_counts(c);
+  if (rc) return rc;
+  const uint64_t npk = c.npk, nframes = c.nframes;
+  if (c.dyn) {
+    rx.last_pos.resize(std::min<uint64_t>(npk, c.npk_ub));
+    if (rx.quality_on) rx.last_quality.resize(std::min<uint64_t>(npk, c.npk_ub));
+    if ((rc = rx_check_capacity(c))) return rc;
+    if (!h->dev_ptrs && c.nbytes) HIPCHK(h, hipMemcpy(c.payload_out, c.d_pay, c.nbytes, hipMemcpyDeviceToHost));
   }
   rx.last_swallowed.assign(rx.npeaks, 0);
   if (nframes) {
@@ -1050,20 +1072,111 @@ static int rx_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_
     HIPCHK(h, hipMemcpy(inv.data(), rx.invalid.p, nframes, hipMemcpyDeviceToHost));
     for (uint64_t f = 0; f < nframes && rx.j0 + f < rx.npeaks; f++) rx.last_swallowed[rx.j0 + f] = inv[f];
   }
-  if (npk > 0) payload_off[npk] = nbytes;
-  *npkt = (int)npk;
+  if (npk > 0) c.payload_off[npk] = c.nbytes;
+  *c.npkt = (int)npk;
   if (rx.csi_on) {
     rx.csi_n = npk;
-    rx.csi_ok.assign(crc_ok, crc_ok + npk);
+    rx.csi_ok.assign(c.crc_ok, c.crc_ok + npk);
   }
-  if (stats) {
+  if (c.stats) {
     uint64_t nok = 0;
-    for (uint64_t i = 0; i < npk; i++) nok += crc_ok[i] ? 1 : 0;
-    stats->packets = npk;
-    stats->crc_ok = nok;
-    stats->overflow = hc[CT_OVERFLOW] & 0xFFFFFFFFull;
+    for (uint64_t i = 0; i < npk; i++) nok += c.crc_ok[i] ? 1 : 0;
+    c.stats->packets = npk;
+    c.stats->crc_ok = nok;
   }
   return OFDM_OK;
+}
+
+// validate the arguments, reset what the last call left
+static int rx_begin(RxCall& c) {
+  ofdm_handle* h = c.h;
+  if (!c.npkt || c.max_pkts < 0 || (c.nsamples && !c.iq)) FAIL(h, OFDM_E_INVAL, "null argument");
+  if (c.max_pkts > 0 && (!c.payload_off || !c.payload_len || !c.crc_ok)) FAIL(h, OFDM_E_INVAL, "null metadata array");
+  *c.npkt = 0;
+  if (c.payload_off) c.payload_off[0] = 0;
+  if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
+  RxState& rx = h->rx;
+  rx.nsamples = c.nsamples;
+  rx.npeaks = rx.nframes = rx.j0 = rx.nsym_total = rx.raw_tap_bytes = rx.run_slots = 0;
+  rx.last_pos.clear();
+  rx.last_swallowed.clear();
+  rx.last_quality.clear();
+  rx.quality_valid = rx.quality_on;
+  rx.csi_valid = rx.csi_on;
+  rx.csi_n = 0;
+  rx.csi_ok.clear();
+  if (c.stats) c.stats->samples = c.nsamples;
+  return OFDM_OK;
+}
+
+// the input stage (already queued when the caller went through ofdm_rx_submit)
+static int rx_input(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  if (rx.sub_valid && rx.sub_iq == c.iq && rx.sub_n == c.nsamples) {
+    c.d_x = rx.sub_dx;
+    rx.in_event_at_end = h->cfg.sync_mode != OFDM_SYNC_PN || h->sense.rx_on;
+  } else {
+    int rcs = rx_submit_impl(h, c.iq, c.nsamples, &c.d_x);
+    if (rcs != OFDM_OK) return rcs;
+  }
+  rx.sub_valid = false;
+  // chan_filt: the filtered stream, or -- SYNC "fixed": gr.multiply_const_cc(1.0) -- the input itself
+  rx.y_ptr = c.fixed ? c.d_x : rx.y.as<c32>();
+  return OFDM_OK;
+}
+
+// which count path this call takes (RxCall::dyn)
+static bool rx_counts_on_device(const ofdm_handle* h) {
+  const uint32_t probes = (1u << OFDM_TAP_RX_SIGMIX) | (1u << OFDM_TAP_RX_NCO) | (1u << OFDM_TAP_RX_FFT) | (1u << OFDM_TAP_RX_ACQ) |
+                          (1u << OFDM_TAP_RX_SINK) | (1u << OFDM_TAP_RX_SAMPLER) | (1u << OFDM_TAP_RX_PACKETS);
+  return !h->rx.nco_ref_on && !(h->tap_mask & probes) && !getenv("OFDM_RX_SYNCS");
+}
+
+static int rx_impl(RxCall& c) {
+  ofdm_handle* h = c.h;
+  int rc = rx_begin(c);
+  if (rc || c.nsamples == 0) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  c.fixed = h->cfg.sync_mode == OFDM_SYNC_FIXED;
+  if ((rc = rx_input(c))) return rc;
+  if ((rc = rx_timing(c)) || c.done) return rc;  // flags -> splice -> frames / NCO / sampler
+  // From here on nothing the HOST needs is known before the end of the call, unless this call reads the counts as it goes
+  c.dyn = rx_counts_on_device(h);
+  c.nframes = c.npeaks;  // (dyn: an upper bound until the final read-back)
+  if (!c.dyn && ((rc = rx_read_counts(c)) || c.nframes == 0)) return rc;
+  c.dynf.lo = c.dyn ? reinterpret_cast<const unsigned int*>(rx_ctr(h) + CT_NLO) : nullptr;
+  c.dynf.hi = c.dyn ? reinterpret_cast<const unsigned int*>(rx_ctr(h) + CT_NHI) : nullptr;
+  c.dynf.npeaks = (uint32_t)c.npeaks;
+  if ((rc = rx_demodulate(c))) return rc;
+  {
+    ProfScope span(h->prof, OFDM_K_DEFRAME, h->stream);
+    if ((rc = rx_chains(c)) || (rc = rx_tap_pass(c)) || (rc = rx_deframe_count(c))) return rc;
+    if (!c.dyn && ((rc = rx_read_counts(c)) || (rc = rx_check_capacity(c)))) return rc;
+    if ((rc = rx_outputs(c))) return rc;
+  }
+  return rx_finish(c);
+}
+
+extern "C" int ofdm_rx(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples, uint8_t* payload_out, uint64_t payload_cap,
+                       uint64_t* payload_off, uint32_t* payload_len, uint8_t* crc_ok, int max_pkts, int* npkt,
+                       ofdm_stats* stats) {
+  if (!h) return OFDM_E_INVAL;
+  h->rx.in_event_at_end = false;
+  RxCall c{h, iq, nsamples, payload_out, payload_cap, payload_off, payload_len, crc_ok, max_pkts, npkt, stats};
+  const int rc = rx_impl(c);
+  h->rx.sub_valid = false;
+  h->rx.sub_hold = false;
+  // the fused sensor works on its own stream beside the peak pass and the demodulator: joined here, before the caller
+  // gets its input buffer back
+  if (h->sense.rx_on && h->sense.side) (void)hipStreamSynchronize(h->sense.side);
+  h->prof.collect();  // every exit of the call comes through here, its spans closed
+  if (h->rx.in_event_at_end) {  // the input was read to the end of the call (SYNC "fixed", fused sensing)
+    h->rx.in_event_at_end = false;
+    rx_note_input(h, iq, nsamples);
+    if (hipEventRecord(h->ev_rx_in, h->stream) == hipSuccess) h->rx_in_pending = true;
+  }
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1272,16 +1385,8 @@ extern "C" int ofdm_set_rx_csi(ofdm_handle* h, int enable) {
   return OFDM_OK;
 }
 
-// the four packet-row arrays of the last call in csi_rows: eq | pre | err | ref, [csi_rows_cap][stride] each
-static CsiRows csi_packet_rows(const RxState& rx) {
-  const uint64_t cell = rx.csi_rows_cap * (uint64_t)rx.csi_stride;
-  CsiRows pk;
-  pk.eq = rx.csi_rows.as<c32>();
-  pk.pre = reinterpret_cast<float*>(pk.eq + cell);
-  pk.err = pk.pre + cell;
-  pk.ref = pk.err + cell;
-  return pk;
-}
+// the four packet-row arrays of the last call
+static CsiRows csi_packet_rows(const RxState& rx) { return csi_carve(rx.csi_rows, rx.csi_rows_cap, (uint64_t)rx.csi_stride); }
 
 extern "C" int ofdm_rx_csi(ofdm_handle* h, int first, int count, ofdm_c32* eq, float* pre_power, float* err, float* ref, int* n) {
   if (!h) return OFDM_E_INVAL;

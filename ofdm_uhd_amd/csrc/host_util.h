@@ -129,3 +129,18 @@ struct Profiler {
     open = -1;
   }
 };
+
+// A span that ends where its scope ends, whichever way the function is left; end() closes it earlier.  One span is
+// open at a time (Profiler::open): scopes follow each other, they do not nest.
+struct ProfScope {
+  Profiler& prof;
+  hipStream_t stream;
+  bool open = true;
+  ProfScope(Profiler& p, int kernel, hipStream_t s) : prof(p), stream(s) { prof.begin(kernel, s); }
+  ProfScope(const ProfScope&) = delete;
+  void end() {
+    if (open) prof.end(stream);
+    open = false;
+  }
+  ~ProfScope() { end(); }
+};

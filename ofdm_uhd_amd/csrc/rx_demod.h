@@ -1339,53 +1339,3 @@ __global__ void __launch_bounds__(256) k_sigmix_tap(const c32* __restrict__ y, u
   if (nco) nco[i] = rot;
   if (sigmix) sigmix[i] = cmul(y[i], rot);
 }
-
-// ------------------------------------------------------------------------------------
-// receive-side workspaces
-// ------------------------------------------------------------------------------------
-struct RxState {
-  DevBuf recs, x_stage, y, metric, presel, tile_B, tile_np, tile_first, tile_pieces, avg_in, cand_u, cand_P, counters, counts, offsets,
-      partial, peaks, peak_P, angle, step, inc, Phi, K, nsym, sym_base, res, raw, invalid, chain_list, key, pos,
-      out_payload, out_off, out_len, out_ok, out_pos, inc_acc, Phi_u, peaks2, peak_P2, fstep, pre_inv, stash_peaks, stash_P, tap_fft, tap_acq, tap_sink, tap_demapped, raw_tap, raw_lens, raw_pos, tap_sampler, tap_sigmix, tap_nco, qual_frame, qual_out,
-      csi_frame, csi_rows, csi_part, csi_sum, run_rows;
-  uint64_t nsamples = 0, npeaks = 0, nframes = 0, j0 = 0, nsym_total = 0, raw_tap_bytes = 0;
-  uint64_t run_slots = 0;  // OFDM_TAP_RX_RUN_AVG: piece slots of the last call (unwritten ones hold NaN)
-  const c32* y_ptr = nullptr;  // chan_filt's output of the last call: rx.y, or the input itself (SYNC "fixed")
-  // ofdm_rx_submit: the input stage of the next ofdm_rx call is already queued for this buffer
-  bool sub_valid = false, in_event_at_end = false;
-  bool front_done = false;  // the fused front end (filter + pre-selection) of the pending call has been queued
-  bool sub_hold = false;  // a submitted input stage whose buffer stays in use until the end of the ofdm_rx that picks it up
-  const void* sub_iq = nullptr;
-  uint64_t sub_n = 0;
-  const c32* sub_dx = nullptr;
-  uint64_t origin = 0;  // index, in its capture, of the first sample of the ofdm_rx calls (ofdm_rx_set_origin)
-  std::vector<uint64_t> last_pos;  // host copy: flag sample of every packet of the last call
-  // chunked streams (ofdm_rx_set_flag_history): flags settled by earlier calls replace whatever this call
-  // detects up to trust_after; the NCO line of the flag before them
-  bool nco_ref_on = false;
-  int64_t nco_ref_peak = 0, nco_trust_after = 0;
-  uint64_t nco_ref_u = 0;
-  double nco_ref_step = 0.0;
-  std::vector<uint64_t> hist_flags;
-  std::vector<double> hist_steps;
-  std::vector<uint8_t> hist_swallowed;
-  std::vector<uint8_t> last_swallowed;  // per flag of the last call: its frame was swallowed by an earlier packet
-  // link quality (ofdm_set_rx_quality): on for the following calls; whether the last call ran with it, its records
-  bool quality_on = false, quality_valid = false;
-  std::vector<ofdm_pkt_quality> last_quality;
-  // per-subcarrier channel state (ofdm_set_rx_csi): on for the following calls; whether the last call ran with it, its
-  // packet count and CRC verdicts.  The rows themselves stay in csi_rows (device) until the next call.
-  bool csi_on = false, csi_valid = false;
-  uint64_t csi_n = 0, csi_rows_cap = 0;
-  int csi_stride = 0;
-  std::vector<uint8_t> csi_ok;
-  void release() {
-    DevBuf* all[] = {&recs, &x_stage, &y,      &metric,  &presel, &tile_B,   &tile_np,  &tile_first, &tile_pieces, &avg_in,     &cand_u,
-                     &cand_P,  &counters, &counts, &offsets,  &partial,  &peaks,       &peak_P,     &angle,
-                     &step,    &inc,    &Phi,     &K,        &nsym,     &sym_base,    &res,        &raw,
-                     &invalid, &chain_list, &key, &pos,      &out_payload, &out_off,  &out_len,    &out_ok,
-                     &out_pos, &inc_acc, &Phi_u, &peaks2, &peak_P2, &fstep, &pre_inv, &stash_peaks, &stash_P, &tap_fft, &tap_acq, &tap_sink, &tap_demapped, &raw_tap, &raw_lens, &raw_pos, &tap_sampler, &tap_sigmix, &tap_nco, &qual_frame, &qual_out,
-                     &csi_frame, &csi_rows, &csi_part, &csi_sum, &run_rows};
-    for (DevBuf* b : all) b->release();
-  }
-};
