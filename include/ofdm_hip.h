@@ -17,7 +17,9 @@
  *   - a handle is single-owner (not thread-safe) and bound to one GPU and one
  *     HIP stream.  Calls return after the stream has drained unless stated.
  *   - IQ samples are interleaved float32 (I,Q) = gr_complex, the format of
- *     gr.file_sink(gr.sizeof_gr_complex, ...) (ofdm.py:124-131).
+ *     gr.file_sink(gr.sizeof_gr_complex, ...) (ofdm.py:124-131), unless the handle was
+ *     switched to 16-bit IQ (ofdm_sc16: the wire format of a USRP and of most recorded
+ *     captures) with ofdm_set_rx_iq_format / ofdm_set_tx_iq_format below.
  */
 #ifndef OFDM_HIP_H
 #define OFDM_HIP_H
@@ -29,6 +31,10 @@
 extern "C" {
 #endif
 
+/* 6 still: the 16-bit IQ entry points (ofdm_set_rx_iq_format / ofdm_set_tx_iq_format) are additions -- no struct,
+ * prototype or default behaviour of version 6 changed, a caller built against it runs unchanged.  Consequence:
+ * ofdm_abi_version() does not tell whether a library has the two setters; a caller that must run on older builds of
+ * version 6 looks the symbols up (dlsym). */
 #define OFDM_ABI_VERSION 6
 
 #define OFDM_MAX_FFT 4096
@@ -155,6 +161,29 @@ int ofdm_set_tx_amplitude(ofdm_handle *h, float ampl);
  * string holds a non-hex digit or allocates more carriers than occupied_tones (the
  * blocks' std::invalid_argument); the previous map then stays in force. */
 int ofdm_set_carrier_map(ofdm_handle *h, const char *hex);
+/* --- 16-bit IQ at the engine boundary -------------------------------------------------------------------------------
+ * Per handle and per direction; OFDM_IQ_FC32 (interleaved float32) is the default and runs exactly what it always ran.
+ * With OFDM_IQ_SC16 the `iq` / `iq_out` argument of the calls named below points to ofdm_sc16 (cast it; 4-byte aligned)
+ * and nsamples / iq_cap keep counting samples; host or device pointers as the handle was created.
+ *   receive   x.re = (float)i.re * scale, same for im: one float32 multiply, int16 -> float32 is exact.  Default
+ *             scale 2^-15.  The channel filter, the sensor and (SYNC "fixed") a small expand kernel convert as they
+ *             load: the receiver computes bit for bit what it computes from the expanded float array.
+ *   transmit  q = clamp(rintf(x * scale), -32768, 32767) per part: one float32 multiply, round half to even, NaN -> 0,
+ *             clamped in float before the integer conversion.  Default scale 2^15.  Quantised at the store, after
+ *             amplitude and the fused channel (noise and carrier offset are applied in float), the noise-only lead-in
+ *             and tail included.
+ * Any finite scale > 0 is accepted (a driver's own convention, e.g. 32767); scale is ignored with OFDM_IQ_FC32.  The
+ * two defaults are exact powers of two: an sc16 TX -> RX loop returns the quantised grid exactly.
+ * OFDM_E_INVAL: unknown format; scale not finite and positive; a change of the receive format while an ofdm_rx_submit
+ * is pending; sc16 receive together with the opt-in fused front end (OFDM_FRONT=1, float only).  The calls that take
+ * samples return OFDM_E_INVAL for an ofdm_sc16 pointer that is not 4-byte aligned (a sample is moved as one dword).
+ * What stays float32: ofdm_channel (in place on a float buffer), every debug tap, the --log probe files. */
+typedef struct ofdm_sc16 {
+  int16_t re, im;
+} ofdm_sc16;
+enum { OFDM_IQ_FC32 = 0, OFDM_IQ_SC16 = 1 };
+int ofdm_set_rx_iq_format(ofdm_handle *h, int format, float scale); /* ofdm_rx, ofdm_rx_submit, ofdm_sense, fused sensing */
+int ofdm_set_tx_iq_format(ofdm_handle *h, int format, float scale); /* ofdm_tx, ofdm_tx_async */
 /* channel applied inside ofdm_tx; NULL disables it */
 int ofdm_set_channel(ofdm_handle *h, const ofdm_chan *chan);
 
@@ -190,7 +219,7 @@ int ofdm_tx_async(ofdm_handle *h, const uint8_t *payloads, const uint64_t *paylo
 int ofdm_wait(ofdm_handle *h);
 
 /* standalone channel on an existing IQ buffer (same generator as the fused one;
- * sample n of the buffer is stream sample index0+n) */
+ * sample n of the buffer is stream sample index0+n).  Always float32, whatever the handle's IQ formats. */
 int ofdm_channel(ofdm_handle *h, ofdm_c32 *iq, uint64_t n, const ofdm_chan *chan, uint64_t index0);
 
 /* --- receive: ofdm_demod (ofdm.py:221-261) = ofdm_receiver (ofdm_receiver.py~:131-142)

@@ -29,6 +29,7 @@ OFDM_F_PAD_FOR_USRP = 1 << 1
  TAP_RX_FRAMES, TAP_RX_FFT, TAP_RX_ACQ, TAP_RX_SINK, TAP_RX_PACKETS, TAP_TX_MAPPER, TAP_TX_IFFT, TAP_RX_SAMPLER,
  TAP_RX_SIGMIX, TAP_RX_NCO, TAP_RX_PRESEL, TAP_RX_DEMAPPED, TAP_RX_RUN_AVG, TAP_COUNT) = range(20)
 SYNC_PN, SYNC_FIXED = 0, 1
+OFDM_IQ_FC32, OFDM_IQ_SC16 = 0, 1
 
 (K_FRAME, K_TX, K_CHAN, K_SYNC, K_PEAK, K_DEMOD, K_DEFRAME, K_SENSE, K_FILTER, K_EXACT, K_FRONT, K_COUNT) = range(12)
 OFDM_SENSE_MAX_FFT = 4096
@@ -36,6 +37,10 @@ OFDM_SENSE_MAX_FFT = 4096
 
 class ofdm_c32(C.Structure):
     _fields_ = [("re", C.c_float), ("im", C.c_float)]
+
+
+class ofdm_sc16(C.Structure):
+    _fields_ = [("re", C.c_int16), ("im", C.c_int16)]
 
 
 class ofdm_cfg(C.Structure):
@@ -131,6 +136,7 @@ EXPORTS = (
     "ofdm_rx_sense_result", "ofdm_sense_device_msgs", "ofdm_sense_redecide",
     "ofdm_rx_packet_pos", "ofdm_rx_nco_state", "ofdm_rx_set_flag_history", "ofdm_rx_set_origin", "ofdm_rx_submit", "ofdm_rx_snr",
     "ofdm_set_rx_quality", "ofdm_rx_quality", "ofdm_set_rx_csi", "ofdm_rx_csi", "ofdm_rx_csi_summary",
+    "ofdm_set_rx_iq_format", "ofdm_set_tx_iq_format",
 )
 
 _LIB = None
@@ -162,6 +168,8 @@ def _declare(lib):
     lib.ofdm_channel.argtypes = [H, vp, C.c_uint64, C.POINTER(ofdm_chan), C.c_uint64]
     lib.ofdm_rx.argtypes = [H, vp, C.c_uint64, u8p, C.c_uint64, u64p, u32p, C.POINTER(C.c_uint8),
                             C.c_int, C.POINTER(C.c_int), C.POINTER(ofdm_stats)]
+    lib.ofdm_set_rx_iq_format.argtypes = [H, C.c_int, C.c_float]
+    lib.ofdm_set_tx_iq_format.argtypes = [H, C.c_int, C.c_float]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

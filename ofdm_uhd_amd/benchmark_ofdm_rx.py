@@ -39,7 +39,7 @@ class rx_accounting(object):
                 print(line)
 
 
-def main(argv=None):
+def make_parser():
     parser = OptionParser(option_class=_options.eng_option, conflict_handler="resolve")
     expert_grp = parser.add_option_group("Expert")
     parser.add_option("", "--snr", type="eng_float", default=30, help="set the SNR of the channel in dB [default=%default]")
@@ -51,6 +51,11 @@ def main(argv=None):
     parser.add_option("", "--link-quality", action="store_true", default=False,
                       help="append the packet's link quality (preamble SNR, decision SNR in dB, carrier offset in "
                            "subcarrier spacings) to each packet line [default=%default]")
+    parser.add_option("", "--iq-format", type="choice", choices=list(iqio.FORMATS), default="fc32",
+                      help="sample format of the IQ file: fc32 (interleaved float32) or sc16 (interleaved int16, the "
+                           "format of rx_samples_to_file and most capture tools) [default=%default]")
+    parser.add_option("", "--iq-scale", type="eng_float", default=None,
+                      help="with sc16: value of one LSB (sample = int16 * scale) [default=2^-15]")
     parser.add_option("", "--csi-report", default=None,
                       help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
                            "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
@@ -58,6 +63,11 @@ def main(argv=None):
                       help="print the hex carrier map of the carriers whose SNR reaches this many dB [default=off]")
     receive_path.receive_path.add_options(parser, expert_grp)
     ofdm.ofdm_demod.add_options(parser, expert_grp)
+    return parser
+
+
+def main(argv=None):
+    parser = make_parser()
     (options, args) = parser.parse_args(argv)
     if len(args) != 0:
         parser.print_help(sys.stderr)
@@ -70,7 +80,8 @@ def main(argv=None):
         rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
         rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
-    rxpath.run(iqio.file_source(options.from_file), chunk_samples=int(options.chunk_samples))
+    # (receive_path takes --iq-format / --iq-scale from the options)
+    rxpath.run(iqio.file_source(options.from_file, fmt=options.iq_format), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     if options.csi_report is not None:
         rep = rxpath.ofdm_rx.carrier_report()

@@ -34,7 +34,7 @@ def build_payloads(options, data_source=None):
         pktno += 1
 
 
-def main(argv=None):
+def make_parser():
     parser = OptionParser(option_class=_options.eng_option, conflict_handler="resolve")
     expert_grp = parser.add_option_group("Expert")
     parser.add_option("-s", "--size", type="eng_float", default=1024, help="set packet size [default=%default]")
@@ -43,8 +43,18 @@ def main(argv=None):
     parser.add_option("", "--discontinuous", action="store_true", default=False, help="enable discontinuous mode")
     parser.add_option("", "--from-file", default=None, help="use file for packet contents")
     parser.add_option("", "--to-file", default="ofdm_tx.dat", help="write the modulated IQ here [default=%default]")
+    parser.add_option("", "--iq-format", type="choice", choices=list(iqio.FORMATS), default="fc32",
+                      help="sample format of the IQ file: fc32 (interleaved float32) or sc16 (interleaved int16, the "
+                           "format of rx_samples_to_file and most capture tools) [default=%default]")
+    parser.add_option("", "--iq-scale", type="eng_float", default=None,
+                      help="with sc16: full scale (int16 = rint(sample * scale), saturating) [default=2^15]")
     transmit_path.transmit_path.add_options(parser, expert_grp)
     ofdm.ofdm_mod.add_options(parser, expert_grp)
+    return parser
+
+
+def main(argv=None):
+    parser = make_parser()
     (options, args) = parser.parse_args(argv)
     if len(args) != 0:
         parser.print_help()
@@ -55,7 +65,7 @@ def main(argv=None):
         print(os.path.getsize(options.from_file))
 
     txpath = transmit_path.transmit_path(options)
-    sink = iqio.file_sink(options.to_file)
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format from the options)
     txpath.connect(sink)
     npk = 0
     for payload in build_payloads(options, src):

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/ofdm_hip.h"
 
 #define WAVE 64
@@ -22,6 +24,32 @@ __device__ __forceinline__ c32 mk(float re, float im) {
   z.im = im;
   return z;
 }
+// ---- 16-bit IQ at the engine boundary (ofdm_sc16: int16 I, int16 Q, one dword per sample) --------------------------
+// The kernels that read or write the caller's sample buffer take the sample type as a template parameter; the float
+// instantiations go through the c32 overloads below, which are the plain loads and stores they always were.
+struct __align__(4) sc16 {
+  int16_t re, im;
+};
+static_assert(sizeof(sc16) == 4 && sizeof(ofdm_sc16) == 4, "sc16 must be an interleaved int16 pair");
+
+// receive: x = (float)i * scale, one float32 multiply per part (int16 -> float32 is exact)
+__device__ __forceinline__ c32 iq_load(const c32* x, int64_t i, float) { return x[i]; }
+__device__ __forceinline__ c32 iq_load(const sc16* x, int64_t i, float scale) {
+  const uint32_t w = reinterpret_cast<const uint32_t*>(x)[i];
+  return mk((float)(int16_t)(w & 0xFFFFu) * scale, (float)(int16_t)(w >> 16) * scale);
+}
+// transmit: q = clamp(rintf(x * scale), -32768, 32767), round-half-even, NaN -> 0, clamped in float
+__device__ __forceinline__ uint32_t iq_quant(float x, float scale) {
+  float r = rintf(x * scale);
+  r = (r == r) ? r : 0.0f;  // (before the clamp: fmaxf would turn NaN into the bound)
+  r = fminf(fmaxf(r, -32768.0f), 32767.0f);
+  return (uint32_t)(int)r & 0xFFFFu;
+}
+__device__ __forceinline__ void iq_store(c32* o, int64_t i, c32 v, float) { o[i] = v; }
+__device__ __forceinline__ void iq_store(sc16* o, int64_t i, c32 v, float scale) {
+  reinterpret_cast<uint32_t*>(o)[i] = iq_quant(v.re, scale) | (iq_quant(v.im, scale) << 16);
+}
+
 __device__ __forceinline__ c32 cadd(c32 a, c32 b) { return mk(a.re + b.re, a.im + b.im); }
 __device__ __forceinline__ c32 csub(c32 a, c32 b) { return mk(a.re - b.re, a.im - b.im); }
 // gr_complex product: two products and one add per part, separately rounded

@@ -94,12 +94,20 @@ struct ofdm_handle {
   bool chan_on = false;
   ofdm_chan chan;
 
+  // sample format of the caller's IQ buffers, per direction (ofdm_set_rx_iq_format / ofdm_set_tx_iq_format)
+  int rx_fmt = OFDM_IQ_FC32, tx_fmt = OFDM_IQ_FC32;
+  float rx_scale = 1.0f / 32768.0f, tx_scale = 32768.0f;
+
   uint32_t tap_mask = 0;
   Profiler prof;
 
   RxState rx;  // receive-side workspaces (rx_state.h)
   SenseState sense;
 };
+
+// bytes per sample of the caller's receive / transmit buffers
+static size_t rx_ss(const ofdm_handle* h) { return h->rx_fmt == OFDM_IQ_SC16 ? sizeof(sc16) : sizeof(c32); }
+static size_t tx_ss(const ofdm_handle* h) { return h->tx_fmt == OFDM_IQ_SC16 ? sizeof(sc16) : sizeof(c32); }
 
 // ------------------------------------------------------------------------------
 static int ilog2_ceil(unsigned v) {
@@ -222,6 +230,7 @@ static TxParams make_tx_params(const ofdm_handle* h) {
   p.cfo = h->chan.cfo;
   p.seed = h->chan.seed;
   p.stream = h->chan.stream_id;
+  p.qscale = h->tx_scale;
   return p;
 }
 
@@ -573,6 +582,30 @@ extern "C" int ofdm_set_channel(ofdm_handle* h, const ofdm_chan* c) {
   return OFDM_OK;
 }
 
+static bool front_fused(const ofdm_handle* h);
+
+extern "C" int ofdm_set_rx_iq_format(ofdm_handle* h, int format, float scale) {
+  if (!h) return OFDM_E_INVAL;
+  if (format != OFDM_IQ_FC32 && format != OFDM_IQ_SC16) FAIL(h, OFDM_E_INVAL, "unknown IQ format");
+  if (format == OFDM_IQ_SC16 && !(std::isfinite(scale) && scale > 0.0f)) FAIL(h, OFDM_E_INVAL, "IQ scale must be finite and positive");
+  if (h->rx.sub_valid && format != h->rx_fmt) FAIL(h, OFDM_E_INVAL, "receive IQ format changed while an ofdm_rx_submit is pending");
+  if (format == OFDM_IQ_SC16 && front_fused(h)) FAIL(h, OFDM_E_INVAL, "the fused front end (OFDM_FRONT=1) takes float32 samples only");
+  if (h->rx.sub_valid && format == OFDM_IQ_SC16 && scale != h->rx_scale)
+    FAIL(h, OFDM_E_INVAL, "receive IQ scale changed while an ofdm_rx_submit is pending");
+  h->rx_fmt = format;
+  if (format == OFDM_IQ_SC16) h->rx_scale = scale;
+  return OFDM_OK;
+}
+
+extern "C" int ofdm_set_tx_iq_format(ofdm_handle* h, int format, float scale) {
+  if (!h) return OFDM_E_INVAL;
+  if (format != OFDM_IQ_FC32 && format != OFDM_IQ_SC16) FAIL(h, OFDM_E_INVAL, "unknown IQ format");
+  if (format == OFDM_IQ_SC16 && !(std::isfinite(scale) && scale > 0.0f)) FAIL(h, OFDM_E_INVAL, "IQ scale must be finite and positive");
+  h->tx_fmt = format;
+  if (format == OFDM_IQ_SC16) h->tx_scale = scale;
+  return OFDM_OK;
+}
+
 extern "C" int ofdm_set_taps(ofdm_handle* h, uint32_t mask) {
   if (!h) return OFDM_E_INVAL;
   h->tap_mask = mask;
@@ -725,21 +758,31 @@ extern "C" int ofdm_make_packets(ofdm_handle* h, const uint8_t* payloads, const 
   return OFDM_OK;
 }
 
-template <int N>
-static void launch_tx_mod(ofdm_handle* h, const TxParams& p, const uint8_t* d_framed, uint32_t uniform_spp, uint64_t nsym,
-                          uint64_t lead, c32* d_out, c32* d_freq_tap, c32* d_ifft_tap) {
+template <int N, typename OT>
+static void launch_tx_mod_t(ofdm_handle* h, const TxParams& p, const uint8_t* d_framed, uint32_t uniform_spp, uint64_t nsym,
+                            uint64_t lead, OT* d_out, c32* d_freq_tap, c32* d_ifft_tap) {
   constexpr int SPW = TxGeom<N>::SPW, WG = TxGeom<N>::WG;
   const size_t shmem = (size_t)TxGeom<N>::lds_bytes();  // transforms' buffers | constellation
   const unsigned grid = (unsigned)((nsym + SPW - 1) / SPW);
   // (a batch without transmit-side taps and without a carrier offset runs the kernel compiled without them: tx.h)
   if (!d_freq_tap && !d_ifft_tap && !(p.chan_on && p.cfo != 0.0f))
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_mod<N, true>), dim3(grid), dim3(WG), shmem, h->txs, p, d_framed,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_mod<N, true, OT>), dim3(grid), dim3(WG), shmem, h->txs, p, d_framed,
                        h->d_framed_off.as<uint64_t>(), h->d_sym_off.as<uint64_t>(), h->d_sym_pkt.as<uint32_t>(),
                        uniform_spp, nsym, lead, d_out, d_freq_tap, d_ifft_tap);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_mod<N, false>), dim3(grid), dim3(WG), shmem, h->txs, p, d_framed,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_mod<N, false, OT>), dim3(grid), dim3(WG), shmem, h->txs, p, d_framed,
                        h->d_framed_off.as<uint64_t>(), h->d_sym_off.as<uint64_t>(), h->d_sym_pkt.as<uint32_t>(),
                        uniform_spp, nsym, lead, d_out, d_freq_tap, d_ifft_tap);
+}
+
+// d_out: the caller's (or the staging) buffer in the handle's transmit format
+template <int N>
+static void launch_tx_mod(ofdm_handle* h, const TxParams& p, const uint8_t* d_framed, uint32_t uniform_spp, uint64_t nsym,
+                          uint64_t lead, void* d_out, c32* d_freq_tap, c32* d_ifft_tap) {
+  if (h->tx_fmt == OFDM_IQ_SC16)
+    launch_tx_mod_t<N>(h, p, d_framed, uniform_spp, nsym, lead, static_cast<sc16*>(d_out), d_freq_tap, d_ifft_tap);
+  else
+    launch_tx_mod_t<N>(h, p, d_framed, uniform_spp, nsym, lead, static_cast<c32*>(d_out), d_freq_tap, d_ifft_tap);
 }
 
 static int launch_noise(ofdm_handle* h, hipStream_t st, c32* d_iq, uint64_t n, uint64_t index0, int zero_input, const ofdm_chan& ch) {
@@ -749,6 +792,19 @@ static int launch_noise(ofdm_handle* h, hipStream_t st, c32* d_iq, uint64_t n, u
   hipLaunchKernelGGL(k_channel, dim3(grid), dim3(256), 0, st, d_iq, n, index0, zero_input, ch.sigma, ch.cfo,
                      ch.seed, ch.stream_id);
   h->prof.end(st);
+  HIPCHK(h, hipGetLastError());
+  return OFDM_OK;
+}
+
+// noise-only region [first, first + n) of a transmit buffer in the handle's transmit format
+static int launch_tx_noise(ofdm_handle* h, void* d_out, uint64_t first, uint64_t n) {
+  if (h->tx_fmt != OFDM_IQ_SC16) return launch_noise(h, h->txs, static_cast<c32*>(d_out) + first, n, first, 1, h->chan);
+  if (n == 0) return OFDM_OK;
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 256 * 8);
+  h->prof.begin(OFDM_K_CHAN, h->txs);
+  hipLaunchKernelGGL(k_noise_sc16, dim3(grid), dim3(256), 0, h->txs, static_cast<sc16*>(d_out) + first, n, first, h->chan.sigma,
+                     h->chan.cfo, h->chan.seed, h->chan.stream_id, h->tx_scale);
+  h->prof.end(h->txs);
   HIPCHK(h, hipGetLastError());
   return OFDM_OK;
 }
@@ -775,18 +831,19 @@ static int tx_enqueue(ofdm_handle* h, const uint8_t* payloads, const uint64_t* p
   if (total > iq_cap) FAIL(h, OFDM_E_CAPACITY, "iq_out too small (see ofdm_tx_frame_count)");
   if (total == 0) return OFDM_OK;
   if (!iq_out) FAIL(h, OFDM_E_INVAL, "null iq_out");
+  if (h->tx_fmt == OFDM_IQ_SC16 && ((uintptr_t)iq_out & 3u)) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   // A submitted receive stage that reads its input to the end of the call (SYNC "fixed", fused sensing) has recorded
   // no event this batch could wait on: refilling THAT buffer now would race with the receiver.
   if (h->rx.sub_hold && h->rx.sub_valid) {
-    const uintptr_t a0 = (uintptr_t)iq_out, a1 = a0 + total * sizeof(c32);
-    const uintptr_t b0 = (uintptr_t)h->rx.sub_iq, b1 = b0 + h->rx.sub_n * sizeof(c32);
+    const uintptr_t a0 = (uintptr_t)iq_out, a1 = a0 + total * tx_ss(h);
+    const uintptr_t b0 = (uintptr_t)h->rx.sub_iq, b1 = b0 + h->rx.sub_n * rx_ss(h);
     if (a0 < b1 && b0 < a1)
       FAIL(h, OFDM_E_INVAL, "ofdm_tx into the buffer of a submitted ofdm_rx that reads it to the end of the call (SYNC fixed / fused sensing): call ofdm_rx first");
   }
   // the receiver may still be reading the buffer this batch writes (ofdm_rx_submit / ofdm_rx in flight)
   if (h->txs != h->stream) {
-    const uintptr_t o0 = (uintptr_t)iq_out, o1 = o0 + total * sizeof(c32);
+    const uintptr_t o0 = (uintptr_t)iq_out, o1 = o0 + total * tx_ss(h);
     // (host-pointer mode stages through the handle's own buffers: always ordered)
     const bool all = !h->dev_ptrs;
     if (h->rx_in_pending && (all || (o0 < h->rx_in_hi[0] && h->rx_in_lo[0] < o1))) HIPCHK(h, hipStreamWaitEvent(h->txs, h->ev_rx_in, 0));
@@ -794,10 +851,10 @@ static int tx_enqueue(ofdm_handle* h, const uint8_t* payloads, const uint64_t* p
       HIPCHK(h, hipStreamWaitEvent(h->txs, h->ev_rx_in_old, 0));
   }
 
-  c32* d_out = reinterpret_cast<c32*>(iq_out);
+  void* d_out = iq_out;  // (ofdm_sc16 samples when the transmit format says so)
   if (!h->dev_ptrs) {
-    HIPCHK(h, h->d_iq_stage.ensure(total * sizeof(c32)));
-    d_out = h->d_iq_stage.as<c32>();
+    HIPCHK(h, h->d_iq_stage.ensure(total * tx_ss(h)));
+    d_out = h->d_iq_stage.p;
   }
   if (npkt > 0) {
     const uint8_t* d_payloads = nullptr;
@@ -842,12 +899,12 @@ static int tx_enqueue(ofdm_handle* h, const uint8_t* payloads, const uint64_t* p
   h->last_tx_framed_bytes = npkt ? h->framed_off[npkt] : 0;
   // noise-only lead-in and tail (the modulator covers everything in between)
   if (h->chan_on) {
-    rc = launch_noise(h, h->txs, d_out, lead, 0, 1, h->chan);
+    rc = launch_tx_noise(h, d_out, 0, lead);
     if (rc) return rc;
-    rc = launch_noise(h, h->txs, d_out + lead + nsym * (uint64_t)h->L, tail, lead + nsym * (uint64_t)h->L, 1, h->chan);
+    rc = launch_tx_noise(h, d_out, lead + nsym * (uint64_t)h->L, tail);
     if (rc) return rc;
   }
-  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, total * sizeof(c32), hipMemcpyDeviceToHost, h->txs));
+  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, total * tx_ss(h), hipMemcpyDeviceToHost, h->txs));
   HIPCHK(h, hipEventRecord(h->ev_tx_done, h->txs));
   h->tx_pending = true;
   return OFDM_OK;

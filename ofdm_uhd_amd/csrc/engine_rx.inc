@@ -259,7 +259,7 @@ static void rx_note_input(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples)
   h->rx_in_lo[1] = h->rx_in_lo[0];
   h->rx_in_hi[1] = h->rx_in_hi[0];
   h->rx_in_lo[0] = (uintptr_t)iq;
-  h->rx_in_hi[0] = (uintptr_t)iq + nsamples * sizeof(c32);
+  h->rx_in_hi[0] = (uintptr_t)iq + nsamples * rx_ss(h);
 }
 
 // fused front end: channel filter + Schmidl-Cox pre-selection in one pass over x (k_sync<W, true, F>)
@@ -293,7 +293,8 @@ static int launch_front(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
 }
 
 // channel filter: x -> y (streaming)
-static int launch_filter(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
+template <typename XT>
+static int launch_filter_t(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
   const int F = h->filtF;
   const uint64_t bpr = 256 / (F / 8);
   const uint64_t nblk = (nsamples + (uint64_t)fp.goff + (uint64_t)fp.B - 1) / (uint64_t)fp.B;
@@ -303,16 +304,20 @@ static int launch_filter(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
   {
     ProfScope span(h->prof, OFDM_K_FILTER, h->stream);
     switch (F) {
-      case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<64>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 128: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<128>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 256: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<256>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 512: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<512>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
-      case 1024: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<1024>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 64: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<64, XT>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 128: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<128, XT>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 256: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<256, XT>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 512: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<512, XT>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
+      case 1024: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chan_filter<1024, XT>), dim3(fgrid), dim3(256), fsh, h->stream, fp); break;
       default: FAIL(h, OFDM_E_INVAL, "unsupported channel filter transform length");
     }
   }
   HIPCHK(h, hipGetLastError());
   return OFDM_OK;
+}
+
+static int launch_filter(ofdm_handle* h, FilterParams& fp, uint64_t nsamples) {
+  return h->rx_fmt == OFDM_IQ_SC16 ? launch_filter_t<sc16>(h, fp, nsamples) : launch_filter_t<c32>(h, fp, nsamples);
 }
 
 // ------------------------------------------------------------------------------------
@@ -326,10 +331,15 @@ static int rx_submit_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples,
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   if (h->tx_pending && h->txs != h->stream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_tx_done, 0));
   h->tx_pending = false;
+  // (d_x: the input on the device in the handle's receive format -- ofdm_sc16 samples when that says so)
   const c32* d_x = reinterpret_cast<const c32*>(iq);
+  if (h->rx_fmt == OFDM_IQ_SC16) {
+    if ((uintptr_t)iq & 3u) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
+    if (front_fused(h)) FAIL(h, OFDM_E_INVAL, "the fused front end (OFDM_FRONT=1) takes float32 samples only");
+  }
   if (!h->dev_ptrs) {
-    HIPCHK(h, rx.x_stage.ensure(nsamples * sizeof(c32)));
-    HIPCHK(h, hipMemcpyAsync(rx.x_stage.p, iq, nsamples * sizeof(c32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, rx.x_stage.ensure(nsamples * rx_ss(h)));
+    HIPCHK(h, hipMemcpyAsync(rx.x_stage.p, iq, nsamples * rx_ss(h), hipMemcpyHostToDevice, h->stream));
     d_x = rx.x_stage.as<c32>();
   }
   *d_x_out = d_x;
@@ -346,6 +356,7 @@ static int rx_submit_impl(ofdm_handle* h, const ofdm_c32* iq, uint64_t nsamples,
   fp.y = rx.y.as<c32>();
   fp.Hf = h->d_Hf.as<c32>();
   fp.twF = h->d_twF.as<c32>();
+  fp.xscale = h->rx_scale;
   rx.front_done = false;
   if (int rc = front_fused(h) ? launch_front(h, fp, nsamples) : launch_filter(h, fp, nsamples)) return rc;
   if (!h->sense.rx_on) {
@@ -1123,6 +1134,15 @@ static int rx_input(RxCall& c) {
   rx.sub_valid = false;
   // chan_filt: the filtered stream, or -- SYNC "fixed": gr.multiply_const_cc(1.0) -- the input itself
   rx.y_ptr = c.fixed ? c.d_x : rx.y.as<c32>();
+  if (c.fixed && h->rx_fmt == OFDM_IQ_SC16) {
+    // no filter to convert in, and the demodulator gathers float samples: expand once into the y workspace
+    HIPCHK(h, rx.y.ensure(c.nsamples * sizeof(c32)));
+    const unsigned grid = (unsigned)std::min<uint64_t>((c.nsamples + 255) / 256, 256 * 8);
+    hipLaunchKernelGGL(k_expand_sc16, dim3(grid), dim3(256), 0, h->stream, reinterpret_cast<const sc16*>(c.d_x), c.nsamples,
+                       h->rx_scale, rx.y.as<c32>());
+    HIPCHK(h, hipGetLastError());
+    rx.y_ptr = rx.y.as<c32>();
+  }
   return OFDM_OK;
 }
 

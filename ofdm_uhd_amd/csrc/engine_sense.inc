@@ -20,18 +20,25 @@ extern "C" int ofdm_sense_count(const ofdm_sense_cfg* sc, uint64_t nsamples, uin
 
 static int sense_decide_enqueue(ofdm_handle* h, const ofdm_sense_cfg* sc, uint64_t nd, hipStream_t s);
 
-template <int NS>
-static void sense_launch_n(SenseParams p, uint64_t nm, hipStream_t s) {
+template <int NS, typename XT>
+static void sense_launch_t(SenseParams p, uint64_t nm, hipStream_t s) {
   if (sense_lds_bytes(NS) > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sense<NS>), hipFuncAttributeMaxDynamicSharedMemorySize, sense_lds_bytes(NS));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sense<NS, XT>), hipFuncAttributeMaxDynamicSharedMemorySize, sense_lds_bytes(NS));
   for (uint64_t m0 = 0; m0 < nm; m0 += 65535) {
     p.msg0 = m0;
     const unsigned ny = (unsigned)std::min<uint64_t>(65535, nm - m0);
-    hipLaunchKernelGGL(k_sense<NS>, dim3(p.nsplit, ny), dim3(sense_threads(NS)), sense_lds_bytes(NS), s, p);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sense<NS, XT>), dim3(p.nsplit, ny), dim3(sense_threads(NS)), sense_lds_bytes(NS), s, p);
   }
 }
+template <int NS>
+static void sense_launch_n(SenseParams p, uint64_t nm, hipStream_t s, bool in16) {
+  if (in16)
+    sense_launch_t<NS, sc16>(p, nm, s);
+  else
+    sense_launch_t<NS, c32>(p, nm, s);
+}
 
-// enqueue the sensing kernels for `d_x` on stream `s`; results stay in h->sense buffers
+// enqueue the sensing kernels for `d_x` (samples in the handle's receive format) on stream `s`; results stay in h->sense buffers
 static int sense_enqueue(ofdm_handle* h, const ofdm_sense_cfg* sc, const c32* d_x, uint64_t nsamples, hipStream_t s) {
   SenseState& ss = h->sense;
   const int S = (int)sc->fft_size;
@@ -62,6 +69,8 @@ static int sense_enqueue(ofdm_handle* h, const ofdm_sense_cfg* sc, const c32* d_
 
   SenseParams p;
   p.x = d_x;
+  p.xscale = h->rx_scale;
+  const bool in16 = h->rx_fmt == OFDM_IQ_SC16;
   p.win = ss.d_win.as<float>();
   p.tw = ss.d_tw.as<c32>();
   p.msgs = ss.d_msgs.as<float>();
@@ -74,13 +83,13 @@ static int sense_enqueue(ofdm_handle* h, const ofdm_sense_cfg* sc, const c32* d_
   p.nsplit = std::max(1u, std::min(max_split, want));
   h->prof.begin(OFDM_K_SENSE, s);
   switch (S) {
-    case 64: sense_launch_n<64>(p, nm, s); break;
-    case 128: sense_launch_n<128>(p, nm, s); break;
-    case 256: sense_launch_n<256>(p, nm, s); break;
-    case 512: sense_launch_n<512>(p, nm, s); break;
-    case 1024: sense_launch_n<1024>(p, nm, s); break;
-    case 2048: sense_launch_n<2048>(p, nm, s); break;
-    default: sense_launch_n<4096>(p, nm, s); break;
+    case 64: sense_launch_n<64>(p, nm, s, in16); break;
+    case 128: sense_launch_n<128>(p, nm, s, in16); break;
+    case 256: sense_launch_n<256>(p, nm, s, in16); break;
+    case 512: sense_launch_n<512>(p, nm, s, in16); break;
+    case 1024: sense_launch_n<1024>(p, nm, s, in16); break;
+    case 2048: sense_launch_n<2048>(p, nm, s, in16); break;
+    default: sense_launch_n<4096>(p, nm, s, in16); break;
   }
   HIPCHK(h, hipGetLastError());
   if (nd > 0) {
@@ -114,6 +123,7 @@ extern "C" int ofdm_sense(ofdm_handle* h, const ofdm_sense_cfg* sc, const ofdm_c
   if (!h) return OFDM_E_INVAL;
   if (!sense_cfg_ok(sc)) FAIL(h, OFDM_E_INVAL, "bad ofdm_sense_cfg (struct_size, fft_size 64..4096 pow2, dwell_delay>=1, avg_msgs>=1)");
   if (nsamples && !iq) FAIL(h, OFDM_E_INVAL, "null argument");
+  if (h->rx_fmt == OFDM_IQ_SC16 && ((uintptr_t)iq & 3u)) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
   const c32* d_x = reinterpret_cast<const c32*>(iq);
   uint64_t nm = 0;
@@ -121,8 +131,8 @@ extern "C" int ofdm_sense(ofdm_handle* h, const ofdm_sense_cfg* sc, const ofdm_c
   if (!h->dev_ptrs && nm) {
     // only whole message periods are ever read
     const uint64_t used = nm * ((uint64_t)sc->tune_delay + sc->dwell_delay) * sc->fft_size;
-    HIPCHK(h, h->sense.x_stage.ensure(used * sizeof(c32)));
-    HIPCHK(h, hipMemcpyAsync(h->sense.x_stage.p, iq, used * sizeof(c32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, h->sense.x_stage.ensure(used * rx_ss(h)));
+    HIPCHK(h, hipMemcpyAsync(h->sense.x_stage.p, iq, used * rx_ss(h), hipMemcpyHostToDevice, h->stream));
     d_x = h->sense.x_stage.as<c32>();
   }
   int rc = sense_enqueue(h, sc, d_x, nsamples, h->stream);

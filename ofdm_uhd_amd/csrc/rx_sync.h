@@ -129,6 +129,7 @@ struct FilterParams {
   c32* y;
   const c32* Hf;   // [F] transform of the taps, scaled by 1/F
   const c32* twF;  // [F] exp(-2 pi i k / F)
+  float xscale;    // k_chan_filter<F, sc16>: x points to int16 pairs, sample = (float)int16 * xscale (common.h iq_load)
 };
 
 #ifndef FILTER_W
@@ -137,7 +138,9 @@ struct FilterParams {
 #ifndef FILTER_PK
 #define FILTER_PK true  // hand-packed butterflies (fft.h): the transform is all this kernel does
 #endif
-template <int F>
+// XT: the sample type of the input, c32 or sc16 (one dword per point, still lane-consecutive: 256 B per wave and load;
+// converted in registers, everything behind the load is the same code).
+template <int F, typename XT = c32>
 __global__ void __launch_bounds__(256, FILTER_W) k_chan_filter(FilterParams p) {
   constexpr int TF = F / 8;     // threads per block of the filter
   constexpr int BPR = 256 / TF; // blocks per round of a workgroup
@@ -161,15 +164,33 @@ __global__ void __launch_bounds__(256, FILTER_W) k_chan_filter(FilterParams p) {
   };
   auto load_window = [&](c32 (&xn)[8], uint64_t rr) {
     const int64_t x0 = (int64_t)((rr * BPR + (uint64_t)g) * (uint64_t)B) - p.goff - ntm1 + t;
-    if (interior(rr)) {  // (uniform)
-      const c32* px = p.x + x0;
+    // (the float body is kept verbatim, NOT routed through iq_load like the 16-bit one below: written that way the
+    // compiler allocates the float kernel differently -- 2 spilled VGPRs fewer at F = 128..512 -- and this change leaves
+    // every float instantiation's code as it was.  The duplication is deliberate.)
+    if constexpr (std::is_same<XT, c32>::value) {
+      if (interior(rr)) {  // (uniform)
+        const c32* px = p.x + x0;
 #pragma unroll
-      for (int m = 0; m < 8; m++) xn[m] = px[m * TF];
+        for (int m = 0; m < 8; m++) xn[m] = px[m * TF];
+      } else {
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+          const int64_t xi = x0 + m * TF;
+          xn[m] = (xi >= 0 && (uint64_t)xi < p.nsamples) ? p.x[xi] : mk(0.f, 0.f);
+        }
+      }
     } else {
+      const XT* xs = reinterpret_cast<const XT*>(p.x);
+      if (interior(rr)) {  // (uniform)
+        const XT* px = xs + x0;
 #pragma unroll
-      for (int m = 0; m < 8; m++) {
-        const int64_t xi = x0 + m * TF;
-        xn[m] = (xi >= 0 && (uint64_t)xi < p.nsamples) ? p.x[xi] : mk(0.f, 0.f);
+        for (int m = 0; m < 8; m++) xn[m] = iq_load(px, m * TF, p.xscale);
+      } else {
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+          const int64_t xi = x0 + m * TF;
+          xn[m] = (xi >= 0 && (uint64_t)xi < p.nsamples) ? iq_load(xs, xi, p.xscale) : mk(0.f, 0.f);
+        }
       }
     }
   };

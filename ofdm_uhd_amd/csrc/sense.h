@@ -30,6 +30,7 @@ struct SenseParams {
   uint32_t tune_delay, dwell_delay;
   uint32_t nsplit;     // workgroups per message
   uint64_t msg0;       // first message of this launch (grid.y is limited to 65535)
+  float xscale;        // k_sense<NS, sc16>: x points to int16 pairs, sample = (float)int16 * xscale (common.h iq_load)
 };
 
 constexpr int sense_threads(int ns) { return ns / 8 < 256 ? 256 : ns / 8; }
@@ -42,7 +43,8 @@ constexpr int sense_lds_bytes(int ns) {
   return sense_groups(ns) * fft_lds_bytes(ns) + (sense_lean(ns) ? fft_tw_lds_points(ns) * (int)sizeof(c32) : 0);
 }
 
-template <int NS>
+// XT: the sample type of the stream, c32 or sc16 (4 B/sample, converted in registers behind the same coalesced load)
+template <int NS, typename XT = c32>
 __global__ void __launch_bounds__(sense_threads(NS), sense_lean(NS) ? 4 : 1) k_sense(SenseParams p) {
   constexpr int TPT = NS / 8;          // threads per transform
   constexpr int G = sense_groups(NS);  // transforms in flight per workgroup
@@ -80,9 +82,9 @@ __global__ void __launch_bounds__(sense_threads(NS), sense_lean(NS) ? 4 : 1) k_s
   {
     const uint32_t f = blockIdx.x * G + g;
     const bool live = f < p.dwell_delay;
-    const c32* src = p.x + (v0 + (live ? f : 0)) * (uint64_t)NS;
+    const XT* src = reinterpret_cast<const XT*>(p.x) + (v0 + (live ? f : 0)) * (uint64_t)NS;
 #pragma unroll
-    for (int m = 0; m < 8; m++) nx[m] = live ? src[t + m * TPT] : mk(0.f, 0.f);
+    for (int m = 0; m < 8; m++) nx[m] = live ? iq_load(src, t + m * TPT, p.xscale) : mk(0.f, 0.f);
   }
   for (uint32_t r = 0; r < rounds; r++) {
     const uint32_t f = r * stride + blockIdx.x * G + g;
@@ -93,9 +95,9 @@ __global__ void __launch_bounds__(sense_threads(NS), sense_lean(NS) ? 4 : 1) k_s
     {
       const uint32_t fn = f + stride;
       const bool ln = (r + 1 < rounds) && fn < p.dwell_delay;
-      const c32* src = p.x + (v0 + (ln ? fn : 0)) * (uint64_t)NS;
+      const XT* src = reinterpret_cast<const XT*>(p.x) + (v0 + (ln ? fn : 0)) * (uint64_t)NS;
 #pragma unroll
-      for (int m = 0; m < 8; m++) nx[m] = ln ? src[t + m * TPT] : mk(0.f, 0.f);
+      for (int m = 0; m < 8; m++) nx[m] = ln ? iq_load(src, t + m * TPT, p.xscale) : mk(0.f, 0.f);
     }
     if constexpr (LEAN) {
       int tt = t;  // opaque copy, renewed every round: keeps the passes' LDS addresses out of the registers

@@ -31,6 +31,7 @@ struct TxParams {
   int chan_on;
   float sigma, cfo;
   uint64_t seed, stream;
+  float qscale;  // k_tx_mod<N, LEAN, sc16>: tx_scale of the 16-bit output (common.h iq_store)
 };
 
 // ---------------------------------------------------------------------------------
@@ -234,11 +235,14 @@ struct TxGeom {
 #ifndef TX_WAVES
 #define TX_WAVES 1  // minimum waves per SIMD the register allocation must admit (1: no constraint)
 #endif
-template <int N, bool LEAN>
+// OT: the sample type of the output, c32 or sc16.  The 16-bit variant quantises at the store, after scale, amplitude and
+// the fused channel (noise and carrier offset are applied in float, then quantised: what an ADC does); one dword per
+// lane and store, lane-consecutive like the float stores.
+template <int N, bool LEAN, typename OT = c32>
 __global__ void __launch_bounds__(TxGeom<N>::WG, TX_WAVES)
     k_tx_mod(TxParams p, const uint8_t* __restrict__ framed, const uint64_t* __restrict__ framed_off,
              const uint64_t* __restrict__ sym_off, const uint32_t* __restrict__ sym_pkt, uint32_t uniform_spp,
-             uint64_t nsym, uint64_t lead, c32* __restrict__ out, c32* __restrict__ freq_tap,
+             uint64_t nsym, uint64_t lead, OT* __restrict__ out, c32* __restrict__ freq_tap,
              c32* __restrict__ ifft_tap) {
   constexpr int T = TxGeom<N>::T, SPW = TxGeom<N>::SPW;
   // LEAN: the kernel of a batch without transmit-side taps and without a carrier offset in the synthetic channel (the
@@ -393,7 +397,7 @@ __global__ void __launch_bounds__(TxGeom<N>::WG, TX_WAVES)
     for (int m = 0; m < 8; m++) ifft_tap[sym * N + (uint64_t)(t + m * T)] = e[m];
   }
   const uint64_t base = lead + sym * (uint64_t)p.L;
-  c32* o = out + base;
+  OT* o = out + base;
   c32 v[8];
 #pragma unroll
   for (int m = 0; m < 8; m++) {
@@ -407,8 +411,8 @@ __global__ void __launch_bounds__(TxGeom<N>::WG, TX_WAVES)
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int n = t + m * T;
-      o[p.CP + n] = v[m];
-      if (n >= N - p.CP) o[n - (N - p.CP)] = v[m];  // ofdm_cyclic_prefixer: out[0:CP] = in[N-CP:N]
+      iq_store(o, p.CP + n, v[m], p.qscale);
+      if (n >= N - p.CP) iq_store(o, n - (N - p.CP), v[m], p.qscale);  // ofdm_cyclic_prefixer: out[0:CP] = in[N-CP:N]
     }
     return;
   }
@@ -450,7 +454,7 @@ __global__ void __launch_bounds__(TxGeom<N>::WG, TX_WAVES)
     } else {
       a = channel_apply(v[m], base + (uint64_t)pos, p.sigma, p.cfo, p.seed, p.stream);
     }
-    o[pos] = a;
+    iq_store(o, pos, a, p.qscale);
     if (n >= N - p.CP) {  // ofdm_cyclic_prefixer: out[0:CP] = in[N-CP:N]
       const int pc = n - (N - p.CP);
       c32 b = v[m];
@@ -460,7 +464,7 @@ __global__ void __launch_bounds__(TxGeom<N>::WG, TX_WAVES)
       } else {
         b = channel_apply(v[m], base + (uint64_t)pc, p.sigma, p.cfo, p.seed, p.stream);
       }
-      o[pc] = b;
+      iq_store(o, pc, b, p.qscale);
     }
   }
 }
@@ -475,4 +479,16 @@ __global__ void __launch_bounds__(256) k_channel(c32* __restrict__ iq, uint64_t 
     c32 x = zero_input ? mk(0.0f, 0.0f) : iq[i];
     iq[i] = channel_apply(x, index0 + i, sigma, cfo, seed, stream);
   }
+}
+// the noise-only lead-in / tail of a 16-bit transmit buffer: the same noise, quantised like the modulator's samples
+__global__ void __launch_bounds__(256) k_noise_sc16(sc16* __restrict__ iq, uint64_t n, uint64_t index0, float sigma, float cfo,
+                                                     uint64_t seed, uint64_t stream, float qscale) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    iq_store(iq, (int64_t)i, channel_apply(mk(0.0f, 0.0f), index0 + i, sigma, cfo, seed, stream), qscale);
+}
+// SYNC "fixed" has no channel filter to convert in: a 16-bit capture is expanded into the y workspace once
+__global__ void __launch_bounds__(256) k_expand_sc16(const sc16* __restrict__ x, uint64_t n, float scale, c32* __restrict__ y) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) y[i] = iq_load(x, (int64_t)i, scale);
 }

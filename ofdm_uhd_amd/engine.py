@@ -5,6 +5,11 @@ takes / returns NumPy arrays; in device mode (``device_ptrs=True``) the bulk
 arguments are raw device pointers (e.g. ``torch.Tensor.data_ptr()``), which is
 what bench.py uses so that nothing crosses PCIe inside the timed region.
 
+IQ samples are complex64 unless a direction was switched to 16-bit IQ
+(``set_rx_iq_format("sc16")`` / ``set_tx_iq_format("sc16")``): then they are
+``int16`` arrays of shape ``(n, 2)`` (iqio.to_sc16 / from_sc16 define the
+conversion), and a device pointer points to int16 pairs.
+
 There is no CPU implementation behind this class: if the library is missing,
 importing fails loudly (see _abi.load).
 """
@@ -12,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, config
+from . import _abi, config, iqio
 
 
 def _quality_dtype():
@@ -72,6 +77,8 @@ class Engine(object):
         self.occ = cfg.occupied_tones
         self.last_stats = {}
         self._rx_sense_cfg = None
+        self.rx_iq_format = self.tx_iq_format = "fc32"
+        self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
     # -- plumbing ---------------------------------------------------------------
     def close(self):
@@ -113,6 +120,28 @@ class Engine(object):
         ch = _abi.ofdm_chan(sigma=sigma, cfo=cfo, seed=seed, stream_id=stream_id, lead_samples=lead,
                             tail_samples=tail)
         self._check(self._lib.ofdm_set_channel(self._h, C.byref(ch)))
+
+    def set_rx_iq_format(self, fmt="fc32", scale=None):
+        """Sample format of what rx / rx_submit_device / rx_device / sense are handed from now on: "fc32"
+        (complex64) or "sc16" (int16 (n, 2); sample = int16 * scale, default 2^-15)."""
+        scale = iqio.check_scale(scale, iqio.RX_SCALE)
+        self._check(self._lib.ofdm_set_rx_iq_format(self._h, iqio.FORMATS.index(iqio.check_format(fmt)), scale))
+        self.rx_iq_format, self.rx_iq_scale = fmt, scale
+
+    def set_tx_iq_format(self, fmt="fc32", scale=None):
+        """Sample format of what tx / tx_device produce from now on: "fc32" or "sc16" (int16 (n, 2) =
+        clamp(rint(sample * scale)), default scale 2^15)."""
+        scale = iqio.check_scale(scale, iqio.TX_SCALE)
+        self._check(self._lib.ofdm_set_tx_iq_format(self._h, iqio.FORMATS.index(iqio.check_format(fmt)), scale))
+        self.tx_iq_format, self.tx_iq_scale = fmt, scale
+
+    def _rx_samples(self, iq):
+        """A host array in the receive format, contiguous; a dtype of the other format is refused, never reinterpreted."""
+        if self.rx_iq_format == "sc16":
+            return iqio.as_sc16(iq)
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("int16 samples handed to an engine in fc32 mode (set_rx_iq_format(\"sc16\") first)")
+        return np.ascontiguousarray(iq, np.complex64)
 
     def set_taps(self, *taps):
         mask = 0
@@ -165,11 +194,11 @@ class Engine(object):
         return nsym.value, nsamp.value
 
     def tx(self, payloads):
-        """Host mode: list of payload bytes -> complex64 IQ (incl. channel lead/tail if set)."""
+        """Host mode: list of payload bytes -> IQ in the transmit format (incl. channel lead/tail if set)."""
         assert not self.device_ptrs
         blob, offs, lens = pack_payloads(payloads)
         _, nsamp = self.tx_frame_count(lens)
-        iq = np.zeros(max(nsamp, 1), np.complex64)
+        iq = np.zeros((max(nsamp, 1), 2), np.int16) if self.tx_iq_format == "sc16" else np.zeros(max(nsamp, 1), np.complex64)
         ns = C.c_uint64(0)
         st = _abi.ofdm_stats()
         self._check(self._lib.ofdm_tx(self._h, _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
@@ -199,6 +228,8 @@ class Engine(object):
     def channel(self, iq, sigma=0.0, cfo=0.0, seed=0xC0FFEE, stream_id=0, index0=0):
         """Host mode: returns a new array with the synthetic channel applied."""
         assert not self.device_ptrs
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("channel() works on complex64 samples only (ofdm_channel is float32 whatever the IQ formats)")
         out = np.ascontiguousarray(iq, np.complex64).copy()
         ch = _abi.ofdm_chan(sigma=sigma, cfo=cfo, seed=seed, stream_id=stream_id, lead_samples=0, tail_samples=0)
         self._check(self._lib.ofdm_channel(self._h, _ptr(out), len(out), C.byref(ch), index0))
@@ -206,10 +237,10 @@ class Engine(object):
 
     # -- RX ----------------------------------------------------------------------
     def rx(self, iq, max_pkts=None, payload_cap=None):
-        """Host mode: complex64 IQ -> list of (ok, payload) in stream order, exactly the pairs the
+        """Host mode: IQ in the receive format -> list of (ok, payload) in stream order, exactly the pairs the
         reference hands to its rx callback (ofdm.py:300-305)."""
         assert not self.device_ptrs
-        iq = np.ascontiguousarray(iq, np.complex64)
+        iq = self._rx_samples(iq)
         if max_pkts is None:
             max_pkts = len(iq) // self.L + 16
         if payload_cap is None:
@@ -373,7 +404,7 @@ class Engine(object):
         if self.device_ptrs:
             ptr, n = C.c_void_p(int(iq)), int(nsamples)
         else:
-            iq = np.ascontiguousarray(iq, np.complex64)
+            iq = self._rx_samples(iq)
             ptr, n = (_ptr(iq) if len(iq) else None), len(iq)
         nm, nd = self.sense_count(sc, n)
         msgs, mean, bits, hexs = self._sense_outputs(sc, nm, nd)

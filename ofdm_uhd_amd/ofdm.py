@@ -26,13 +26,16 @@ class ofdm_mod(object):
     Send packets by calling send_pkt
     """
 
-    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0):
+    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
                compatibility: the reference blocks send_pkt at this depth, ofdm.py:148;
                here packets are batched until flush)
         @param pad_for_usrp: If true, packets are padded such that they end up a multiple of 128 samples
+        @param iq_format: "fc32" (complex64 samples) or "sc16": flush() returns, and the sink is written, int16
+               arrays of shape (n, 2), quantised on the GPU as iqio.to_sc16 defines it
+        @param iq_scale: full scale of the 16-bit samples (None: 2^15)
         """
         self._pad_for_usrp = pad_for_usrp
         self._msgq_limit = msgq_limit
@@ -49,6 +52,8 @@ class ofdm_mod(object):
         # the modulator alone has unit gain after its 1/sqrt(N) (ofdm.py:114); transmit_path sets the amplitude
         cfg_opts = _copy_options(options, tx_amplitude=1.0)
         self._engine = engine.Engine(cfg_opts, pad_for_usrp=pad_for_usrp, device_id=device_id)
+        if iqio.check_format(iq_format) != "fc32":
+            self._engine.set_tx_iq_format(iq_format, iq_scale)
         self._pending = []
         self._sink = None
         self.symbols_sent = 0
@@ -163,7 +168,8 @@ class ofdm_demod(object):
     app via the callback.
     """
 
-    def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False):
+    def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
+                 iq_scale=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -173,6 +179,9 @@ class ofdm_demod(object):
             ``callback``
         @param csi: per-subcarrier channel state: ``last_csi`` holds the rows of the packets the last work() / feed()
             returned, carrier_report() / suggest_carrier_map() aggregate the CRC-ok ones (csi.py)
+        @param iq_format: "fc32" (complex64 samples) or "sc16": work / feed / flush take int16 arrays of shape (n, 2)
+            (flat 2n accepted) and the GPU converts them as it loads (iqio.from_sc16 defines the arithmetic)
+        @param iq_scale: value of one LSB of the 16-bit samples (None: 2^-15)
         """
         self._modulation = options.modulation
         self._fft_length = options.fft_length
@@ -185,6 +194,8 @@ class ofdm_demod(object):
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
         self._engine = engine.Engine(options, device_id=device_id)
+        if iqio.check_format(iq_format) != "fc32":
+            self._engine.set_rx_iq_format(iq_format, iq_scale)
         if quality_callback is not None:
             self._engine.set_rx_quality(True)
         # link-quality records of the packets the last work() / feed() returned (quality_callback only)
@@ -268,8 +279,11 @@ class ofdm_demod(object):
         lookback = (34 + 3 + (L + T - 1) // T) * T
         return T, span, lookback
 
+    def _no_samples(self):
+        return np.zeros((0, 2), np.int16) if self._engine.rx_iq_format == "sc16" else np.zeros(0, np.complex64)
+
     def reset_stream(self):
-        self._s_tail = np.zeros(0, np.complex64)   # samples carried into the next call
+        self._s_tail = self._no_samples()          # samples carried into the next call (in the receive format)
         self._s_abs = 0                            # absolute index of _s_tail[0]
         self._s_final = -1                         # every flag <= this absolute index has been dealt with
         # settled flags still of interest: (abs flag, phase in 2^-64 turn, step, swallowed); before any flag
@@ -303,7 +317,7 @@ class ofdm_demod(object):
             raise ValueError("feed() needs SYNC 'pn': ofdm_sync_fixed's flags are positions in the whole capture")
         self._streaming = True
         T, span, lookback = self._stream_geometry()
-        iq = np.ascontiguousarray(iq, np.complex64)
+        iq = self._engine._rx_samples(iq)
         buf = np.concatenate([self._s_tail, iq]) if len(self._s_tail) else iq
         base = self._s_abs
         total = base + len(buf)
@@ -410,7 +424,7 @@ class ofdm_demod(object):
         return _csi.suggest_carrier_map(self.carrier_report(), self._engine.cfg, min_snr_db, respect_current)
 
     def flush(self):
-        return self.feed(np.zeros(0, np.complex64), flush=True)
+        return self.feed(self._no_samples(), flush=True)
 
     def reset_carrier_map(self, carrier_map_new):
         """The frame sink's side of reset_carrier_map: streams demodulated from now on are

@@ -79,6 +79,9 @@ class sensor(object):
         parser.add_option("-d", "--decim", type="intx", default=16)
         parser.add_option("-i", "--input_file", default="", metavar="FILE")
         parser.add_option("-S", "--sense-bins", type="int", default=64)
+        parser.add_option("", "--iq-format", type="choice", choices=list(iqio.FORMATS), default="fc32",
+                          help="sample format of -i FILE: fc32 or sc16 (interleaved int16)")
+        parser.add_option("", "--iq-scale", type="eng_float", default=None, help="with sc16: value of one LSB [2^-15]")
         (options, _args) = parser.parse_args(list(argv) if argv is not None else [])
         self.options = options
         self.min_freq, self.max_freq = options.start, options.stop
@@ -90,7 +93,7 @@ class sensor(object):
         # the file branch's rate (:93); the USRP branch's `100**6/decim` (:86) is a typo for it
         self.samp_rate = 100e6 / options.decim
         if source is None and options.input_file:
-            source = iqio.file_source(options.input_file, True)
+            source = iqio.file_source(options.input_file, True, fmt=options.iq_format)
         self.u = source
         self.freq_step = 0  # :95
         self.min_center_freq = (self.min_freq + self.max_freq) / 2
@@ -121,16 +124,21 @@ class sensor(object):
             from .engine import Engine
             from .options import default_options
             self._engine = Engine(default_options())
+        # the command line decides the format; --iq-scale, where given, the scale (also of an engine handed in)
+        if self.options.iq_format != self._engine.rx_iq_format or (
+                self.options.iq_format == "sc16" and self.options.iq_scale is not None
+                and float(self.options.iq_scale) != self._engine.rx_iq_scale):
+            self._engine.set_rx_iq_format(self.options.iq_format, self.options.iq_scale)
         return self._engine
 
     def _samples(self, iq):
         if iq is not None:
-            return np.ascontiguousarray(iq, np.complex64)
+            return iqio._keep(iq)
         if self.u is None:
             raise ValueError("sensor has no source: give -i FILE, source= or pass iq")
         if hasattr(self.u, "read_all"):
             return self.u.read_all()
-        return np.ascontiguousarray(self.u, np.complex64)
+        return iqio._keep(self.u)
 
     def run(self, iq=None):
         """Engine.sense over the whole source: dict with msgs / mean / bits / hex."""

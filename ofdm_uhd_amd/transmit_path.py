@@ -17,15 +17,22 @@ _FLAGS = (
 
 
 class transmit_path(object):
-    def __init__(self, options, device_id=0, apply_carrier_map=False):
+    def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
-        given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too)."""
+        given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
+        ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
+        ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none."""
         opts = copy.copy(options)
+        if iq_format is None:
+            iq_format = getattr(opts, "iq_format", None) or "fc32"
+        if iq_scale is None:
+            iq_scale = getattr(opts, "iq_scale", None)
         self._apply_carrier_map = bool(apply_carrier_map)
         self._verbose = bool(getattr(opts, "verbose", False))
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
-        self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id)
+        self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
+                                     iq_scale=iq_scale)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
