@@ -12,6 +12,7 @@
 #include "../../include/ofdm_hip.h"
 
 #define WAVE 64
+constexpr int CU_LDS_BYTES = 160 * 1024;  // LDS of one compute unit (gfx950), shared by the workgroups it holds
 
 struct c32 {
   float re, im;

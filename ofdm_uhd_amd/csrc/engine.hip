@@ -16,6 +16,7 @@
 #include "tx.h"
 #include "rx_sync.h"
 #include "rx_demod.h"
+#include "rx_deframe.h"
 #include "rx_state.h"
 #include "sense.h"
 

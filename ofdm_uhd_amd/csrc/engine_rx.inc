@@ -50,19 +50,19 @@ static int launch_demod(ofdm_handle* h, const DemodParams& q0) {
     return (size_t)demod_lds_bytes(N, twl, sm, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid, csi);
   };
   constexpr int CU_WAVES = 4 * demod_waves_per_simd(N);  // waves a CU holds at the kernel's register budget
-  auto wgs = [&](size_t b) { return std::max<size_t>(1, std::min<size_t>(std::max(1, CU_WAVES / WAVES), (160 * 1024) / b)); };
+  auto wgs = [&](size_t b) { return std::max<size_t>(1, std::min<size_t>(std::max(1, CU_WAVES / WAVES), CU_LDS_BYTES / b)); };
   constexpr bool base_twl = !fft_onebuf(N);
   const size_t w0 = wgs(bytes(base_twl, false));
   bool twl = base_twl;
-  if constexpr (fft_onebuf(N)) twl = wgs(bytes(true, false)) == w0 && bytes(true, false) <= 160 * 1024;
-  q.smap_lds = (wgs(bytes(twl, true)) == w0 && bytes(twl, true) <= 160 * 1024) ? 1 : 0;
+  if constexpr (fft_onebuf(N)) twl = wgs(bytes(true, false)) == w0 && bytes(true, false) <= CU_LDS_BYTES;
+  q.smap_lds = (wgs(bytes(twl, true)) == w0 && bytes(twl, true) <= CU_LDS_BYTES) ? 1 : 0;
   if (const char* e = getenv("OFDM_DEMOD_LDS")) {  // tuning knob: bit 0 twiddles (N >= 2048), bit 1 carrier map
     const int v = atoi(e);
     if constexpr (fft_onebuf(N)) twl = (v & 1) != 0;
     q.smap_lds = (v >> 1) & 1;
   }
   const size_t shmem = bytes(twl, q.smap_lds != 0);
-  if (shmem > 160 * 1024) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_rx_demod");
+  if (shmem > CU_LDS_BYTES) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_rx_demod");
   if constexpr (fft_onebuf(N)) {
     return twl ? launch_demod_v<N, true>(h, q, shmem) : launch_demod_v<N, false>(h, q, shmem);
   } else {
@@ -213,7 +213,7 @@ static bool front_fused(const ofdm_handle* h) {
   if (F > 512) return false;
   const int HY = (h->N + 7) / 8 * 8, C = (B + 7) / 8 * 8;
   if (HY + C > SYNC_TILE || h->CP > SYNC_TILE) return false;
-  return front_lds_layout(sync_ring_samples(HY), h->CP, B, F).total <= 160 * 1024 / 3;
+  return front_lds_layout(sync_ring_samples(HY), h->CP, B, F).total <= CU_LDS_BYTES / 3;
 }
 
 // k_sync over the whole filtered stream (the float32 pre-selection; the counters are cleared first)
@@ -226,11 +226,11 @@ static int launch_sync(ofdm_handle* h, SyncParams& sp) {
   if (int rs = stamps_prepare(h, sp, nseg)) return rs;
 #endif
   const size_t sync_shmem = sync_lds_layout(sp.R, sp.HM).total;
-  if (sync_shmem > 160 * 1024) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_sync");
+  if (sync_shmem > CU_LDS_BYTES) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_sync");
   {
     ProfScope span(h->prof, OFDM_K_SYNC, h->stream);
     // register budget for as many workgroups per CU as the LDS footprint admits (5 at C2, fewer for long symbols)
-    int wg = (int)std::min<size_t>(SYNC_MAX_WG, (160 * 1024) / sync_shmem);
+    int wg = (int)std::min<size_t>(SYNC_MAX_WG, CU_LDS_BYTES / sync_shmem);
     if (const char* w = getenv("OFDM_SYNC_W")) wg = std::min(wg, atoi(w));  // tuning knob: a larger register budget
     bool fixed_layout = sp.R - (int)T <= (int)T;  // history no longer than a tile: [history | tile] at fixed LDS places
     if (const char* e = getenv("OFDM_SYNC_STATIC")) fixed_layout = fixed_layout && atoi(e) != 0;  // tuning knob
