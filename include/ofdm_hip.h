@@ -34,7 +34,7 @@ extern "C" {
 /* 6 still: the 16-bit IQ entry points (ofdm_set_rx_iq_format / ofdm_set_tx_iq_format) are additions -- no struct,
  * prototype or default behaviour of version 6 changed, a caller built against it runs unchanged.  Consequence:
  * ofdm_abi_version() does not tell whether a library has the two setters; a caller that must run on older builds of
- * version 6 looks the symbols up (dlsym). */
+ * version 6 looks the symbols up (dlsym).  The same holds for the wideband front end (ofdm_set_ddc ... ofdm_ddc_last_ms). */
 #define OFDM_ABI_VERSION 6
 
 #define OFDM_MAX_FFT 4096
@@ -361,6 +361,57 @@ int ofdm_sense_device_msgs(ofdm_handle *h, void **d_msgs, uint64_t *nmsgs, uint3
 /* ... and re-take the decisions (mean / bits / hex) from the reduced bodies; read them with
  * ofdm_rx_sense_result.  Both calls order themselves after the sensing kernels. */
 int ofdm_sense_redecide(ofdm_handle *h, const ofdm_sense_cfg *sc);
+
+/* --- wideband receive: tune and decimate ahead of ofdm_rx (DDC) -------------------------------------------------------
+ * Replaces what the reference leaves to its radio (usrp2.source_32fc.set_decim / set_center_freq,
+ * usrp_receive_path.py) for captures taken wider than the modem's rate, with several links sharing the band: GNU Radio's
+ * gr.freq_xlating_fir_filter_ccf(decimation, taps, center_freq, sampling_freq) with integer-turn phase bookkeeping, so
+ * that any chunking of the stream gives the same bits.  A standalone, stateful stage: ofdm_rx and every other entry
+ * point run exactly what they ran; with no DDC configured nothing here launches, allocates or copies.
+ *   input     wideband samples x[n], n an absolute index counted from the last reset (ofdm_set_ddc, ofdm_ddc_reset);
+ *             samples before that reset's first index are zero.  Format: the handle's receive IQ format and scale
+ *             (ofdm_set_rx_iq_format), converted as the channel filter converts (one float32 multiply per part).
+ *   table     c[k] = complex64(h[k] exp(j 2 pi fc k)), k in [0, ntaps): float64 on the host, rounded once;
+ *             ofdm_ddc_taps returns exactly what the kernel multiplies with.
+ *   output    m exists for every m >= 0 with m R <= the last input index seen:
+ *               v[m] = sum_k c[k] x[m R - k]     float32; the order of the additions is a function of k alone
+ *               y[m] = v[m] r[m]                 r[m] = complex64(expj(-2 pi Phi_m / 2^64)), Phi_m = m D mod 2^64,
+ *             D = frac(fc R) 2^64 truncated to an integer, 0 where frac rounds up to 1 (the integer-turn convention of the receiver's NCO); expj is
+ *             the engine's bit-reproducible float64 evaluation, not the hardware's sin / cos.
+ *   state     the last ntaps - 1 converted samples and the absolute index of the next input sample.  A call with
+ *             input indices [a, a + n) produces the outputs m with a <= m R < a + n -- possibly none.  A stream fed in
+ *             any segmentation gives bit-identical outputs.
+ * Pointers are host or device as the handle was created; in device mode iq_out can be handed straight to ofdm_rx /
+ * ofdm_rx_submit on the same handle (same stream, no host round trip).  ofdm_ddc returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, decimation, ntaps, a non-finite tap, |center_freq| > 0.5; ofdm_ddc / ofdm_ddc_reset /
+ * ofdm_ddc_count / ofdm_ddc_taps without a configuration; an ofdm_sc16 pointer not 4-byte (float32: 8-byte) aligned.
+ * Also OFDM_E_INVAL: a first_sample_index above 2^62, or a call that would take the stream's sample index past 2^63
+ * (indices and phases are computed in 64-bit integers that must not wrap).
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_ddc_count says (*nout is set); the stream state is then unchanged. */
+#define OFDM_DDC_MAX_TAPS 1024
+typedef struct ofdm_ddc_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_ddc_cfg) */
+  uint32_t decimation;  /* R, 1..64, any integer (set_decim) */
+  uint32_t ntaps;       /* 1..OFDM_DDC_MAX_TAPS */
+  uint32_t reserved;
+  double center_freq;   /* fc, cycles per INPUT sample, [-0.5, 0.5] (set_center_freq / sampling_freq) */
+  float taps[OFDM_DDC_MAX_TAPS]; /* real low-pass prototype at the input rate (gr.firdes.low_pass) */
+} ofdm_ddc_cfg;
+/* gr.freq_xlating_fir_filter_ccf ctor = usrp2.source_32fc.set_decim + set_center_freq; NULL: none.  Resets the stream
+ * state (history zero, next input index 0). */
+int ofdm_set_ddc(ofdm_handle *h, const ofdm_ddc_cfg *cfg);
+/* a new stream whose first sample has this absolute index (a retune / a gap in the capture): history zero */
+int ofdm_ddc_reset(ofdm_handle *h, uint64_t first_sample_index);
+/* outputs the NEXT ofdm_ddc call of nin samples produces, from the current state (gr_sync_decimator's fixed ratio,
+ * exact for any R and any start) */
+int ofdm_ddc_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* gr.freq_xlating_fir_filter_ccf::work on the next nin samples of the stream */
+int ofdm_ddc(ofdm_handle *h, const void *iq_in, uint64_t nin, ofdm_c32 *iq_out, uint64_t out_cap, uint64_t *nout);
+/* freq_xlating_fir_filter_ccf's internal band-pass taps: the table the kernel multiplies with (out NULL: size query) */
+int ofdm_ddc_taps(const ofdm_handle *h, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_ddc in the last ofdm_ddc, which must have run with profiling on (ofdm_prof_enable) and produced
+ * output; OFDM_E_INVAL otherwise.  Separate from ofdm_prof_get: the OFDM_K_* table is unchanged. */
+int ofdm_ddc_last_ms(const ofdm_handle *h, double *ms);
 
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and

@@ -14,6 +14,7 @@ OFDM_MAX_ARITY = 256
 OFDM_MASK_LEN = 4096
 OFDM_MAX_PKT_LEN = 4096
 OFDM_MAX_CARRIER_HEX = 1024
+OFDM_DDC_MAX_TAPS = 1024
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -126,6 +127,17 @@ class ofdm_pkt_quality(C.Structure):
     ]
 
 
+class ofdm_ddc_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("center_freq", C.c_double),
+        ("taps", C.c_float * OFDM_DDC_MAX_TAPS),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -137,6 +149,7 @@ EXPORTS = (
     "ofdm_rx_packet_pos", "ofdm_rx_nco_state", "ofdm_rx_set_flag_history", "ofdm_rx_set_origin", "ofdm_rx_submit", "ofdm_rx_snr",
     "ofdm_set_rx_quality", "ofdm_rx_quality", "ofdm_set_rx_csi", "ofdm_rx_csi", "ofdm_rx_csi_summary",
     "ofdm_set_rx_iq_format", "ofdm_set_tx_iq_format",
+    "ofdm_set_ddc", "ofdm_ddc_reset", "ofdm_ddc_count", "ofdm_ddc", "ofdm_ddc_taps", "ofdm_ddc_last_ms",
 )
 
 _LIB = None
@@ -170,6 +183,12 @@ def _declare(lib):
                             C.c_int, C.POINTER(C.c_int), C.POINTER(ofdm_stats)]
     lib.ofdm_set_rx_iq_format.argtypes = [H, C.c_int, C.c_float]
     lib.ofdm_set_tx_iq_format.argtypes = [H, C.c_int, C.c_float]
+    lib.ofdm_set_ddc.argtypes = [H, C.POINTER(ofdm_ddc_cfg)]
+    lib.ofdm_ddc_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_ddc_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_ddc.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
+    lib.ofdm_ddc_taps.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_ddc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

@@ -56,6 +56,12 @@ def make_parser():
                            "format of rx_samples_to_file and most capture tools) [default=%default]")
     parser.add_option("", "--iq-scale", type="eng_float", default=None,
                       help="with sc16: value of one LSB (sample = int16 * scale) [default=2^-15]")
+    parser.add_option("", "--ddc-decim", type="intx", default=0,
+                      help="the IQ file is a wideband capture at this multiple of the modem's rate: tune and decimate "
+                           "it on the GPU first (the radio's set_decim; 0 = off) [default=%default]")
+    parser.add_option("", "--ddc-freq", type="eng_float", default=0.0,
+                      help="with --ddc-decim: centre of the link in the capture, cycles per sample in [-0.5, 0.5] "
+                           "(the radio's set_center_freq over the capture's rate) [default=%default]")
     parser.add_option("", "--csi-report", default=None,
                       help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
                            "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
@@ -80,7 +86,7 @@ def main(argv=None):
         rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
         rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
-    # (receive_path takes --iq-format / --iq-scale from the options)
+    # (receive_path takes --iq-format / --iq-scale and --ddc-decim / --ddc-freq from the options)
     rxpath.run(iqio.file_source(options.from_file, fmt=options.iq_format), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     if options.csi_report is not None:

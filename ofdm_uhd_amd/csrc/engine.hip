@@ -19,6 +19,7 @@
 #include "rx_deframe.h"
 #include "rx_state.h"
 #include "sense.h"
+#include "ddc.h"
 
 static std::string g_create_error;
 
@@ -104,6 +105,7 @@ struct ofdm_handle {
 
   RxState rx;  // receive-side workspaces (rx_state.h)
   SenseState sense;
+  DdcState ddc;  // wideband front end (ddc.h / engine_ddc.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -527,6 +529,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   for (DevBuf* b : bufs) b->release();
   h->h_meta.release();
   h->rx.release();
+  h->ddc.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -957,3 +960,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 
 #include "engine_sense.inc"
 #include "engine_rx.inc"
+#include "engine_ddc.inc"

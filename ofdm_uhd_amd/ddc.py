@@ -1,0 +1,71 @@
+"""Wideband receive front end: tune to one link of a wider capture and decimate to the modem's rate.
+
+The reference leaves this to its radio (``usrp2.source_32fc.set_decim`` / ``set_center_freq`` in
+usrp_receive_path.py, predictive_sense.py, dual_channel/dual_channel.py); with files and arrays in the
+radio's place the stage is GNU Radio's ``gr.freq_xlating_fir_filter_ccf(decimation, taps, center_freq,
+sampling_freq)``, run on the GPU by ``Engine.ddc`` (csrc/ddc.h).  This module holds the host side: the
+low-pass design, the normative band-pass table and the configuration struct.
+
+Frequencies are in cycles per INPUT (wideband) sample.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, firdes
+
+MAX_TAPS = _abi.OFDM_DDC_MAX_TAPS
+MAX_DECIM = 64
+# narrowest transition gr.firdes.low_pass turns into at most MAX_TAPS taps: int(53 / (22 w)) forced odd <= 1023
+_MIN_TRANSITION = 53.0 / (22.0 * (MAX_TAPS - 0.5))
+
+
+def design(decimation, occupied_fraction, transition=None):
+    """Real low-pass prototype at the wideband rate for a link that fills ``occupied_fraction`` of the band that
+    remains after decimation (occupied_tones / fft_length): ``firdes.low_pass`` taps as float32, odd length.
+
+    The signal's edge lies at occupied_fraction / (2R); the first spectrum that folds onto it after decimation begins
+    at 1/R - occupied_fraction / (2R).  Default transition: half that gap, (1 - occupied_fraction) / (2R), widened
+    where needed so that ntaps <= OFDM_DDC_MAX_TAPS.  The pass-band edge handed to low_pass (its 6 dB point) is the
+    signal's edge plus half the transition."""
+    R = int(decimation)
+    if not 1 <= R <= MAX_DECIM:
+        raise ValueError("decimation must be in [1, %d]" % MAX_DECIM)
+    of = float(occupied_fraction)
+    if not 0.0 < of <= 1.0:
+        raise ValueError("occupied_fraction must be in (0, 1]")
+    if transition is None:
+        transition = max((1.0 - of) / (2.0 * R), _MIN_TRANSITION)
+    transition = float(transition)
+    if firdes.compute_ntaps(1.0, transition) > MAX_TAPS:
+        raise ValueError("transition %g needs more than %d taps" % (transition, MAX_TAPS))
+    cutoff = min(of / (2.0 * R) + 0.5 * transition, 0.5)
+    return np.asarray(firdes.low_pass(1.0, 1.0, cutoff, transition, firdes.WIN_HAMMING), np.float32)
+
+
+def bandpass_taps(taps, fc):
+    """The normative table c[k] = complex64(h[k] exp(j 2 pi fc k)): float32 taps, float64 arithmetic, rounded once.
+    (``Engine.ddc_taps`` returns the table the kernel holds, computed the same way by the library's libm.)"""
+    h = np.asarray(taps, np.float32).astype(np.float64)
+    k = np.arange(len(h), dtype=np.float64)
+    a = 2.0 * np.pi * float(fc) * k
+    return (h * np.cos(a) + 1j * (h * np.sin(a))).astype(np.complex64)
+
+
+def ddc_cfg(decimation, center_freq, taps=None, occupied_fraction=None, transition=None):
+    """ofdm_ddc_cfg for Engine.set_ddc; ``taps=None`` designs them from ``occupied_fraction``."""
+    if taps is None:
+        if occupied_fraction is None:
+            raise ValueError("ddc_cfg needs taps or occupied_fraction")
+        taps = design(decimation, occupied_fraction, transition)
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    if not 1 <= len(taps) <= MAX_TAPS:
+        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
+    cfg = _abi.ofdm_ddc_cfg()
+    cfg.struct_size = C.sizeof(_abi.ofdm_ddc_cfg)
+    cfg.decimation = int(decimation)
+    cfg.ntaps = len(taps)
+    cfg.reserved = 0
+    cfg.center_freq = float(center_freq)
+    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg

@@ -77,6 +77,7 @@ class Engine(object):
         self.occ = cfg.occupied_tones
         self.last_stats = {}
         self._rx_sense_cfg = None
+        self.ddc_cfg = None     # the wideband front end's configuration in force (set_ddc), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -338,6 +339,59 @@ class Engine(object):
         self._check(rc)
         n = npk.value
         return n, off[:n + 1], ln[:n], ok[:n]
+
+    # -- wideband front end (tune and decimate ahead of rx) ---------------------------------
+    def set_ddc(self, cfg=None, **kw):
+        """Configure the front end (usrp2.source_32fc.set_decim + set_center_freq; gr.freq_xlating_fir_filter_ccf):
+        an ``ofdm_ddc_cfg`` (ddc.ddc_cfg) or its keywords (decimation=, center_freq=, taps= / occupied_fraction=).
+        ``set_ddc(None)`` with no keywords removes it.  Resets the stream state."""
+        if cfg is None and kw:
+            from . import ddc as _ddc
+            cfg = _ddc.ddc_cfg(**kw)
+        self._check(self._lib.ofdm_set_ddc(self._h, C.byref(cfg) if cfg is not None else None))
+        self.ddc_cfg = cfg
+
+    def ddc_reset(self, first_sample_index=0):
+        """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
+        self._check(self._lib.ofdm_ddc_reset(self._h, int(first_sample_index)))
+
+    def ddc_count(self, nin):
+        """Outputs the next ddc() call of ``nin`` samples produces, from the current stream state."""
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc_count(self._h, int(nin), C.byref(n)))
+        return n.value
+
+    def ddc(self, iq):
+        """Host mode: the next samples of the wideband stream (in the receive IQ format) -> the narrowband complex64
+        samples they complete (possibly none).  Stateful: any segmentation of a stream gives the same bits."""
+        assert not self.device_ptrs
+        iq = self._rx_samples(iq)
+        out = np.zeros(max(self.ddc_count(len(iq)), 1), np.complex64)
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def ddc_device(self, iq_ptr, nin, out_ptr, out_cap):
+        """Device mode: both buffers are device pointers; ``out_ptr`` can go straight to rx_device / rx_submit_device
+        (same stream).  Returns the number of outputs written."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
+        return n.value
+
+    def ddc_taps(self):
+        """The band-pass table c[k] the kernel multiplies with (complex64)."""
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_ddc_taps(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.complex64)
+        self._check(self._lib.ofdm_ddc_taps(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def ddc_last_ms(self):
+        """HIP-event time of k_ddc in the last ddc() / ddc_device() (needs prof_enable())."""
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_ddc_last_ms(self._h, C.byref(ms)))
+        return ms.value
 
     # -- chunked streams --------------------------------------------------------------
     def rx_packet_pos(self):

@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -169,7 +169,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None):
+                 iq_scale=None, ddc=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -182,6 +182,10 @@ class ofdm_demod(object):
         @param iq_format: "fc32" (complex64 samples) or "sc16": work / feed / flush take int16 arrays of shape (n, 2)
             (flat 2n accepted) and the GPU converts them as it loads (iqio.from_sc16 defines the arithmetic)
         @param iq_scale: value of one LSB of the 16-bit samples (None: 2^-15)
+        @param ddc: wideband front end, ``dict(decimation=, center_freq=, taps=None)`` (center_freq in cycles per
+            wideband sample): work / feed / flush then take the WIDEBAND stream (in ``iq_format``), the engine's
+            stateful tune-and-decimate stage (ddc.py, Engine.ddc) turns it into the complex64 stream at the modem's
+            rate and the paths below run on that, unchanged.  ``taps=None``: ddc.design for occupied_tones / fft_length
         """
         self._modulation = options.modulation
         self._fft_length = options.fft_length
@@ -194,7 +198,14 @@ class ofdm_demod(object):
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
         self._engine = engine.Engine(options, device_id=device_id)
-        if iqio.check_format(iq_format) != "fc32":
+        self._ddc = None
+        if ddc is not None:
+            # the 16-bit format, if any, is the wideband side's: the stage's output (the receiver's input) is complex64
+            self._ddc = (iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE))
+            d = dict(ddc)
+            self._engine.set_ddc(_ddc.ddc_cfg(d.pop("decimation"), d.pop("center_freq"), taps=d.pop("taps", None),
+                                              occupied_fraction=self._occupied_tones / float(self._fft_length), **d))
+        elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_rx_iq_format(iq_format, iq_scale)
         if quality_callback is not None:
             self._engine.set_rx_quality(True)
@@ -225,11 +236,31 @@ class ofdm_demod(object):
     def engine(self):
         return self._engine
 
+    def _tune(self, iq, restart=False):
+        """The wideband front end, where one is configured: the next wideband samples in, the narrowband samples they
+        complete out (``restart``: the samples begin a new stream)."""
+        if self._ddc is None:
+            return iq
+        eng = self._engine
+        if restart:
+            eng.ddc_reset(0)
+        if len(iq) == 0:
+            return np.zeros(0, np.complex64)
+        fmt, scale = self._ddc
+        if fmt == "fc32":
+            return eng.ddc(iq)
+        eng.set_rx_iq_format(fmt, scale)
+        try:
+            return eng.ddc(iq)
+        finally:
+            eng.set_rx_iq_format("fc32")
+
     def work(self, iq):
         """Demodulate one contiguous IQ stream; fires the callback per packet and returns the
         list of (ok, payload)."""
         if self._streaming:
             self.reset_stream()  # a one-shot call ends any chunked stream (and drops its carried history)
+        iq = self._tune(iq, restart=True)
         pkts = self._engine.rx(iq)
         if self._quality_callback is not None:
             self.last_quality = self._engine.rx_quality()
@@ -292,6 +323,8 @@ class ofdm_demod(object):
         self._s_sym = None                         # (abs flag, symbol ordinal) of the last final flag (link quality)
         self._engine.set_flag_history(None)
         self._engine.set_origin(0)
+        if self._ddc is not None:
+            self._engine.ddc_reset(0)
         self._streaming = False
         self._log_samples = 0
 
@@ -315,6 +348,8 @@ class ofdm_demod(object):
         ``flush=True`` (or flush()) ends the stream: everything still held back is delivered."""
         if self._engine.cfg.sync_mode != engine._abi.SYNC_PN:
             raise ValueError("feed() needs SYNC 'pn': ofdm_sync_fixed's flags are positions in the whole capture")
+        # (the first chunk of a stream starts the front end afresh too: a work() before it leaves its capture's end there)
+        iq = self._tune(iq, restart=not self._streaming)
         self._streaming = True
         T, span, lookback = self._stream_geometry()
         iq = self._engine._rx_samples(iq)

@@ -82,6 +82,11 @@ class sensor(object):
         parser.add_option("", "--iq-format", type="choice", choices=list(iqio.FORMATS), default="fc32",
                           help="sample format of -i FILE: fc32 or sc16 (interleaved int16)")
         parser.add_option("", "--iq-scale", type="eng_float", default=None, help="with sc16: value of one LSB [2^-15]")
+        parser.add_option("", "--ddc-decim", type="intx", default=0,
+                          help="sense behind the wideband front end: tune and decimate the source by this factor "
+                               "first (0 = off)")
+        parser.add_option("", "--ddc-freq", type="eng_float", default=0.0,
+                          help="with --ddc-decim: centre of the sensed band, cycles per source sample in [-0.5, 0.5]")
         (options, _args) = parser.parse_args(list(argv) if argv is not None else [])
         self.options = options
         self.min_freq, self.max_freq = options.start, options.stop
@@ -141,8 +146,27 @@ class sensor(object):
         return iqio._keep(self.u)
 
     def run(self, iq=None):
-        """Engine.sense over the whole source: dict with msgs / mean / bits / hex."""
-        return self.engine().sense(self.sense_cfg(), self._samples(iq))
+        """Engine.sense over the whole source: dict with msgs / mean / bits / hex.  With --ddc-decim the source is a
+        wideband capture (in --iq-format): the engine's front end tunes and decimates it, the sensor sees the
+        complex64 result (the sensed band fills the decimated rate: a 0.8 / R wide low-pass).  An engine handed in
+        with a front end of its own gets that configuration back afterwards (its stream starts afresh)."""
+        eng, x = self.engine(), self._samples(iq)
+        if not self.options.ddc_decim:
+            return eng.sense(self.sense_cfg(), x)
+        prev = eng.ddc_cfg
+        eng.set_ddc(decimation=int(self.options.ddc_decim), center_freq=float(self.options.ddc_freq), occupied_fraction=0.8)
+        try:
+            y = eng.ddc(x)
+        finally:
+            eng.set_ddc(prev)
+        fmt, scale = eng.rx_iq_format, eng.rx_iq_scale
+        if fmt == "fc32":
+            return eng.sense(self.sense_cfg(), y)
+        eng.set_rx_iq_format("fc32")
+        try:
+            return eng.sense(self.sense_cfg(), y)
+        finally:
+            eng.set_rx_iq_format(fmt, scale)
 
     def messages(self, iq=None):
         """The messages bin_statistics_f would post, in order (what tb.msgq delivers)."""

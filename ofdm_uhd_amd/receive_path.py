@@ -5,21 +5,29 @@ from . import ofdm
 
 
 class receive_path(object):
-    def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None):
+    def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
+                 ddc=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
-        ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none."""
+        ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
+        ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
+        ``ddc_decim`` / ``ddc_freq`` (--ddc-decim / --ddc-freq), no front end where ddc_decim is unset or 0 (what the
+        reference sets on its radio: set_decim / set_center_freq, usrp_receive_path.py)."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if iq_format is None:
             iq_format = getattr(options, "iq_format", None) or "fc32"
         if iq_scale is None:
             iq_scale = getattr(options, "iq_scale", None)
 
+        if ddc is None and getattr(options, "ddc_decim", None):
+            ddc = dict(decimation=int(options.ddc_decim), center_freq=float(getattr(options, "ddc_freq", 0.0) or 0.0))
+
         self._verbose = getattr(options, "verbose", False)
         self._log = getattr(options, "log", False)
         self._rx_callback = rx_callback      # this callback is fired when there's a packet available
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
-                                       quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale)
+                                       quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
+                                       ddc=ddc)
 
         if self._verbose:
             self._print_verbage()
