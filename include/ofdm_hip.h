@@ -413,6 +413,62 @@ int ofdm_ddc_taps(const ofdm_handle *h, ofdm_c32 *out, int cap, int *n);
  * output; OFDM_E_INVAL otherwise.  Separate from ofdm_prof_get: the OFDM_K_* table is unchanged. */
 int ofdm_ddc_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband transmit: interpolate and translate (DUC) behind ofdm_tx -------------
+ * The mirror image of the stage above.  The reference leaves it to its radio (sink.set_interp / set_center_freq,
+ * usrp_transmit_path.py:79-88; generic_usrp.set_interp; the two-channel transmitter of dual_channel/dual_channel.py);
+ * with files and arrays in the radio's place it is a stateful polyphase interpolating FIR followed by a frequency
+ * shift, which can add its output onto a band that already holds other links and can store 16-bit IQ.
+ * Definition.  x[m]: narrowband complex64 samples, m an absolute index counted from the last reset (x is zero before
+ * that reset's first index); L = interpolation; h[k], k in [0, ntaps): real float32 taps at the OUTPUT rate; fc in
+ * cycles per OUTPUT sample.  For every input index m and phase p in [0, L) the output index is n = m L + p:
+ *   v[n] = sum over q >= 0 with p + q L < ntaps of  h[p + q L] * x[m - q]     float32; real tap times complex sample
+ *   y[n] = v[n] * r[n]      r[n] = complex64(expj(+2 pi Phi_n / 2^64)),  Phi_n = n D mod 2^64,
+ *                           D = frac(fc) * 2^64 truncated, 0 where frac rounds up to 1 (the DDC's convention)
+ *   out[n] = store(y[n] + add[n])  when an `add` buffer is given: one float32 addition per part
+ *          = store(y[n])           otherwise
+ *   additions v[n] is one chain in ascending q, begun at +0, of fused multiply-adds on the (re, im) pair: its value is
+ *             a function of n alone.  A phase without a tap (ntaps <= p) gives v[n] = 0.
+ *   product   y = v r is the gr_complex product: two products and one addition per part, separately rounded.
+ *   phasor    r[n] depends on n and the configuration only; it is the engine's bit-reproducible float64 evaluation of
+ *             expj at the phase (int64)Phi_n * 2 pi / 2^64, once per output, rounded to complex64 once -- not the
+ *             hardware's sin / cos.
+ *   store     complex64, or ofdm_sc16 by the transmit rule: clamp(rintf(part * scale), -32768, 32767), NaN -> 0,
+ *             clamped in float.
+ *   state     the last Q = (ntaps - 1) / L inputs and the absolute index of the next input.  A call with nin inputs
+ *             produces exactly nin * L outputs.  A stream fed in any segmentation gives bit-identical outputs; calls
+ *             of 0 inputs and calls shorter than Q are included.
+ * Pointers are host or device as the handle was created.  iq_in is always complex64, whatever the handle's transmit
+ * format; out_format is the stage's own.  add (may be NULL) is complex64 with nin * L samples and may be iq_out
+ * itself when out_format is OFDM_IQ_FC32: each output sample is read before it is written, by the same thread.
+ * Like ofdm_ddc, ofdm_duc orders itself behind an ofdm_tx_async still in flight on the transmit stream (in device
+ * mode ofdm_tx_async's iq_out can be handed straight to it) and returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, interpolation, ntaps, out_format or out_scale, a non-finite tap, |center_freq| > 0.5;
+ * ofdm_duc / ofdm_duc_reset without a configuration; a float32 pointer not 8-byte (ofdm_sc16: 4-byte) aligned; a
+ * first_input_index, or a call, that would take an output index past 2^63.  A refused configuration leaves the one
+ * in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap < nin * L (*nout is set); the stream state is then unchanged. */
+#define OFDM_DUC_MAX_TAPS 1024
+typedef struct ofdm_duc_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_duc_cfg) */
+  uint32_t interpolation; /* L, 1..64, any integer (set_interp) */
+  uint32_t ntaps;         /* 1..OFDM_DUC_MAX_TAPS */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  double center_freq;     /* fc, cycles per OUTPUT sample, [-0.5, 0.5] (set_center_freq / sampling_freq) */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  uint32_t reserved;
+  float taps[OFDM_DUC_MAX_TAPS]; /* real low-pass prototype at the output rate, gain L in its pass band */
+} ofdm_duc_cfg;
+/* sink.set_interp + set_center_freq; NULL: none.  Resets the stream state (history zero, next input index 0). */
+int ofdm_set_duc(ofdm_handle *h, const ofdm_duc_cfg *cfg);
+/* a new stream whose first input has this absolute index: history zero, outputs begin at index L * first */
+int ofdm_duc_reset(ofdm_handle *h, uint64_t first_input_index);
+/* the next nin samples of the narrowband stream in, nin * L wideband samples out (added onto `add` where given) */
+int ofdm_duc(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const ofdm_c32 *add, void *iq_out, uint64_t out_cap,
+             uint64_t *nout);
+/* HIP-event time of k_duc in the last ofdm_duc, which must have run with profiling on (ofdm_prof_enable) and produced
+ * output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_duc_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -15,6 +15,7 @@ OFDM_MASK_LEN = 4096
 OFDM_MAX_PKT_LEN = 4096
 OFDM_MAX_CARRIER_HEX = 1024
 OFDM_DDC_MAX_TAPS = 1024
+OFDM_DUC_MAX_TAPS = 1024
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -138,6 +139,19 @@ class ofdm_ddc_cfg(C.Structure):
     ]
 
 
+class ofdm_duc_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interpolation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("center_freq", C.c_double),
+        ("out_scale", C.c_float),
+        ("reserved", C.c_uint32),
+        ("taps", C.c_float * OFDM_DUC_MAX_TAPS),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -150,6 +164,7 @@ EXPORTS = (
     "ofdm_set_rx_quality", "ofdm_rx_quality", "ofdm_set_rx_csi", "ofdm_rx_csi", "ofdm_rx_csi_summary",
     "ofdm_set_rx_iq_format", "ofdm_set_tx_iq_format",
     "ofdm_set_ddc", "ofdm_ddc_reset", "ofdm_ddc_count", "ofdm_ddc", "ofdm_ddc_taps", "ofdm_ddc_last_ms",
+    "ofdm_set_duc", "ofdm_duc_reset", "ofdm_duc", "ofdm_duc_last_ms",
 )
 
 _LIB = None
@@ -189,6 +204,10 @@ def _declare(lib):
     lib.ofdm_ddc.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
     lib.ofdm_ddc_taps.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_ddc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_duc.argtypes = [H, C.POINTER(ofdm_duc_cfg)]
+    lib.ofdm_duc_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_duc.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+    lib.ofdm_duc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

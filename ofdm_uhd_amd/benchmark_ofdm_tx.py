@@ -48,6 +48,12 @@ def make_parser():
                            "format of rx_samples_to_file and most capture tools) [default=%default]")
     parser.add_option("", "--iq-scale", type="eng_float", default=None,
                       help="with sc16: full scale (int16 = rint(sample * scale), saturating) [default=2^15]")
+    parser.add_option("", "--duc-interp", type="intx", default=0,
+                      help="write a wideband IQ file at this multiple of the modem's rate: interpolate and shift the "
+                           "signal on the GPU (the radio's set_interp; 0 = off) [default=%default]")
+    parser.add_option("", "--duc-freq", type="eng_float", default=0.0,
+                      help="with --duc-interp: centre of the link in the wideband file, cycles per sample in "
+                           "[-0.5, 0.5] (the radio's set_center_freq over the file's rate) [default=%default]")
     transmit_path.transmit_path.add_options(parser, expert_grp)
     ofdm.ofdm_mod.add_options(parser, expert_grp)
     return parser
@@ -65,7 +71,7 @@ def main(argv=None):
         print(os.path.getsize(options.from_file))
 
     txpath = transmit_path.transmit_path(options)
-    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format from the options)
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format and --duc-interp / --duc-freq from the options)
     txpath.connect(sink)
     npk = 0
     for payload in build_payloads(options, src):

@@ -20,6 +20,7 @@
 #include "rx_state.h"
 #include "sense.h"
 #include "ddc.h"
+#include "duc.h"
 
 static std::string g_create_error;
 
@@ -106,6 +107,7 @@ struct ofdm_handle {
   RxState rx;  // receive-side workspaces (rx_state.h)
   SenseState sense;
   DdcState ddc;  // wideband front end (ddc.h / engine_ddc.inc)
+  DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -530,6 +532,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->h_meta.release();
   h->rx.release();
   h->ddc.release();
+  h->duc.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -961,3 +964,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_sense.inc"
 #include "engine_rx.inc"
 #include "engine_ddc.inc"
+#include "engine_duc.inc"

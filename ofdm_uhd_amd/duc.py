@@ -1,0 +1,54 @@
+"""Wideband transmit: place this modem's signal at an offset inside a band L times as wide.
+
+The reference leaves this to its radio (``sink.set_interp`` / ``set_center_freq`` in usrp_transmit_path.py,
+``generic_usrp.set_interp``, the two-channel transmitter of dual_channel/dual_channel.py); with files and arrays in
+the radio's place the stage is a polyphase interpolating FIR followed by a frequency shift, run on the GPU by
+``Engine.duc`` (csrc/duc.h) -- the mirror image of ddc.py.  This module holds the host side: the low-pass design and
+the configuration struct.
+
+Frequencies are in cycles per OUTPUT (wideband) sample.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, ddc, iqio
+
+MAX_TAPS = _abi.OFDM_DUC_MAX_TAPS
+MAX_INTERP = 64
+
+
+def design(interpolation, occupied_fraction, transition=None):
+    """Real low-pass prototype at the wideband rate for a link that fills ``occupied_fraction`` of the modem's band
+    (occupied_tones / fft_length): ``L * ddc.design(L, ...)`` as float32, odd length.
+
+    The image geometry is the decimator's alias geometry: the signal's edge lies at occupied_fraction / (2L), the first
+    image that zero stuffing creates begins at 1/L - occupied_fraction / (2L).  The factor L restores unit pass-band
+    gain after zero stuffing (each polyphase branch sums to about 1)."""
+    L = int(interpolation)
+    if not 1 <= L <= MAX_INTERP:
+        raise ValueError("interpolation must be in [1, %d]" % MAX_INTERP)
+    return (np.float32(L) * ddc.design(L, occupied_fraction, transition)).astype(np.float32)
+
+
+def duc_cfg(interpolation, center_freq, taps=None, occupied_fraction=None, transition=None, out_format="fc32",
+            out_scale=None):
+    """ofdm_duc_cfg for Engine.set_duc; ``taps=None`` designs them from ``occupied_fraction``.  ``out_format`` is
+    "fc32" or "sc16" (``out_scale`` None: 2^15)."""
+    if taps is None:
+        if occupied_fraction is None:
+            raise ValueError("duc_cfg needs taps or occupied_fraction")
+        taps = design(interpolation, occupied_fraction, transition)
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    if not 1 <= len(taps) <= MAX_TAPS:
+        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
+    cfg = _abi.ofdm_duc_cfg()
+    cfg.struct_size = C.sizeof(_abi.ofdm_duc_cfg)
+    cfg.interpolation = int(interpolation)
+    cfg.ntaps = len(taps)
+    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
+    cfg.center_freq = float(center_freq)
+    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
+    cfg.reserved = 0
+    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg

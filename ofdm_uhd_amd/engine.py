@@ -78,6 +78,7 @@ class Engine(object):
         self.last_stats = {}
         self._rx_sense_cfg = None
         self.ddc_cfg = None     # the wideband front end's configuration in force (set_ddc), None without one
+        self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -391,6 +392,59 @@ class Engine(object):
         """HIP-event time of k_ddc in the last ddc() / ddc_device() (needs prof_enable())."""
         ms = C.c_double(0)
         self._check(self._lib.ofdm_ddc_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- wideband transmit (interpolate and translate behind tx) -------------------------------
+    def set_duc(self, cfg=None, **kw):
+        """Configure the transmit stage (sink.set_interp + set_center_freq): an ``ofdm_duc_cfg`` (duc.duc_cfg) or its
+        keywords (interpolation=, center_freq=, taps= / occupied_fraction=, out_format=, out_scale=).
+        ``set_duc(None)`` with no keywords removes it.  Resets the stream state."""
+        if cfg is None and kw:
+            from . import duc as _duc
+            cfg = _duc.duc_cfg(**kw)
+        self._check(self._lib.ofdm_set_duc(self._h, C.byref(cfg) if cfg is not None else None))
+        self.duc_cfg = cfg
+
+    def duc_reset(self, first=0):
+        """Start a new narrowband stream whose first sample has this absolute index (outputs begin at L * first); the
+        filter history is zero."""
+        self._check(self._lib.ofdm_duc_reset(self._h, int(first)))
+
+    def duc(self, iq, add=None):
+        """Host mode: the next complex64 samples of the narrowband stream -> len(iq) * L wideband samples (complex64,
+        or int16 of shape (n, 2) with out_format "sc16"), added onto the complex64 band ``add`` where one is given.
+        Stateful: any segmentation of a stream gives the same bits."""
+        assert not self.device_ptrs
+        if self.duc_cfg is None:
+            raise ValueError("duc() without set_duc()")
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("duc() takes complex64 samples (its 16-bit side is the output)")
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        no = len(iq) * int(self.duc_cfg.interpolation)
+        if add is not None:
+            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
+            if len(add) != no:
+                raise ValueError("add must hold len(iq) * interpolation samples")
+        sc16 = self.duc_cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_duc(self._h, _ptr(iq) if len(iq) else None, len(iq),
+                                       _ptr(add) if add is not None and no else None, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def duc_device(self, iq_ptr, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; ``iq_ptr`` can be what tx_device(wait=False) is filling (same
+        handle), ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns the number of outputs written."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_duc(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
+                                       C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
+        return n.value
+
+    def duc_last_ms(self):
+        """HIP-event time of k_duc in the last duc() / duc_device() (needs prof_enable())."""
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_duc_last_ms(self._h, C.byref(ms)))
         return ms.value
 
     # -- chunked streams --------------------------------------------------------------

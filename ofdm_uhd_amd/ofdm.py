@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -26,7 +26,7 @@ class ofdm_mod(object):
     Send packets by calling send_pkt
     """
 
-    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None):
+    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
@@ -36,6 +36,12 @@ class ofdm_mod(object):
         @param iq_format: "fc32" (complex64 samples) or "sc16": flush() returns, and the sink is written, int16
                arrays of shape (n, 2), quantised on the GPU as iqio.to_sc16 defines it
         @param iq_scale: full scale of the 16-bit samples (None: 2^15)
+        @param duc: wideband transmit stage, ``dict(interpolation=, center_freq=, taps=None)`` (center_freq in cycles
+               per wideband sample): flush() modulates in float32 and returns, and writes to the sink, the WIDEBAND
+               stream in ``iq_format`` -- the engine's stateful interpolate-and-translate stage (duc.py, Engine.duc)
+               stores it; the stream continues across flush() calls (a batch's filter tail comes out in front of the
+               next batch) until flush(end=True) / send_pkt(eof=True).  ``taps=None``: duc.design for
+               occupied_tones / fft_length
         """
         self._pad_for_usrp = pad_for_usrp
         self._msgq_limit = msgq_limit
@@ -52,7 +58,15 @@ class ofdm_mod(object):
         # the modulator alone has unit gain after its 1/sqrt(N) (ofdm.py:114); transmit_path sets the amplitude
         cfg_opts = _copy_options(options, tx_amplitude=1.0)
         self._engine = engine.Engine(cfg_opts, pad_for_usrp=pad_for_usrp, device_id=device_id)
-        if iqio.check_format(iq_format) != "fc32":
+        self._duc = duc is not None
+        self._duc_live = False       # the wideband stream holds samples whose filter tail is still to come
+        if self._duc:
+            # the 16-bit format, if any, is the wideband side's: the modulator's output (the stage's input) is complex64
+            d = dict(duc)
+            self._engine.set_duc(_duc.duc_cfg(d.pop("interpolation"), d.pop("center_freq"), taps=d.pop("taps", None),
+                                              occupied_fraction=self._occupied_tones / float(self._fft_length),
+                                              out_format=iqio.check_format(iq_format), out_scale=iq_scale, **d))
+        elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
         self._pending = []
         self._sink = None
@@ -88,7 +102,7 @@ class ofdm_mod(object):
         @type payload: bytes (str is encoded latin-1)
         """
         if eof:
-            self.flush()  # gr.message(1): no more packets (ofdm.py:142)
+            self.flush(end=True)  # gr.message(1): no more packets (ofdm.py:142)
             return
         if isinstance(payload, str):
             payload = payload.encode("latin-1")
@@ -107,16 +121,31 @@ class ofdm_mod(object):
         self.flush()
         self._engine.set_carrier_map(carrier_map_new)
 
-    def flush(self):
-        """Modulate everything queued so far; returns the samples (also written to the sink)."""
-        if not self._pending:
+    def flush(self, end=False):
+        """Modulate everything queued so far; returns the samples (also written to the sink).  With a wideband stage
+        (duc=) they are the wideband stream's next samples; ``end=True`` then appends the filter's tail (Q zero
+        narrowband samples pushed through) and starts the stage afresh."""
+        end = end and self._duc and (self._duc_live or bool(self._pending))
+        if not self._pending and not end:
             return None
-        pending, self._pending = self._pending, []   # a failing batch never poisons the queue
-        iq = self._engine.tx(pending)
-        self.symbols_sent += self._engine.last_stats.get("symbols", 0)
-        self.packets_sent += len(pending)
-        if self._log:
-            self._write_logs(iq)
+        iq = None
+        if self._pending:
+            pending, self._pending = self._pending, []   # a failing batch never poisons the queue
+            iq = self._engine.tx(pending)
+            self.symbols_sent += self._engine.last_stats.get("symbols", 0)
+            self.packets_sent += len(pending)
+            if self._log:
+                self._write_logs(iq)
+        if self._duc:
+            eng = self._engine
+            parts = [eng.duc(iq)] if iq is not None else []
+            self._duc_live = True
+            if end:
+                cfg = eng.duc_cfg
+                parts.append(eng.duc(np.zeros((cfg.ntaps - 1) // cfg.interpolation, np.complex64)))
+                eng.duc_reset(0)
+                self._duc_live = False
+            iq = np.concatenate(parts) if len(parts) > 1 else parts[0]
         if self._sink is not None:
             self._sink.write(iq)
         return iq

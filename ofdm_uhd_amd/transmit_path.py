@@ -17,22 +17,27 @@ _FLAGS = (
 
 
 class transmit_path(object):
-    def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None):
+    def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
-        ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none."""
+        ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
+        ``duc``: wideband transmit stage of ofdm_mod, ``dict(interpolation=, center_freq=, taps=None)``; None: the
+        options' ``duc_interp`` / ``duc_freq`` (--duc-interp / --duc-freq), no stage where duc_interp is unset or 0
+        (what the reference sets on its radio: set_interp / set_center_freq, usrp_transmit_path.py)."""
         opts = copy.copy(options)
         if iq_format is None:
             iq_format = getattr(opts, "iq_format", None) or "fc32"
         if iq_scale is None:
             iq_scale = getattr(opts, "iq_scale", None)
+        if duc is None and getattr(opts, "duc_interp", None):
+            duc = dict(interpolation=int(opts.duc_interp), center_freq=float(getattr(opts, "duc_freq", 0.0) or 0.0))
         self._apply_carrier_map = bool(apply_carrier_map)
         self._verbose = bool(getattr(opts, "verbose", False))
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
-                                     iq_scale=iq_scale)
+                                     iq_scale=iq_scale, duc=duc)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
@@ -59,8 +64,8 @@ class transmit_path(object):
             self.carrier_map_old = carrier_map_new
         return self.ofdm_tx.send_pkt(payload, eof)
 
-    def flush(self):
-        return self.ofdm_tx.flush()
+    def flush(self, end=False):
+        return self.ofdm_tx.flush(end)
 
     # -- command line ---------------------------------------------------------------
     @staticmethod
