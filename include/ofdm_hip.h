@@ -413,6 +413,57 @@ int ofdm_ddc_taps(const ofdm_handle *h, ofdm_c32 *out, int cap, int *n);
  * output; OFDM_E_INVAL otherwise.  Separate from ofdm_prof_get: the OFDM_K_* table is unchanged. */
 int ofdm_ddc_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband receive: every link of a capture in one pass (DDC bank) -------------------------------------------------
+ * The receive-side counterpart of adding several links onto one band (ofdm_duc with `add`): one decimation R, one real
+ * prototype h[0..ntaps) and K centre frequencies give K narrowband streams from ONE pass over the wideband stream,
+ * where K calls of ofdm_ddc read and stage the capture K times (dual_channel/dual_channel.py tunes one radio channel
+ * per link).  Additions only: OFDM_ABI_VERSION stays 6 and the OFDM_K_* table is unchanged.
+ * Definition.  Link i of the bank is the DDC above with (decimation = R, taps = h, center_freq = fc[i]), bit for bit:
+ *   table     c_i[k] = complex64(h[k] exp(j 2 pi fc_i k)), float64 on the host, rounded once (ofdm_ddc_bank_taps);
+ *   phase     D_i = frac(fc_i R) 2^64 truncated, 0 where frac rounds up to 1;
+ *   input     the handle's receive IQ format and scale, converted as the DDC converts;
+ *   output    of a call with input indices [a, a + n): every m with a <= m R < a + n, the same set for every link;
+ *   additions tap k = q R + p belongs to chain q mod NG (NG = 1 for R <= 4, 4 otherwise); a chain adds its taps in
+ *             ascending k into A += c.re * (x.re, x.im), B += c.im * (x.re, x.im), packed fused multiply-adds begun at
+ *             +0; the chains are added in ascending order; v = (A.re - B.im, A.im + B.re);
+ *   rotation  y[m] = v[m] r_i[m], the unfused complex product, r_i[m] = complex64(expj(-2 pi (m D_i mod 2^64) / 2^64)).
+ * Nothing depends on where a call, a chunk or a tile starts, on K, or on a link's position in the list: link i's
+ * stream equals what ofdm_ddc gives for fc_i, under any segmentation.  Equal frequencies are allowed and give equal
+ * outputs.
+ *   state     the last ntaps - 1 converted samples and the absolute index of the next input sample, shared by all
+ *             links and separate from the single DDC's: a handle may have both configured, neither disturbs the other.
+ * Pointers are host or device as the handle was created; ordering behind an ofdm_tx_async in flight and the alignment
+ * rules are ofdm_ddc's.  Link i's outputs go to the contiguous run iq_out + i * link_stride (samples); out_cap and
+ * *nout count outputs PER LINK.  With no bank configured nothing here launches, allocates or copies.
+ * OFDM_E_INVAL: as for the DDC (bad struct_size, decimation, ntaps, a non-finite tap, a call without a configuration,
+ * misaligned input, first_sample_index above 2^62, a sample index past 2^63), and: nlinks 0 or above
+ * OFDM_DDC_BANK_MAX_LINKS, any |center_freq[i]| > 0.5 or NaN, link >= nlinks, link_stride < *nout with nlinks > 1.  A
+ * refused configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_ddc_bank_count says (*nout is set); the stream state is then unchanged. */
+#define OFDM_DDC_BANK_MAX_LINKS 8
+typedef struct ofdm_ddc_bank_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_ddc_bank_cfg) */
+  uint32_t decimation;  /* R, 1..64, shared by the links */
+  uint32_t ntaps;       /* 1..OFDM_DDC_MAX_TAPS */
+  uint32_t nlinks;      /* K, 1..OFDM_DDC_BANK_MAX_LINKS */
+  double center_freq[OFDM_DDC_BANK_MAX_LINKS]; /* fc[i], cycles per INPUT sample, [-0.5, 0.5]; the first nlinks count */
+  float taps[OFDM_DDC_MAX_TAPS];               /* real low-pass prototype at the input rate, shared by the links */
+} ofdm_ddc_bank_cfg;
+/* K freq_xlating_fir_filter_ccf ctors on one stream; NULL: none.  Resets the bank's stream state. */
+int ofdm_set_ddc_bank(ofdm_handle *h, const ofdm_ddc_bank_cfg *cfg);
+/* a new stream whose first sample has this absolute index: history zero */
+int ofdm_ddc_bank_reset(ofdm_handle *h, uint64_t first_sample_index);
+/* outputs PER LINK the next ofdm_ddc_bank call of nin samples produces, from the current state */
+int ofdm_ddc_bank_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of the stream through every link: link i at iq_out + i * link_stride, out_cap per link */
+int ofdm_ddc_bank(ofdm_handle *h, const void *iq_in, uint64_t nin, ofdm_c32 *iq_out, uint64_t link_stride, uint64_t out_cap,
+                  uint64_t *nout);
+/* the table of one link as the kernel multiplies with it (out NULL: size query) */
+int ofdm_ddc_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_ddc_bank in the last ofdm_ddc_bank, which must have run with profiling on and produced output;
+ * OFDM_E_INVAL otherwise. */
+int ofdm_ddc_bank_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband transmit: interpolate and translate (DUC) behind ofdm_tx -------------
  * The mirror image of the stage above.  The reference leaves it to its radio (sink.set_interp / set_center_freq,
  * usrp_transmit_path.py:79-88; generic_usrp.set_interp; the two-channel transmitter of dual_channel/dual_channel.py);

@@ -15,6 +15,7 @@ OFDM_MASK_LEN = 4096
 OFDM_MAX_PKT_LEN = 4096
 OFDM_MAX_CARRIER_HEX = 1024
 OFDM_DDC_MAX_TAPS = 1024
+OFDM_DDC_BANK_MAX_LINKS = 8
 OFDM_DUC_MAX_TAPS = 1024
 
 OFDM_OK = 0
@@ -139,6 +140,17 @@ class ofdm_ddc_cfg(C.Structure):
     ]
 
 
+class ofdm_ddc_bank_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("nlinks", C.c_uint32),
+        ("center_freq", C.c_double * OFDM_DDC_BANK_MAX_LINKS),
+        ("taps", C.c_float * OFDM_DDC_MAX_TAPS),
+    ]
+
+
 class ofdm_duc_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -165,6 +177,8 @@ EXPORTS = (
     "ofdm_set_rx_iq_format", "ofdm_set_tx_iq_format",
     "ofdm_set_ddc", "ofdm_ddc_reset", "ofdm_ddc_count", "ofdm_ddc", "ofdm_ddc_taps", "ofdm_ddc_last_ms",
     "ofdm_set_duc", "ofdm_duc_reset", "ofdm_duc", "ofdm_duc_last_ms",
+    "ofdm_set_ddc_bank", "ofdm_ddc_bank_reset", "ofdm_ddc_bank_count", "ofdm_ddc_bank", "ofdm_ddc_bank_taps",
+    "ofdm_ddc_bank_last_ms",
 )
 
 _LIB = None
@@ -204,6 +218,12 @@ def _declare(lib):
     lib.ofdm_ddc.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
     lib.ofdm_ddc_taps.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_ddc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_ddc_bank.argtypes = [H, C.POINTER(ofdm_ddc_bank_cfg)]
+    lib.ofdm_ddc_bank_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_ddc_bank_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_ddc_bank.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
+    lib.ofdm_ddc_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_ddc_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_duc.argtypes = [H, C.POINTER(ofdm_duc_cfg)]
     lib.ofdm_duc_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_duc.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]

@@ -59,9 +59,13 @@ def make_parser():
     parser.add_option("", "--ddc-decim", type="intx", default=0,
                       help="the IQ file is a wideband capture at this multiple of the modem's rate: tune and decimate "
                            "it on the GPU first (the radio's set_decim; 0 = off) [default=%default]")
-    parser.add_option("", "--ddc-freq", type="eng_float", default=0.0,
+    parser.add_option("", "--ddc-freq", type="eng_float", default=None,
                       help="with --ddc-decim: centre of the link in the capture, cycles per sample in [-0.5, 0.5] "
-                           "(the radio's set_center_freq over the capture's rate) [default=%default]")
+                           "(the radio's set_center_freq over the capture's rate) [default=0.0]")
+    parser.add_option("", "--ddc-freqs", default=None,
+                      help="with --ddc-decim, instead of --ddc-freq: comma-separated centres of ALL links in the capture; "
+                           "they are extracted in one pass on the GPU (ofdm_demod_bank), one account per link, and "
+                           "--to-file gets .linkN appended [default=off]")
     parser.add_option("", "--csi-report", default=None,
                       help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
                            "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
@@ -72,12 +76,48 @@ def make_parser():
     return parser
 
 
+def _main_bank(parser, options):
+    """--ddc-freqs: every link of the wideband file through one ofdm_demod_bank; returns the per-link accounts."""
+    if options.ddc_freq is not None:
+        parser.error("--ddc-freqs and --ddc-freq are mutually exclusive")
+    if not options.ddc_decim:
+        parser.error("--ddc-freqs needs --ddc-decim")
+    if options.link_quality or options.csi_report is not None or options.suggest_map is not None:
+        parser.error("--ddc-freqs does not combine with --link-quality, --csi-report or --suggest-map")
+    try:
+        freqs = [float(f) for f in options.ddc_freqs.split(",")]
+    except ValueError:
+        parser.error("--ddc-freqs takes comma-separated numbers")
+    files = [open("%s.link%d" % (options.to_file, i), "wb") for i in range(len(freqs))]
+    accts = [rx_accounting(f) for f in files]
+    bank = None
+    try:
+        bank = ofdm.ofdm_demod_bank(options, freqs, int(options.ddc_decim), iq_format=options.iq_format,
+                                    iq_scale=options.iq_scale,
+                                    callback=lambda link, ok, payload: accts[link].rx_callback(ok, payload))
+        source = iqio.file_source(options.from_file, fmt=options.iq_format)
+        if int(options.chunk_samples):
+            for piece in source.read_chunks(int(options.chunk_samples)):
+                bank.feed(piece)
+            bank.flush()
+        else:
+            bank.work(source.read_all())
+    finally:
+        if bank is not None:
+            bank.close()
+        for f in files:
+            f.close()
+    return accts
+
+
 def main(argv=None):
     parser = make_parser()
     (options, args) = parser.parse_args(argv)
     if len(args) != 0:
         parser.print_help(sys.stderr)
         sys.exit(1)
+    if options.ddc_freqs is not None:
+        return _main_bank(parser, options)
 
     packet_file = open(options.to_file, 'wb')
     acct = rx_accounting(packet_file)

@@ -20,6 +20,7 @@
 #include "rx_state.h"
 #include "sense.h"
 #include "ddc.h"
+#include "ddc_bank.h"
 #include "duc.h"
 
 static std::string g_create_error;
@@ -107,6 +108,7 @@ struct ofdm_handle {
   RxState rx;  // receive-side workspaces (rx_state.h)
   SenseState sense;
   DdcState ddc;  // wideband front end (ddc.h / engine_ddc.inc)
+  DdcBankState bank;  // all links of a capture in one pass (ddc_bank.h / engine_ddc_bank.inc)
   DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
 };
 
@@ -532,6 +534,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->h_meta.release();
   h->rx.release();
   h->ddc.release();
+  h->bank.release();
   h->duc.release();
   {
     SenseState& ss = h->sense;
@@ -964,4 +967,5 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_sense.inc"
 #include "engine_rx.inc"
 #include "engine_ddc.inc"
+#include "engine_ddc_bank.inc"
 #include "engine_duc.inc"

@@ -16,6 +16,7 @@ from . import _abi, firdes
 
 MAX_TAPS = _abi.OFDM_DDC_MAX_TAPS
 MAX_DECIM = 64
+MAX_LINKS = _abi.OFDM_DDC_BANK_MAX_LINKS
 # narrowest transition gr.firdes.low_pass turns into at most MAX_TAPS taps: int(53 / (22 w)) forced odd <= 1023
 _MIN_TRANSITION = 53.0 / (22.0 * (MAX_TAPS - 0.5))
 
@@ -67,5 +68,32 @@ def ddc_cfg(decimation, center_freq, taps=None, occupied_fraction=None, transiti
     cfg.ntaps = len(taps)
     cfg.reserved = 0
     cfg.center_freq = float(center_freq)
+    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg
+
+
+def bank_cfg(decimation, center_freqs, taps=None, occupied_fraction=None, transition=None):
+    """ofdm_ddc_bank_cfg for Engine.set_ddc_bank: one decimation and one prototype, one centre frequency per link
+    (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed).  ``taps=None``
+    designs the prototype from ``occupied_fraction`` as ddc_cfg does."""
+    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    if not 1 <= len(fcs) <= MAX_LINKS:
+        raise ValueError("a DDC bank has 1 to %d links" % MAX_LINKS)
+    if not all(abs(f) <= 0.5 for f in fcs):
+        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
+    if taps is None:
+        if occupied_fraction is None:
+            raise ValueError("bank_cfg needs taps or occupied_fraction")
+        taps = design(decimation, occupied_fraction, transition)
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    if not 1 <= len(taps) <= MAX_TAPS:
+        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
+    cfg = _abi.ofdm_ddc_bank_cfg()
+    cfg.struct_size = C.sizeof(_abi.ofdm_ddc_bank_cfg)
+    cfg.decimation = int(decimation)
+    cfg.ntaps = len(taps)
+    cfg.nlinks = len(fcs)
+    for i, f in enumerate(fcs):
+        cfg.center_freq[i] = f
     C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg

@@ -78,6 +78,7 @@ class Engine(object):
         self.last_stats = {}
         self._rx_sense_cfg = None
         self.ddc_cfg = None     # the wideband front end's configuration in force (set_ddc), None without one
+        self.ddc_bank_cfg = None  # the DDC bank's configuration in force (set_ddc_bank), None without one
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
@@ -392,6 +393,64 @@ class Engine(object):
         """HIP-event time of k_ddc in the last ddc() / ddc_device() (needs prof_enable())."""
         ms = C.c_double(0)
         self._check(self._lib.ofdm_ddc_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- DDC bank: every link of a wideband capture in one pass ------------------------------
+    def set_ddc_bank(self, cfg=None, **kw):
+        """Configure the bank: an ``ofdm_ddc_bank_cfg`` (ddc.bank_cfg) or its keywords (decimation=, center_freqs=,
+        taps= / occupied_fraction=).  ``set_ddc_bank(None)`` with no keywords removes it.  Resets the bank's stream
+        state; the single front end (set_ddc) is a separate stage and keeps its own."""
+        if cfg is None and kw:
+            from . import ddc as _ddc
+            cfg = _ddc.bank_cfg(**kw)
+        self._check(self._lib.ofdm_set_ddc_bank(self._h, C.byref(cfg) if cfg is not None else None))
+        self.ddc_bank_cfg = cfg
+
+    def ddc_bank_reset(self, first_sample_index=0):
+        """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
+        self._check(self._lib.ofdm_ddc_bank_reset(self._h, int(first_sample_index)))
+
+    def ddc_bank_count(self, nin):
+        """Outputs PER LINK the next ddc_bank() call of ``nin`` samples produces, from the current stream state."""
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc_bank_count(self._h, int(nin), C.byref(n)))
+        return n.value
+
+    def ddc_bank(self, iq):
+        """Host mode: the next samples of the wideband stream (in the receive IQ format) -> complex64 of shape
+        (K, nout): row i is what ddc() gives for link i's frequency.  Stateful like ddc()."""
+        assert not self.device_ptrs
+        if self.ddc_bank_cfg is None:
+            raise ValueError("ddc_bank() without set_ddc_bank()")
+        iq = self._rx_samples(iq)
+        K = int(self.ddc_bank_cfg.nlinks)
+        cap = max(self.ddc_bank_count(len(iq)), 1)
+        out = np.zeros((K, cap), np.complex64)
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc_bank(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), cap, cap, C.byref(n)))
+        return out[:, :n.value]
+
+    def ddc_bank_device(self, iq_ptr, nin, out_ptr, link_stride, out_cap):
+        """Device mode: both buffers are device pointers; link i's run begins ``link_stride`` samples after link
+        i - 1's and can go straight to rx_device / rx_submit_device.  Returns the number of outputs per link."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_ddc_bank(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(link_stride),
+                                            int(out_cap), C.byref(n)))
+        return n.value
+
+    def ddc_bank_taps(self, link):
+        """The band-pass table of one link as the kernel multiplies with it (complex64)."""
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_ddc_bank_taps(self._h, int(link), None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.complex64)
+        self._check(self._lib.ofdm_ddc_bank_taps(self._h, int(link), _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def ddc_bank_last_ms(self):
+        """HIP-event time of k_ddc_bank in the last ddc_bank() / ddc_bank_device() (needs prof_enable())."""
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_ddc_bank_last_ms(self._h, C.byref(ms)))
         return ms.value
 
     # -- wideband transmit (interpolate and translate behind tx) -------------------------------

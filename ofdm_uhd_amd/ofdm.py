@@ -583,3 +583,91 @@ def _copy_options(options, **overrides):
     for k, v in overrides.items():
         setattr(o, k, v)
     return o
+
+
+class ofdm_demod_bank(object):
+    """
+    Demodulates every link of one wideband capture: K links that share the decimation and the low-pass prototype and
+    differ in their centre frequency (the receive-side counterpart of adding links onto one band with Engine.duc).
+
+    One engine owns the DDC bank (Engine.ddc_bank: all K narrowband streams from one pass over the wideband samples);
+    each stream goes to a plain ofdm_demod of its own.  Link i returns what ofdm_demod(options_i, ddc=dict(decimation=,
+    center_freq=center_freqs[i], taps=)) returns on the same samples.
+    """
+
+    def __init__(self, options, center_freqs, decimation, taps=None, callback=None, iq_format="fc32", iq_scale=None,
+                 device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
+        @param decimation: wideband rate over the modem's rate, 1..64
+        @param taps: the shared prototype; None: ddc.design for the largest occupied_tones / fft_length of the links
+        @param callback: function of three args: link, ok, payload -- per call fired for link 0's packets, then link
+            1's, and so on
+        @param iq_format, iq_scale: format of the WIDEBAND samples, as for ofdm_demod
+        """
+        # every argument is checked before the first engine exists
+        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != len(fcs):
+                raise ValueError("ofdm_demod_bank needs one options object, or one per centre frequency")
+        else:
+            opts = [options] * len(fcs)
+        if callback is not None and not callable(callback):
+            raise ValueError("callback must be callable: callback(link, ok, payload)")
+        fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        cfg = _ddc.bank_cfg(decimation, fcs, taps=taps, occupied_fraction=occ)   # ValueError: K, frequencies, R, taps
+        self._callback = callback
+        self._links = []
+        self._engine = engine.Engine(opts[0], device_id=device_id)
+        try:
+            if fmt != "fc32":
+                self._engine.set_rx_iq_format(fmt, scale)
+            self._engine.set_ddc_bank(cfg)
+            for i, o in enumerate(opts):
+                cb = (lambda ok, payload, link=i: self._callback(link, ok, payload)) if callback is not None else None
+                self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
+        except Exception:
+            self.close()
+            raise
+        self._streaming = False
+
+    def engine(self):
+        """The engine that owns the bank."""
+        return self._engine
+
+    def links(self):
+        """The K per-link demodulators, in the order of the centre frequencies."""
+        return list(self._links)
+
+    def _tune(self, iq, restart):
+        eng = self._engine
+        if restart:
+            eng.ddc_bank_reset(0)
+        if len(iq) == 0:
+            return np.zeros((len(self._links), 0), np.complex64)
+        return eng.ddc_bank(iq)
+
+    def work(self, iq):
+        """Demodulate one contiguous wideband stream: a list of K packet lists."""
+        self._streaming = False
+        y = self._tune(iq, restart=True)
+        return [d.work(y[i]) for i, d in enumerate(self._links)]
+
+    def feed(self, iq, flush=False):
+        """The next chunk of a continuous wideband capture: per link, the packets that became final."""
+        y = self._tune(iq, restart=not self._streaming)
+        self._streaming = not flush
+        return [d.feed(y[i], flush) for i, d in enumerate(self._links)]
+
+    def flush(self):
+        return self.feed(np.zeros((0, 2), np.int16) if self._engine.rx_iq_format == "sc16" else np.zeros(0, np.complex64),
+                         flush=True)
+
+    def close(self):
+        """Closes the bank's engine and the K link engines."""
+        for d in self._links:
+            d.engine().close()
+        self._engine.close()
