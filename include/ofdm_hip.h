@@ -464,6 +464,68 @@ int ofdm_ddc_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, i
  * OFDM_E_INVAL otherwise. */
 int ofdm_ddc_bank_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband receive: rational-rate resampler (L / M) with tuning ahead of ofdm_rx -----------------------------------
+ * The stages above need a capture whose rate is an integer multiple of the modem's.  Recorded captures often are not
+ * (a radio answers a rate request with the rate it can make: "Actual sps for rate", uhd_interface.py): a file taken at
+ * 25 MS/s that holds a 10 MS/s link has the ratio 5/2.  GNU Radio's blks2.rational_resampler_ccf(interpolation,
+ * decimation, taps) fills that gap; this stage is that resampler fused with the DDC's frequency translation, so one
+ * pass over the capture tunes to a link and brings it to the modem's rate for any L / M.  A standalone, stateful stage;
+ * additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and with no resampler configured nothing
+ * here launches, allocates or copies.
+ * Definition.  x[i]: wideband samples, i an absolute index counted from the last reset (ofdm_set_resamp,
+ * ofdm_resamp_reset), zero before that reset's first index; the handle's receive IQ format and scale, converted as
+ * the DDC converts (one float32 multiply per part).  L = interpolation, M = decimation, any integers in 1..64 (the
+ * library does not reduce them); h[k], k in [0, ntaps): real float32 taps at L times the input rate; fc in cycles per
+ * INPUT sample.
+ *   table     c[k] = complex64(h[k] exp(j 2 pi fc k / L)): float64 on the host, rounded once; ofdm_resamp_taps returns
+ *             exactly what the kernel multiplies with.
+ *   output n  sits at position n M on the L-times grid:  i_n = floor(n M / L),  p_n = n M mod L
+ *               v[n] = sum over q >= 0 with p_n + q L < ntaps of  c[p_n + q L] * x[i_n - q]      float32
+ *               y[n] = v[n] r[n]   r[n] = complex64(expj(-2 pi Phi_n / 2^64)),  Phi_n = n D mod 2^64
+ *             D = frac(fc M / L) 2^64 truncated, 0 where frac rounds up to 1 (fc * M / L evaluated in float64).
+ *   additions A += c.re * (x.re, x.im), B += c.im * (x.re, x.im): packed fused multiply-adds begun at +0;
+ *             v = (A.re - B.im, A.im + B.re).  Tap q of an output belongs to chain q mod NG, a chain adds in ascending
+ *             q, the chains are added in ascending order.  NG is a function of (L, M) alone: with
+ *             KC = 16, 8, 4, 2, 1 for max(L, M) <= 1, 2, 4, 8, 64 it is 4 where L * KC < 4 and 1 otherwise.
+ *   rotation  the unfused complex product with the engine's bit-reproducible float64 expj (as in the DDC).
+ *   outputs   a call with input indices [a, a + n) produces every output with a <= i_n < a + n:
+ *             count = ceil((a + n) L / M) - ceil(a L / M), possibly 0; a phase without a tap gives v = 0.
+ *   state     the last (ntaps - 1) / L converted inputs and the absolute index of the next input; separate from the
+ *             DDC's and the bank's: a handle may hold all three.
+ * Nothing depends on where a call, a chunk or a tile starts: any segmentation of a stream gives bit-identical
+ * outputs.  With L = 1 this is the DDC's definition (the summation order, hence the last bits, are this stage's own).
+ * The stream's input index must stay at or below 2^56, as a reset value and after a call (i L and n M then fit 64-bit
+ * integers); a call or reset that breaks this is refused.
+ * Pointers are host or device as the handle was created; ordering behind an ofdm_tx_async in flight and the alignment
+ * rules are ofdm_ddc's.  ofdm_resamp returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, interpolation or decimation outside 1..64, ntaps outside 1..OFDM_RESAMP_MAX_TAPS, a
+ * non-finite tap, |center_freq| > 0.5 or NaN; ofdm_resamp / ofdm_resamp_reset / ofdm_resamp_count / ofdm_resamp_taps
+ * without a configuration; an ofdm_sc16 pointer not 4-byte (float32: 8-byte) aligned; the index limit above.  A
+ * refused configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_resamp_count says (*nout is set); the stream state is then unchanged. */
+#define OFDM_RESAMP_MAX_TAPS 1024
+typedef struct ofdm_resamp_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_resamp_cfg) */
+  uint32_t interpolation; /* L, 1..64 */
+  uint32_t decimation;    /* M, 1..64 */
+  uint32_t ntaps;         /* 1..OFDM_RESAMP_MAX_TAPS */
+  double center_freq;     /* fc, cycles per INPUT sample, [-0.5, 0.5] */
+  float taps[OFDM_RESAMP_MAX_TAPS]; /* real low-pass prototype at L times the input rate, gain L in its pass band */
+} ofdm_resamp_cfg;
+/* rational_resampler_ccf's ctor behind a tuner; NULL: none.  Resets the stream state (history zero, next input 0). */
+int ofdm_set_resamp(ofdm_handle *h, const ofdm_resamp_cfg *cfg);
+/* a new stream whose first sample has this absolute index (at most 2^56): history zero */
+int ofdm_resamp_reset(ofdm_handle *h, uint64_t first_sample_index);
+/* outputs the NEXT ofdm_resamp call of nin samples produces, from the current state */
+int ofdm_resamp_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of the wideband stream in, the samples at L / M times their rate that they complete out */
+int ofdm_resamp(ofdm_handle *h, const void *iq_in, uint64_t nin, ofdm_c32 *iq_out, uint64_t out_cap, uint64_t *nout);
+/* the table the kernel multiplies with (out NULL: size query) */
+int ofdm_resamp_taps(const ofdm_handle *h, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_resamp in the last ofdm_resamp, which must have run with profiling on (ofdm_prof_enable) and
+ * produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_resamp_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband transmit: interpolate and translate (DUC) behind ofdm_tx -------------
  * The mirror image of the stage above.  The reference leaves it to its radio (sink.set_interp / set_center_freq,
  * usrp_transmit_path.py:79-88; generic_usrp.set_interp; the two-channel transmitter of dual_channel/dual_channel.py);

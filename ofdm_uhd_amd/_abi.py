@@ -16,6 +16,7 @@ OFDM_MAX_PKT_LEN = 4096
 OFDM_MAX_CARRIER_HEX = 1024
 OFDM_DDC_MAX_TAPS = 1024
 OFDM_DDC_BANK_MAX_LINKS = 8
+OFDM_RESAMP_MAX_TAPS = 1024
 OFDM_DUC_MAX_TAPS = 1024
 
 OFDM_OK = 0
@@ -164,6 +165,17 @@ class ofdm_duc_cfg(C.Structure):
     ]
 
 
+class ofdm_resamp_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interpolation", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("center_freq", C.c_double),
+        ("taps", C.c_float * OFDM_RESAMP_MAX_TAPS),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -179,6 +191,7 @@ EXPORTS = (
     "ofdm_set_duc", "ofdm_duc_reset", "ofdm_duc", "ofdm_duc_last_ms",
     "ofdm_set_ddc_bank", "ofdm_ddc_bank_reset", "ofdm_ddc_bank_count", "ofdm_ddc_bank", "ofdm_ddc_bank_taps",
     "ofdm_ddc_bank_last_ms",
+    "ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps", "ofdm_resamp_last_ms",
 )
 
 _LIB = None
@@ -224,6 +237,12 @@ def _declare(lib):
     lib.ofdm_ddc_bank.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
     lib.ofdm_ddc_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_ddc_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_resamp.argtypes = [H, C.POINTER(ofdm_resamp_cfg)]
+    lib.ofdm_resamp_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_resamp_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_resamp.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
+    lib.ofdm_resamp_taps.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_resamp_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_duc.argtypes = [H, C.POINTER(ofdm_duc_cfg)]
     lib.ofdm_duc_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_duc.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]

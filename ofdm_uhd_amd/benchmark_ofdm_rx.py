@@ -66,6 +66,7 @@ def make_parser():
                       help="with --ddc-decim, instead of --ddc-freq: comma-separated centres of ALL links in the capture; "
                            "they are extracted in one pass on the GPU (ofdm_demod_bank), one account per link, and "
                            "--to-file gets .linkN appended [default=off]")
+    _options.add_resamp_options(parser)
     parser.add_option("", "--csi-report", default=None,
                       help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
                            "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
@@ -126,7 +127,7 @@ def main(argv=None):
         rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
         rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
-    # (receive_path takes --iq-format / --iq-scale and --ddc-decim / --ddc-freq from the options)
+    # (receive_path takes --iq-format / --iq-scale, --ddc-decim / --ddc-freq and --resamp-* from the options)
     rxpath.run(iqio.file_source(options.from_file, fmt=options.iq_format), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     if options.csi_report is not None:

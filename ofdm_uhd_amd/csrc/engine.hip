@@ -22,6 +22,7 @@
 #include "ddc.h"
 #include "ddc_bank.h"
 #include "duc.h"
+#include "resamp.h"
 
 static std::string g_create_error;
 
@@ -110,6 +111,7 @@ struct ofdm_handle {
   DdcState ddc;  // wideband front end (ddc.h / engine_ddc.inc)
   DdcBankState bank;  // all links of a capture in one pass (ddc_bank.h / engine_ddc_bank.inc)
   DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
+  ResampState resamp;  // rational-rate front end (resamp.h / engine_resamp.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -536,6 +538,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->ddc.release();
   h->bank.release();
   h->duc.release();
+  h->resamp.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -969,3 +972,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_ddc.inc"
 #include "engine_ddc_bank.inc"
 #include "engine_duc.inc"
+#include "engine_resamp.inc"

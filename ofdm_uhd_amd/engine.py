@@ -79,6 +79,7 @@ class Engine(object):
         self._rx_sense_cfg = None
         self.ddc_cfg = None     # the wideband front end's configuration in force (set_ddc), None without one
         self.ddc_bank_cfg = None  # the DDC bank's configuration in force (set_ddc_bank), None without one
+        self.resamp_cfg = None  # the rational-rate front end's configuration in force (set_resamp), None without one
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
@@ -393,6 +394,59 @@ class Engine(object):
         """HIP-event time of k_ddc in the last ddc() / ddc_device() (needs prof_enable())."""
         ms = C.c_double(0)
         self._check(self._lib.ofdm_ddc_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- rational-rate front end (tune and resample by L / M ahead of rx) ----------------------
+    def set_resamp(self, cfg=None, **kw):
+        """Configure the resampler (blks2.rational_resampler_ccf behind a tuner): an ``ofdm_resamp_cfg``
+        (resample.resamp_cfg) or its keywords (interpolation=, decimation=, center_freq=, taps= / occupied_fraction=).
+        ``set_resamp(None)`` with no keywords removes it.  Resets the stream state; the DDC and the bank keep theirs."""
+        if cfg is None and kw:
+            from . import resample as _resample
+            cfg = _resample.resamp_cfg(**kw)
+        self._check(self._lib.ofdm_set_resamp(self._h, C.byref(cfg) if cfg is not None else None))
+        self.resamp_cfg = cfg
+
+    def resamp_reset(self, first_sample_index=0):
+        """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
+        self._check(self._lib.ofdm_resamp_reset(self._h, int(first_sample_index)))
+
+    def resamp_count(self, nin):
+        """Outputs the next resamp() call of ``nin`` samples produces, from the current stream state."""
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_resamp_count(self._h, int(nin), C.byref(n)))
+        return n.value
+
+    def resamp(self, iq):
+        """Host mode: the next samples of the wideband stream (in the receive IQ format) -> the complex64 samples at
+        L / M times their rate that they complete (possibly none).  Stateful: any segmentation gives the same bits."""
+        assert not self.device_ptrs
+        iq = self._rx_samples(iq)
+        out = np.zeros(max(self.resamp_count(len(iq)), 1), np.complex64)
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_resamp(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def resamp_device(self, iq_ptr, nin, out_ptr, out_cap):
+        """Device mode: both buffers are device pointers; ``out_ptr`` can go straight to rx_device / rx_submit_device
+        (same stream).  Returns the number of outputs written."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_resamp(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
+        return n.value
+
+    def resamp_taps(self):
+        """The band-pass table c[k] the kernel multiplies with (complex64)."""
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_resamp_taps(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.complex64)
+        self._check(self._lib.ofdm_resamp_taps(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def resamp_last_ms(self):
+        """HIP-event time of k_resamp in the last resamp() / resamp_device() (needs prof_enable())."""
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_resamp_last_ms(self._h, C.byref(ms)))
         return ms.value
 
     # -- DDC bank: every link of a wideband capture in one pass ------------------------------

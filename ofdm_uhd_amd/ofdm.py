@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, resample as _resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -198,7 +198,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None):
+                 iq_scale=None, ddc=None, resample=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -215,7 +215,12 @@ class ofdm_demod(object):
             wideband sample): work / feed / flush then take the WIDEBAND stream (in ``iq_format``), the engine's
             stateful tune-and-decimate stage (ddc.py, Engine.ddc) turns it into the complex64 stream at the modem's
             rate and the paths below run on that, unchanged.  ``taps=None``: ddc.design for occupied_tones / fft_length
+        @param resample: the same for a capture whose rate is M / L times the modem's, no integer multiple of it:
+            ``dict(interpolation=, decimation=, center_freq=0.0, taps=None)``, the engine's rational-rate stage
+            (resample.py, Engine.resamp) in the DDC's place; ``taps=None``: resample.design.  Not together with ``ddc``
         """
+        if ddc is not None and resample is not None:
+            raise ValueError("ofdm_demod takes ddc= or resample=, not both")
         self._modulation = options.modulation
         self._fft_length = options.fft_length
         self._occupied_tones = options.occupied_tones
@@ -227,13 +232,22 @@ class ofdm_demod(object):
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
         self._engine = engine.Engine(options, device_id=device_id)
-        self._ddc = None
-        if ddc is not None:
+        self._ddc = None             # (format, scale, stage) of the wideband front end: stage is "ddc" or "resamp"
+        if ddc is not None or resample is not None:
             # the 16-bit format, if any, is the wideband side's: the stage's output (the receiver's input) is complex64
-            self._ddc = (iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE))
-            d = dict(ddc)
-            self._engine.set_ddc(_ddc.ddc_cfg(d.pop("decimation"), d.pop("center_freq"), taps=d.pop("taps", None),
-                                              occupied_fraction=self._occupied_tones / float(self._fft_length), **d))
+            fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
+            occ = self._occupied_tones / float(self._fft_length)
+            if ddc is not None:
+                d = dict(ddc)
+                self._engine.set_ddc(_ddc.ddc_cfg(d.pop("decimation"), d.pop("center_freq"), taps=d.pop("taps", None),
+                                                  occupied_fraction=occ, **d))
+                self._ddc = (fmt, scale, "ddc")
+            else:
+                d = dict(resample)
+                self._engine.set_resamp(_resample.resamp_cfg(d.pop("interpolation"), d.pop("decimation"),
+                                                             d.pop("center_freq", 0.0), taps=d.pop("taps", None),
+                                                             occupied_fraction=occ, **d))
+                self._ddc = (fmt, scale, "resamp")
         elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_rx_iq_format(iq_format, iq_scale)
         if quality_callback is not None:
@@ -271,16 +285,17 @@ class ofdm_demod(object):
         if self._ddc is None:
             return iq
         eng = self._engine
+        fmt, scale, stage = self._ddc
         if restart:
-            eng.ddc_reset(0)
+            getattr(eng, stage + "_reset")(0)
         if len(iq) == 0:
             return np.zeros(0, np.complex64)
-        fmt, scale = self._ddc
+        run = getattr(eng, stage)        # Engine.ddc / Engine.resamp, looked up per call
         if fmt == "fc32":
-            return eng.ddc(iq)
+            return run(iq)
         eng.set_rx_iq_format(fmt, scale)
         try:
-            return eng.ddc(iq)
+            return run(iq)
         finally:
             eng.set_rx_iq_format("fc32")
 
@@ -353,7 +368,7 @@ class ofdm_demod(object):
         self._engine.set_flag_history(None)
         self._engine.set_origin(0)
         if self._ddc is not None:
-            self._engine.ddc_reset(0)
+            getattr(self._engine, self._ddc[2] + "_reset")(0)
         self._streaming = False
         self._log_samples = 0
 

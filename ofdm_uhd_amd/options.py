@@ -34,6 +34,29 @@ class eng_option(optparse.Option):
     TYPE_CHECKER["intx"] = _intx
 
 
+def add_resamp_options(parser):
+    """--resamp-interp / --resamp-decim / --resamp-freq: the source is a wideband capture at decim / interp times the
+    modem's rate (no integer multiple needed); resample.py, Engine.resamp."""
+    parser.add_option("", "--resamp-interp", type="intx", default=0,
+                      help="with --resamp-decim: the capture runs at decim / interp times the modem's rate; tune and "
+                           "resample it on the GPU first (0 = off) [default=%default]")
+    parser.add_option("", "--resamp-decim", type="intx", default=0,
+                      help="decimation of the rational-rate front end, 1..64 (0 = off) [default=%default]")
+    parser.add_option("", "--resamp-freq", type="eng_float", default=0.0,
+                      help="with --resamp-interp / --resamp-decim: centre of the link in the capture, cycles per "
+                           "sample in [-0.5, 0.5] [default=%default]")
+
+
+def resamp_from_options(options):
+    """dict(interpolation=, decimation=, center_freq=) from --resamp-*, None where the flags are unset or 0; one of
+    the two ratios alone means the other is 1."""
+    L, M = getattr(options, "resamp_interp", None), getattr(options, "resamp_decim", None)
+    if not L and not M:
+        return None
+    return dict(interpolation=int(L or 1), decimation=int(M or 1),
+                center_freq=float(getattr(options, "resamp_freq", 0.0) or 0.0))
+
+
 def default_options(**overrides):
     """An options object carrying every hot-path flag at the reference's default."""
     v = optparse.Values()

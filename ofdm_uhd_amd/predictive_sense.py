@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from . import config, iqio, window
-from .options import eng_option
+from .options import add_resamp_options, eng_option, resamp_from_options
 
 
 class parse_msg(object):
@@ -87,6 +87,7 @@ class sensor(object):
                                "first (0 = off)")
         parser.add_option("", "--ddc-freq", type="eng_float", default=0.0,
                           help="with --ddc-decim: centre of the sensed band, cycles per source sample in [-0.5, 0.5]")
+        add_resamp_options(parser)
         (options, _args) = parser.parse_args(list(argv) if argv is not None else [])
         self.options = options
         self.min_freq, self.max_freq = options.start, options.stop
@@ -151,14 +152,26 @@ class sensor(object):
         complex64 result (the sensed band fills the decimated rate: a 0.8 / R wide low-pass).  An engine handed in
         with a front end of its own gets that configuration back afterwards (its stream starts afresh)."""
         eng, x = self.engine(), self._samples(iq)
-        if not self.options.ddc_decim:
+        resamp = resamp_from_options(self.options)
+        if self.options.ddc_decim and resamp:
+            raise ValueError("--ddc-decim and --resamp-* are two front ends: give one")
+        if resamp:
+            # the rational-rate front end in the DDC's place (a 0.8 M / L wide low-pass at the capture's rate)
+            prev = eng.resamp_cfg
+            eng.set_resamp(occupied_fraction=0.8, **resamp)
+            try:
+                y = eng.resamp(x)
+            finally:
+                eng.set_resamp(prev)
+        elif self.options.ddc_decim:
+            prev = eng.ddc_cfg
+            eng.set_ddc(decimation=int(self.options.ddc_decim), center_freq=float(self.options.ddc_freq), occupied_fraction=0.8)
+            try:
+                y = eng.ddc(x)
+            finally:
+                eng.set_ddc(prev)
+        else:
             return eng.sense(self.sense_cfg(), x)
-        prev = eng.ddc_cfg
-        eng.set_ddc(decimation=int(self.options.ddc_decim), center_freq=float(self.options.ddc_freq), occupied_fraction=0.8)
-        try:
-            y = eng.ddc(x)
-        finally:
-            eng.set_ddc(prev)
         fmt, scale = eng.rx_iq_format, eng.rx_iq_scale
         if fmt == "fc32":
             return eng.sense(self.sense_cfg(), y)

@@ -1,17 +1,19 @@
 """receive_path: hands the sample stream to ofdm_demod (receive_path.py:29-58)."""
 import copy
 
-from . import ofdm
+from . import ofdm, options as _options
 
 
 class receive_path(object):
     def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
-                 ddc=None):
+                 ddc=None, resample=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
         ``ddc_decim`` / ``ddc_freq`` (--ddc-decim / --ddc-freq), no front end where ddc_decim is unset or 0 (what the
-        reference sets on its radio: set_decim / set_center_freq, usrp_receive_path.py)."""
+        reference sets on its radio: set_decim / set_center_freq, usrp_receive_path.py).
+        ``resample``: rational-rate front end of ofdm_demod, ``dict(interpolation=, decimation=, center_freq=0.0,
+        taps=None)``; None: the options' ``resamp_interp`` / ``resamp_decim`` / ``resamp_freq`` (--resamp-*)."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if iq_format is None:
             iq_format = getattr(options, "iq_format", None) or "fc32"
@@ -21,13 +23,16 @@ class receive_path(object):
         if ddc is None and getattr(options, "ddc_decim", None):
             ddc = dict(decimation=int(options.ddc_decim), center_freq=float(getattr(options, "ddc_freq", 0.0) or 0.0))
 
+        if resample is None:
+            resample = _options.resamp_from_options(options)
+
         self._verbose = getattr(options, "verbose", False)
         self._log = getattr(options, "log", False)
         self._rx_callback = rx_callback      # this callback is fired when there's a packet available
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
                                        quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
-                                       ddc=ddc)
+                                       ddc=ddc, resample=resample)
 
         if self._verbose:
             self._print_verbage()

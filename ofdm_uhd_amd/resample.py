@@ -1,0 +1,87 @@
+"""Wideband receive front end for captures whose rate is no integer multiple of the modem's: tune to one link and
+resample by L / M.
+
+A radio answers a rate request with the rate it can make (the reference's wrapper prints "Actual sps for rate",
+uhd_interface.py), and recorded captures come at whatever rate the recorder ran at.  GNU Radio's stage for this is
+``blks2.rational_resampler_ccf(interpolation, decimation, taps)``; here it is fused with the frequency translation of
+ddc.py and run on the GPU by ``Engine.resamp`` (csrc/resamp.h).  This module holds the host side: the low-pass
+design, the normative band-pass table, the configuration struct and the output count.
+
+Frequencies are in cycles per INPUT (wideband) sample; the taps live at L times the input rate.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, ddc, firdes
+
+MAX_TAPS = _abi.OFDM_RESAMP_MAX_TAPS
+MAX_RATIO = 64
+
+
+def _check_ratio(interpolation, decimation):
+    L, M = int(interpolation), int(decimation)
+    if not 1 <= L <= MAX_RATIO:
+        raise ValueError("interpolation must be in [1, %d]" % MAX_RATIO)
+    if not 1 <= M <= MAX_RATIO:
+        raise ValueError("decimation must be in [1, %d]" % MAX_RATIO)
+    return L, M
+
+
+def design(interpolation, decimation, occupied_fraction, transition=None):
+    """Real low-pass prototype at L times the wideband rate for a link that fills ``occupied_fraction`` of the output
+    band (occupied_tones / fft_length): ``firdes.low_pass(L, 1.0, of / (2M) + transition / 2, transition)`` as
+    float32, odd length -- ddc.design at R = M with gain L (the zero-stuffing by L takes 1 / L away).
+
+    Frequencies here are in cycles per sample of the L-times grid, on which the output rate is 1 / M and the input
+    rate 1 / L.  The signal's edge lies at of / (2M); the first spectrum that folds onto it after decimation begins at
+    1/M - of / (2M).  Default transition: half that gap, (1 - of) / (2M), widened where needed so that
+    ntaps <= OFDM_RESAMP_MAX_TAPS.  ValueError where of * L > M: the link is then wider than the capture."""
+    L, M = _check_ratio(interpolation, decimation)
+    of = float(occupied_fraction)
+    if not 0.0 < of <= 1.0:
+        raise ValueError("occupied_fraction must be in (0, 1]")
+    if of * L > M:
+        raise ValueError("a link that fills %g of the output band is wider than the capture at L / M = %d / %d" % (of, L, M))
+    if transition is None:
+        transition = max((1.0 - of) / (2.0 * M), ddc._MIN_TRANSITION)
+    transition = float(transition)
+    if firdes.compute_ntaps(1.0, transition) > MAX_TAPS:
+        raise ValueError("transition %g needs more than %d taps" % (transition, MAX_TAPS))
+    cutoff = min(of / (2.0 * M) + 0.5 * transition, 0.5)
+    return np.asarray(firdes.low_pass(float(L), 1.0, cutoff, transition, firdes.WIN_HAMMING), np.float32)
+
+
+def bandpass_taps(taps, fc, interpolation):
+    """The normative table c[k] = complex64(h[k] exp(j 2 pi fc k / L)): float32 taps, float64 arithmetic, rounded
+    once.  (``Engine.resamp_taps`` returns the table the kernel holds, computed the same way by the library's libm.)"""
+    h = np.asarray(taps, np.float32).astype(np.float64)
+    k = np.arange(len(h), dtype=np.float64)
+    a = 2.0 * np.pi * float(fc) * k / float(int(interpolation))
+    return (h * np.cos(a) + 1j * (h * np.sin(a))).astype(np.complex64)
+
+
+def count(first, n, interpolation, decimation):
+    """Outputs of a call with input indices [first, first + n): every m with first <= floor(m M / L) < first + n,
+    ceil((first + n) L / M) - ceil(first L / M)."""
+    L, M = int(interpolation), int(decimation)
+    return -(-(int(first) + int(n)) * L // M) - -(-int(first) * L // M)
+
+
+def resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupied_fraction=None, transition=None):
+    """ofdm_resamp_cfg for Engine.set_resamp; ``taps=None`` designs them from ``occupied_fraction``."""
+    if taps is None:
+        if occupied_fraction is None:
+            raise ValueError("resamp_cfg needs taps or occupied_fraction")
+        taps = design(interpolation, decimation, occupied_fraction, transition)
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    if not 1 <= len(taps) <= MAX_TAPS:
+        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
+    cfg = _abi.ofdm_resamp_cfg()
+    cfg.struct_size = C.sizeof(_abi.ofdm_resamp_cfg)
+    cfg.interpolation = int(interpolation)
+    cfg.decimation = int(decimation)
+    cfg.ntaps = len(taps)
+    cfg.center_freq = float(center_freq)
+    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg
