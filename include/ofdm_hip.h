@@ -582,6 +582,73 @@ int ofdm_duc(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const ofdm_c32
  * output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_duc_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband transmit: rational-rate resampler (L / M) behind ofdm_tx -------------------------------------------------
+ * The DUC above needs a band whose rate is an integer multiple of the modem's.  A band at 25 MS/s that is to hold
+ * 10 MS/s links has the ratio 5/2: GNU Radio's blks2.rational_resampler_ccf(interpolation, decimation, taps) in front
+ * of the radio's set_center_freq fills that gap, and this stage is that resampler followed by the DUC's frequency
+ * shift, `add` and 16-bit store -- the transmit-side counterpart of ofdm_resamp.  A standalone, stateful stage;
+ * additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and with the stage not configured nothing
+ * here launches, allocates or copies.
+ * Definition.  x[i]: narrowband complex64 samples, i an absolute index counted from the last reset
+ * (ofdm_set_tx_resamp, ofdm_tx_resamp_reset), zero before that reset's first index.  L = interpolation,
+ * M = decimation, any integers in 1..64 (the library does not reduce them; either may be the larger); h[k],
+ * k in [0, ntaps): real float32 taps at L times the input rate; fc in cycles per OUTPUT sample.
+ *   output n  sits at position n M on the L-times grid:  i_n = floor(n M / L),  p_n = n M mod L
+ *               v[n] = sum over q >= 0 with p_n + q L < ntaps of  h[p_n + q L] * x[i_n - q]     real tap times complex sample
+ *               y[n] = v[n] * r[n]   r[n] = complex64(expj(+2 pi Phi_n / 2^64)),  Phi_n = n D mod 2^64,
+ *                                    D = frac(fc) * 2^64 truncated, 0 where frac rounds up to 1 (the DDC's convention)
+ *               out[n] = store(y[n] + add[n])  when an `add` buffer is given: one float32 addition per part
+ *                      = store(y[n])           otherwise
+ *   additions v[n] is ONE chain in ascending q, begun at +0, of fused multiply-adds on the (re, im) pair: its value is
+ *             a function of n alone.  A phase without a tap (ntaps <= p_n) gives v[n] = 0.
+ *   product   y = v r is the gr_complex product: two products and one addition per part, separately rounded.
+ *   phasor    the engine's bit-reproducible float64 evaluation of expj at the phase (int64)Phi_n * 2 pi / 2^64, once
+ *             per output, rounded to complex64 once -- not the hardware's sin / cos.
+ *   store     complex64, or ofdm_sc16 by the transmit rule: clamp(rintf(part * scale), -32768, 32767), NaN -> 0,
+ *             clamped in float.  out_format and out_scale are the stage's own, as in ofdm_duc_cfg.
+ *   outputs   a call with input indices [a, a + nin) produces every output with a <= i_n < a + nin:
+ *             count = ceil((a + nin) L / M) - ceil(a L / M), possibly 0 when L < M; `add` has that many samples.
+ *   state     the last Q = (ntaps - 1) / L inputs and the absolute index of the next input; separate from the DUC's: a
+ *             handle may hold both.
+ * Nothing depends on where a call, a chunk or a tile starts: any segmentation of a stream gives bit-identical
+ * outputs; calls of 0 inputs, calls shorter than Q and calls that produce nothing are included.  With M = 1 this is
+ * ofdm_duc's definition, chain and rotation included: the outputs are bit-identical to ofdm_duc's.
+ * The stream's input index must stay at or below 2^56, as a reset value and after a call (i L and n M then fit 64-bit
+ * integers); a call or reset that breaks this is refused.
+ * Pointers are host or device as the handle was created.  iq_in is always complex64, whatever the handle's transmit
+ * format.  add (may be NULL) is complex64 and may be iq_out itself when out_format is OFDM_IQ_FC32: each output sample
+ * is read before it is written, by the same thread.  Like ofdm_duc, ofdm_tx_resamp orders itself behind an
+ * ofdm_tx_async still in flight on the transmit stream and returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, interpolation or decimation outside 1..64, ntaps outside 1..OFDM_TX_RESAMP_MAX_TAPS,
+ * bad out_format or out_scale, a non-finite tap, |center_freq| > 0.5 or NaN; ofdm_tx_resamp / ofdm_tx_resamp_reset /
+ * ofdm_tx_resamp_count without a configuration; a float32 pointer not 8-byte (ofdm_sc16: 4-byte) aligned; the index
+ * limit above.  A refused configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_tx_resamp_count says (*nout is set); the stream state is then unchanged. */
+#define OFDM_TX_RESAMP_MAX_TAPS 1024
+typedef struct ofdm_tx_resamp_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_tx_resamp_cfg) */
+  uint32_t interpolation; /* L, 1..64 */
+  uint32_t decimation;    /* M, 1..64 */
+  uint32_t ntaps;         /* 1..OFDM_TX_RESAMP_MAX_TAPS */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  double center_freq;     /* fc, cycles per OUTPUT sample, [-0.5, 0.5] */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  uint32_t reserved;
+  float taps[OFDM_TX_RESAMP_MAX_TAPS]; /* real low-pass prototype at L times the input rate, gain L in its pass band */
+} ofdm_tx_resamp_cfg;
+/* rational_resampler_ccf's ctor + set_center_freq; NULL: none.  Resets the stream state (history zero, next input 0). */
+int ofdm_set_tx_resamp(ofdm_handle *h, const ofdm_tx_resamp_cfg *cfg);
+/* a new stream whose first input has this absolute index (at most 2^56): history zero */
+int ofdm_tx_resamp_reset(ofdm_handle *h, uint64_t first_input_index);
+/* outputs the NEXT ofdm_tx_resamp call of nin samples produces, from the current state */
+int ofdm_tx_resamp_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of the narrowband stream in, the wideband samples they complete out (added onto `add` where given) */
+int ofdm_tx_resamp(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const ofdm_c32 *add, void *iq_out, uint64_t out_cap,
+                   uint64_t *nout);
+/* HIP-event time of k_tx_resamp in the last ofdm_tx_resamp, which must have run with profiling on (ofdm_prof_enable)
+ * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_tx_resamp_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -18,6 +18,7 @@ OFDM_DDC_MAX_TAPS = 1024
 OFDM_DDC_BANK_MAX_LINKS = 8
 OFDM_RESAMP_MAX_TAPS = 1024
 OFDM_DUC_MAX_TAPS = 1024
+OFDM_TX_RESAMP_MAX_TAPS = 1024
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -176,6 +177,20 @@ class ofdm_resamp_cfg(C.Structure):
     ]
 
 
+class ofdm_tx_resamp_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interpolation", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("center_freq", C.c_double),
+        ("out_scale", C.c_float),
+        ("reserved", C.c_uint32),
+        ("taps", C.c_float * OFDM_TX_RESAMP_MAX_TAPS),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -192,6 +207,7 @@ EXPORTS = (
     "ofdm_set_ddc_bank", "ofdm_ddc_bank_reset", "ofdm_ddc_bank_count", "ofdm_ddc_bank", "ofdm_ddc_bank_taps",
     "ofdm_ddc_bank_last_ms",
     "ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps", "ofdm_resamp_last_ms",
+    "ofdm_set_tx_resamp", "ofdm_tx_resamp_reset", "ofdm_tx_resamp_count", "ofdm_tx_resamp", "ofdm_tx_resamp_last_ms",
 )
 
 _LIB = None
@@ -247,6 +263,11 @@ def _declare(lib):
     lib.ofdm_duc_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_duc.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
     lib.ofdm_duc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_tx_resamp.argtypes = [H, C.POINTER(ofdm_tx_resamp_cfg)]
+    lib.ofdm_tx_resamp_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_tx_resamp_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_tx_resamp.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+    lib.ofdm_tx_resamp_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

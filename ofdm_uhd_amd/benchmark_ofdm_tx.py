@@ -54,6 +54,7 @@ def make_parser():
     parser.add_option("", "--duc-freq", type="eng_float", default=0.0,
                       help="with --duc-interp: centre of the link in the wideband file, cycles per sample in "
                            "[-0.5, 0.5] (the radio's set_center_freq over the file's rate) [default=%default]")
+    _options.add_tx_resamp_options(parser)
     transmit_path.transmit_path.add_options(parser, expert_grp)
     ofdm.ofdm_mod.add_options(parser, expert_grp)
     return parser
@@ -71,7 +72,7 @@ def main(argv=None):
         print(os.path.getsize(options.from_file))
 
     txpath = transmit_path.transmit_path(options)
-    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format and --duc-interp / --duc-freq from the options)
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format and --duc-interp / --duc-freq, --tx-resamp-* from the options)
     txpath.connect(sink)
     npk = 0
     for payload in build_payloads(options, src):

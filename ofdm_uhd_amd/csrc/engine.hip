@@ -23,6 +23,7 @@
 #include "ddc_bank.h"
 #include "duc.h"
 #include "resamp.h"
+#include "tx_resamp.h"
 
 static std::string g_create_error;
 
@@ -112,6 +113,7 @@ struct ofdm_handle {
   DdcBankState bank;  // all links of a capture in one pass (ddc_bank.h / engine_ddc_bank.inc)
   DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
   ResampState resamp;  // rational-rate front end (resamp.h / engine_resamp.inc)
+  TxResampState tx_resamp;  // rational-rate transmit stage (tx_resamp.h / engine_tx_resamp.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -539,6 +541,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->bank.release();
   h->duc.release();
   h->resamp.release();
+  h->tx_resamp.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -973,3 +976,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_ddc_bank.inc"
 #include "engine_duc.inc"
 #include "engine_resamp.inc"
+#include "engine_tx_resamp.inc"

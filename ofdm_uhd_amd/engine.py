@@ -81,6 +81,7 @@ class Engine(object):
         self.ddc_bank_cfg = None  # the DDC bank's configuration in force (set_ddc_bank), None without one
         self.resamp_cfg = None  # the rational-rate front end's configuration in force (set_resamp), None without one
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
+        self.tx_resamp_cfg = None  # the rational-rate transmit stage's configuration in force (set_tx_resamp), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -558,6 +559,65 @@ class Engine(object):
         """HIP-event time of k_duc in the last duc() / duc_device() (needs prof_enable())."""
         ms = C.c_double(0)
         self._check(self._lib.ofdm_duc_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- rational-rate transmit (resample by L / M and translate behind tx) ---------------------
+    def set_tx_resamp(self, cfg=None, **kw):
+        """Configure the rational-rate transmit stage (blks2.rational_resampler_ccf + set_center_freq): an
+        ``ofdm_tx_resamp_cfg`` (tx_resample.tx_resamp_cfg) or its keywords (interpolation=, decimation=, center_freq=,
+        taps= / occupied_fraction=, out_format=, out_scale=).  ``set_tx_resamp(None)`` with no keywords removes it.
+        Resets the stream state; the DUC keeps its own."""
+        if cfg is None and kw:
+            from . import tx_resample as _tx_resample
+            cfg = _tx_resample.tx_resamp_cfg(**kw)
+        self._check(self._lib.ofdm_set_tx_resamp(self._h, C.byref(cfg) if cfg is not None else None))
+        self.tx_resamp_cfg = cfg
+
+    def tx_resamp_reset(self, first=0):
+        """Start a new narrowband stream whose first sample has this absolute index; the filter history is zero."""
+        self._check(self._lib.ofdm_tx_resamp_reset(self._h, int(first)))
+
+    def tx_resamp_count(self, nin):
+        """Outputs the next tx_resamp() call of ``nin`` samples produces, from the current stream state."""
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_tx_resamp_count(self._h, int(nin), C.byref(n)))
+        return n.value
+
+    def tx_resamp(self, iq, add=None):
+        """Host mode: the next complex64 samples of the narrowband stream -> the wideband samples at L / M times their
+        rate that they complete (possibly none; complex64, or int16 of shape (n, 2) with out_format "sc16"), added
+        onto the complex64 band ``add`` where one is given.  Stateful: any segmentation gives the same bits."""
+        assert not self.device_ptrs
+        if self.tx_resamp_cfg is None:
+            raise ValueError("tx_resamp() without set_tx_resamp()")
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("tx_resamp() takes complex64 samples (its 16-bit side is the output)")
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        no = self.tx_resamp_count(len(iq))
+        if add is not None:
+            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
+            if len(add) != no:
+                raise ValueError("add must hold tx_resamp_count(len(iq)) samples")
+        sc16 = self.tx_resamp_cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_tx_resamp(self._h, _ptr(iq) if len(iq) else None, len(iq),
+                                             _ptr(add) if add is not None and no else None, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def tx_resamp_device(self, iq_ptr, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; ``iq_ptr`` can be what tx_device(wait=False) is filling (same
+        handle), ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns the number of outputs written."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_tx_resamp(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
+                                             C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
+        return n.value
+
+    def tx_resamp_last_ms(self):
+        """HIP-event time of k_tx_resamp in the last tx_resamp() / tx_resamp_device() (needs prof_enable())."""
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_tx_resamp_last_ms(self._h, C.byref(ms)))
         return ms.value
 
     # -- chunked streams --------------------------------------------------------------

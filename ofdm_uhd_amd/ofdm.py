@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, resample as _resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -26,7 +26,8 @@ class ofdm_mod(object):
     Send packets by calling send_pkt
     """
 
-    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None):
+    def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
+                 resample=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
@@ -42,7 +43,13 @@ class ofdm_mod(object):
                stores it; the stream continues across flush() calls (a batch's filter tail comes out in front of the
                next batch) until flush(end=True) / send_pkt(eof=True).  ``taps=None``: duc.design for
                occupied_tones / fft_length
+        @param resample: the same for a band whose rate is L / M times the modem's, no integer multiple of it:
+               ``dict(interpolation=, decimation=, center_freq=0.0, taps=None)``, the engine's rational-rate transmit
+               stage (tx_resample.py, Engine.tx_resamp) in the DUC's place; ``taps=None``: tx_resample.design.  Not
+               together with ``duc``
         """
+        if duc is not None and resample is not None:
+            raise ValueError("ofdm_mod takes duc= or resample=, not both")
         self._pad_for_usrp = pad_for_usrp
         self._msgq_limit = msgq_limit
         self._modulation = options.modulation
@@ -58,14 +65,22 @@ class ofdm_mod(object):
         # the modulator alone has unit gain after its 1/sqrt(N) (ofdm.py:114); transmit_path sets the amplitude
         cfg_opts = _copy_options(options, tx_amplitude=1.0)
         self._engine = engine.Engine(cfg_opts, pad_for_usrp=pad_for_usrp, device_id=device_id)
-        self._duc = duc is not None
+        self._duc = None             # the wideband stage in force: "duc" or "tx_resamp" (Engine.<stage>, <stage>_reset, <stage>_cfg)
         self._duc_live = False       # the wideband stream holds samples whose filter tail is still to come
-        if self._duc:
+        occ = self._occupied_tones / float(self._fft_length)
+        if duc is not None:
             # the 16-bit format, if any, is the wideband side's: the modulator's output (the stage's input) is complex64
             d = dict(duc)
             self._engine.set_duc(_duc.duc_cfg(d.pop("interpolation"), d.pop("center_freq"), taps=d.pop("taps", None),
-                                              occupied_fraction=self._occupied_tones / float(self._fft_length),
+                                              occupied_fraction=occ,
                                               out_format=iqio.check_format(iq_format), out_scale=iq_scale, **d))
+            self._duc = "duc"
+        elif resample is not None:
+            d = dict(resample)
+            self._engine.set_tx_resamp(_tx_resample.tx_resamp_cfg(
+                d.pop("interpolation"), d.pop("decimation"), d.pop("center_freq", 0.0), taps=d.pop("taps", None),
+                occupied_fraction=occ, out_format=iqio.check_format(iq_format), out_scale=iq_scale, **d))
+            self._duc = "tx_resamp"
         elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
         self._pending = []
@@ -123,9 +138,9 @@ class ofdm_mod(object):
 
     def flush(self, end=False):
         """Modulate everything queued so far; returns the samples (also written to the sink).  With a wideband stage
-        (duc=) they are the wideband stream's next samples; ``end=True`` then appends the filter's tail (Q zero
+        (duc= / resample=) they are the wideband stream's next samples (with resample= possibly none yet); ``end=True`` then appends the filter's tail (Q zero
         narrowband samples pushed through) and starts the stage afresh."""
-        end = end and self._duc and (self._duc_live or bool(self._pending))
+        end = end and self._duc is not None and (self._duc_live or bool(self._pending))
         if not self._pending and not end:
             return None
         iq = None
@@ -136,14 +151,15 @@ class ofdm_mod(object):
             self.packets_sent += len(pending)
             if self._log:
                 self._write_logs(iq)
-        if self._duc:
+        if self._duc is not None:
             eng = self._engine
-            parts = [eng.duc(iq)] if iq is not None else []
+            run = getattr(eng, self._duc)        # Engine.duc / Engine.tx_resamp, looked up per call
+            parts = [run(iq)] if iq is not None else []
             self._duc_live = True
             if end:
-                cfg = eng.duc_cfg
-                parts.append(eng.duc(np.zeros((cfg.ntaps - 1) // cfg.interpolation, np.complex64)))
-                eng.duc_reset(0)
+                cfg = getattr(eng, self._duc + "_cfg")
+                parts.append(run(np.zeros((cfg.ntaps - 1) // cfg.interpolation, np.complex64)))
+                getattr(eng, self._duc + "_reset")(0)
                 self._duc_live = False
             iq = np.concatenate(parts) if len(parts) > 1 else parts[0]
         if self._sink is not None:

@@ -57,6 +57,29 @@ def resamp_from_options(options):
                 center_freq=float(getattr(options, "resamp_freq", 0.0) or 0.0))
 
 
+def add_tx_resamp_options(parser):
+    """--tx-resamp-interp / --tx-resamp-decim / --tx-resamp-freq: the sink is a wideband band at interp / decim times
+    the modem's rate (no integer multiple needed); tx_resample.py, Engine.tx_resamp."""
+    parser.add_option("", "--tx-resamp-interp", type="intx", default=0,
+                      help="with --tx-resamp-decim: write a wideband IQ file at interp / decim times the modem's rate; "
+                           "resample and shift the signal on the GPU (0 = off) [default=%default]")
+    parser.add_option("", "--tx-resamp-decim", type="intx", default=0,
+                      help="decimation of the rational-rate transmit stage, 1..64 (0 = off) [default=%default]")
+    parser.add_option("", "--tx-resamp-freq", type="eng_float", default=0.0,
+                      help="with --tx-resamp-interp / --tx-resamp-decim: centre of the link in the wideband file, "
+                           "cycles per sample in [-0.5, 0.5] [default=%default]")
+
+
+def tx_resamp_from_options(options):
+    """dict(interpolation=, decimation=, center_freq=) from --tx-resamp-*, None where the flags are unset or 0; one of
+    the two ratios alone means the other is 1."""
+    L, M = getattr(options, "tx_resamp_interp", None), getattr(options, "tx_resamp_decim", None)
+    if not L and not M:
+        return None
+    return dict(interpolation=int(L or 1), decimation=int(M or 1),
+                center_freq=float(getattr(options, "tx_resamp_freq", 0.0) or 0.0))
+
+
 def default_options(**overrides):
     """An options object carrying every hot-path flag at the reference's default."""
     v = optparse.Values()

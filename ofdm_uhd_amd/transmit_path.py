@@ -3,7 +3,7 @@
 the gain stage (gr.multiply_const_cc ``amp``) is folded into the modulator kernel's store."""
 import copy
 
-from . import ofdm
+from . import ofdm, options as _options
 
 # flag, group, keyword arguments of the reference's option table (transmit_path.py:72-79)
 _FLAGS = (
@@ -17,14 +17,18 @@ _FLAGS = (
 
 
 class transmit_path(object):
-    def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None):
+    def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
+                 resample=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``duc``: wideband transmit stage of ofdm_mod, ``dict(interpolation=, center_freq=, taps=None)``; None: the
         options' ``duc_interp`` / ``duc_freq`` (--duc-interp / --duc-freq), no stage where duc_interp is unset or 0
-        (what the reference sets on its radio: set_interp / set_center_freq, usrp_transmit_path.py)."""
+        (what the reference sets on its radio: set_interp / set_center_freq, usrp_transmit_path.py).
+        ``resample``: rational-rate transmit stage of ofdm_mod, ``dict(interpolation=, decimation=, center_freq=0.0,
+        taps=None)``; None: the options' ``tx_resamp_interp`` / ``tx_resamp_decim`` / ``tx_resamp_freq``
+        (--tx-resamp-*)."""
         opts = copy.copy(options)
         if iq_format is None:
             iq_format = getattr(opts, "iq_format", None) or "fc32"
@@ -32,12 +36,14 @@ class transmit_path(object):
             iq_scale = getattr(opts, "iq_scale", None)
         if duc is None and getattr(opts, "duc_interp", None):
             duc = dict(interpolation=int(opts.duc_interp), center_freq=float(getattr(opts, "duc_freq", 0.0) or 0.0))
+        if resample is None:
+            resample = _options.tx_resamp_from_options(opts)
         self._apply_carrier_map = bool(apply_carrier_map)
         self._verbose = bool(getattr(opts, "verbose", False))
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
-                                     iq_scale=iq_scale, duc=duc)
+                                     iq_scale=iq_scale, duc=duc, resample=resample)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
