@@ -155,38 +155,17 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc(DdcParams q) {
   }
 }
 
-// the last H = ntaps - 1 converted samples after this call, into the other history buffer: a call shorter than H keeps
-// the tail of the old history, which is therefore never overwritten while it is read
-template <typename XT>
-__global__ void __launch_bounds__(256) k_ddc_hist(const XT* __restrict__ x, uint64_t nin, const c32* __restrict__ old,
-                                                  c32* __restrict__ nw, int H, float scale) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= H) return;
-  const int64_t gi = (int64_t)nin - H + i;
-  nw[i] = gi >= 0 ? iq_load(x, gi, scale) : old[(int64_t)i + (int64_t)nin];
-}
+// (the history kernel is k_stream_hist, stream_hist.h, with H = ntaps - 1)
 
-// host side (engine_ddc.inc)
-struct DdcState {
-  bool on = false;
+// host side (engine_ddc.inc): StreamStage (host_util.h) and the DDC's own
+struct DdcState : StreamStage {
   int R = 1, ntaps = 1;
   double fc = 0.0;
   uint64_t D = 0;          // frac(fc R) in 2^-64 turn
-  uint64_t next = 0;       // absolute index of the next input sample
-  int cur = 0;             // d_hist[cur] holds the samples before `next`
   std::vector<c32> tab;    // the table the kernel multiplies with
-  DevBuf d_tab, d_hist[2], d_in, d_out;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;      // last_ms is of the last ofdm_ddc
+  DevBuf d_tab;
   void release() {
     d_tab.release();
-    d_hist[0].release();
-    d_hist[1].release();
-    d_in.release();
-    d_out.release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    StreamStage::release();
   }
 };

@@ -181,27 +181,15 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc_bank(DdcBankParams q) {
   if (K - l0 >= 1) ddc_bank_pass<1, OPT, TJ>(q, xs, tap, cmb, l0, M0, tid);
 }
 
-// host side (engine_ddc_bank.inc): the stream state is the bank's own, shared by its links
-struct DdcBankState {
-  bool on = false;
+// host side (engine_ddc_bank.inc): the stream state (StreamStage, host_util.h) is the bank's own, shared by its links
+struct DdcBankState : StreamStage {
   int R = 1, ntaps = 1, K = 0;
   double fc[DDC_BANK_MAX_LINKS] = {};
   uint64_t D[DDC_BANK_MAX_LINKS] = {};
-  uint64_t next = 0;       // absolute index of the next input sample
-  int cur = 0;             // d_hist[cur] holds the samples before `next`
   std::vector<c32> tab;    // link i's table at tab[i * ntaps], as ofdm_ddc_bank_taps returns it
-  DevBuf d_tab, d_hist[2], d_in, d_out;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;      // last_ms is of the last ofdm_ddc_bank
+  DevBuf d_tab;
   void release() {
     d_tab.release();
-    d_hist[0].release();
-    d_hist[1].release();
-    d_in.release();
-    d_out.release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    StreamStage::release();
   }
 };

@@ -130,38 +130,18 @@ __global__ void __launch_bounds__(DUC_THREADS) k_duc(DucParams q) {
   }
 }
 
-// the last Q samples after this call, into the other history buffer: a call shorter than Q keeps the tail of the old
-// history, which is therefore never overwritten while it is read
-__global__ void __launch_bounds__(256) k_duc_hist(const c32* __restrict__ x, uint64_t nin, const c32* __restrict__ old,
-                                                  c32* __restrict__ nw, int Q) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  const int64_t gi = (int64_t)nin - Q + i;
-  nw[i] = gi >= 0 ? x[gi] : old[(int64_t)i + (int64_t)nin];
-}
+// (the history kernel is k_stream_hist<c32>, stream_hist.h, with H = Q: the last Q inputs after a call)
 
-// host side (engine_duc.inc)
-struct DucState {
-  bool on = false;
-  int L = 1, ntaps = 1, Q = 0;
+// host side (engine_duc.inc): StreamStage (host_util.h; hist = Q) and the DUC's own
+struct DucState : StreamStage {
+  int L = 1, ntaps = 1;
   int out_fmt = OFDM_IQ_FC32;
   float out_scale = 32768.0f;
   uint64_t D = 0;     // frac(fc) in 2^-64 turn
-  uint64_t next = 0;  // absolute index of the next input sample
-  int cur = 0;        // d_hist[cur] holds the Q samples before `next`
-  DevBuf d_taps, d_hist[2], d_in, d_add, d_out;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;  // last_ms is of the last ofdm_duc
+  DevBuf d_taps, d_add;
   void release() {
     d_taps.release();
-    d_hist[0].release();
-    d_hist[1].release();
-    d_in.release();
     d_add.release();
-    d_out.release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    StreamStage::release();
   }
 };

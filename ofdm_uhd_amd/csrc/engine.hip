@@ -19,6 +19,7 @@
 #include "rx_deframe.h"
 #include "rx_state.h"
 #include "sense.h"
+#include "stream_hist.h"
 #include "ddc.h"
 #include "ddc_bank.h"
 #include "duc.h"
@@ -972,6 +973,7 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 
 #include "engine_sense.inc"
 #include "engine_rx.inc"
+#include "engine_stage.inc"
 #include "engine_ddc.inc"
 #include "engine_ddc_bank.inc"
 #include "engine_duc.inc"

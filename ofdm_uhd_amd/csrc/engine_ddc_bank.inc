@@ -1,82 +1,51 @@
-// engine_ddc_bank.inc -- host side of the DDC bank (ddc_bank.h): configuration, stream state, launches.
-// Included by engine.hip after engine_ddc.inc (ddc_turns, ddc_first_output, DDC_MAX_INDEX).
-
-static int ddc_bank_zero_history(ofdm_handle* h) {
-  DdcBankState& d = h->bank;
-  const size_t bytes = sizeof(c32) * (size_t)std::max(d.ntaps - 1, 1);
-  for (int i = 0; i < 2; i++) HIPCHK(h, hipMemsetAsync(d.d_hist[i].p, 0, bytes, h->stream));
-  d.cur = 0;
-  return OFDM_OK;
-}
+// engine_ddc_bank.inc -- host side of the DDC bank (ddc_bank.h): configuration, launches, the per-link copy-back.
+// Included by engine.hip after engine_stage.inc and engine_ddc.inc (DDC_MAX_INDEX).
 
 /* K gr.freq_xlating_fir_filter_ccf ctors that share decimation and prototype (dual_channel/dual_channel.py tunes one
  * radio channel per link) */
 extern "C" int ofdm_set_ddc_bank(ofdm_handle* h, const ofdm_ddc_bank_cfg* cfg) {
   if (!h) return OFDM_E_INVAL;
   DdcBankState& d = h->bank;
-  if (!cfg) {
-    d.on = false;
-    d.next = 0;
-    d.timed = false;
-    return OFDM_OK;
-  }
+  if (!cfg) return stage_off(d);
   if (cfg->struct_size != sizeof(ofdm_ddc_bank_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank_cfg.struct_size does not match this library");
   if (cfg->decimation < 1 || cfg->decimation > DDC_MAX_DECIM) FAIL(h, OFDM_E_INVAL, "DDC bank decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_DDC_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "DDC bank ntaps must be in [1, 1024]");
   if (cfg->nlinks < 1 || cfg->nlinks > OFDM_DDC_BANK_MAX_LINKS) FAIL(h, OFDM_E_INVAL, "DDC bank nlinks must be in [1, 8]");
   for (uint32_t i = 0; i < cfg->nlinks; i++)
     if (!(fabs(cfg->center_freq[i]) <= 0.5)) FAIL(h, OFDM_E_INVAL, "DDC bank center_freq must be in [-0.5, 0.5] cycles per sample");
-  for (uint32_t k = 0; k < cfg->ntaps; k++)
-    if (!std::isfinite(cfg->taps[k])) FAIL(h, OFDM_E_INVAL, "DDC bank taps must be finite");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipStreamSynchronize(h->stream));  // a call in flight may still read the old tables
-  d.on = false;
+  if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "DDC bank taps must be finite");
+  RCCHK(stage_disarm(h, d));
   d.R = (int)cfg->decimation;
   d.ntaps = (int)cfg->ntaps;
   d.K = (int)cfg->nlinks;
   const int KP = (d.K + 1) & ~1;
-  // the band-pass tables: float64, rounded once (the DDC's formula); the device copy is link-minor
-  d.tab.resize((size_t)d.K * d.ntaps);
+  // every link's table is the DDC's; the device copy is link-minor
+  d.tab.clear();
   std::vector<c32> dev((size_t)d.ntaps * KP, c32{0.f, 0.f});
   for (int i = 0; i < d.K; i++) {
     d.fc[i] = cfg->center_freq[i];
     d.D[i] = ddc_turns(d.fc[i] * (double)d.R);
-    for (int k = 0; k < d.ntaps; k++) {
-      const double a = 2.0 * M_PI * d.fc[i] * (double)k;
-      const c32 c = c32{(float)((double)cfg->taps[k] * cos(a)), (float)((double)cfg->taps[k] * sin(a))};
-      d.tab[(size_t)i * d.ntaps + k] = c;
-      dev[(size_t)k * KP + i] = c;
-    }
+    const std::vector<c32> c = bandpass_table(cfg->taps, d.ntaps, d.fc[i], 1);
+    d.tab.insert(d.tab.end(), c.begin(), c.end());
+    for (int k = 0; k < d.ntaps; k++) dev[(size_t)k * KP + i] = c[k];
   }
   HIPCHK(h, upload(d.d_tab, dev.data(), dev.size()));
-  for (int i = 0; i < 2; i++) HIPCHK(h, d.d_hist[i].ensure(sizeof(c32) * (size_t)std::max(d.ntaps - 1, 1)));
-  int rc = ddc_bank_zero_history(h);
-  if (rc) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  d.next = 0;
-  d.timed = false;
-  d.on = true;
-  return OFDM_OK;
+  return stage_arm(h, d, d.ntaps - 1);
 }
 
 extern "C" int ofdm_ddc_bank_reset(ofdm_handle* h, uint64_t first_sample_index) {
   if (!h) return OFDM_E_INVAL;
-  DdcBankState& d = h->bank;
-  if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank_reset without ofdm_set_ddc_bank");
+  if (!h->bank.on) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank_reset without ofdm_set_ddc_bank");
   if (first_sample_index > DDC_MAX_INDEX) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank_reset: first_sample_index must be at most 2^62");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  int rc = ddc_bank_zero_history(h);
-  if (rc) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  d.next = first_sample_index;
-  return OFDM_OK;
+  return stage_reset(h, h->bank, first_sample_index);
 }
 
+// (nin is not bounded here, as in ofdm_ddc_count)
 extern "C" int ofdm_ddc_bank_count(const ofdm_handle* h, uint64_t nin, uint64_t* nout) {
   if (!h || !nout) return OFDM_E_INVAL;
   const DdcBankState& d = h->bank;
   if (!d.on) return OFDM_E_INVAL;
-  *nout = ddc_first_output(d.next + nin, (uint64_t)d.R) - ddc_first_output(d.next, (uint64_t)d.R);
+  *nout = first_output(d.next + nin, 1, (uint64_t)d.R) - first_output(d.next, 1, (uint64_t)d.R);
   return OFDM_OK;
 }
 
@@ -84,18 +53,12 @@ extern "C" int ofdm_ddc_bank_taps(const ofdm_handle* h, int link, ofdm_c32* out,
   if (!h || !n) return OFDM_E_INVAL;
   const DdcBankState& d = h->bank;
   if (!d.on || link < 0 || link >= d.K) return OFDM_E_INVAL;
-  *n = d.ntaps;
-  if (!out) return OFDM_OK;
-  if (cap < d.ntaps) return OFDM_E_CAPACITY;
-  memcpy(out, d.tab.data() + (size_t)link * d.ntaps, sizeof(c32) * (size_t)d.ntaps);
-  return OFDM_OK;
+  return stage_taps_out(d.tab.data() + (size_t)link * d.ntaps, d.ntaps, out, cap, n);
 }
 
 extern "C" int ofdm_ddc_bank_last_ms(const ofdm_handle* h, double* ms) {
-  if (!h || !ms) return OFDM_E_INVAL;
-  if (!h->bank.timed) return OFDM_E_INVAL;
-  *ms = h->bank.last_ms;
-  return OFDM_OK;
+  if (!h) return OFDM_E_INVAL;
+  return stage_last_ms(h->bank, ms);
 }
 
 template <typename XT, int OPT, int TJ>
@@ -122,30 +85,24 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
   DdcBankState& d = h->bank;
   if (!nout) FAIL(h, OFDM_E_INVAL, "null argument");
   if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank without ofdm_set_ddc_bank");
-  const bool s16 = h->rx_fmt == OFDM_IQ_SC16;
-  if (nin && !iq_in) FAIL(h, OFDM_E_INVAL, "null iq_in");
-  if (s16 && ((uintptr_t)iq_in & 3u)) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
-  if (!s16 && ((uintptr_t)iq_in & 7u)) FAIL(h, OFDM_E_INVAL, "float32 IQ buffers must be 8-byte aligned");
+  RCCHK(stage_check_rx_in(h, iq_in, nin));
   const uint64_t R = (uint64_t)d.R, a = d.next, K = (uint64_t)d.K;
   // (indices stay below 2^63: a + nin, the tile's M0 R and the signed sample offsets in the kernel cannot wrap)
   if (nin > DDC_MAX_INDEX || a + nin > 2 * DDC_MAX_INDEX) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank: the stream's sample index would pass 2^63");
-  const uint64_t m0 = ddc_first_output(a, R), no = ddc_first_output(a + nin, R) - m0;
+  const uint64_t m0 = first_output(a, 1, R), no = first_output(a + nin, 1, R) - m0;
   *nout = no;
   if (no > out_cap) FAIL(h, OFDM_E_CAPACITY, "iq_out too small per link (see ofdm_ddc_bank_count)");
   if (K > 1 && link_stride < no) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank: link_stride is smaller than the outputs of one link");
   if (no && !iq_out) FAIL(h, OFDM_E_INVAL, "null iq_out");
   d.timed = false;
   if (nin == 0) return OFDM_OK;
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  // a transmit batch still in flight (ofdm_tx_async) may be writing the caller's input
-  if (h->tx_pending && h->txs != h->stream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_tx_done, 0));
+  RCCHK(stage_enter(h));
 
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
   uint64_t stride = link_stride;
   if (!h->dev_ptrs) {
-    HIPCHK(h, d.d_in.ensure(nin * rx_ss(h)));
-    HIPCHK(h, hipMemcpyAsync(d.d_in.p, iq_in, nin * rx_ss(h), hipMemcpyHostToDevice, h->stream));
+    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
     d_in = d.d_in.p;
     if (no) {
       HIPCHK(h, d.d_out.ensure(K * no * sizeof(c32)));
@@ -153,12 +110,7 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
       stride = no;
     }
   }
-  const int H = d.ntaps - 1;
   const bool timing = h->prof.on && no > 0;
-  if (timing && !d.ev_a) {
-    HIPCHK(h, hipEventCreate(&d.ev_a));
-    HIPCHK(h, hipEventCreate(&d.ev_b));
-  }
   if (no) {
     const DdcGeom g = ddc_geom(d.R);
     DdcBankParams p;
@@ -174,7 +126,7 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
     p.b.magic = (1ull << 32) / R + 1;
     p.b.R = d.R;
     p.b.ntaps = d.ntaps;
-    p.b.Q = H / d.R;
+    p.b.Q = d.hist / d.R;
     p.b.W = ddc_pitch(g.T(), p.b.Q);
     p.b.scale = h->rx_scale;
     for (int i = 0; i < d.K; i++) p.D[i] = d.D[i];
@@ -184,34 +136,13 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
     const uint64_t grid = (no + (uint64_t)g.T() - 1) / (uint64_t)g.T();
     if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank: call too long (split it)");
     const size_t lds = ddc_bank_lds_bytes(d.R, d.ntaps, d.K);
-    if (timing) HIPCHK(h, hipEventRecord(d.ev_a, h->stream));
-    int rc = s16 ? launch_ddc_bank<sc16>(h, p, g, (unsigned)grid, lds) : launch_ddc_bank<c32>(h, p, g, (unsigned)grid, lds);
-    if (rc) return rc;
-    if (timing) HIPCHK(h, hipEventRecord(d.ev_b, h->stream));
-    HIPCHK(h, hipGetLastError());
+    RCCHK(stage_time_begin(h, d, timing));
+    RCCHK(h->rx_fmt == OFDM_IQ_SC16 ? launch_ddc_bank<sc16>(h, p, g, (unsigned)grid, lds) : launch_ddc_bank<c32>(h, p, g, (unsigned)grid, lds));
+    RCCHK(stage_time_end(h, d, timing));
   }
-  if (H > 0) {
-    const unsigned grid = (unsigned)((H + 255) / 256);
-    c32* nw = d.d_hist[d.cur ^ 1].as<c32>();
-    if (s16)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ddc_hist<sc16>), dim3(grid), dim3(256), 0, h->stream, static_cast<const sc16*>(d_in), nin,
-                         d.d_hist[d.cur].as<c32>(), nw, H, h->rx_scale);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ddc_hist<c32>), dim3(grid), dim3(256), 0, h->stream, static_cast<const c32*>(d_in), nin,
-                         d.d_hist[d.cur].as<c32>(), nw, H, h->rx_scale);
-    HIPCHK(h, hipGetLastError());
-  }
+  RCCHK(stage_roll_rx_history(h, d, d_in, nin));
   if (!h->dev_ptrs && no)
     for (uint64_t i = 0; i < K; i++)
       HIPCHK(h, hipMemcpyAsync(iq_out + i * link_stride, d_out + i * no, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (H > 0) d.cur ^= 1;
-  d.next = a + nin;
-  if (timing) {
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, d.ev_a, d.ev_b));
-    d.last_ms = (double)ms;
-    d.timed = true;
-  }
-  return OFDM_OK;
+  return stage_finish(h, d, nin, timing);
 }

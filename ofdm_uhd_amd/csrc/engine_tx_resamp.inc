@@ -1,90 +1,51 @@
-// engine_tx_resamp.inc -- host side of the rational-rate transmit stage (tx_resamp.h): configuration, stream state,
-// launches.  Included by engine.hip after engine_ddc.inc (ddc_turns).
+// engine_tx_resamp.inc -- host side of the rational-rate transmit stage (tx_resamp.h): configuration, index limits,
+// launches.  Included by engine.hip after engine_stage.inc (the stream skeleton it shares with the other stages).
 
 constexpr uint64_t TX_RESAMP_MAX_INDEX = 1ull << 56;  // largest input index: i L and n M stay inside 64-bit integers
-
-static int tx_resamp_zero_history(ofdm_handle* h) {
-  TxResampState& d = h->tx_resamp;
-  const size_t bytes = sizeof(c32) * (size_t)std::max(d.Q, 1);
-  for (int i = 0; i < 2; i++) HIPCHK(h, hipMemsetAsync(d.d_hist[i].p, 0, bytes, h->stream));
-  d.cur = 0;
-  return OFDM_OK;
-}
 
 /* blks2.rational_resampler_ccf(interpolation, decimation, taps) in front of the radio's set_center_freq */
 extern "C" int ofdm_set_tx_resamp(ofdm_handle* h, const ofdm_tx_resamp_cfg* cfg) {
   if (!h) return OFDM_E_INVAL;
   TxResampState& d = h->tx_resamp;
-  if (!cfg) {
-    d.on = false;
-    d.next = 0;
-    d.timed = false;
-    return OFDM_OK;
-  }
+  if (!cfg) return stage_off(d);
   if (cfg->struct_size != sizeof(ofdm_tx_resamp_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp_cfg.struct_size does not match this library");
   if (cfg->interpolation < 1 || cfg->interpolation > TX_RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "transmit resampler interpolation must be in [1, 64]");
   if (cfg->decimation < 1 || cfg->decimation > TX_RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "transmit resampler decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_TX_RESAMP_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "transmit resampler ntaps must be in [1, 1024]");
-  if (cfg->out_format != OFDM_IQ_FC32 && cfg->out_format != OFDM_IQ_SC16) FAIL(h, OFDM_E_INVAL, "unknown transmit resampler out_format");
-  float scale = 32768.0f;
-  if (cfg->out_format == OFDM_IQ_SC16 && cfg->out_scale != 0.0f) {
-    if (!(std::isfinite(cfg->out_scale) && cfg->out_scale > 0.0f)) FAIL(h, OFDM_E_INVAL, "transmit resampler out_scale must be finite and positive (0: 2^15)");
-    scale = cfg->out_scale;
-  }
+  float scale;
+  RCCHK(stage_out_scale(h, "transmit resampler", cfg->out_format, cfg->out_scale, &scale));
   if (!(fabs(cfg->center_freq) <= 0.5)) FAIL(h, OFDM_E_INVAL, "transmit resampler center_freq must be in [-0.5, 0.5] cycles per output sample");
-  for (uint32_t k = 0; k < cfg->ntaps; k++)
-    if (!std::isfinite(cfg->taps[k])) FAIL(h, OFDM_E_INVAL, "transmit resampler taps must be finite");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  HIPCHK(h, hipStreamSynchronize(h->stream));  // a call in flight may still read the old taps
-  d.on = false;
+  if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "transmit resampler taps must be finite");
+  RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
   d.M = (int)cfg->decimation;
   d.ntaps = (int)cfg->ntaps;
-  d.Q = (d.ntaps - 1) / d.L;
   d.out_fmt = (int)cfg->out_format;
   d.out_scale = scale;
   d.D = ddc_turns(cfg->center_freq);
   HIPCHK(h, upload(d.d_taps, cfg->taps, (size_t)d.ntaps));
-  for (int i = 0; i < 2; i++) HIPCHK(h, d.d_hist[i].ensure(sizeof(c32) * (size_t)std::max(d.Q, 1)));
-  int rc = tx_resamp_zero_history(h);
-  if (rc) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  d.next = 0;
-  d.timed = false;
-  d.on = true;
-  return OFDM_OK;
+  return stage_arm(h, d, (d.ntaps - 1) / d.L);
 }
 
 extern "C" int ofdm_tx_resamp_reset(ofdm_handle* h, uint64_t first_input_index) {
   if (!h) return OFDM_E_INVAL;
-  TxResampState& d = h->tx_resamp;
-  if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp_reset without ofdm_set_tx_resamp");
+  if (!h->tx_resamp.on) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp_reset without ofdm_set_tx_resamp");
   if (first_input_index > TX_RESAMP_MAX_INDEX) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp_reset: first_input_index must be at most 2^56");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  int rc = tx_resamp_zero_history(h);
-  if (rc) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  d.next = first_input_index;
-  return OFDM_OK;
+  return stage_reset(h, h->tx_resamp, first_input_index);
 }
-
-// the first output n with i_n = floor(n M / L) >= a: ceil(a L / M)   (a <= 2^56, L <= 64: no overflow)
-static uint64_t tx_resamp_first_output(uint64_t a, uint64_t L, uint64_t M) { return (a * L + M - 1) / M; }
 
 extern "C" int ofdm_tx_resamp_count(const ofdm_handle* h, uint64_t nin, uint64_t* nout) {
   if (!h || !nout) return OFDM_E_INVAL;
   const TxResampState& d = h->tx_resamp;
   if (!d.on) return OFDM_E_INVAL;
   if (nin > TX_RESAMP_MAX_INDEX || d.next + nin > TX_RESAMP_MAX_INDEX) return OFDM_E_INVAL;
-  *nout = tx_resamp_first_output(d.next + nin, (uint64_t)d.L, (uint64_t)d.M) - tx_resamp_first_output(d.next, (uint64_t)d.L, (uint64_t)d.M);
+  *nout = first_output(d.next + nin, (uint64_t)d.L, (uint64_t)d.M) - first_output(d.next, (uint64_t)d.L, (uint64_t)d.M);
   return OFDM_OK;
 }
 
 extern "C" int ofdm_tx_resamp_last_ms(const ofdm_handle* h, double* ms) {
-  if (!h || !ms) return OFDM_E_INVAL;
-  if (!h->tx_resamp.timed) return OFDM_E_INVAL;
-  *ms = h->tx_resamp.last_ms;
-  return OFDM_OK;
+  if (!h) return OFDM_E_INVAL;
+  return stage_last_ms(h->tx_resamp, ms);
 }
 
 template <typename OUT, bool ADD>
@@ -106,13 +67,10 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
   if (!nout) FAIL(h, OFDM_E_INVAL, "null argument");
   if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp without ofdm_set_tx_resamp");
   const bool s16 = d.out_fmt == OFDM_IQ_SC16;
-  if (nin && !iq_in) FAIL(h, OFDM_E_INVAL, "null iq_in");
-  if (((uintptr_t)iq_in & 7u) || ((uintptr_t)add & 7u)) FAIL(h, OFDM_E_INVAL, "float32 IQ buffers must be 8-byte aligned");
-  if (s16 && ((uintptr_t)iq_out & 3u)) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
-  if (!s16 && ((uintptr_t)iq_out & 7u)) FAIL(h, OFDM_E_INVAL, "float32 IQ buffers must be 8-byte aligned");
+  RCCHK(stage_check_tx_bufs(h, s16, iq_in, nin, add, iq_out));
   const uint64_t L = (uint64_t)d.L, M = (uint64_t)d.M, a = d.next;
   if (nin > TX_RESAMP_MAX_INDEX || a + nin > TX_RESAMP_MAX_INDEX) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp: the stream's input index would pass 2^56");
-  const uint64_t n0 = tx_resamp_first_output(a, L, M), no = tx_resamp_first_output(a + nin, L, M) - n0;
+  const uint64_t n0 = first_output(a, L, M), no = first_output(a + nin, L, M) - n0;
   *nout = no;
   if (no > out_cap) FAIL(h, OFDM_E_CAPACITY, "iq_out too small (see ofdm_tx_resamp_count)");
   if (no && !iq_out) FAIL(h, OFDM_E_INVAL, "null iq_out");
@@ -122,22 +80,18 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
   const uint64_t TJ = (uint64_t)g.TJ(), J0 = n0 / L;
   const uint64_t grid = no ? ((n0 + no + L - 1) / L - J0 + TJ - 1) / TJ : 0;
   if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp: call too long (split it)");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  // a transmit batch still in flight (ofdm_tx_async) may be writing the caller's input
-  if (h->tx_pending && h->txs != h->stream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_tx_done, 0));
+  RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
   const c32* d_in = reinterpret_cast<const c32*>(iq_in);
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
   if (!h->dev_ptrs) {
-    HIPCHK(h, d.d_in.ensure(nin * sizeof(c32)));
-    HIPCHK(h, hipMemcpyAsync(d.d_in.p, iq_in, nin * sizeof(c32), hipMemcpyHostToDevice, h->stream));
+    RCCHK(stage_upload(h, d.d_in, iq_in, nin * sizeof(c32)));
     d_in = d.d_in.as<c32>();
     if (no) {
       if (add) {
-        HIPCHK(h, d.d_add.ensure(no * sizeof(c32)));
-        HIPCHK(h, hipMemcpyAsync(d.d_add.p, add, no * sizeof(c32), hipMemcpyHostToDevice, h->stream));
+        RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
         d_add = d.d_add.as<c32>();
       }
       HIPCHK(h, d.d_out.ensure(no * oss));
@@ -145,10 +99,6 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
     }
   }
   const bool timing = h->prof.on && no > 0;
-  if (timing && !d.ev_a) {
-    HIPCHK(h, hipEventCreate(&d.ev_a));
-    HIPCHK(h, hipEventCreate(&d.ev_b));
-  }
   if (no) {
     TxResampParams p;
     memset(&p, 0, sizeof(p));
@@ -168,14 +118,14 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
     p.L = d.L;
     p.M = d.M;
     p.ntaps = d.ntaps;
-    p.Q = d.Q;
-    p.QM = resamp_hist_periods(d.Q, d.M);
+    p.Q = d.hist;
+    p.QM = resamp_hist_periods(p.Q, d.M);
     p.W = resamp_pitch(g.TJ(), p.QM);
     p.TP = g.TJ() | 1;
     p.KC = g.kc;
     p.scale = d.out_scale;
     const size_t lds = tx_resamp_lds_bytes(d.L, d.M, d.ntaps);
-    if (timing) HIPCHK(h, hipEventRecord(d.ev_a, h->stream));
+    RCCHK(stage_time_begin(h, d, timing));
     if (s16) {
       if (add) HIPCHK(h, (launch_tx_resamp<sc16, true>(h, p, (unsigned)grid, lds)));
       else HIPCHK(h, (launch_tx_resamp<sc16, false>(h, p, (unsigned)grid, lds)));
@@ -183,23 +133,9 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
       if (add) HIPCHK(h, (launch_tx_resamp<c32, true>(h, p, (unsigned)grid, lds)));
       else HIPCHK(h, (launch_tx_resamp<c32, false>(h, p, (unsigned)grid, lds)));
     }
-    if (timing) HIPCHK(h, hipEventRecord(d.ev_b, h->stream));
-    HIPCHK(h, hipGetLastError());
+    RCCHK(stage_time_end(h, d, timing));
   }
-  if (d.Q > 0) {
-    hipLaunchKernelGGL(k_duc_hist, dim3((unsigned)((d.Q + 255) / 256)), dim3(256), 0, h->stream, d_in, nin, d.d_hist[d.cur].as<c32>(),
-                       d.d_hist[d.cur ^ 1].as<c32>(), d.Q);
-    HIPCHK(h, hipGetLastError());
-  }
+  RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));
   if (!h->dev_ptrs && no) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (d.Q > 0) d.cur ^= 1;
-  d.next = a + nin;
-  if (timing) {
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, d.ev_a, d.ev_b));
-    d.last_ms = (double)ms;
-    d.timed = true;
-  }
-  return OFDM_OK;
+  return stage_finish(h, d, nin, timing);
 }

@@ -58,6 +58,30 @@ struct PinBuf {
   }
 };
 
+// What the five wideband stream stages (DDC, DDC bank, DUC, both resamplers) share on the host: where the stream
+// stands, the carried history and its double buffer, the host-mode staging buffers and the HIP-event pair of the
+// last call.  Each stage's state derives from it and adds its own rates, tables and output format; the code that
+// works on these fields is engine_stage.inc.
+struct StreamStage {
+  bool on = false;
+  uint64_t next = 0;  // absolute index of the next input sample
+  int cur = 0;        // d_hist[cur] holds the `hist` samples before `next`
+  int hist = 0;       // samples of history a call reaches back: ntaps - 1 (DDC, bank), Q = (ntaps - 1) / L (the others)
+  DevBuf d_hist[2], d_in, d_out;
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  double last_ms = 0.0;
+  bool timed = false;  // last_ms is of the stage's last call
+  void release() {
+    d_hist[0].release();
+    d_hist[1].release();
+    d_in.release();
+    d_out.release();
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+    ev_a = ev_b = nullptr;
+  }
+};
+
 struct ProfSpan {
   int kernel;
   hipEvent_t a, b;

@@ -21,9 +21,10 @@
 // odd pitch) and leave in output order: every global store of a wave is one contiguous run.
 #pragma once
 #include "common.h"
-#include "ddc.h"  // ddc_f2, ddc_f4, k_ddc_hist
+#include "ddc.h"  // ddc_f2, ddc_f4
 #include "host_util.h"
 #include "rx_demod.h"  // nco_radians, dexpj
+#include "stream_hist.h"  // k_stream_hist
 
 constexpr int RESAMP_THREADS = 256;
 constexpr int RESAMP_MAX_RATIO = 64;  // largest L and largest M
@@ -169,29 +170,17 @@ __global__ void __launch_bounds__(RESAMP_THREADS) k_resamp(ResampParams q) {
   }
 }
 
-// (the history kernel is k_ddc_hist with H = Q: the last Q converted samples after a call, into the other buffer)
+// (the history kernel is k_stream_hist, stream_hist.h, with H = Q: the last Q converted samples after a call)
 
-// host side (engine_resamp.inc)
-struct ResampState {
-  bool on = false;
-  int L = 1, M = 1, ntaps = 1, Q = 0;
+// host side (engine_resamp.inc): StreamStage (host_util.h; hist = Q) and the resampler's own
+struct ResampState : StreamStage {
+  int L = 1, M = 1, ntaps = 1;
   double fc = 0.0;
   uint64_t D = 0;          // frac(fc M / L) in 2^-64 turn
-  uint64_t next = 0;       // absolute index of the next input sample
-  int cur = 0;             // d_hist[cur] holds the Q samples before `next`
   std::vector<c32> tab;    // the table the kernel multiplies with
-  DevBuf d_tab, d_hist[2], d_in, d_out;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;      // last_ms is of the last ofdm_resamp
+  DevBuf d_tab;
   void release() {
     d_tab.release();
-    d_hist[0].release();
-    d_hist[1].release();
-    d_in.release();
-    d_out.release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    StreamStage::release();
   }
 };

@@ -21,10 +21,10 @@
 #pragma once
 #include "common.h"
 #include "ddc.h"  // ddc_f2, ddc_f4
-#include "duc.h"  // k_duc_hist
 #include "host_util.h"
 #include "resamp.h"    // resamp_geom, resamp_hist_periods, resamp_pitch
 #include "rx_demod.h"  // nco_radians, dexpj
+#include "stream_hist.h"  // k_stream_hist
 
 constexpr int TX_RESAMP_THREADS = 256;
 constexpr int TX_RESAMP_MAX_RATIO = 64;       // largest L and largest M
@@ -155,30 +155,18 @@ __global__ void __launch_bounds__(TX_RESAMP_THREADS) k_tx_resamp(TxResampParams 
   }
 }
 
-// (the history kernel is k_duc_hist: the last Q inputs after a call, into the other buffer)
+// (the history kernel is k_stream_hist<c32>, stream_hist.h, with H = Q: the last Q inputs after a call)
 
-// host side (engine_tx_resamp.inc)
-struct TxResampState {
-  bool on = false;
-  int L = 1, M = 1, ntaps = 1, Q = 0;
+// host side (engine_tx_resamp.inc): StreamStage (host_util.h; hist = Q) and the stage's own
+struct TxResampState : StreamStage {
+  int L = 1, M = 1, ntaps = 1;
   int out_fmt = OFDM_IQ_FC32;
   float out_scale = 32768.0f;
   uint64_t D = 0;     // frac(fc) in 2^-64 turn
-  uint64_t next = 0;  // absolute index of the next input sample
-  int cur = 0;        // d_hist[cur] holds the Q samples before `next`
-  DevBuf d_taps, d_hist[2], d_in, d_add, d_out;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;  // last_ms is of the last ofdm_tx_resamp
+  DevBuf d_taps, d_add;
   void release() {
     d_taps.release();
-    d_hist[0].release();
-    d_hist[1].release();
-    d_in.release();
     d_add.release();
-    d_out.release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    StreamStage::release();
   }
 };

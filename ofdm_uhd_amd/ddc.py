@@ -44,31 +44,39 @@ def design(decimation, occupied_fraction, transition=None):
     return np.asarray(firdes.low_pass(1.0, 1.0, cutoff, transition, firdes.WIN_HAMMING), np.float32)
 
 
-def bandpass_taps(taps, fc):
-    """The normative table c[k] = complex64(h[k] exp(j 2 pi fc k)): float32 taps, float64 arithmetic, rounded once.
-    (``Engine.ddc_taps`` returns the table the kernel holds, computed the same way by the library's libm.)"""
+def bandpass_taps(taps, fc, interpolation=1):
+    """The normative table c[k] = complex64(h[k] exp(j 2 pi fc k / L)): float32 taps, float64 arithmetic, rounded
+    once; L = 1 for the DDC and the bank (the division is then exact).  (``Engine.ddc_taps`` / ``resamp_taps`` return
+    the table the kernel holds, computed the same way by the library's libm.)"""
     h = np.asarray(taps, np.float32).astype(np.float64)
     k = np.arange(len(h), dtype=np.float64)
-    a = 2.0 * np.pi * float(fc) * k
+    a = 2.0 * np.pi * float(fc) * k / float(int(interpolation))
     return (h * np.cos(a) + 1j * (h * np.sin(a))).astype(np.complex64)
+
+
+def _cfg_with_taps(struct, who, max_taps, taps, occupied_fraction, design_taps):
+    """A zeroed ``struct`` (one of the five stages' configurations) with struct_size, ntaps and taps filled in: the
+    given taps as float32 or, with ``taps=None``, what ``design_taps()`` makes of ``occupied_fraction``."""
+    if taps is None:
+        if occupied_fraction is None:
+            raise ValueError("%s needs taps or occupied_fraction" % who)
+        taps = design_taps()
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    if not 1 <= len(taps) <= max_taps:
+        raise ValueError("ntaps must be in [1, %d]" % max_taps)
+    cfg = struct()
+    cfg.struct_size = C.sizeof(struct)
+    cfg.ntaps = len(taps)
+    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg
 
 
 def ddc_cfg(decimation, center_freq, taps=None, occupied_fraction=None, transition=None):
     """ofdm_ddc_cfg for Engine.set_ddc; ``taps=None`` designs them from ``occupied_fraction``."""
-    if taps is None:
-        if occupied_fraction is None:
-            raise ValueError("ddc_cfg needs taps or occupied_fraction")
-        taps = design(decimation, occupied_fraction, transition)
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    if not 1 <= len(taps) <= MAX_TAPS:
-        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
-    cfg = _abi.ofdm_ddc_cfg()
-    cfg.struct_size = C.sizeof(_abi.ofdm_ddc_cfg)
+    cfg = _cfg_with_taps(_abi.ofdm_ddc_cfg, "ddc_cfg", MAX_TAPS, taps, occupied_fraction,
+                         lambda: design(decimation, occupied_fraction, transition))
     cfg.decimation = int(decimation)
-    cfg.ntaps = len(taps)
-    cfg.reserved = 0
     cfg.center_freq = float(center_freq)
-    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg
 
 
@@ -81,19 +89,10 @@ def bank_cfg(decimation, center_freqs, taps=None, occupied_fraction=None, transi
         raise ValueError("a DDC bank has 1 to %d links" % MAX_LINKS)
     if not all(abs(f) <= 0.5 for f in fcs):
         raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
-    if taps is None:
-        if occupied_fraction is None:
-            raise ValueError("bank_cfg needs taps or occupied_fraction")
-        taps = design(decimation, occupied_fraction, transition)
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    if not 1 <= len(taps) <= MAX_TAPS:
-        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
-    cfg = _abi.ofdm_ddc_bank_cfg()
-    cfg.struct_size = C.sizeof(_abi.ofdm_ddc_bank_cfg)
+    cfg = _cfg_with_taps(_abi.ofdm_ddc_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
+                         lambda: design(decimation, occupied_fraction, transition))
     cfg.decimation = int(decimation)
-    cfg.ntaps = len(taps)
     cfg.nlinks = len(fcs)
     for i, f in enumerate(fcs):
         cfg.center_freq[i] = f
-    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg

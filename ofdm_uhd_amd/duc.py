@@ -8,8 +8,6 @@ the configuration struct.
 
 Frequencies are in cycles per OUTPUT (wideband) sample.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _abi, ddc, iqio
@@ -35,20 +33,10 @@ def duc_cfg(interpolation, center_freq, taps=None, occupied_fraction=None, trans
             out_scale=None):
     """ofdm_duc_cfg for Engine.set_duc; ``taps=None`` designs them from ``occupied_fraction``.  ``out_format`` is
     "fc32" or "sc16" (``out_scale`` None: 2^15)."""
-    if taps is None:
-        if occupied_fraction is None:
-            raise ValueError("duc_cfg needs taps or occupied_fraction")
-        taps = design(interpolation, occupied_fraction, transition)
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    if not 1 <= len(taps) <= MAX_TAPS:
-        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
-    cfg = _abi.ofdm_duc_cfg()
-    cfg.struct_size = C.sizeof(_abi.ofdm_duc_cfg)
+    cfg = ddc._cfg_with_taps(_abi.ofdm_duc_cfg, "duc_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, occupied_fraction, transition))
     cfg.interpolation = int(interpolation)
-    cfg.ntaps = len(taps)
     cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
     cfg.center_freq = float(center_freq)
     cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    cfg.reserved = 0
-    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg

@@ -14,6 +14,7 @@ There is no CPU implementation behind this class: if the library is missing,
 importing fails loudly (see _abi.load).
 """
 import ctypes as C
+import importlib
 
 import numpy as np
 
@@ -344,132 +345,152 @@ class Engine(object):
         n = npk.value
         return n, off[:n + 1], ln[:n], ok[:n]
 
+    # -- the five wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
+    def _stage_set(self, name, maker, cfg, kw):
+        """ofdm_set_<name>: ``cfg`` or, from keywords, what ``maker`` ("module.function" of this package) builds."""
+        if cfg is None and kw:
+            mod, fn = maker.split(".")
+            cfg = getattr(importlib.import_module("." + mod, __package__), fn)(**kw)
+        self._check(getattr(self._lib, "ofdm_set_" + name)(self._h, C.byref(cfg) if cfg is not None else None))
+        setattr(self, name + "_cfg", cfg)
+
+    def _stage_reset(self, name, first):
+        self._check(getattr(self._lib, "ofdm_%s_reset" % name)(self._h, int(first)))
+
+    def _stage_count(self, name, nin):
+        n = C.c_uint64(0)
+        self._check(getattr(self._lib, "ofdm_%s_count" % name)(self._h, int(nin), C.byref(n)))
+        return n.value
+
+    def _stage_taps(self, name, *link):
+        fn = getattr(self._lib, "ofdm_%s_taps" % name)
+        n = C.c_int(0)
+        self._check(fn(self._h, *(link + (None, 0, C.byref(n)))))
+        out = np.zeros(n.value, np.complex64)
+        self._check(fn(self._h, *(link + (_ptr(out), n.value, C.byref(n)))))
+        return out
+
+    def _stage_last_ms(self, name):
+        ms = C.c_double(0)
+        self._check(getattr(self._lib, "ofdm_%s_last_ms" % name)(self._h, C.byref(ms)))
+        return ms.value
+
+    def _stage_call(self, name, *args):
+        """ofdm_<name>(handle, args..., &nout) -> nout"""
+        n = C.c_uint64(0)
+        self._check(getattr(self._lib, "ofdm_" + name)(self._h, *(args + (C.byref(n),))))
+        return n.value
+
+    def _stage_device(self, name, *args):
+        assert self.device_ptrs
+        return self._stage_call(name, *args)
+
+    def _rx_stage(self, name, iq):
+        """Host mode of a receive stage with one output run: ddc() and resamp()."""
+        assert not self.device_ptrs
+        iq = self._rx_samples(iq)
+        out = np.zeros(max(self._stage_count(name, len(iq)), 1), np.complex64)
+        return out[:self._stage_call(name, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), len(out))]
+
+    def _tx_stage(self, name, iq, add, count, add_size):
+        """Host mode of a transmit stage, duc() and tx_resamp(): ``count`` gives the outputs of len(iq) inputs."""
+        assert not self.device_ptrs
+        cfg = getattr(self, name + "_cfg")
+        if cfg is None:
+            raise ValueError("%s() without set_%s()" % (name, name))
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("%s() takes complex64 samples (its 16-bit side is the output)" % name)
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        no = count(len(iq))
+        if add is not None:
+            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
+            if len(add) != no:
+                raise ValueError("add must hold %s samples" % add_size)
+        sc16 = cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
+        return out[:self._stage_call(name, _ptr(iq) if len(iq) else None, len(iq),
+                                     _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
+
     # -- wideband front end (tune and decimate ahead of rx) ---------------------------------
     def set_ddc(self, cfg=None, **kw):
         """Configure the front end (usrp2.source_32fc.set_decim + set_center_freq; gr.freq_xlating_fir_filter_ccf):
         an ``ofdm_ddc_cfg`` (ddc.ddc_cfg) or its keywords (decimation=, center_freq=, taps= / occupied_fraction=).
         ``set_ddc(None)`` with no keywords removes it.  Resets the stream state."""
-        if cfg is None and kw:
-            from . import ddc as _ddc
-            cfg = _ddc.ddc_cfg(**kw)
-        self._check(self._lib.ofdm_set_ddc(self._h, C.byref(cfg) if cfg is not None else None))
-        self.ddc_cfg = cfg
+        self._stage_set("ddc", "ddc.ddc_cfg", cfg, kw)
 
     def ddc_reset(self, first_sample_index=0):
         """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
-        self._check(self._lib.ofdm_ddc_reset(self._h, int(first_sample_index)))
+        self._stage_reset("ddc", first_sample_index)
 
     def ddc_count(self, nin):
         """Outputs the next ddc() call of ``nin`` samples produces, from the current stream state."""
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc_count(self._h, int(nin), C.byref(n)))
-        return n.value
+        return self._stage_count("ddc", nin)
 
     def ddc(self, iq):
         """Host mode: the next samples of the wideband stream (in the receive IQ format) -> the narrowband complex64
         samples they complete (possibly none).  Stateful: any segmentation of a stream gives the same bits."""
-        assert not self.device_ptrs
-        iq = self._rx_samples(iq)
-        out = np.zeros(max(self.ddc_count(len(iq)), 1), np.complex64)
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), len(out), C.byref(n)))
-        return out[:n.value]
+        return self._rx_stage("ddc", iq)
 
     def ddc_device(self, iq_ptr, nin, out_ptr, out_cap):
         """Device mode: both buffers are device pointers; ``out_ptr`` can go straight to rx_device / rx_submit_device
         (same stream).  Returns the number of outputs written."""
-        assert self.device_ptrs
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
-        return n.value
+        return self._stage_device("ddc", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap))
 
     def ddc_taps(self):
         """The band-pass table c[k] the kernel multiplies with (complex64)."""
-        n = C.c_int(0)
-        self._check(self._lib.ofdm_ddc_taps(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, np.complex64)
-        self._check(self._lib.ofdm_ddc_taps(self._h, _ptr(out), n.value, C.byref(n)))
-        return out
+        return self._stage_taps("ddc")
 
     def ddc_last_ms(self):
         """HIP-event time of k_ddc in the last ddc() / ddc_device() (needs prof_enable())."""
-        ms = C.c_double(0)
-        self._check(self._lib.ofdm_ddc_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._stage_last_ms("ddc")
 
     # -- rational-rate front end (tune and resample by L / M ahead of rx) ----------------------
     def set_resamp(self, cfg=None, **kw):
         """Configure the resampler (blks2.rational_resampler_ccf behind a tuner): an ``ofdm_resamp_cfg``
         (resample.resamp_cfg) or its keywords (interpolation=, decimation=, center_freq=, taps= / occupied_fraction=).
         ``set_resamp(None)`` with no keywords removes it.  Resets the stream state; the DDC and the bank keep theirs."""
-        if cfg is None and kw:
-            from . import resample as _resample
-            cfg = _resample.resamp_cfg(**kw)
-        self._check(self._lib.ofdm_set_resamp(self._h, C.byref(cfg) if cfg is not None else None))
-        self.resamp_cfg = cfg
+        self._stage_set("resamp", "resample.resamp_cfg", cfg, kw)
 
     def resamp_reset(self, first_sample_index=0):
         """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
-        self._check(self._lib.ofdm_resamp_reset(self._h, int(first_sample_index)))
+        self._stage_reset("resamp", first_sample_index)
 
     def resamp_count(self, nin):
         """Outputs the next resamp() call of ``nin`` samples produces, from the current stream state."""
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_resamp_count(self._h, int(nin), C.byref(n)))
-        return n.value
+        return self._stage_count("resamp", nin)
 
     def resamp(self, iq):
         """Host mode: the next samples of the wideband stream (in the receive IQ format) -> the complex64 samples at
         L / M times their rate that they complete (possibly none).  Stateful: any segmentation gives the same bits."""
-        assert not self.device_ptrs
-        iq = self._rx_samples(iq)
-        out = np.zeros(max(self.resamp_count(len(iq)), 1), np.complex64)
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_resamp(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), len(out), C.byref(n)))
-        return out[:n.value]
+        return self._rx_stage("resamp", iq)
 
     def resamp_device(self, iq_ptr, nin, out_ptr, out_cap):
         """Device mode: both buffers are device pointers; ``out_ptr`` can go straight to rx_device / rx_submit_device
         (same stream).  Returns the number of outputs written."""
-        assert self.device_ptrs
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_resamp(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
-        return n.value
+        return self._stage_device("resamp", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap))
 
     def resamp_taps(self):
         """The band-pass table c[k] the kernel multiplies with (complex64)."""
-        n = C.c_int(0)
-        self._check(self._lib.ofdm_resamp_taps(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, np.complex64)
-        self._check(self._lib.ofdm_resamp_taps(self._h, _ptr(out), n.value, C.byref(n)))
-        return out
+        return self._stage_taps("resamp")
 
     def resamp_last_ms(self):
         """HIP-event time of k_resamp in the last resamp() / resamp_device() (needs prof_enable())."""
-        ms = C.c_double(0)
-        self._check(self._lib.ofdm_resamp_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._stage_last_ms("resamp")
 
     # -- DDC bank: every link of a wideband capture in one pass ------------------------------
     def set_ddc_bank(self, cfg=None, **kw):
         """Configure the bank: an ``ofdm_ddc_bank_cfg`` (ddc.bank_cfg) or its keywords (decimation=, center_freqs=,
         taps= / occupied_fraction=).  ``set_ddc_bank(None)`` with no keywords removes it.  Resets the bank's stream
         state; the single front end (set_ddc) is a separate stage and keeps its own."""
-        if cfg is None and kw:
-            from . import ddc as _ddc
-            cfg = _ddc.bank_cfg(**kw)
-        self._check(self._lib.ofdm_set_ddc_bank(self._h, C.byref(cfg) if cfg is not None else None))
-        self.ddc_bank_cfg = cfg
+        self._stage_set("ddc_bank", "ddc.bank_cfg", cfg, kw)
 
     def ddc_bank_reset(self, first_sample_index=0):
         """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
-        self._check(self._lib.ofdm_ddc_bank_reset(self._h, int(first_sample_index)))
+        self._stage_reset("ddc_bank", first_sample_index)
 
     def ddc_bank_count(self, nin):
         """Outputs PER LINK the next ddc_bank() call of ``nin`` samples produces, from the current stream state."""
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc_bank_count(self._h, int(nin), C.byref(n)))
-        return n.value
+        return self._stage_count("ddc_bank", nin)
 
     def ddc_bank(self, iq):
         """Host mode: the next samples of the wideband stream (in the receive IQ format) -> complex64 of shape
@@ -481,85 +502,49 @@ class Engine(object):
         K = int(self.ddc_bank_cfg.nlinks)
         cap = max(self.ddc_bank_count(len(iq)), 1)
         out = np.zeros((K, cap), np.complex64)
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc_bank(self._h, _ptr(iq) if len(iq) else None, len(iq), _ptr(out), cap, cap, C.byref(n)))
-        return out[:, :n.value]
+        return out[:, :self._stage_call("ddc_bank", _ptr(iq) if len(iq) else None, len(iq), _ptr(out), cap, cap)]
 
     def ddc_bank_device(self, iq_ptr, nin, out_ptr, link_stride, out_cap):
         """Device mode: both buffers are device pointers; link i's run begins ``link_stride`` samples after link
         i - 1's and can go straight to rx_device / rx_submit_device.  Returns the number of outputs per link."""
-        assert self.device_ptrs
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_ddc_bank(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(link_stride),
-                                            int(out_cap), C.byref(n)))
-        return n.value
+        return self._stage_device("ddc_bank", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(link_stride),
+                                  int(out_cap))
 
     def ddc_bank_taps(self, link):
         """The band-pass table of one link as the kernel multiplies with it (complex64)."""
-        n = C.c_int(0)
-        self._check(self._lib.ofdm_ddc_bank_taps(self._h, int(link), None, 0, C.byref(n)))
-        out = np.zeros(n.value, np.complex64)
-        self._check(self._lib.ofdm_ddc_bank_taps(self._h, int(link), _ptr(out), n.value, C.byref(n)))
-        return out
+        return self._stage_taps("ddc_bank", int(link))
 
     def ddc_bank_last_ms(self):
         """HIP-event time of k_ddc_bank in the last ddc_bank() / ddc_bank_device() (needs prof_enable())."""
-        ms = C.c_double(0)
-        self._check(self._lib.ofdm_ddc_bank_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._stage_last_ms("ddc_bank")
 
     # -- wideband transmit (interpolate and translate behind tx) -------------------------------
     def set_duc(self, cfg=None, **kw):
         """Configure the transmit stage (sink.set_interp + set_center_freq): an ``ofdm_duc_cfg`` (duc.duc_cfg) or its
         keywords (interpolation=, center_freq=, taps= / occupied_fraction=, out_format=, out_scale=).
         ``set_duc(None)`` with no keywords removes it.  Resets the stream state."""
-        if cfg is None and kw:
-            from . import duc as _duc
-            cfg = _duc.duc_cfg(**kw)
-        self._check(self._lib.ofdm_set_duc(self._h, C.byref(cfg) if cfg is not None else None))
-        self.duc_cfg = cfg
+        self._stage_set("duc", "duc.duc_cfg", cfg, kw)
 
     def duc_reset(self, first=0):
         """Start a new narrowband stream whose first sample has this absolute index (outputs begin at L * first); the
         filter history is zero."""
-        self._check(self._lib.ofdm_duc_reset(self._h, int(first)))
+        self._stage_reset("duc", first)
 
     def duc(self, iq, add=None):
         """Host mode: the next complex64 samples of the narrowband stream -> len(iq) * L wideband samples (complex64,
         or int16 of shape (n, 2) with out_format "sc16"), added onto the complex64 band ``add`` where one is given.
         Stateful: any segmentation of a stream gives the same bits."""
-        assert not self.device_ptrs
-        if self.duc_cfg is None:
-            raise ValueError("duc() without set_duc()")
-        if np.asarray(iq).dtype == np.int16:
-            raise ValueError("duc() takes complex64 samples (its 16-bit side is the output)")
-        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
-        no = len(iq) * int(self.duc_cfg.interpolation)
-        if add is not None:
-            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
-            if len(add) != no:
-                raise ValueError("add must hold len(iq) * interpolation samples")
-        sc16 = self.duc_cfg.out_format == _abi.OFDM_IQ_SC16
-        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_duc(self._h, _ptr(iq) if len(iq) else None, len(iq),
-                                       _ptr(add) if add is not None and no else None, _ptr(out), len(out), C.byref(n)))
-        return out[:n.value]
+        return self._tx_stage("duc", iq, add, lambda n: n * int(self.duc_cfg.interpolation), "len(iq) * interpolation")
 
     def duc_device(self, iq_ptr, nin, out_ptr, out_cap, add_ptr=None):
         """Device mode: all buffers are device pointers; ``iq_ptr`` can be what tx_device(wait=False) is filling (same
         handle), ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns the number of outputs written."""
-        assert self.device_ptrs
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_duc(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
-                                       C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
-        return n.value
+        return self._stage_device("duc", C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
+                                  C.c_void_p(out_ptr), int(out_cap))
 
     def duc_last_ms(self):
         """HIP-event time of k_duc in the last duc() / duc_device() (needs prof_enable())."""
-        ms = C.c_double(0)
-        self._check(self._lib.ofdm_duc_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._stage_last_ms("duc")
 
     # -- rational-rate transmit (resample by L / M and translate behind tx) ---------------------
     def set_tx_resamp(self, cfg=None, **kw):
@@ -567,58 +552,31 @@ class Engine(object):
         ``ofdm_tx_resamp_cfg`` (tx_resample.tx_resamp_cfg) or its keywords (interpolation=, decimation=, center_freq=,
         taps= / occupied_fraction=, out_format=, out_scale=).  ``set_tx_resamp(None)`` with no keywords removes it.
         Resets the stream state; the DUC keeps its own."""
-        if cfg is None and kw:
-            from . import tx_resample as _tx_resample
-            cfg = _tx_resample.tx_resamp_cfg(**kw)
-        self._check(self._lib.ofdm_set_tx_resamp(self._h, C.byref(cfg) if cfg is not None else None))
-        self.tx_resamp_cfg = cfg
+        self._stage_set("tx_resamp", "tx_resample.tx_resamp_cfg", cfg, kw)
 
     def tx_resamp_reset(self, first=0):
         """Start a new narrowband stream whose first sample has this absolute index; the filter history is zero."""
-        self._check(self._lib.ofdm_tx_resamp_reset(self._h, int(first)))
+        self._stage_reset("tx_resamp", first)
 
     def tx_resamp_count(self, nin):
         """Outputs the next tx_resamp() call of ``nin`` samples produces, from the current stream state."""
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_tx_resamp_count(self._h, int(nin), C.byref(n)))
-        return n.value
+        return self._stage_count("tx_resamp", nin)
 
     def tx_resamp(self, iq, add=None):
         """Host mode: the next complex64 samples of the narrowband stream -> the wideband samples at L / M times their
         rate that they complete (possibly none; complex64, or int16 of shape (n, 2) with out_format "sc16"), added
         onto the complex64 band ``add`` where one is given.  Stateful: any segmentation gives the same bits."""
-        assert not self.device_ptrs
-        if self.tx_resamp_cfg is None:
-            raise ValueError("tx_resamp() without set_tx_resamp()")
-        if np.asarray(iq).dtype == np.int16:
-            raise ValueError("tx_resamp() takes complex64 samples (its 16-bit side is the output)")
-        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
-        no = self.tx_resamp_count(len(iq))
-        if add is not None:
-            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
-            if len(add) != no:
-                raise ValueError("add must hold tx_resamp_count(len(iq)) samples")
-        sc16 = self.tx_resamp_cfg.out_format == _abi.OFDM_IQ_SC16
-        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_tx_resamp(self._h, _ptr(iq) if len(iq) else None, len(iq),
-                                             _ptr(add) if add is not None and no else None, _ptr(out), len(out), C.byref(n)))
-        return out[:n.value]
+        return self._tx_stage("tx_resamp", iq, add, self.tx_resamp_count, "tx_resamp_count(len(iq))")
 
     def tx_resamp_device(self, iq_ptr, nin, out_ptr, out_cap, add_ptr=None):
         """Device mode: all buffers are device pointers; ``iq_ptr`` can be what tx_device(wait=False) is filling (same
         handle), ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns the number of outputs written."""
-        assert self.device_ptrs
-        n = C.c_uint64(0)
-        self._check(self._lib.ofdm_tx_resamp(self._h, C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
-                                             C.c_void_p(out_ptr), int(out_cap), C.byref(n)))
-        return n.value
+        return self._stage_device("tx_resamp", C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
+                                  C.c_void_p(out_ptr), int(out_cap))
 
     def tx_resamp_last_ms(self):
         """HIP-event time of k_tx_resamp in the last tx_resamp() / tx_resamp_device() (needs prof_enable())."""
-        ms = C.c_double(0)
-        self._check(self._lib.ofdm_tx_resamp_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._stage_last_ms("tx_resamp")
 
     # -- chunked streams --------------------------------------------------------------
     def rx_packet_pos(self):

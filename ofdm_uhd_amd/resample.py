@@ -9,8 +9,6 @@ design, the normative band-pass table, the configuration struct and the output c
 
 Frequencies are in cycles per INPUT (wideband) sample; the taps live at L times the input rate.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _abi, ddc, firdes
@@ -55,10 +53,7 @@ def design(interpolation, decimation, occupied_fraction, transition=None):
 def bandpass_taps(taps, fc, interpolation):
     """The normative table c[k] = complex64(h[k] exp(j 2 pi fc k / L)): float32 taps, float64 arithmetic, rounded
     once.  (``Engine.resamp_taps`` returns the table the kernel holds, computed the same way by the library's libm.)"""
-    h = np.asarray(taps, np.float32).astype(np.float64)
-    k = np.arange(len(h), dtype=np.float64)
-    a = 2.0 * np.pi * float(fc) * k / float(int(interpolation))
-    return (h * np.cos(a) + 1j * (h * np.sin(a))).astype(np.complex64)
+    return ddc.bandpass_taps(taps, fc, interpolation)
 
 
 def count(first, n, interpolation, decimation):
@@ -70,18 +65,9 @@ def count(first, n, interpolation, decimation):
 
 def resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupied_fraction=None, transition=None):
     """ofdm_resamp_cfg for Engine.set_resamp; ``taps=None`` designs them from ``occupied_fraction``."""
-    if taps is None:
-        if occupied_fraction is None:
-            raise ValueError("resamp_cfg needs taps or occupied_fraction")
-        taps = design(interpolation, decimation, occupied_fraction, transition)
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    if not 1 <= len(taps) <= MAX_TAPS:
-        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
-    cfg = _abi.ofdm_resamp_cfg()
-    cfg.struct_size = C.sizeof(_abi.ofdm_resamp_cfg)
+    cfg = ddc._cfg_with_taps(_abi.ofdm_resamp_cfg, "resamp_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, decimation, occupied_fraction, transition))
     cfg.interpolation = int(interpolation)
     cfg.decimation = int(decimation)
-    cfg.ntaps = len(taps)
     cfg.center_freq = float(center_freq)
-    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg

@@ -9,24 +9,18 @@ low-pass design, the output count, the phase step and the configuration struct.
 
 Frequencies are in cycles per OUTPUT (wideband) sample; the taps live at L times the input rate.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
-from . import _abi, ddc, duc, firdes, iqio
+from . import _abi, ddc, duc, firdes, iqio, resample
 
 MAX_TAPS = _abi.OFDM_TX_RESAMP_MAX_TAPS
-MAX_RATIO = 64
+MAX_RATIO = resample.MAX_RATIO
 
 
-def _check_ratio(interpolation, decimation):
-    L, M = int(interpolation), int(decimation)
-    if not 1 <= L <= MAX_RATIO:
-        raise ValueError("interpolation must be in [1, %d]" % MAX_RATIO)
-    if not 1 <= M <= MAX_RATIO:
-        raise ValueError("decimation must be in [1, %d]" % MAX_RATIO)
-    return L, M
+_check_ratio = resample._check_ratio   # the two resamplers take the same ratios and count their outputs alike
+count = resample.count
 
 
 def design(interpolation, decimation, occupied_fraction, transition=None):
@@ -60,13 +54,6 @@ def design(interpolation, decimation, occupied_fraction, transition=None):
     return np.asarray(firdes.low_pass(float(L), 1.0, cutoff, transition, firdes.WIN_HAMMING), np.float32)
 
 
-def count(first, n, interpolation, decimation):
-    """Outputs of a call with input indices [first, first + n): every m with first <= floor(m M / L) < first + n,
-    ceil((first + n) L / M) - ceil(first L / M)."""
-    L, M = int(interpolation), int(decimation)
-    return -(-(int(first) + int(n)) * L // M) - -(-int(first) * L // M)
-
-
 def phase_step(center_freq):
     """D of the definition: frac(fc) in units of 2^-64 turn, truncated; a fraction that rounds up to 1 is 0."""
     t = float(center_freq)
@@ -83,21 +70,11 @@ def tx_resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupie
                   out_format="fc32", out_scale=None):
     """ofdm_tx_resamp_cfg for Engine.set_tx_resamp; ``taps=None`` designs them from ``occupied_fraction``.
     ``out_format`` is "fc32" or "sc16" (``out_scale`` None: 2^15)."""
-    if taps is None:
-        if occupied_fraction is None:
-            raise ValueError("tx_resamp_cfg needs taps or occupied_fraction")
-        taps = design(interpolation, decimation, occupied_fraction, transition)
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    if not 1 <= len(taps) <= MAX_TAPS:
-        raise ValueError("ntaps must be in [1, %d]" % MAX_TAPS)
-    cfg = _abi.ofdm_tx_resamp_cfg()
-    cfg.struct_size = C.sizeof(_abi.ofdm_tx_resamp_cfg)
+    cfg = ddc._cfg_with_taps(_abi.ofdm_tx_resamp_cfg, "tx_resamp_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, decimation, occupied_fraction, transition))
     cfg.interpolation = int(interpolation)
     cfg.decimation = int(decimation)
-    cfg.ntaps = len(taps)
     cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
     cfg.center_freq = float(center_freq)
     cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    cfg.reserved = 0
-    C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
     return cfg
