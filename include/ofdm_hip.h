@@ -464,6 +464,70 @@ int ofdm_ddc_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, i
  * OFDM_E_INVAL otherwise. */
 int ofdm_ddc_bank_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband receive: polyphase-FFT channeliser for links on the k/M grid --------------------------------------------
+ * Where the links of a capture sit on a uniform grid (dual_channel/dual_channel.py tunes one radio channel per link;
+ * the sensing apps step through every slot of a band), link c at centre frequency c/M with decimation M, the DDC's
+ * rotation is exactly 1 and the bank's K filters collapse into ONE real-tap polyphase filter followed by an M-point
+ * transform per output index: all M channels for 2 ntaps multiply-adds plus O(M log M), and up to 64 of them.  A
+ * standalone, stateful stage; additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and with no
+ * channeliser configured nothing here launches, allocates or copies.
+ * Definition.  M = nchannels, one of 2, 4, 8, 16, 32, 64; h[k], k in [0, ntaps): real float32 taps at the wideband
+ * rate (ntaps < M is allowed: a branch without taps is 0); channel c in [0, M) sits at c/M cycles per input sample, so
+ * c >= M/2 is the negative frequency (c - M)/M.  x[n]: wideband samples, n an absolute index counted from the last
+ * reset (ofdm_set_pfb, ofdm_pfb_reset), zero before that reset's first index; the handle's receive IQ format and
+ * scale, converted as the DDC converts.
+ *   branches  u_p[m] = sum over q >= 0 with q M + p < ntaps of  h[q M + p] * x[(m - q) M - p],   p = 0..M-1:
+ *             float32, ONE chain of packed fused multiply-adds on (re, im), ascending q, begun at +0
+ *   table     w[j] = complex64(exp(+2 pi i j / M)), j in [0, M): float64 on the host, rounded once
+ *   output    y_c[m] = sum_p u_p[m] w[(c p) mod M], evaluated in float32 by the radix-2 decimation-in-time recursion
+ *               D_1(v) = v;   E = D_{n/2}(v[0], v[2], ...),  O = D_{n/2}(v[1], v[3], ...)
+ *               t[c] = O[c] w[c M / n]    the unfused complex product; t[0] = O[0] (index 0 is not multiplied)
+ *               D_n(v)[c] = E[c] + t[c],  D_n(v)[c + n/2] = E[c] - t[c]        c in [0, n/2)
+ *             y[m] = D_M(u_0[m], ..., u_{M-1}[m]).  Schedule: M <= 16 is evaluated whole by one thread per output
+ *             index; M = 32 and 64 in two steps of the same recursion -- the M/8 sub-transforms of size 8 (over
+ *             p = r + (M/8) k), then the levels n = 16 .. M for the entries with equal c mod 8 -- the same operations
+ *             on the same operands.
+ *   outputs   the DDC's with R = M: a call with input indices [a, a + n) produces every m with a <= m M < a + n.
+ * The bits of y_c[m] are a function of (m, c) and (M, h) alone: not of which channels are selected, their order or
+ * number (the whole transform is computed, only selected rows are stored), nor of where a call, a chunk or a tile
+ * starts.  A channel may be selected more than once; the rows are then equal.  Mathematically y_c[m] is the DDC bank's
+ * link (R = M, h, fc = c/M); the order of the additions, hence the last bits, are this stage's own.
+ *   state     the last ntaps - 1 converted samples (two buffers taking turns) and the absolute index of the next input
+ *             sample: the channeliser's own, separate from every other stage's.
+ * Pointers are host or device as the handle was created; ordering behind an ofdm_tx_async in flight and the alignment
+ * rules are ofdm_ddc's.  Selected channel i's outputs go to the contiguous run iq_out + i * chan_stride (samples);
+ * out_cap and *nout count outputs PER CHANNEL.  ofdm_pfb returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, nchannels not in the set, ntaps outside 1..OFDM_PFB_MAX_TAPS, nsel 0 or above
+ * nchannels, a channel >= nchannels, a non-finite tap; a call without a configuration; an ofdm_sc16 input not 4-byte
+ * (float32 input or iq_out: 8-byte) aligned; chan_stride < *nout with nsel > 1; first_sample_index above 2^62 or a
+ * sample index past 2^63; a call too long for one grid (split it).  A refused configuration leaves the one in force
+ * (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_pfb_count says (*nout is set); the stream state is then unchanged. */
+#define OFDM_PFB_MAX_CHANNELS 64
+#define OFDM_PFB_MAX_TAPS 1024
+typedef struct ofdm_pfb_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_pfb_cfg) */
+  uint32_t nchannels;   /* M: 2, 4, 8, 16, 32 or 64; also the decimation */
+  uint32_t ntaps;       /* 1..OFDM_PFB_MAX_TAPS */
+  uint32_t nsel;        /* K, 1..nchannels */
+  uint8_t channel[OFDM_PFB_MAX_CHANNELS]; /* the selected channels, each in [0, nchannels); the first nsel count */
+  float taps[OFDM_PFB_MAX_TAPS];          /* real low-pass prototype at the input rate, shared by the channels */
+} ofdm_pfb_cfg;
+/* one set_center_freq per radio channel of a uniform grid (dual_channel.py; the band scan of the sensing apps); NULL:
+ * none.  Resets the channeliser's stream state. */
+int ofdm_set_pfb(ofdm_handle *h, const ofdm_pfb_cfg *cfg);
+/* a new stream whose first sample has this absolute index (a retune / a gap in the capture): history zero */
+int ofdm_pfb_reset(ofdm_handle *h, uint64_t first_sample_index);
+/* outputs PER CHANNEL the next ofdm_pfb call of nin samples produces, from the current state */
+int ofdm_pfb_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of the stream through every channel of the grid (what the per-channel tuners of dual_channel.py
+ * deliver, for all slots at once): selected channel i at iq_out + i * chan_stride, out_cap per channel */
+int ofdm_pfb(ofdm_handle *h, const void *iq_in, uint64_t nin, ofdm_c32 *iq_out, uint64_t chan_stride, uint64_t out_cap,
+             uint64_t *nout);
+/* HIP-event time of k_pfb in the last ofdm_pfb, which must have run with profiling on and produced output;
+ * OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_pfb_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband receive: rational-rate resampler (L / M) with tuning ahead of ofdm_rx -----------------------------------
  * The stages above need a capture whose rate is an integer multiple of the modem's.  Recorded captures often are not
  * (a radio answers a rate request with the rate it can make: "Actual sps for rate", uhd_interface.py): a file taken at

@@ -19,6 +19,8 @@ OFDM_DDC_BANK_MAX_LINKS = 8
 OFDM_RESAMP_MAX_TAPS = 1024
 OFDM_DUC_MAX_TAPS = 1024
 OFDM_TX_RESAMP_MAX_TAPS = 1024
+OFDM_PFB_MAX_CHANNELS = 64
+OFDM_PFB_MAX_TAPS = 1024
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -153,6 +155,17 @@ class ofdm_ddc_bank_cfg(C.Structure):
     ]
 
 
+class ofdm_pfb_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nchannels", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("nsel", C.c_uint32),
+        ("channel", C.c_uint8 * OFDM_PFB_MAX_CHANNELS),
+        ("taps", C.c_float * OFDM_PFB_MAX_TAPS),
+    ]
+
+
 class ofdm_duc_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -208,6 +221,7 @@ EXPORTS = (
     "ofdm_ddc_bank_last_ms",
     "ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps", "ofdm_resamp_last_ms",
     "ofdm_set_tx_resamp", "ofdm_tx_resamp_reset", "ofdm_tx_resamp_count", "ofdm_tx_resamp", "ofdm_tx_resamp_last_ms",
+    "ofdm_set_pfb", "ofdm_pfb_reset", "ofdm_pfb_count", "ofdm_pfb", "ofdm_pfb_last_ms",
 )
 
 _LIB = None
@@ -253,6 +267,11 @@ def _declare(lib):
     lib.ofdm_ddc_bank.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
     lib.ofdm_ddc_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_ddc_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_pfb.argtypes = [H, C.POINTER(ofdm_pfb_cfg)]
+    lib.ofdm_pfb_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_pfb_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_pfb.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
+    lib.ofdm_pfb_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_resamp.argtypes = [H, C.POINTER(ofdm_resamp_cfg)]
     lib.ofdm_resamp_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_resamp_count.argtypes = [H, C.c_uint64, u64p]

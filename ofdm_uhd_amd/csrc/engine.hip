@@ -25,6 +25,7 @@
 #include "duc.h"
 #include "resamp.h"
 #include "tx_resamp.h"
+#include "pfb.h"
 
 static std::string g_create_error;
 
@@ -115,6 +116,7 @@ struct ofdm_handle {
   DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
   ResampState resamp;  // rational-rate front end (resamp.h / engine_resamp.inc)
   TxResampState tx_resamp;  // rational-rate transmit stage (tx_resamp.h / engine_tx_resamp.inc)
+  PfbState pfb;  // polyphase-FFT channeliser for links on the k/M grid (pfb.h / engine_pfb.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -543,6 +545,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->duc.release();
   h->resamp.release();
   h->tx_resamp.release();
+  h->pfb.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -979,3 +982,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_duc.inc"
 #include "engine_resamp.inc"
 #include "engine_tx_resamp.inc"
+#include "engine_pfb.inc"

@@ -83,6 +83,7 @@ class Engine(object):
         self.resamp_cfg = None  # the rational-rate front end's configuration in force (set_resamp), None without one
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.tx_resamp_cfg = None  # the rational-rate transmit stage's configuration in force (set_tx_resamp), None without one
+        self.pfb_cfg = None     # the channeliser's configuration in force (set_pfb), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -517,6 +518,43 @@ class Engine(object):
     def ddc_bank_last_ms(self):
         """HIP-event time of k_ddc_bank in the last ddc_bank() / ddc_bank_device() (needs prof_enable())."""
         return self._stage_last_ms("ddc_bank")
+
+    # -- polyphase-FFT channeliser: every link of a capture whose links sit on the k/M grid ------------
+    def set_pfb(self, cfg=None, **kw):
+        """Configure the channeliser: an ``ofdm_pfb_cfg`` (pfb.pfb_cfg) or its keywords (nchannels=, channels=,
+        taps= / occupied_fraction=).  ``set_pfb(None)`` with no keywords removes it.  Resets the channeliser's stream
+        state; every other stage keeps its own."""
+        self._stage_set("pfb", "pfb.pfb_cfg", cfg, kw)
+
+    def pfb_reset(self, first_sample_index=0):
+        """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
+        self._stage_reset("pfb", first_sample_index)
+
+    def pfb_count(self, nin):
+        """Outputs PER CHANNEL the next pfb() call of ``nin`` samples produces, from the current stream state."""
+        return self._stage_count("pfb", nin)
+
+    def pfb(self, iq):
+        """Host mode: the next samples of the wideband stream (in the receive IQ format) -> complex64 of shape
+        (K, nout): row i is selected channel i, the link at channels[i] / M decimated by M.  Stateful like ddc()."""
+        assert not self.device_ptrs
+        if self.pfb_cfg is None:
+            raise ValueError("pfb() without set_pfb()")
+        iq = self._rx_samples(iq)
+        K = int(self.pfb_cfg.nsel)
+        cap = max(self.pfb_count(len(iq)), 1)
+        out = np.zeros((K, cap), np.complex64)
+        return out[:, :self._stage_call("pfb", _ptr(iq) if len(iq) else None, len(iq), _ptr(out), cap, cap)]
+
+    def pfb_device(self, iq_ptr, nin, out_ptr, chan_stride, out_cap):
+        """Device mode: both buffers are device pointers; selected channel i's run begins ``chan_stride`` samples
+        after channel i - 1's and can go straight to rx_device / rx_submit_device.  Returns the outputs per channel."""
+        return self._stage_device("pfb", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(chan_stride),
+                                  int(out_cap))
+
+    def pfb_last_ms(self):
+        """HIP-event time of k_pfb in the last pfb() / pfb_device() (needs prof_enable())."""
+        return self._stage_last_ms("pfb")
 
     # -- wideband transmit (interpolate and translate behind tx) -------------------------------
     def set_duc(self, cfg=None, **kw):

@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -702,3 +702,60 @@ class ofdm_demod_bank(object):
         for d in self._links:
             d.engine().close()
         self._engine.close()
+
+
+class ofdm_demod_channelizer(ofdm_demod_bank):
+    """
+    Demodulates links that sit on a uniform grid of one wideband capture: M channels at centre frequencies c/M cycles
+    per wideband sample, each decimated by M (a radio that watches every slot of a band).  ofdm_demod_bank with the
+    polyphase-FFT channeliser (Engine.pfb) in the DDC bank's place: one real-tap filter and one M-point transform serve
+    all channels, up to 64 of them.  work, feed, flush, links and close are the bank's.
+    """
+
+    def __init__(self, options, nchannels, channels=None, taps=None, callback=None, iq_format="fc32", iq_scale=None,
+                 device_id=0):
+        """
+        @param options: one options object for all kept channels, or a list of K for links that differ in modulation
+        @param nchannels: M, one of 2, 4, 8, 16, 32, 64: the grid and the decimation
+        @param channels: the K channels to demodulate, in [0, M) or signed in [-M/2, M/2); None: all M in order
+        @param taps: the shared prototype; None: pfb.design for the largest occupied_tones / fft_length of the links
+        @param callback: function of three args: channel_position, ok, payload -- per call fired for position 0's
+            packets, then position 1's, and so on
+        @param iq_format, iq_scale: format of the WIDEBAND samples, as for ofdm_demod
+        """
+        # every argument is checked before the first engine exists
+        channels = None if channels is None else list(channels)
+        K = int(nchannels) if channels is None else len(channels)
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != K:
+                raise ValueError("ofdm_demod_channelizer needs one options object, or one per kept channel")
+        else:
+            opts = [options] * K
+        if callback is not None and not callable(callback):
+            raise ValueError("callback must be callable: callback(channel_position, ok, payload)")
+        fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        cfg = _pfb.pfb_cfg(nchannels, channels, taps=taps, occupied_fraction=occ)   # ValueError: M, K, channels, taps
+        self._callback = callback
+        self._links = []
+        self._engine = engine.Engine(opts[0], device_id=device_id)
+        try:
+            if fmt != "fc32":
+                self._engine.set_rx_iq_format(fmt, scale)
+            self._engine.set_pfb(cfg)
+            for i, o in enumerate(opts):
+                cb = (lambda ok, payload, pos=i: self._callback(pos, ok, payload)) if callback is not None else None
+                self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
+        except Exception:
+            self.close()
+            raise
+        self._streaming = False
+
+    def _tune(self, iq, restart):
+        eng = self._engine
+        if restart:
+            eng.pfb_reset(0)
+        if len(iq) == 0:
+            return np.zeros((len(self._links), 0), np.complex64)
+        return eng.pfb(iq)
