@@ -646,6 +646,73 @@ int ofdm_duc(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const ofdm_c32
  * output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_duc_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband transmit: polyphase-FFT synthesis bank for links on the c/M grid ----------------------------------------
+ * The transmit mirror of the channeliser (ofdm_pfb): where the links of a band sit on a uniform grid (the two-channel
+ * transmitter of dual_channel/dual_channel.py, one set_center_freq per radio channel), link c at centre frequency c/M
+ * with interpolation M, the DUC's rotation is periodic with period M and the K passes of ofdm_duc(..., add = band)
+ * collapse into ONE real-tap polyphase filter behind one M-point transform per input index: about 2 ntaps / M
+ * multiply-adds and 8 bytes written per output sample, whatever the number of links.  A band built here is what
+ * ofdm_pfb takes apart.  A standalone, stateful stage; additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is
+ * unchanged, and with no synthesis bank configured nothing here launches, allocates or copies.
+ * Definition.  M = nchannels, one of 2, 4, 8, 16, 32, 64, also the interpolation; K = nsel selected channels c_i in
+ * [0, M), all different; h[k], k in [0, ntaps): real float32 taps at the OUTPUT rate (ntaps < M is allowed: a phase
+ * without a tap gives 0); x_i[m]: selected channel i's narrowband complex64 stream, m an absolute index counted from
+ * the last reset (ofdm_set_pfb_synth, ofdm_pfb_synth_reset), zero before that reset's first index.  Channel c sits at
+ * c/M cycles per output sample, so c >= M/2 is the negative frequency (c - M)/M.
+ *   column    z_c[m] = x_i[m] where c = c_i, (+0, +0) for every channel not selected
+ *   table     w[j] = complex64(exp(+2 pi i j / M)), j in [0, M): ofdm_pfb's table, float64 on the host, rounded once
+ *   spread    V[m] = D_M(z_0[m], ..., z_{M-1}[m]), V_p[m] = sum_c z_c[m] w[(c p) mod M]: D_M is ofdm_pfb's radix-2
+ *             decimation-in-time recursion, the same function with the same schedule (M <= 16 whole; M = 32 and 64 in
+ *             the two steps M = 8 * (M/8)), here over the channel index c, giving the phase p.  The WHOLE transform is
+ *             evaluated, zeros included.
+ *   filter    output n = m M + p, p in [0, M):
+ *               v[n] = sum over q >= 0 with q M + p < ntaps of  h[q M + p] * V_p[m - q]
+ *             float32, ONE chain of packed fused multiply-adds on (re, im), ascending q, begun at +0
+ *   store     out[n] = store(v[n] + add[n]) when an `add` buffer is given (one float32 addition per part), else
+ *             store(v[n]); complex64, or ofdm_sc16 by the transmit rule of ofdm_duc (out_format / out_scale are the
+ *             stage's own).
+ * There is no rotation: it is the transform.  Mathematically out = sum_i ofdm_duc(x_i; L = M, h, fc = c_i / M); the
+ * order of the additions, hence the last bits, are this stage's own.  The bits of out[n] are a function of n, of
+ * (M, h) and of the M-vector of channel inputs alone: never of the order in which the channels are listed, nor of
+ * where a call, a chunk or a tile starts.  With channel 0 alone selected every butterfly adds or subtracts a zero,
+ * V_p[m] = x[m] exactly, and the output equals ofdm_duc's at L = M, fc = 0 as numbers (the sign of a zero may differ).
+ *   state     the last Q = (ntaps - 1) / M inputs of every selected channel (two buffers taking turns) and the absolute
+ *             index of the next input: the bank's own, separate from every other stage's (a handle may hold the
+ *             channeliser and the synthesis bank together).  A call with nin input indices per channel produces exactly
+ *             nin * M outputs; calls of 0 and calls shorter than Q are included.
+ * Selected channel i's nin inputs are the contiguous run iq_in + i * chan_stride (samples): the layout ofdm_pfb
+ * writes.  add (may be NULL) is complex64 with nin * M samples and may be iq_out itself when out_format is
+ * OFDM_IQ_FC32: each output sample is read before it is written, by the same thread.  Pointers are host or device as
+ * the handle was created.  Like ofdm_duc, ofdm_pfb_synth orders itself behind an ofdm_tx_async still in flight and
+ * returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, nchannels not in the set, ntaps outside 1..OFDM_PFB_MAX_TAPS, nsel 0 or above
+ * nchannels, a channel >= nchannels, a channel listed twice, a bad out_format or out_scale, a non-finite tap;
+ * ofdm_pfb_synth / ofdm_pfb_synth_reset without a configuration; a float32 pointer not 8-byte (ofdm_sc16: 4-byte)
+ * aligned; chan_stride < nin with nsel > 1; a first_input_index, or a call, that would take an output index past
+ * 2^63; a call too long for one grid (split it).  A refused configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap < nin * M (*nout is set); the stream state is then unchanged. */
+typedef struct ofdm_pfb_synth_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_pfb_synth_cfg) */
+  uint32_t nchannels;   /* M: 2, 4, 8, 16, 32 or 64; also the interpolation */
+  uint32_t ntaps;       /* 1..OFDM_PFB_MAX_TAPS */
+  uint32_t nsel;        /* K, 1..nchannels */
+  uint32_t out_format;  /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;      /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  uint8_t channel[OFDM_PFB_MAX_CHANNELS]; /* the selected channels, each in [0, nchannels), all different; the first nsel count */
+  float taps[OFDM_PFB_MAX_TAPS];          /* real low-pass prototype at the output rate, gain M in its pass band */
+} ofdm_pfb_synth_cfg;
+/* one set_center_freq per radio channel of a uniform grid, transmit side; NULL: none.  Resets the stream state
+ * (history zero, next input index 0). */
+int ofdm_set_pfb_synth(ofdm_handle *h, const ofdm_pfb_synth_cfg *cfg);
+/* a new stream whose first input has this absolute index: history zero, outputs begin at index M * first */
+int ofdm_pfb_synth_reset(ofdm_handle *h, uint64_t first_input_index);
+/* the next nin samples of every selected channel in, the nin * M samples of the band out (added onto `add` where given) */
+int ofdm_pfb_synth(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t chan_stride, uint64_t nin, const ofdm_c32 *add,
+                   void *iq_out, uint64_t out_cap, uint64_t *nout);
+/* HIP-event time of k_pfb_synth in the last ofdm_pfb_synth, which must have run with profiling on (ofdm_prof_enable)
+ * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_pfb_synth_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband transmit: rational-rate resampler (L / M) behind ofdm_tx -------------------------------------------------
  * The DUC above needs a band whose rate is an integer multiple of the modem's.  A band at 25 MS/s that is to hold
  * 10 MS/s links has the ratio 5/2: GNU Radio's blks2.rational_resampler_ccf(interpolation, decimation, taps) in front

@@ -166,6 +166,19 @@ class ofdm_pfb_cfg(C.Structure):
     ]
 
 
+class ofdm_pfb_synth_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nchannels", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("nsel", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("out_scale", C.c_float),
+        ("channel", C.c_uint8 * OFDM_PFB_MAX_CHANNELS),
+        ("taps", C.c_float * OFDM_PFB_MAX_TAPS),
+    ]
+
+
 class ofdm_duc_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -222,6 +235,7 @@ EXPORTS = (
     "ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps", "ofdm_resamp_last_ms",
     "ofdm_set_tx_resamp", "ofdm_tx_resamp_reset", "ofdm_tx_resamp_count", "ofdm_tx_resamp", "ofdm_tx_resamp_last_ms",
     "ofdm_set_pfb", "ofdm_pfb_reset", "ofdm_pfb_count", "ofdm_pfb", "ofdm_pfb_last_ms",
+    "ofdm_set_pfb_synth", "ofdm_pfb_synth_reset", "ofdm_pfb_synth", "ofdm_pfb_synth_last_ms",
 )
 
 _LIB = None
@@ -272,6 +286,10 @@ def _declare(lib):
     lib.ofdm_pfb_count.argtypes = [H, C.c_uint64, u64p]
     lib.ofdm_pfb.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
     lib.ofdm_pfb_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_pfb_synth.argtypes = [H, C.POINTER(ofdm_pfb_synth_cfg)]
+    lib.ofdm_pfb_synth_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_pfb_synth.argtypes = [H, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p]
+    lib.ofdm_pfb_synth_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_resamp.argtypes = [H, C.POINTER(ofdm_resamp_cfg)]
     lib.ofdm_resamp_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_resamp_count.argtypes = [H, C.c_uint64, u64p]

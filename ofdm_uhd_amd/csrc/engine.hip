@@ -26,6 +26,7 @@
 #include "resamp.h"
 #include "tx_resamp.h"
 #include "pfb.h"
+#include "pfb_synth.h"
 
 static std::string g_create_error;
 
@@ -117,6 +118,7 @@ struct ofdm_handle {
   ResampState resamp;  // rational-rate front end (resamp.h / engine_resamp.inc)
   TxResampState tx_resamp;  // rational-rate transmit stage (tx_resamp.h / engine_tx_resamp.inc)
   PfbState pfb;  // polyphase-FFT channeliser for links on the k/M grid (pfb.h / engine_pfb.inc)
+  PfbSynthState pfb_synth;  // its transmit mirror: the synthesis bank (pfb_synth.h / engine_pfb_synth.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -546,6 +548,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->resamp.release();
   h->tx_resamp.release();
   h->pfb.release();
+  h->pfb_synth.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -983,3 +986,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_resamp.inc"
 #include "engine_tx_resamp.inc"
 #include "engine_pfb.inc"
+#include "engine_pfb_synth.inc"

@@ -84,6 +84,7 @@ class Engine(object):
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.tx_resamp_cfg = None  # the rational-rate transmit stage's configuration in force (set_tx_resamp), None without one
         self.pfb_cfg = None     # the channeliser's configuration in force (set_pfb), None without one
+        self.pfb_synth_cfg = None  # the synthesis bank's configuration in force (set_pfb_synth), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -555,6 +556,56 @@ class Engine(object):
     def pfb_last_ms(self):
         """HIP-event time of k_pfb in the last pfb() / pfb_device() (needs prof_enable())."""
         return self._stage_last_ms("pfb")
+
+    # -- polyphase-FFT synthesis bank: every link of a band on the c/M grid in one pass over it ------------
+    def set_pfb_synth(self, cfg=None, **kw):
+        """Configure the synthesis bank: an ``ofdm_pfb_synth_cfg`` (pfb.synth_cfg) or its keywords (nchannels=,
+        channels=, taps= / occupied_fraction=, out_format=, out_scale=).  ``set_pfb_synth(None)`` with no keywords
+        removes it.  Resets the bank's stream state; every other stage keeps its own."""
+        self._stage_set("pfb_synth", "pfb.synth_cfg", cfg, kw)
+
+    def pfb_synth_reset(self, first=0):
+        """Start new narrowband streams whose first samples have this absolute index (outputs begin at M * first);
+        the filter history is zero."""
+        self._stage_reset("pfb_synth", first)
+
+    def pfb_synth(self, x, add=None):
+        """Host mode: the next samples of the K narrowband streams, complex64 of shape (K, nin), row i on channel
+        channels[i] -> nin * M samples of the band (complex64, or int16 of shape (n, 2) with out_format "sc16"), added
+        onto the complex64 band ``add`` where one is given.  Stateful: any segmentation gives the same bits."""
+        assert not self.device_ptrs
+        cfg = self.pfb_synth_cfg
+        if cfg is None:
+            raise ValueError("pfb_synth() without set_pfb_synth()")
+        if np.asarray(x).dtype == np.int16:
+            raise ValueError("pfb_synth() takes complex64 samples (its 16-bit side is the output)")
+        x = np.ascontiguousarray(x, np.complex64)
+        K = int(cfg.nsel)
+        if x.ndim == 1 and K == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[0] != K:
+            raise ValueError("pfb_synth() takes complex64 of shape (nsel, nin)")
+        nin = x.shape[1]
+        no = nin * int(cfg.nchannels)
+        if add is not None:
+            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
+            if len(add) != no:
+                raise ValueError("add must hold nin * nchannels samples")
+        sc16 = cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
+        return out[:self._stage_call("pfb_synth", _ptr(x) if nin else None, nin, nin,
+                                     _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
+
+    def pfb_synth_device(self, iq_ptr, chan_stride, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; selected channel i's ``nin`` inputs begin ``chan_stride``
+        samples after channel i - 1's (what pfb_device writes; what tx_device(wait=False) is filling, same handle),
+        ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns the number of outputs written."""
+        return self._stage_device("pfb_synth", C.c_void_p(iq_ptr), int(chan_stride), int(nin),
+                                  C.c_void_p(add_ptr) if add_ptr else None, C.c_void_p(out_ptr), int(out_cap))
+
+    def pfb_synth_last_ms(self):
+        """HIP-event time of k_pfb_synth in the last pfb_synth() / pfb_synth_device() (needs prof_enable())."""
+        return self._stage_last_ms("pfb_synth")
 
     # -- wideband transmit (interpolate and translate behind tx) -------------------------------
     def set_duc(self, cfg=None, **kw):

@@ -616,6 +616,101 @@ def _copy_options(options, **overrides):
     return o
 
 
+class ofdm_mod_channelizer(object):
+    """
+    Modulates links onto a uniform grid of one wideband band: M channels at centre frequencies c/M cycles per wideband
+    sample, each interpolated by M (the transmit mirror of ofdm_demod_channelizer, which takes such a band apart).
+
+    K plain ofdm_mod produce the narrowband streams; one engine owns the polyphase-FFT synthesis bank
+    (Engine.pfb_synth: one real-tap filter and one M-point transform place all K links in one pass over the band,
+    where Engine.duc(iq, add=band) needs one pass per link).
+    """
+
+    def __init__(self, options, nchannels, channels=None, taps=None, iq_format="fc32", iq_scale=None, device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param nchannels: M, one of 2, 4, 8, 16, 32, 64: the grid and the interpolation
+        @param channels: the K channels that carry a link, in [0, M) or signed in [-M/2, M/2), all different; None:
+            all M in order
+        @param taps: the shared prototype; None: pfb.synth_design for the largest occupied_tones / fft_length
+        @param iq_format, iq_scale: format of the WIDEBAND samples flush() returns, as for ofdm_mod(duc=)
+        """
+        # every argument is checked before the first engine exists
+        channels = None if channels is None else list(channels)
+        K = int(nchannels) if channels is None else len(channels)
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != K:
+                raise ValueError("ofdm_mod_channelizer needs one options object, or one per channel")
+        else:
+            opts = [options] * K
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        cfg = _pfb.synth_cfg(nchannels, channels, taps=taps, occupied_fraction=occ,
+                             out_format=iqio.check_format(iq_format), out_scale=iq_scale)   # ValueError: M, K, channels, taps
+        self._links = []
+        self._live = False       # the band holds samples whose filter tail is still to come
+        self._engine = engine.Engine(opts[0], device_id=device_id)
+        try:
+            self._engine.set_pfb_synth(cfg)
+            for o in opts:
+                self._links.append(ofdm_mod(o, device_id=device_id))
+        except Exception:
+            self.close()
+            raise
+
+    def engine(self):
+        """The engine that owns the synthesis bank."""
+        return self._engine
+
+    def links(self):
+        """The K per-link modulators, in the order of the channels."""
+        return list(self._links)
+
+    def send_pkt(self, position, payload=''):
+        """Queue ``payload`` on the link at ``position`` of the channel list (ofdm_mod.send_pkt's checks)."""
+        self._links[position].send_pkt(payload)
+
+    def flush(self, end=False):
+        """Modulate everything queued on every link and return the band's next samples.  The shorter streams are padded
+        with zeros to the longest one's length; the zeros are part of those streams.  The band continues across
+        flush() calls (a batch's filter tail comes out in front of the next batch); ``end=True`` appends the tail (Q
+        zero columns pushed through) and starts the bank afresh.  None when there is nothing to send.  Every link is
+        modulated before the band moves: if one link's batch fails, the batch is dropped on ALL links (as ofdm_mod
+        drops a failing batch) and the bank has not run, so the links stay in step."""
+        pending = any(m._pending for m in self._links)
+        end = end and (self._live or pending)
+        if not pending and not end:
+            return None
+        eng = self._engine
+        cfg = eng.pfb_synth_cfg
+        parts = []
+        if pending:
+            try:
+                iqs = [m.flush() for m in self._links]
+            except Exception:
+                for m in self._links:
+                    del m._pending[:]
+                raise
+            n = max(len(iq) for iq in iqs if iq is not None)
+            x = np.zeros((len(iqs), n), np.complex64)
+            for i, iq in enumerate(iqs):
+                if iq is not None:
+                    x[i, :len(iq)] = iq
+            parts.append(eng.pfb_synth(x))
+            self._live = True
+        if end:
+            parts.append(eng.pfb_synth(np.zeros((len(self._links), (cfg.ntaps - 1) // cfg.nchannels), np.complex64)))
+            eng.pfb_synth_reset(0)
+            self._live = False
+        return np.concatenate(parts) if len(parts) > 1 else parts[0]
+
+    def close(self):
+        """Closes the bank's engine and the K link engines."""
+        for m in self._links:
+            m.engine().close()
+        self._engine.close()
+
+
 class ofdm_demod_bank(object):
     """
     Demodulates every link of one wideband capture: K links that share the decimation and the low-pass prototype and
