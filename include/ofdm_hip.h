@@ -713,6 +713,80 @@ int ofdm_pfb_synth(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t chan_stride, 
  * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_pfb_synth_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband transmit: every link of a band at arbitrary centre frequencies in one pass (DUC bank) -------------------
+ * The transmit counterpart of the DDC bank, and what replaces one ofdm_duc(..., add = band) pass per link (the
+ * two-channel transmitter of dual_channel/dual_channel.py; one sink.set_interp + set_center_freq per link,
+ * usrp_transmit_path.py:79-88): one interpolation L, one real prototype h[0..ntaps) and K centre frequencies place K
+ * narrowband streams on the band in ONE pass.  K passes of the DUC move the band K times through memory and evaluate
+ * the float64 phasor r[n] once per OUTPUT and pass; here the shift moves to the input side,
+ *   h[k] x[m - q] e^{j 2 pi fc n} = (h[k] e^{j 2 pi fc k}) (x[m - q] e^{j 2 pi fc L (m - q)}),   n = m L + p, k = p + q L,
+ * one phasor per INPUT sample and link, and all links add into one accumulator pair before a single store.  The order
+ * of the additions, hence the last bits, are this stage's own: it is not bit-identical to K DUC passes.  A standalone,
+ * stateful stage; additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and with no bank
+ * configured nothing here launches, allocates or copies.
+ * Definition.  K = nlinks links, 1..OFDM_DUC_BANK_MAX_LINKS; L = interpolation in [1, 64], shared; h[k], k in
+ * [0, ntaps): real float32 taps at the OUTPUT rate, shared; fc_i in [-0.5, 0.5] cycles per OUTPUT sample; x_i[m]:
+ * link i's narrowband complex64 stream, m an absolute index counted from the last reset (ofdm_set_duc_bank,
+ * ofdm_duc_bank_reset), zero before that reset's first index.
+ *   phase     D_i = frac(fc_i) * 2^64 truncated, 0 where frac rounds up to 1 (the DUC's convention);
+ *             E_i = (L * D_i) mod 2^64, the advance per INPUT sample.
+ *   rotation  xr_i[m] = x_i[m] * r_i[m], r_i[m] = complex64(expj(+2 pi (m E_i mod 2^64) / 2^64)): the engine's
+ *             bit-reproducible float64 evaluation of expj at the phase (int64)(m E_i) * 2 pi / 2^64 (the DUC's),
+ *             rounded to complex64 once; the product is the gr_complex product: two products and one addition per
+ *             part, separately rounded.  A function of the absolute m and the configuration alone.
+ *   table     c_i[k] = complex64(h[k] exp(j 2 pi fc_i k)), float64 on the host, rounded once (ofdm_duc_bank_taps):
+ *             the DDC bank's table.
+ *   sums      for output n = m L + p, p in [0, L): A and B are each ONE chain of packed fused multiply-adds on the
+ *             (re, im) pair, begun at +0; the links in ascending i, inside a link q ascending over p + q L < ntaps:
+ *               A = fma(re c_i[p + q L], xr_i[m - q], A),   B = fma(im c_i[p + q L], xr_i[m - q], B)
+ *             v[n] = (A.re - B.im, A.im + B.re), one float32 operation per part.  A phase without a tap
+ *             (ntaps <= p) gives v[n] = 0.  The value depends on n and the configuration (the order of the list
+ *             included), never on where a call, a chunk or a tile starts.
+ *   store     out[n] = store(v[n] + add[n]) when an `add` buffer is given (one float32 addition per part), else
+ *             store(v[n]); complex64, or ofdm_sc16 by the transmit rule of ofdm_duc (out_format / out_scale are the
+ *             stage's own, as in ofdm_duc_cfg).
+ *   state     the last Q = (ntaps - 1) / L RAW inputs of every link (two buffers taking turns; they are rotated when
+ *             they are used, never stored rotated) and the absolute index of the next input: the bank's own, separate
+ *             from every other stage's.  A call with nin inputs per link produces exactly nin * L outputs; any
+ *             segmentation gives the same bits, calls of 0 inputs and calls shorter than Q included.
+ * With K = 1 and fc = 0 the output equals ofdm_duc's at fc = 0, and with K = 1 and h = {1.0} it equals ofdm_duc's at
+ * the same fc, as numbers (the sign of a zero may differ): the phasor, the phase convention and the product are the
+ * DUC's.  Link i's nin inputs are the contiguous run iq_in + i * link_stride (samples), as in ofdm_pfb_synth.  add
+ * (may be NULL) is complex64 with nin * L samples and may be iq_out itself when out_format is OFDM_IQ_FC32: each
+ * output sample is read before it is written, by the same thread.  Pointers are host or device as the handle was
+ * created.  Like ofdm_duc, ofdm_duc_bank orders itself behind an ofdm_tx_async still in flight and returns after the
+ * stream drained.
+ * OFDM_E_INVAL: bad struct_size, interpolation, ntaps, nlinks, out_format or out_scale, a non-finite tap, any
+ * |center_freq[i]| > 0.5 or NaN; ofdm_duc_bank / ofdm_duc_bank_reset without a configuration; link >= nlinks; a
+ * float32 pointer not 8-byte (ofdm_sc16: 4-byte) aligned; link_stride < nin with nlinks > 1; a first_input_index, or
+ * a call, that would take an output index past 2^63; a call too long for one grid (split it).  A refused
+ * configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap < nin * L (*nout is set); the stream state is then unchanged. */
+#define OFDM_DUC_BANK_MAX_LINKS 8
+typedef struct ofdm_duc_bank_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_duc_bank_cfg) */
+  uint32_t interpolation; /* L, 1..64, shared by the links */
+  uint32_t ntaps;         /* 1..OFDM_DUC_MAX_TAPS */
+  uint32_t nlinks;        /* K, 1..OFDM_DUC_BANK_MAX_LINKS */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  double center_freq[OFDM_DUC_BANK_MAX_LINKS]; /* fc[i], cycles per OUTPUT sample, [-0.5, 0.5]; the first nlinks count */
+  float taps[OFDM_DUC_MAX_TAPS];               /* real low-pass prototype at the output rate, gain L in its pass band */
+} ofdm_duc_bank_cfg;
+/* K times sink.set_interp + set_center_freq on one band; NULL: none.  Resets the bank's stream state (history zero,
+ * next input index 0). */
+int ofdm_set_duc_bank(ofdm_handle *h, const ofdm_duc_bank_cfg *cfg);
+/* a new stream whose first input has this absolute index: history zero, outputs begin at index L * first */
+int ofdm_duc_bank_reset(ofdm_handle *h, uint64_t first_input_index);
+/* the next nin samples of every link in, the nin * L samples of the band out (added onto `add` where given) */
+int ofdm_duc_bank(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t link_stride, uint64_t nin, const ofdm_c32 *add,
+                  void *iq_out, uint64_t out_cap, uint64_t *nout);
+/* the table of one link as the kernel multiplies with it (out NULL: size query) */
+int ofdm_duc_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_duc_bank in the last ofdm_duc_bank, which must have run with profiling on (ofdm_prof_enable)
+ * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_duc_bank_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband transmit: rational-rate resampler (L / M) behind ofdm_tx -------------------------------------------------
  * The DUC above needs a band whose rate is an integer multiple of the modem's.  A band at 25 MS/s that is to hold
  * 10 MS/s links has the ratio 5/2: GNU Radio's blks2.rational_resampler_ccf(interpolation, decimation, taps) in front

@@ -23,6 +23,7 @@
 #include "ddc.h"
 #include "ddc_bank.h"
 #include "duc.h"
+#include "duc_bank.h"
 #include "resamp.h"
 #include "tx_resamp.h"
 #include "pfb.h"
@@ -119,6 +120,7 @@ struct ofdm_handle {
   TxResampState tx_resamp;  // rational-rate transmit stage (tx_resamp.h / engine_tx_resamp.inc)
   PfbState pfb;  // polyphase-FFT channeliser for links on the k/M grid (pfb.h / engine_pfb.inc)
   PfbSynthState pfb_synth;  // its transmit mirror: the synthesis bank (pfb_synth.h / engine_pfb_synth.inc)
+  DucBankState duc_bank;  // all links of a band at arbitrary centre frequencies in one pass (duc_bank.h / engine_duc_bank.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -549,6 +551,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->tx_resamp.release();
   h->pfb.release();
   h->pfb_synth.release();
+  h->duc_bank.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -987,3 +990,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_tx_resamp.inc"
 #include "engine_pfb.inc"
 #include "engine_pfb_synth.inc"
+#include "engine_duc_bank.inc"

@@ -137,7 +137,7 @@ extern "C" int ofdm_pfb_synth(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ch
   }
   RCCHK(stage_time_end(h, d, timing));
   if (d.Q > 0) {
-    hipLaunchKernelGGL(k_pfb_synth_hist, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,
+    hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,
                        d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), d.Q);
     HIPCHK(h, hipGetLastError());
   }

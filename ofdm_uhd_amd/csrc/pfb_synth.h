@@ -189,14 +189,7 @@ __global__ void __launch_bounds__(PFS_THREADS) k_pfb_synth(PfbSynthParams q) {
   }
 }
 
-// the last Q inputs of every selected channel after this call, into the other history buffer (k_stream_hist per row)
-__global__ void __launch_bounds__(256) k_pfb_synth_hist(const c32* __restrict__ x, uint64_t stride, uint64_t nin,
-                                                        const c32* __restrict__ old, c32* __restrict__ nw, int Q) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= Q) return;
-  const int64_t i = blockIdx.y, gi = (int64_t)nin - Q + k;
-  nw[i * Q + k] = gi >= 0 ? x[(uint64_t)i * stride + (uint64_t)gi] : old[i * Q + k + (int64_t)nin];
-}
+// (the history kernel is k_stream_hist_rows, stream_hist.h: one row of Q inputs per selected channel)
 
 // host side (engine_pfb_synth.inc): the stream state (StreamStage, host_util.h; hist = K Q) is the bank's own
 struct PfbSynthState : StreamStage {

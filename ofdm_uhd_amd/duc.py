@@ -14,6 +14,7 @@ from . import _abi, ddc, iqio
 
 MAX_TAPS = _abi.OFDM_DUC_MAX_TAPS
 MAX_INTERP = 64
+MAX_LINKS = _abi.OFDM_DUC_BANK_MAX_LINKS
 
 
 def design(interpolation, occupied_fraction, transition=None):
@@ -39,4 +40,30 @@ def duc_cfg(interpolation, center_freq, taps=None, occupied_fraction=None, trans
     cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
     cfg.center_freq = float(center_freq)
     cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
+    return cfg
+
+
+def bank_cfg(interpolation, center_freqs, taps=None, occupied_fraction=None, transition=None, out_format="fc32",
+             out_scale=None):
+    """ofdm_duc_bank_cfg for Engine.set_duc_bank: one interpolation and one prototype, one centre frequency per link
+    (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed), row i of
+    Engine.duc_bank's input at center_freqs[i].  ``taps=None`` designs the prototype from ``occupied_fraction`` as
+    duc_cfg does; ``out_format`` / ``out_scale`` are duc_cfg's."""
+    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    if not 1 <= len(fcs) <= MAX_LINKS:
+        raise ValueError("a DUC bank has 1 to %d links" % MAX_LINKS)
+    if not all(abs(f) <= 0.5 for f in fcs):
+        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
+    cfg = ddc._cfg_with_taps(_abi.ofdm_duc_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, occupied_fraction, transition))
+    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
+        raise ValueError("taps must be finite")
+    cfg.interpolation = int(interpolation)
+    if not 1 <= cfg.interpolation <= MAX_INTERP:
+        raise ValueError("interpolation must be in [1, %d]" % MAX_INTERP)
+    cfg.nlinks = len(fcs)
+    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
+    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
+    for i, f in enumerate(fcs):
+        cfg.center_freq[i] = f
     return cfg

@@ -85,6 +85,7 @@ class Engine(object):
         self.tx_resamp_cfg = None  # the rational-rate transmit stage's configuration in force (set_tx_resamp), None without one
         self.pfb_cfg = None     # the channeliser's configuration in force (set_pfb), None without one
         self.pfb_synth_cfg = None  # the synthesis bank's configuration in force (set_pfb_synth), None without one
+        self.duc_bank_cfg = None  # the DUC bank's configuration in force (set_duc_bank), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -413,6 +414,32 @@ class Engine(object):
         return out[:self._stage_call(name, _ptr(iq) if len(iq) else None, len(iq),
                                      _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
 
+    def _tx_bank_stage(self, name, x, add, rows, factor, shape, add_size):
+        """Host mode of a transmit bank, pfb_synth() and duc_bank(): ``x`` is complex64 of shape (rows, nin) and gives
+        nin * factor outputs; ``shape`` and ``add_size`` name the two in the error messages."""
+        assert not self.device_ptrs
+        cfg = getattr(self, name + "_cfg")
+        if cfg is None:
+            raise ValueError("%s() without set_%s()" % (name, name))
+        if np.asarray(x).dtype == np.int16:
+            raise ValueError("%s() takes complex64 samples (its 16-bit side is the output)" % name)
+        x = np.ascontiguousarray(x, np.complex64)
+        K = int(getattr(cfg, rows))
+        if x.ndim == 1 and K == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or x.shape[0] != K:
+            raise ValueError("%s() takes complex64 of shape %s" % (name, shape))
+        nin = x.shape[1]
+        no = nin * int(getattr(cfg, factor))
+        if add is not None:
+            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
+            if len(add) != no:
+                raise ValueError("add must hold %s samples" % add_size)
+        sc16 = cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
+        return out[:self._stage_call(name, _ptr(x) if nin else None, nin, nin,
+                                     _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
+
     # -- wideband front end (tune and decimate ahead of rx) ---------------------------------
     def set_ddc(self, cfg=None, **kw):
         """Configure the front end (usrp2.source_32fc.set_decim + set_center_freq; gr.freq_xlating_fir_filter_ccf):
@@ -573,28 +600,7 @@ class Engine(object):
         """Host mode: the next samples of the K narrowband streams, complex64 of shape (K, nin), row i on channel
         channels[i] -> nin * M samples of the band (complex64, or int16 of shape (n, 2) with out_format "sc16"), added
         onto the complex64 band ``add`` where one is given.  Stateful: any segmentation gives the same bits."""
-        assert not self.device_ptrs
-        cfg = self.pfb_synth_cfg
-        if cfg is None:
-            raise ValueError("pfb_synth() without set_pfb_synth()")
-        if np.asarray(x).dtype == np.int16:
-            raise ValueError("pfb_synth() takes complex64 samples (its 16-bit side is the output)")
-        x = np.ascontiguousarray(x, np.complex64)
-        K = int(cfg.nsel)
-        if x.ndim == 1 and K == 1:
-            x = x.reshape(1, -1)
-        if x.ndim != 2 or x.shape[0] != K:
-            raise ValueError("pfb_synth() takes complex64 of shape (nsel, nin)")
-        nin = x.shape[1]
-        no = nin * int(cfg.nchannels)
-        if add is not None:
-            add = np.ascontiguousarray(add, np.complex64).reshape(-1)
-            if len(add) != no:
-                raise ValueError("add must hold nin * nchannels samples")
-        sc16 = cfg.out_format == _abi.OFDM_IQ_SC16
-        out = np.zeros((max(no, 1), 2), np.int16) if sc16 else np.zeros(max(no, 1), np.complex64)
-        return out[:self._stage_call("pfb_synth", _ptr(x) if nin else None, nin, nin,
-                                     _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
+        return self._tx_bank_stage("pfb_synth", x, add, "nsel", "nchannels", "(nsel, nin)", "nin * nchannels")
 
     def pfb_synth_device(self, iq_ptr, chan_stride, nin, out_ptr, out_cap, add_ptr=None):
         """Device mode: all buffers are device pointers; selected channel i's ``nin`` inputs begin ``chan_stride``
@@ -634,6 +640,39 @@ class Engine(object):
     def duc_last_ms(self):
         """HIP-event time of k_duc in the last duc() / duc_device() (needs prof_enable())."""
         return self._stage_last_ms("duc")
+
+    # -- DUC bank: every link of a band at arbitrary centre frequencies in one pass over it ------------
+    def set_duc_bank(self, cfg=None, **kw):
+        """Configure the bank: an ``ofdm_duc_bank_cfg`` (duc.bank_cfg) or its keywords (interpolation=, center_freqs=,
+        taps= / occupied_fraction=, out_format=, out_scale=).  ``set_duc_bank(None)`` with no keywords removes it.
+        Resets the bank's stream state; the single stage (set_duc) is a separate one and keeps its own."""
+        self._stage_set("duc_bank", "duc.bank_cfg", cfg, kw)
+
+    def duc_bank_reset(self, first=0):
+        """Start new narrowband streams whose first samples have this absolute index (outputs begin at L * first);
+        the filter history is zero."""
+        self._stage_reset("duc_bank", first)
+
+    def duc_bank(self, x, add=None):
+        """Host mode: the next samples of the K narrowband streams, complex64 of shape (K, nin), row i at
+        center_freqs[i] -> nin * L samples of the band (complex64, or int16 of shape (n, 2) with out_format "sc16"),
+        added onto the complex64 band ``add`` where one is given.  Stateful: any segmentation gives the same bits."""
+        return self._tx_bank_stage("duc_bank", x, add, "nlinks", "interpolation", "(nlinks, nin)", "nin * interpolation")
+
+    def duc_bank_device(self, iq_ptr, link_stride, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; link i's ``nin`` inputs begin ``link_stride`` samples after
+        link i - 1's (what tx_device(wait=False) is filling, same handle), ``add_ptr`` may be ``out_ptr`` itself for
+        complex64 output.  Returns the number of outputs written."""
+        return self._stage_device("duc_bank", C.c_void_p(iq_ptr), int(link_stride), int(nin),
+                                  C.c_void_p(add_ptr) if add_ptr else None, C.c_void_p(out_ptr), int(out_cap))
+
+    def duc_bank_taps(self, link):
+        """The band-pass table of one link as the kernel multiplies with it (complex64)."""
+        return self._stage_taps("duc_bank", int(link))
+
+    def duc_bank_last_ms(self):
+        """HIP-event time of k_duc_bank in the last duc_bank() / duc_bank_device() (needs prof_enable())."""
+        return self._stage_last_ms("duc_bank")
 
     # -- rational-rate transmit (resample by L / M and translate behind tx) ---------------------
     def set_tx_resamp(self, cfg=None, **kw):

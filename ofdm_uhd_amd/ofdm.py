@@ -616,7 +616,84 @@ def _copy_options(options, **overrides):
     return o
 
 
-class ofdm_mod_channelizer(object):
+class _ofdm_mod_links(object):
+    """What ofdm_mod_channelizer and ofdm_mod_bank share: K plain ofdm_mod produce the narrowband streams and one engine
+    owns the stage that places them on the band in one pass.  A subclass checks its arguments, builds the stage's
+    configuration and hands both to _open(); ``_stage`` names the engine's stage (Engine.<stage>, <stage>_reset,
+    <stage>_cfg) and _history() gives its Q."""
+
+    _stage = None
+
+    def _open(self, opts, configure, device_id):
+        self._links = []
+        self._live = False       # the band holds samples whose filter tail is still to come
+        self._engine = engine.Engine(opts[0], device_id=device_id)
+        try:
+            configure(self._engine)
+            for o in opts:
+                self._links.append(ofdm_mod(o, device_id=device_id))
+        except Exception:
+            self.close()
+            raise
+
+    def _history(self, cfg):
+        raise NotImplementedError
+
+    def engine(self):
+        """The engine that owns the stage."""
+        return self._engine
+
+    def links(self):
+        """The K per-link modulators, in the order of the list."""
+        return list(self._links)
+
+    def send_pkt(self, position, payload=''):
+        """Queue ``payload`` on the link at ``position`` of the list (ofdm_mod.send_pkt's checks)."""
+        self._links[position].send_pkt(payload)
+
+    def flush(self, end=False):
+        """Modulate everything queued on every link and return the band's next samples.  The shorter streams are padded
+        with zeros to the longest one's length; the zeros are part of those streams.  The band continues across
+        flush() calls (a batch's filter tail comes out in front of the next batch); ``end=True`` appends the tail (Q
+        zero columns pushed through) and starts the bank afresh.  None when there is nothing to send.  Every link is
+        modulated before the band moves: if one link's batch fails, the batch is dropped on ALL links (as ofdm_mod
+        drops a failing batch) and the bank has not run, so the links stay in step."""
+        pending = any(m._pending for m in self._links)
+        end = end and (self._live or pending)
+        if not pending and not end:
+            return None
+        eng = self._engine
+        run = getattr(eng, self._stage)
+        cfg = getattr(eng, self._stage + "_cfg")
+        parts = []
+        if pending:
+            try:
+                iqs = [m.flush() for m in self._links]
+            except Exception:
+                for m in self._links:
+                    del m._pending[:]
+                raise
+            n = max(len(iq) for iq in iqs if iq is not None)
+            x = np.zeros((len(iqs), n), np.complex64)
+            for i, iq in enumerate(iqs):
+                if iq is not None:
+                    x[i, :len(iq)] = iq
+            parts.append(run(x))
+            self._live = True
+        if end:
+            parts.append(run(np.zeros((len(self._links), self._history(cfg)), np.complex64)))
+            getattr(eng, self._stage + "_reset")(0)
+            self._live = False
+        return np.concatenate(parts) if len(parts) > 1 else parts[0]
+
+    def close(self):
+        """Closes the bank's engine and the K link engines."""
+        for m in self._links:
+            m.engine().close()
+        self._engine.close()
+
+
+class ofdm_mod_channelizer(_ofdm_mod_links):
     """
     Modulates links onto a uniform grid of one wideband band: M channels at centre frequencies c/M cycles per wideband
     sample, each interpolated by M (the transmit mirror of ofdm_demod_channelizer, which takes such a band apart).
@@ -625,6 +702,8 @@ class ofdm_mod_channelizer(object):
     (Engine.pfb_synth: one real-tap filter and one M-point transform place all K links in one pass over the band,
     where Engine.duc(iq, add=band) needs one pass per link).
     """
+
+    _stage = "pfb_synth"
 
     def __init__(self, options, nchannels, channels=None, taps=None, iq_format="fc32", iq_scale=None, device_id=0):
         """
@@ -647,68 +726,47 @@ class ofdm_mod_channelizer(object):
         occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
         cfg = _pfb.synth_cfg(nchannels, channels, taps=taps, occupied_fraction=occ,
                              out_format=iqio.check_format(iq_format), out_scale=iq_scale)   # ValueError: M, K, channels, taps
-        self._links = []
-        self._live = False       # the band holds samples whose filter tail is still to come
-        self._engine = engine.Engine(opts[0], device_id=device_id)
-        try:
-            self._engine.set_pfb_synth(cfg)
-            for o in opts:
-                self._links.append(ofdm_mod(o, device_id=device_id))
-        except Exception:
-            self.close()
-            raise
+        self._open(opts, lambda e: e.set_pfb_synth(cfg), device_id)
 
-    def engine(self):
-        """The engine that owns the synthesis bank."""
-        return self._engine
+    def _history(self, cfg):
+        return (cfg.ntaps - 1) // cfg.nchannels
 
-    def links(self):
-        """The K per-link modulators, in the order of the channels."""
-        return list(self._links)
 
-    def send_pkt(self, position, payload=''):
-        """Queue ``payload`` on the link at ``position`` of the channel list (ofdm_mod.send_pkt's checks)."""
-        self._links[position].send_pkt(payload)
+class ofdm_mod_bank(_ofdm_mod_links):
+    """
+    Modulates links onto one wideband band at arbitrary centre frequencies: K links that share the interpolation and
+    the low-pass prototype and differ in their centre frequency (the transmit counterpart of ofdm_demod_bank, which
+    takes such a band apart; ofdm_mod_channelizer is the cheaper way where the links sit on the c/M grid).
 
-    def flush(self, end=False):
-        """Modulate everything queued on every link and return the band's next samples.  The shorter streams are padded
-        with zeros to the longest one's length; the zeros are part of those streams.  The band continues across
-        flush() calls (a batch's filter tail comes out in front of the next batch); ``end=True`` appends the tail (Q
-        zero columns pushed through) and starts the bank afresh.  None when there is nothing to send.  Every link is
-        modulated before the band moves: if one link's batch fails, the batch is dropped on ALL links (as ofdm_mod
-        drops a failing batch) and the bank has not run, so the links stay in step."""
-        pending = any(m._pending for m in self._links)
-        end = end and (self._live or pending)
-        if not pending and not end:
-            return None
-        eng = self._engine
-        cfg = eng.pfb_synth_cfg
-        parts = []
-        if pending:
-            try:
-                iqs = [m.flush() for m in self._links]
-            except Exception:
-                for m in self._links:
-                    del m._pending[:]
-                raise
-            n = max(len(iq) for iq in iqs if iq is not None)
-            x = np.zeros((len(iqs), n), np.complex64)
-            for i, iq in enumerate(iqs):
-                if iq is not None:
-                    x[i, :len(iq)] = iq
-            parts.append(eng.pfb_synth(x))
-            self._live = True
-        if end:
-            parts.append(eng.pfb_synth(np.zeros((len(self._links), (cfg.ntaps - 1) // cfg.nchannels), np.complex64)))
-            eng.pfb_synth_reset(0)
-            self._live = False
-        return np.concatenate(parts) if len(parts) > 1 else parts[0]
+    K plain ofdm_mod produce the narrowband streams; one engine owns the DUC bank (Engine.duc_bank: all K links in one
+    pass over the band, where Engine.duc(iq, add=band) needs one pass per link).
+    """
 
-    def close(self):
-        """Closes the bank's engine and the K link engines."""
-        for m in self._links:
-            m.engine().close()
-        self._engine.close()
+    _stage = "duc_bank"
+
+    def __init__(self, options, center_freqs, interpolation, taps=None, iq_format="fc32", iq_scale=None, device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
+        @param interpolation: wideband rate over the modem's rate, 1..64
+        @param taps: the shared prototype; None: duc.design for the largest occupied_tones / fft_length of the links
+        @param iq_format, iq_scale: format of the WIDEBAND samples flush() returns, as for ofdm_mod(duc=)
+        """
+        # every argument is checked before the first engine exists
+        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != len(fcs):
+                raise ValueError("ofdm_mod_bank needs one options object, or one per centre frequency")
+        else:
+            opts = [options] * len(fcs)
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        cfg = _duc.bank_cfg(interpolation, fcs, taps=taps, occupied_fraction=occ,
+                            out_format=iqio.check_format(iq_format), out_scale=iq_scale)   # ValueError: K, fc, L, taps
+        self._open(opts, lambda e: e.set_duc_bank(cfg), device_id)
+
+    def _history(self, cfg):
+        return (cfg.ntaps - 1) // cfg.interpolation
 
 
 class ofdm_demod_bank(object):
