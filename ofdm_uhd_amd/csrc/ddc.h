@@ -16,10 +16,7 @@
 #pragma once
 #include "common.h"
 #include "host_util.h"
-#include "rx_demod.h"  // nco_radians, dexpj
-
-typedef float ddc_f2 __attribute__((ext_vector_type(2)));
-typedef float ddc_f4 __attribute__((ext_vector_type(4)));
+#include "stream_tile.h"  // ddc_f2, ddc_f4, ddc_put, nco_rotate
 
 constexpr int DDC_THREADS = 256;
 constexpr int DDC_MAX_DECIM = 64;
@@ -56,18 +53,10 @@ static inline size_t ddc_lds_bytes(int R, int ntaps) {
   return (size_t)((ntaps + 1) & ~1) * sizeof(c32) + (samples > combine ? samples : combine);
 }
 
-__device__ __forceinline__ void ddc_put(c32* xs, const DdcParams& q, int u, c32 v) {
-  const int cc = (int)(((uint64_t)(uint32_t)u * q.magic) >> 32);
-  const int p = q.R - 1 - (u - cc * q.R);
-  xs[p * q.W + cc] = v;
-}
-
 __device__ __forceinline__ void ddc_finish(const DdcParams& q, uint64_t m, ddc_f2 A, ddc_f2 B) {
   const uint64_t o = m - q.m0;
   if (o >= q.nout) return;
-  const c32 v = mk(A.x - B.y, A.y + B.x);
-  const dc r = dexpj(nco_radians(0ull - m * q.D));
-  q.out[o] = cmul(v, mk((float)r.re, (float)r.im));
+  q.out[o] = nco_rotate(mk(A.x - B.y, A.y + B.x), 0ull - m * q.D);
 }
 
 template <typename XT, int OPT, int TJ>
@@ -92,11 +81,11 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc(DdcParams q) {
       const int e = (int)((((uintptr_t)x >> 3) + (uint64_t)g0) & 1u);
       for (int u = 2 * tid - e; u < total; u += 2 * NT) {
         const ddc_f4 v = *reinterpret_cast<const ddc_f4*>(x + (g0 + u));
-        if (u >= 0) ddc_put(xs, q, u, mk(v.x, v.y));
-        if (u + 1 < total) ddc_put(xs, q, u + 1, mk(v.z, v.w));
+        if (u >= 0) ddc_put(xs, q.magic, q.R, q.W, u, mk(v.x, v.y));
+        if (u + 1 < total) ddc_put(xs, q.magic, q.R, q.W, u + 1, mk(v.z, v.w));
       }
     } else {
-      for (int u = tid; u < total; u += NT) ddc_put(xs, q, u, iq_load(x, g0 + u, q.scale));
+      for (int u = tid; u < total; u += NT) ddc_put(xs, q.magic, q.R, q.W, u, iq_load(x, g0 + u, q.scale));
     }
   } else {
     // first and last tiles: the carried history (zeros at the stream start) before x[0], zeros behind the call's end
@@ -109,7 +98,7 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc(DdcParams q) {
       } else if (gi + H >= 0) {
         v = q.hist[gi + H];
       }
-      ddc_put(xs, q, u, v);
+      ddc_put(xs, q.magic, q.R, q.W, u, v);
     }
   }
   __syncthreads();

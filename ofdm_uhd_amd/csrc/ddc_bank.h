@@ -41,9 +41,7 @@ static inline size_t ddc_bank_lds_bytes(int R, int ntaps, int K) {
 __device__ __forceinline__ void ddc_bank_finish(const DdcBankParams& q, int l, uint64_t m, ddc_f2 A, ddc_f2 B) {
   const uint64_t o = m - q.b.m0;
   if (o >= q.b.nout) return;
-  const c32 v = mk(A.x - B.y, A.y + B.x);
-  const dc r = dexpj(nco_radians(0ull - m * q.D[l]));
-  q.b.out[(uint64_t)l * q.stride + o] = cmul(v, mk((float)r.re, (float)r.im));
+  q.b.out[(uint64_t)l * q.stride + o] = nco_rotate(mk(A.x - B.y, A.y + B.x), 0ull - m * q.D[l]);
 }
 
 // links [l0, l0 + LG) of the tile: l0 is even wherever LG > 1
@@ -143,11 +141,11 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc_bank(DdcBankParams q) {
       const int e = (int)((((uintptr_t)x >> 3) + (uint64_t)g0) & 1u);
       for (int u = 2 * tid - e; u < total; u += 2 * NT) {
         const ddc_f4 v = *reinterpret_cast<const ddc_f4*>(x + (g0 + u));
-        if (u >= 0) ddc_put(xs, q.b, u, mk(v.x, v.y));
-        if (u + 1 < total) ddc_put(xs, q.b, u + 1, mk(v.z, v.w));
+        if (u >= 0) ddc_put(xs, q.b.magic, q.b.R, q.b.W, u, mk(v.x, v.y));
+        if (u + 1 < total) ddc_put(xs, q.b.magic, q.b.R, q.b.W, u + 1, mk(v.z, v.w));
       }
     } else {
-      for (int u = tid; u < total; u += NT) ddc_put(xs, q.b, u, iq_load(x, g0 + u, q.b.scale));
+      for (int u = tid; u < total; u += NT) ddc_put(xs, q.b.magic, q.b.R, q.b.W, u, iq_load(x, g0 + u, q.b.scale));
     }
   } else {
     // first and last tiles: the carried history (zeros at the stream start) before x[0], zeros behind the call's end
@@ -160,7 +158,7 @@ __global__ void __launch_bounds__(DDC_THREADS) k_ddc_bank(DdcBankParams q) {
       } else if (gi + H >= 0) {
         v = q.b.hist[gi + H];
       }
-      ddc_put(xs, q.b, u, v);
+      ddc_put(xs, q.b.magic, q.b.R, q.b.W, u, v);
     }
   }
   __syncthreads();

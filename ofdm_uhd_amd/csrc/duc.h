@@ -19,9 +19,8 @@
 // 64 - L banks are hit twice.
 #pragma once
 #include "common.h"
-#include "ddc.h"  // ddc_f2
+#include "ddc.h"  // ddc_f2, stream_tile.h
 #include "host_util.h"
-#include "rx_demod.h"  // nco_radians, dexpj
 
 constexpr int DUC_THREADS = 256;
 constexpr int DUC_MAX_INTERP = 64;
@@ -123,8 +122,7 @@ __global__ void __launch_bounds__(DUC_THREADS) k_duc(DucParams q) {
     const uint64_t o = off + (uint64_t)(tid + i * NT);
     if (o >= q.nout) continue;
     const uint64_t n = q.a * (uint64_t)L + o;
-    const dc r = dexpj(nco_radians(n * q.D));
-    c32 y = cmul(mk(A[i].x, A[i].y), mk((float)r.re, (float)r.im));
+    c32 y = nco_rotate(mk(A[i].x, A[i].y), n * q.D);
     if constexpr (ADD) y = cadd(y, q.add[o]);  // read before the store below: `add` may be `out`
     iq_store(out, (int64_t)o, y, q.scale);
   }

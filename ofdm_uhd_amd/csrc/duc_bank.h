@@ -49,12 +49,6 @@ static inline size_t duc_bank_lds_bytes(int L, int ntaps) {
   return ((size_t)ntaps + (size_t)duc_staged(duc_geom(L).T(), L, Q)) * sizeof(c32);
 }
 
-// xr[m] = x[m] r[m]: the phasor rounded once, the gr_complex product
-__device__ __forceinline__ c32 duc_bank_rot(c32 v, uint64_t phase) {
-  const dc r = dexpj(nco_radians(phase));
-  return cmul(v, mk((float)r.re, (float)r.im));
-}
-
 template <typename OUT, bool ADD, int OPT>
 __global__ void __launch_bounds__(DUC_THREADS) k_duc_bank(DucBankParams q) {
   constexpr int NT = DUC_THREADS, T = NT * OPT;
@@ -97,7 +91,7 @@ __global__ void __launch_bounds__(DUC_THREADS) k_duc_bank(DucBankParams q) {
     for (int k = tid; k < q.ntaps; k += NT) tap[k] = tab[k];
     if (interior) {
       // interior tile: every sample comes from x, no per-sample test against the stream
-      for (int u = tid; u < total; u += NT) xs[u] = duc_bank_rot(x[g0 + u], (m0 + (uint64_t)u) * E);
+      for (int u = tid; u < total; u += NT) xs[u] = nco_rotate(x[g0 + u], (m0 + (uint64_t)u) * E);
     } else {
       // first and last tiles: the carried history (zeros at the stream start) before x[0]; zeros behind the call's end
       // (they feed only outputs the call does not have) and before the oldest sample the history holds
@@ -110,7 +104,7 @@ __global__ void __launch_bounds__(DUC_THREADS) k_duc_bank(DucBankParams q) {
         } else if (gi + Q >= 0) {
           v = hist[gi + Q];
         }
-        xs[u] = duc_bank_rot(v, (m0 + (uint64_t)u) * E);
+        xs[u] = nco_rotate(v, (m0 + (uint64_t)u) * E);
       }
     }
     __syncthreads();

@@ -100,13 +100,7 @@ extern "C" int ofdm_duc(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, con
   p.scale = d.out_scale;
   const size_t lds = duc_lds_bytes(d.L, d.ntaps);  // (never more than 64 KB: no hipFuncSetAttribute)
   RCCHK(stage_time_begin(h, d, timing));
-  if (s16) {
-    if (add) launch_duc<sc16, true>(h, p, g, (unsigned)grid, lds);
-    else launch_duc<sc16, false>(h, p, g, (unsigned)grid, lds);
-  } else {
-    if (add) launch_duc<c32, true>(h, p, g, (unsigned)grid, lds);
-    else launch_duc<c32, false>(h, p, g, (unsigned)grid, lds);
-  }
+  stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_duc<decltype(o), decltype(a)::value>(h, p, g, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
   RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));
   if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));

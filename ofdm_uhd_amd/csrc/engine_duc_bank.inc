@@ -126,13 +126,7 @@ extern "C" int ofdm_duc_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t lin
   p.scale = d.out_scale;
   const size_t lds = duc_bank_lds_bytes(d.L, d.ntaps);
   RCCHK(stage_time_begin(h, d, timing));
-  if (s16) {
-    if (add) launch_duc_bank<sc16, true>(h, p, g, (unsigned)grid, lds);
-    else launch_duc_bank<sc16, false>(h, p, g, (unsigned)grid, lds);
-  } else {
-    if (add) launch_duc_bank<c32, true>(h, p, g, (unsigned)grid, lds);
-    else launch_duc_bank<c32, false>(h, p, g, (unsigned)grid, lds);
-  }
+  stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_duc_bank<decltype(o), decltype(a)::value>(h, p, g, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
   if (d.Q > 0) {
     hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,

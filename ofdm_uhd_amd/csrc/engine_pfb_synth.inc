@@ -128,13 +128,7 @@ extern "C" int ofdm_pfb_synth(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ch
   memcpy(p.pos, d.pos, sizeof(p.pos));
   const size_t lds = pfb_synth_lds_bytes(d.M, d.ntaps);
   RCCHK(stage_time_begin(h, d, timing));
-  if (s16) {
-    if (add) launch_pfb_synth<sc16, true>(h, p, d.M, (unsigned)grid, lds);
-    else launch_pfb_synth<sc16, false>(h, p, d.M, (unsigned)grid, lds);
-  } else {
-    if (add) launch_pfb_synth<c32, true>(h, p, d.M, (unsigned)grid, lds);
-    else launch_pfb_synth<c32, false>(h, p, d.M, (unsigned)grid, lds);
-  }
+  stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_pfb_synth<decltype(o), decltype(a)::value>(h, p, d.M, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
   if (d.Q > 0) {
     hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,

@@ -1,7 +1,8 @@
-// engine_stage.inc -- what the host sides of the five wideband stream stages share (StreamStage, host_util.h): the
-// steps of a configure call, reset, the argument checks, host-mode staging, timing, the history roll and the end of a
-// call.  Included by engine.hip ahead of engine_{ddc,ddc_bank,duc,resamp,tx_resamp}.inc, which keep what is a stage's
-// own: its configuration checks and messages, its table, its index limits, its output count and its launch.
+// engine_stage.inc -- what the host sides of the eight wideband stream stages share (StreamStage, host_util.h): the
+// steps of a configure call, reset, the argument checks, host-mode staging, timing, the history roll, the choice of a
+// transmit kernel's <OUT, ADD> and the end of a call.  Included by engine.hip ahead of
+// engine_{ddc,ddc_bank,pfb,resamp,duc,duc_bank,pfb_synth,tx_resamp}.inc, which keep what is a stage's own: its
+// configuration checks and messages, its table, its index limits, its output count and its launch.
 
 #define RCCHK(expr)         \
   do {                      \
@@ -41,7 +42,7 @@ static bool taps_finite(const float* taps, uint32_t ntaps) {
   return true;
 }
 
-// out_format / out_scale of the two transmit stages (`who` begins their messages): the full scale in force
+// out_format / out_scale of the transmit stages (`who` begins their messages): the full scale in force
 static int stage_out_scale(ofdm_handle* h, const char* who, uint32_t out_format, float out_scale, float* scale) {
   if (out_format != OFDM_IQ_FC32 && out_format != OFDM_IQ_SC16) FAIL(h, OFDM_E_INVAL, std::string("unknown ") + who + " out_format");
   *scale = 32768.0f;
@@ -125,6 +126,14 @@ static int stage_check_tx_bufs(ofdm_handle* h, bool s16, const void* iq_in, uint
   if (s16 && ((uintptr_t)iq_out & 3u)) FAIL(h, OFDM_E_INVAL, "ofdm_sc16 buffers must be 4-byte aligned");
   if (!s16 && ((uintptr_t)iq_out & 7u)) FAIL(h, OFDM_E_INVAL, "float32 IQ buffers must be 8-byte aligned");
   return OFDM_OK;
+}
+
+// a transmit call's output format and whether it adds onto a band, as the <OUT, ADD> of its kernel:
+// f(OUT(), std::bool_constant<ADD>())
+template <typename F>
+static auto stage_tx_variant(bool s16, bool add, F f) {
+  if (s16) return add ? f(sc16{}, std::true_type{}) : f(sc16{}, std::false_type{});
+  return add ? f(c32{}, std::true_type{}) : f(c32{}, std::false_type{});
 }
 
 // the first device work of a call: a transmit batch still in flight (ofdm_tx_async) may be writing the caller's input

@@ -126,13 +126,9 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
     p.scale = d.out_scale;
     const size_t lds = tx_resamp_lds_bytes(d.L, d.M, d.ntaps);
     RCCHK(stage_time_begin(h, d, timing));
-    if (s16) {
-      if (add) HIPCHK(h, (launch_tx_resamp<sc16, true>(h, p, (unsigned)grid, lds)));
-      else HIPCHK(h, (launch_tx_resamp<sc16, false>(h, p, (unsigned)grid, lds)));
-    } else {
-      if (add) HIPCHK(h, (launch_tx_resamp<c32, true>(h, p, (unsigned)grid, lds)));
-      else HIPCHK(h, (launch_tx_resamp<c32, false>(h, p, (unsigned)grid, lds)));
-    }
+    HIPCHK(h, stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) {
+      return launch_tx_resamp<decltype(o), decltype(a)::value>(h, p, (unsigned)grid, lds);
+    }));
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));

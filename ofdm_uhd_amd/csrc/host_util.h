@@ -58,10 +58,10 @@ struct PinBuf {
   }
 };
 
-// What the five wideband stream stages (DDC, DDC bank, DUC, both resamplers) share on the host: where the stream
-// stands, the carried history and its double buffer, the host-mode staging buffers and the HIP-event pair of the
-// last call.  Each stage's state derives from it and adds its own rates, tables and output format; the code that
-// works on these fields is engine_stage.inc.
+// What the eight wideband stream stages (DDC, DDC bank, channeliser, DUC, DUC bank, synthesis bank, both resamplers)
+// share on the host: where the stream stands, the carried history and its double buffer, the host-mode staging buffers
+// and the HIP-event pair of the last call.  Each stage's state derives from it and adds its own rates, tables and
+// output format; the code that works on these fields is engine_stage.inc.
 struct StreamStage {
   bool on = false;
   uint64_t next = 0;  // absolute index of the next input sample

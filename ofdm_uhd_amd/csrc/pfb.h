@@ -100,11 +100,11 @@ __global__ void __launch_bounds__(PFB_THREADS, 4) k_pfb(PfbParams q) {
       const int e = (int)((((uintptr_t)x >> 3) + (uint64_t)g0) & 1u);
       for (int u = 2 * tid - e; u < total; u += 2 * NT) {
         const ddc_f4 v = *reinterpret_cast<const ddc_f4*>(x + (g0 + u));
-        if (u >= 0) ddc_put(xs, q.b, u, mk(v.x, v.y));
-        if (u + 1 < total) ddc_put(xs, q.b, u + 1, mk(v.z, v.w));
+        if (u >= 0) ddc_put(xs, q.b.magic, q.b.R, W, u, mk(v.x, v.y));
+        if (u + 1 < total) ddc_put(xs, q.b.magic, q.b.R, W, u + 1, mk(v.z, v.w));
       }
     } else {
-      for (int u = tid; u < total; u += NT) ddc_put(xs, q.b, u, iq_load(x, g0 + u, q.b.scale));
+      for (int u = tid; u < total; u += NT) ddc_put(xs, q.b.magic, q.b.R, W, u, iq_load(x, g0 + u, q.b.scale));
     }
   } else {
     // first and last tiles: the carried history (zeros at the stream start) before x[0], zeros behind the call's end
@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(PFB_THREADS, 4) k_pfb(PfbParams q) {
       } else if (gi + H >= 0) {
         v = q.b.hist[gi + H];
       }
-      ddc_put(xs, q.b, u, v);
+      ddc_put(xs, q.b.magic, q.b.R, W, u, v);
     }
   }
   __syncthreads();

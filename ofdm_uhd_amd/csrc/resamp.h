@@ -21,9 +21,8 @@
 // odd pitch) and leave in output order: every global store of a wave is one contiguous run.
 #pragma once
 #include "common.h"
-#include "ddc.h"  // ddc_f2, ddc_f4
+#include "ddc.h"  // ddc_f2, ddc_f4, stream_tile.h
 #include "host_util.h"
-#include "rx_demod.h"  // nco_radians, dexpj
 #include "stream_hist.h"  // k_stream_hist
 
 constexpr int RESAMP_THREADS = 256;
@@ -66,11 +65,6 @@ static inline size_t resamp_lds_bytes(int L, int M, int ntaps) {
   return (tab + rows + sums) * sizeof(c32);
 }
 
-__device__ __forceinline__ void resamp_put(c32* xs, const ResampParams& q, int u, c32 v) {
-  const int cc = (int)(((uint64_t)(uint32_t)u * q.magicM) >> 32);
-  xs[(u - cc * q.M) * q.W + cc] = v;
-}
-
 template <typename XT, int NG>
 __global__ void __launch_bounds__(RESAMP_THREADS) k_resamp(ResampParams q) {
   constexpr int NT = RESAMP_THREADS, NW = NT / WAVE;
@@ -94,11 +88,11 @@ __global__ void __launch_bounds__(RESAMP_THREADS) k_resamp(ResampParams q) {
       const int e = (int)((((uintptr_t)x >> 3) + (uint64_t)g0) & 1u);
       for (int u = 2 * tid - e; u < total; u += 2 * NT) {
         const ddc_f4 v = *reinterpret_cast<const ddc_f4*>(x + (g0 + u));
-        if (u >= 0) resamp_put(xs, q, u, mk(v.x, v.y));
-        if (u + 1 < total) resamp_put(xs, q, u + 1, mk(v.z, v.w));
+        if (u >= 0) polyphase_put(xs, q.magicM, q.M, q.W, u, mk(v.x, v.y));
+        if (u + 1 < total) polyphase_put(xs, q.magicM, q.M, q.W, u + 1, mk(v.z, v.w));
       }
     } else {
-      for (int u = tid; u < total; u += NT) resamp_put(xs, q, u, iq_load(x, g0 + u, q.scale));
+      for (int u = tid; u < total; u += NT) polyphase_put(xs, q.magicM, q.M, q.W, u, iq_load(x, g0 + u, q.scale));
     }
   } else {
     // first and last tiles: the carried history (zeros at the stream start) before x[0], zeros behind the call's end
@@ -111,7 +105,7 @@ __global__ void __launch_bounds__(RESAMP_THREADS) k_resamp(ResampParams q) {
       } else if (gi + Q >= 0) {
         v = q.hist[gi + Q];
       }
-      resamp_put(xs, q, u, v);
+      polyphase_put(xs, q.magicM, q.M, q.W, u, v);
     }
   }
   __syncthreads();
@@ -165,8 +159,7 @@ __global__ void __launch_bounds__(RESAMP_THREADS) k_resamp(ResampParams q) {
       for (int c = 1; c < NG; c++) s = s + cmb[c * TO + j];
       v = mk(s.x - s.w, s.y + s.z);
     }
-    const dc rr = dexpj(nco_radians(0ull - n * q.D));
-    q.out[o] = cmul(v, mk((float)rr.re, (float)rr.im));
+    q.out[o] = nco_rotate(v, 0ull - n * q.D);
   }
 }
 

@@ -1,5 +1,6 @@
-// stream_hist.h -- the history kernel of the five wideband stream stages (ddc.h, ddc_bank.h, duc.h, resamp.h,
-// tx_resamp.h): each keeps the last H input samples of its stream for the next call's oldest taps.
+// stream_hist.h -- the history kernels of the eight wideband stream stages: each keeps the last H input samples of its
+// stream (ddc.h, ddc_bank.h, pfb.h, resamp.h, duc.h, tx_resamp.h), or of each of its streams (pfb_synth.h, duc_bank.h),
+// for the next call's oldest taps.  (What the stages' compute kernels share is stream_tile.h.)
 #pragma once
 #include "common.h"
 

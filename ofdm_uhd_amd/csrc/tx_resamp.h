@@ -20,10 +20,9 @@
 // ([r][period], odd pitch) and leave in output order: rotation, optional `add` load, one contiguous store per wave.
 #pragma once
 #include "common.h"
-#include "ddc.h"  // ddc_f2, ddc_f4
+#include "ddc.h"  // ddc_f2, ddc_f4, stream_tile.h
 #include "host_util.h"
 #include "resamp.h"    // resamp_geom, resamp_hist_periods, resamp_pitch
-#include "rx_demod.h"  // nco_radians, dexpj
 #include "stream_hist.h"  // k_stream_hist
 
 constexpr int TX_RESAMP_THREADS = 256;
@@ -68,11 +67,6 @@ static inline size_t tx_resamp_lds_bytes(int L, int M, int ntaps) {
   return tap + (rows + sums) * sizeof(c32);
 }
 
-__device__ __forceinline__ void tx_resamp_put(c32* xs, const TxResampParams& q, int u, c32 v) {
-  const int cc = (int)(((uint64_t)(uint32_t)u * q.magicM) >> 32);
-  xs[(u - cc * q.M) * q.W + cc] = v;
-}
-
 template <typename OUT, bool ADD>
 __global__ void __launch_bounds__(TX_RESAMP_THREADS) k_tx_resamp(TxResampParams q) {
   constexpr int NT = TX_RESAMP_THREADS, NW = NT / WAVE;
@@ -95,8 +89,8 @@ __global__ void __launch_bounds__(TX_RESAMP_THREADS) k_tx_resamp(TxResampParams 
     const int e = (int)((((uintptr_t)x >> 3) + (uint64_t)g0) & 1u);
     for (int u = 2 * tid - e; u < total; u += 2 * NT) {
       const ddc_f4 v = *reinterpret_cast<const ddc_f4*>(x + (g0 + u));
-      if (u >= 0) tx_resamp_put(xs, q, u, mk(v.x, v.y));
-      if (u + 1 < total) tx_resamp_put(xs, q, u + 1, mk(v.z, v.w));
+      if (u >= 0) polyphase_put(xs, q.magicM, q.M, q.W, u, mk(v.x, v.y));
+      if (u + 1 < total) polyphase_put(xs, q.magicM, q.M, q.W, u + 1, mk(v.z, v.w));
     }
   } else {
     // first and last tiles: the carried history (zeros at the stream start) before x[0], zeros behind the call's end
@@ -109,7 +103,7 @@ __global__ void __launch_bounds__(TX_RESAMP_THREADS) k_tx_resamp(TxResampParams 
       } else if (gi + Q >= 0) {
         v = q.hist[gi + Q];
       }
-      tx_resamp_put(xs, q, u, v);
+      polyphase_put(xs, q.magicM, q.M, q.W, u, v);
     }
   }
   __syncthreads();
@@ -147,9 +141,7 @@ __global__ void __launch_bounds__(TX_RESAMP_THREADS) k_tx_resamp(TxResampParams 
     const uint64_t o = n - q.n0;  // (outputs before n0 wrap to huge values)
     if (o >= q.nout) continue;
     const int t = (int)(((uint64_t)(uint32_t)j * q.magicL) >> 32);
-    const c32 v = ob[(j - t * L) * q.TP + t];
-    const dc rr = dexpj(nco_radians(n * q.D));
-    c32 y = cmul(v, mk((float)rr.re, (float)rr.im));
+    c32 y = nco_rotate(ob[(j - t * L) * q.TP + t], n * q.D);
     if constexpr (ADD) y = cadd(y, q.add[o]);  // read before the store below: `add` may be `out`
     iq_store(out, (int64_t)o, y, q.scale);
   }

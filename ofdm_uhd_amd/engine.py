@@ -348,7 +348,7 @@ class Engine(object):
         n = npk.value
         return n, off[:n + 1], ln[:n], ok[:n]
 
-    # -- the five wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
+    # -- the eight wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
     def _stage_set(self, name, maker, cfg, kw):
         """ofdm_set_<name>: ``cfg`` or, from keywords, what ``maker`` ("module.function" of this package) builds."""
         if cfg is None and kw:

@@ -1,22 +1,27 @@
-"""The five wideband stream stages (DDC, DDC bank, receive resampler, DUC, transmit resampler) live on ONE handle.  They
-share one host-side skeleton (StreamStage, csrc/engine_stage.inc); each must still own its history buffers, its staging
-buffers, its stream position and its HIP-event pair.  The per-stage files check the receive stages together and the
-transmit stages together; this is the only place that has all five interleaved."""
+"""The eight wideband stream stages (DDC, DDC bank, receive resampler, DUC, transmit resampler, channeliser, synthesis
+bank, DUC bank) live on ONE handle.  They share one host-side skeleton (StreamStage, csrc/engine_stage.inc); each must
+still own its history buffers, its staging buffers, its stream position and its HIP-event pair.  The per-stage files
+check the receive stages together and the transmit stages together; this is the only place that has all eight
+interleaved."""
 import numpy as np
 import pytest
 
 from helpers import make_cfg
-from ofdm_uhd_amd import ddc, duc, engine, resample, tx_resample
+from ofdm_uhd_amd import ddc, duc, engine, pfb, resample, tx_resample
 
 pytestmark = pytest.mark.gpu
 
-STAGES = ("ddc", "ddc_bank", "resamp", "duc", "tx_resamp")
-# samples of history a stage carries from call to call: ntaps - 1 (DDC, bank), (ntaps - 1) // L (the others)
-HISTORY = {"ddc": 6, "ddc_bank": 6, "resamp": 5, "duc": 2, "tx_resamp": 5}
+STAGES = ("ddc", "ddc_bank", "resamp", "duc", "tx_resamp", "pfb", "pfb_synth", "duc_bank")
+# the stages whose output is (K, nout), and those whose input is (K, nin)
+ROWS_OUT = ("ddc_bank", "pfb")
+ROWS_IN = ("pfb_synth", "duc_bank")
+# samples of history a stage carries from call to call: ntaps - 1 (DDC, bank, channeliser), (ntaps - 1) // L (the
+# others; the synthesis bank and the DUC bank per row, L = M for the synthesis bank)
+HISTORY = {"ddc": 6, "ddc_bank": 6, "resamp": 5, "duc": 2, "tx_resamp": 5, "pfb": 6, "pfb_synth": 5, "duc_bank": 2}
 # chunk 2 is shorter than the stage's history (the history roll keeps the tail of the old one), and still long enough
 # that the call has outputs at the position chunk 1 leaves the stream in (so that it is timed)
 CHUNKS = {"ddc": (1500, 3, 1400), "ddc_bank": (1200, 4, 1801), "resamp": (1001, 3, 2000), "duc": (1300, 1, 900),
-          "tx_resamp": (999, 4, 1600)}
+          "tx_resamp": (999, 4, 1600), "pfb": (1202, 3, 1500), "pfb_synth": (700, 2, 500), "duc_bank": (900, 1, 700)}
 
 
 def _configs():
@@ -27,19 +32,24 @@ def _configs():
             "ddc_bank": ddc.bank_cfg(3, [-0.3, 0.12], taps=t7()),
             "resamp": resample.resamp_cfg(4, 3, -0.17, taps=t23()),
             "duc": duc.duc_cfg(3, 0.25, taps=t7()),
-            "tx_resamp": tx_resample.tx_resamp_cfg(4, 3, -0.2, taps=t23())}
+            "tx_resamp": tx_resample.tx_resamp_cfg(4, 3, -0.2, taps=t23()),
+            "pfb": pfb.pfb_cfg(4, channels=[1, 3], taps=t7()),
+            "pfb_synth": pfb.synth_cfg(4, [1, 3], taps=t23()),
+            "duc_bank": duc.bank_cfg(3, [-0.3, 0.12], taps=t7())}
 
 
 def _chunks(name):
-    """The stage's own stream (a seed per stage), cut into its three chunks."""
+    """The stage's own stream (a seed per stage; one stream per row for the two transmit banks), cut into its three
+    chunks."""
     n = CHUNKS[name]
     rng = np.random.default_rng(100 + STAGES.index(name))
-    x = (0.1 * (rng.standard_normal(sum(n)) + 1j * rng.standard_normal(sum(n)))).astype(np.complex64)
-    return [x[:n[0]], x[n[0]:n[0] + n[1]], x[n[0] + n[1]:]]
+    shape = (2, sum(n)) if name in ROWS_IN else (sum(n),)
+    x = (0.1 * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))).astype(np.complex64)
+    return [x[..., :n[0]], x[..., n[0]:n[0] + n[1]], x[..., n[0] + n[1]:]]
 
 
 def _join(name, parts):
-    return np.concatenate(parts, axis=1 if name == "ddc_bank" else 0)
+    return np.concatenate(parts, axis=1 if name in ROWS_OUT else 0)
 
 
 def _readable(eng, name):
@@ -49,11 +59,11 @@ def _readable(eng, name):
         return False
 
 
-def test_five_stages_interleaved_on_one_handle():
+def test_eight_stages_interleaved_on_one_handle():
     cfgs = _configs()
     chunks = {s: _chunks(s) for s in STAGES}
     for s in STAGES:
-        assert 1 <= len(chunks[s][1]) < HISTORY[s]
+        assert 1 <= chunks[s][1].shape[-1] < HISTORY[s]
 
     # what each stage gives for its chunks on a handle that has nothing else configured
     want = {}
