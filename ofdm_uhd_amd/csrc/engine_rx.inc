@@ -233,7 +233,9 @@ static int launch_sync(ofdm_handle* h, SyncParams& sp) {
     int wg = (int)std::min<size_t>(SYNC_MAX_WG, CU_LDS_BYTES / sync_shmem);
     if (const char* w = getenv("OFDM_SYNC_W")) wg = std::min(wg, atoi(w));  // tuning knob: a larger register budget
     bool fixed_layout = sp.R - (int)T <= (int)T;  // history no longer than a tile: [history | tile] at fixed LDS places
-    if (const char* e = getenv("OFDM_SYNC_STATIC")) fixed_layout = fixed_layout && atoi(e) != 0;  // tuning knob
+    // tuning knob: the ring where the fixed layout would do.  Not where the tile's M values overlay its samples
+    // (sync_mt_overlay: N <= 512) -- only the fixed layout has the tile at one place, the ring would read M for y.
+    if (const char* e = getenv("OFDM_SYNC_STATIC")) fixed_layout = fixed_layout && (atoi(e) != 0 || sync_mt_overlay(sp.R));
     const void* fn = fixed_layout ? (wg >= 6   ? reinterpret_cast<const void*>(&k_sync<6, true>)
                                      : wg == 5 ? reinterpret_cast<const void*>(&k_sync<5, true>)
                                      : wg == 4 ? reinterpret_cast<const void*>(&k_sync<4, true>)

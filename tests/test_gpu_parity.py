@@ -66,7 +66,11 @@ def test_rx_parity(orc, mod, N, occ, CP, plen, npkt, snr, cfo):
     eng = _engine(cfg)
     pay = make_payloads(npkt, plen)
     x = loopback_stream(orc, cfg, pay, snr_db=snr, cfo_bins=cfo)                # ONE input for both receivers
-    pk = _check_rx(orc, cfg, eng, x)
+    ro = oracle_rx(orc, cfg, x)
+    pk = _check_rx(orc, cfg, eng, x, ro)
+    # the same capture on the path production runs -- no tap: the kernel compiled without them, the counts kept on the
+    # device -- against the same oracle result
+    check_rx_tap_free(eng, x, ro, eng.rx_packet_pos().tolist())
     # every packet whose preamble was derotated with a settled frequency estimate is recovered
     good = [p for ok, p in pk if ok]
     assert all(p in pay for p in good)
@@ -75,11 +79,41 @@ def test_rx_parity(orc, mod, N, occ, CP, plen, npkt, snr, cfo):
     eng.close()
 
 
-def _check_rx(orc, cfg, eng, x):
+STAT_KEYS = ("symbols", "samples", "peaks", "frames", "headers_ok", "packets", "crc_ok", "chained_frames")
+
+
+def oracle_rx(orc, cfg, x):
+    """The oracle's result with the taps _check_rx compares."""
     mask = 0
     for t in RX_TAPS:
         mask |= 1 << t
-    ro = orc.rx(cfg, x, mask)
+    return orc.rx(cfg, x, mask)
+
+
+def check_rx_untapped(eng, x, ro, pos):
+    """One eng.rx(x) with whatever instrumentation the handle has on, but no tap: packets (the failed ones byte for
+    byte), timing flags, frames, the eight counters and the packets' positions."""
+    pk = eng.rx(x)
+    assert pk == ro.packets
+    assert eng.tap(_abi.TAP_RX_PEAKS).tolist() == ro.tap(_abi.TAP_RX_PEAKS).tolist()
+    assert eng.tap(_abi.TAP_RX_FRAMES).tolist() == ro.tap(_abi.TAP_RX_FRAMES).tolist()
+    for k in STAT_KEYS:
+        assert eng.last_stats[k] == ro.stats[k], k
+    assert eng.last_stats["overflow"] == 0
+    assert eng.rx_packet_pos().tolist() == pos
+    return pk
+
+
+def check_rx_tap_free(eng, x, ro, pos):
+    """The lean kernel (k_rx_demod<N, TWL, false>) and the device-side counts: what a call without taps, link quality and
+    channel state runs.  pos: rx_packet_pos() of the tapped pass on the same capture."""
+    eng.set_taps()
+    return check_rx_untapped(eng, x, ro, pos)
+
+
+def _check_rx(orc, cfg, eng, x, ro=None):
+    if ro is None:
+        ro = oracle_rx(orc, cfg, x)
     eng.set_taps(*RX_TAPS)
     pk = eng.rx(x)
     # integer / decision outputs: bit-exact
