@@ -590,6 +590,64 @@ int ofdm_resamp_taps(const ofdm_handle *h, ofdm_c32 *out, int cap, int *n);
  * produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_resamp_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband receive: every link of a capture in one pass at a rational rate (resampler bank) ------------------------
+ * What the DDC bank is to ofdm_ddc, for ofdm_resamp: one ratio L / M, one real prototype h[0..ntaps) and K centre
+ * frequencies give K streams at the modem's rate from ONE pass over the wideband stream (a 25 MS/s capture that holds
+ * several 10 MS/s links), where K calls of ofdm_resamp read, convert and stage the capture K times.  Additions only:
+ * OFDM_ABI_VERSION stays 6 and the OFDM_K_* table is unchanged.
+ * Definition.  Link i of the bank is the resampler above with (interpolation = L, decimation = M, taps = h,
+ * center_freq = fc[i]), bit for bit:
+ *   table     c_i[k] = complex64(h[k] exp(j 2 pi fc_i k / L)), float64 on the host, rounded once
+ *             (ofdm_resamp_bank_taps);
+ *   phase     D_i = frac(fc_i M / L) 2^64 truncated, 0 where frac rounds up to 1;
+ *   input     the handle's receive IQ format and scale, converted as the resampler converts;
+ *   output    of a call with input indices [a, a + n): every n with a <= floor(n M / L) < a + n, the same set for every
+ *             link;
+ *   additions tap q of an output belongs to chain q mod NG, NG the resampler's function of (L, M) alone; a chain adds
+ *             its taps in ascending q into A += c.re * (x.re, x.im), B += c.im * (x.re, x.im), packed fused
+ *             multiply-adds begun at +0; the chains are added in ascending order; v = (A.re - B.im, A.im + B.re);
+ *   rotation  y_i[n] = v_i[n] r_i[n], the unfused complex product,
+ *             r_i[n] = complex64(expj(-2 pi (n D_i mod 2^64) / 2^64)).
+ * Nothing depends on where a call, a chunk or a tile starts, on K, or on a link's position in the list: link i's
+ * stream equals what ofdm_resamp gives for fc_i, under any segmentation.  Equal frequencies are allowed and give equal
+ * outputs.
+ *   state     the last (ntaps - 1) / L converted samples and the absolute index of the next input sample, shared by
+ *             all links and separate from the resampler's, the DDC's, the DDC bank's, the channeliser's and the
+ *             transmit stages': a handle may have all of them configured, none disturbs another.
+ * Pointers are host or device as the handle was created; ordering behind an ofdm_tx_async in flight and the alignment
+ * rules are ofdm_ddc's.  Link i's outputs go to the contiguous run iq_out + i * link_stride (samples); out_cap and
+ * *nout count outputs PER LINK.  With no bank configured nothing here launches, allocates or copies.
+ * OFDM_E_INVAL: as for the resampler (bad struct_size, interpolation, decimation, ntaps, a non-finite tap, a call
+ * without a configuration, misaligned input, a stream index above 2^56), and: nlinks 0 or above
+ * OFDM_RESAMP_BANK_MAX_LINKS, any |center_freq[i]| > 0.5 or NaN, link >= nlinks, link_stride < *nout with nlinks > 1.
+ * A refused configuration leaves the one in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_resamp_bank_count says (*nout is set); the stream state is then
+ * unchanged. */
+#define OFDM_RESAMP_BANK_MAX_LINKS 8
+typedef struct ofdm_resamp_bank_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_resamp_bank_cfg) */
+  uint32_t interpolation; /* L, 1..64, shared by the links */
+  uint32_t decimation;    /* M, 1..64, shared by the links */
+  uint32_t ntaps;         /* 1..OFDM_RESAMP_MAX_TAPS */
+  uint32_t nlinks;        /* K, 1..OFDM_RESAMP_BANK_MAX_LINKS */
+  double center_freq[OFDM_RESAMP_BANK_MAX_LINKS]; /* fc[i], cycles per INPUT sample, [-0.5, 0.5]; the first nlinks count */
+  float taps[OFDM_RESAMP_MAX_TAPS]; /* real low-pass prototype at L times the input rate, shared by the links */
+} ofdm_resamp_bank_cfg;
+/* K rational_resampler_ccf ctors behind K tuners on one stream; NULL: none.  Resets the bank's stream state. */
+int ofdm_set_resamp_bank(ofdm_handle *h, const ofdm_resamp_bank_cfg *cfg);
+/* a new stream whose first sample has this absolute index (at most 2^56): history zero */
+int ofdm_resamp_bank_reset(ofdm_handle *h, uint64_t first_sample_index);
+/* outputs PER LINK the next ofdm_resamp_bank call of nin samples produces, from the current state */
+int ofdm_resamp_bank_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of the stream through every link: link i at iq_out + i * link_stride, out_cap per link */
+int ofdm_resamp_bank(ofdm_handle *h, const void *iq_in, uint64_t nin, ofdm_c32 *iq_out, uint64_t link_stride,
+                     uint64_t out_cap, uint64_t *nout);
+/* the table of one link as the kernel multiplies with it (out NULL: size query) */
+int ofdm_resamp_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_resamp_bank in the last ofdm_resamp_bank, which must have run with profiling on and produced
+ * output; OFDM_E_INVAL otherwise. */
+int ofdm_resamp_bank_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- wideband transmit: interpolate and translate (DUC) behind ofdm_tx -------------
  * The mirror image of the stage above.  The reference leaves it to its radio (sink.set_interp / set_center_freq,
  * usrp_transmit_path.py:79-88; generic_usrp.set_interp; the two-channel transmitter of dual_channel/dual_channel.py);

@@ -17,6 +17,7 @@ OFDM_MAX_CARRIER_HEX = 1024
 OFDM_DDC_MAX_TAPS = 1024
 OFDM_DDC_BANK_MAX_LINKS = 8
 OFDM_RESAMP_MAX_TAPS = 1024
+OFDM_RESAMP_BANK_MAX_LINKS = 8
 OFDM_DUC_MAX_TAPS = 1024
 OFDM_DUC_BANK_MAX_LINKS = 8
 OFDM_TX_RESAMP_MAX_TAPS = 1024
@@ -217,6 +218,18 @@ class ofdm_resamp_cfg(C.Structure):
     ]
 
 
+class ofdm_resamp_bank_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interpolation", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("nlinks", C.c_uint32),
+        ("center_freq", C.c_double * OFDM_RESAMP_BANK_MAX_LINKS),
+        ("taps", C.c_float * OFDM_RESAMP_MAX_TAPS),
+    ]
+
+
 class ofdm_tx_resamp_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -247,6 +260,8 @@ EXPORTS = (
     "ofdm_set_ddc_bank", "ofdm_ddc_bank_reset", "ofdm_ddc_bank_count", "ofdm_ddc_bank", "ofdm_ddc_bank_taps",
     "ofdm_ddc_bank_last_ms",
     "ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps", "ofdm_resamp_last_ms",
+    "ofdm_set_resamp_bank", "ofdm_resamp_bank_reset", "ofdm_resamp_bank_count", "ofdm_resamp_bank", "ofdm_resamp_bank_taps",
+    "ofdm_resamp_bank_last_ms",
     "ofdm_set_tx_resamp", "ofdm_tx_resamp_reset", "ofdm_tx_resamp_count", "ofdm_tx_resamp", "ofdm_tx_resamp_last_ms",
     "ofdm_set_pfb", "ofdm_pfb_reset", "ofdm_pfb_count", "ofdm_pfb", "ofdm_pfb_last_ms",
     "ofdm_set_pfb_synth", "ofdm_pfb_synth_reset", "ofdm_pfb_synth", "ofdm_pfb_synth_last_ms",
@@ -311,6 +326,12 @@ def _declare(lib):
     lib.ofdm_resamp.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
     lib.ofdm_resamp_taps.argtypes = [H, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_resamp_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_resamp_bank.argtypes = [H, C.POINTER(ofdm_resamp_bank_cfg)]
+    lib.ofdm_resamp_bank_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_resamp_bank_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_resamp_bank.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, u64p]
+    lib.ofdm_resamp_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_resamp_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_duc.argtypes = [H, C.POINTER(ofdm_duc_cfg)]
     lib.ofdm_duc_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_duc.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]

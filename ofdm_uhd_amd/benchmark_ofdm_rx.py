@@ -67,6 +67,11 @@ def make_parser():
                            "they are extracted in one pass on the GPU (ofdm_demod_bank), one account per link, and "
                            "--to-file gets .linkN appended [default=off]")
     _options.add_resamp_options(parser)
+    parser.add_option("", "--resamp-freqs", default=None,
+                      help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
+                           "ALL links in the capture; they are extracted in one pass on the GPU "
+                           "(ofdm_demod_resamp_bank), one account per link, and --to-file gets .linkN appended "
+                           "[default=off]")
     parser.add_option("", "--csi-report", default=None,
                       help="write the per-carrier channel report over the CRC-ok packets to this file: one line per "
                            "occupied carrier (index, FFT bin, preamble SNR, decision SNR, gain in dB) [default=off]")
@@ -77,25 +82,14 @@ def make_parser():
     return parser
 
 
-def _main_bank(parser, options):
-    """--ddc-freqs: every link of the wideband file through one ofdm_demod_bank; returns the per-link accounts."""
-    if options.ddc_freq is not None:
-        parser.error("--ddc-freqs and --ddc-freq are mutually exclusive")
-    if not options.ddc_decim:
-        parser.error("--ddc-freqs needs --ddc-decim")
-    if options.link_quality or options.csi_report is not None or options.suggest_map is not None:
-        parser.error("--ddc-freqs does not combine with --link-quality, --csi-report or --suggest-map")
-    try:
-        freqs = [float(f) for f in options.ddc_freqs.split(",")]
-    except ValueError:
-        parser.error("--ddc-freqs takes comma-separated numbers")
+def _run_links(options, freqs, make_bank):
+    """Every link of the wideband file through ``make_bank(callback)``, an ofdm_demod_bank or one of its kin: one
+    account and one ``--to-file``.linkN per link; returns the accounts."""
     files = [open("%s.link%d" % (options.to_file, i), "wb") for i in range(len(freqs))]
     accts = [rx_accounting(f) for f in files]
     bank = None
     try:
-        bank = ofdm.ofdm_demod_bank(options, freqs, int(options.ddc_decim), iq_format=options.iq_format,
-                                    iq_scale=options.iq_scale,
-                                    callback=lambda link, ok, payload: accts[link].rx_callback(ok, payload))
+        bank = make_bank(lambda link, ok, payload: accts[link].rx_callback(ok, payload))
         source = iqio.file_source(options.from_file, fmt=options.iq_format)
         if int(options.chunk_samples):
             for piece in source.read_chunks(int(options.chunk_samples)):
@@ -111,12 +105,50 @@ def _main_bank(parser, options):
     return accts
 
 
+def _main_bank(parser, options):
+    """--ddc-freqs: every link of the wideband file through one ofdm_demod_bank; returns the per-link accounts."""
+    if options.ddc_freq is not None:
+        parser.error("--ddc-freqs and --ddc-freq are mutually exclusive")
+    if not options.ddc_decim:
+        parser.error("--ddc-freqs needs --ddc-decim")
+    if options.link_quality or options.csi_report is not None or options.suggest_map is not None:
+        parser.error("--ddc-freqs does not combine with --link-quality, --csi-report or --suggest-map")
+    try:
+        freqs = [float(f) for f in options.ddc_freqs.split(",")]
+    except ValueError:
+        parser.error("--ddc-freqs takes comma-separated numbers")
+    return _run_links(options, freqs, lambda cb: ofdm.ofdm_demod_bank(
+        options, freqs, int(options.ddc_decim), iq_format=options.iq_format, iq_scale=options.iq_scale, callback=cb))
+
+
+def _main_resamp_bank(parser, options):
+    """--resamp-freqs: every link of the wideband file through one ofdm_demod_resamp_bank; returns the per-link
+    accounts."""
+    if options.ddc_decim or options.ddc_freq is not None or options.ddc_freqs is not None:
+        parser.error("--resamp-freqs does not combine with --ddc-decim, --ddc-freq or --ddc-freqs")
+    if options.resamp_freq:
+        parser.error("--resamp-freqs and --resamp-freq are mutually exclusive")
+    if not options.resamp_interp and not options.resamp_decim:
+        parser.error("--resamp-freqs needs --resamp-interp / --resamp-decim")
+    if options.link_quality or options.csi_report is not None or options.suggest_map is not None:
+        parser.error("--resamp-freqs does not combine with --link-quality, --csi-report or --suggest-map")
+    try:
+        freqs = [float(f) for f in options.resamp_freqs.split(",")]
+    except ValueError:
+        parser.error("--resamp-freqs takes comma-separated numbers")
+    L, M = int(options.resamp_interp or 1), int(options.resamp_decim or 1)  # (one of the two alone: the other is 1)
+    return _run_links(options, freqs, lambda cb: ofdm.ofdm_demod_resamp_bank(
+        options, freqs, L, M, iq_format=options.iq_format, iq_scale=options.iq_scale, callback=cb))
+
+
 def main(argv=None):
     parser = make_parser()
     (options, args) = parser.parse_args(argv)
     if len(args) != 0:
         parser.print_help(sys.stderr)
         sys.exit(1)
+    if options.resamp_freqs is not None:
+        return _main_resamp_bank(parser, options)
     if options.ddc_freqs is not None:
         return _main_bank(parser, options)
 

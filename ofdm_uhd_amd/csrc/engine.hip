@@ -25,6 +25,7 @@
 #include "duc.h"
 #include "duc_bank.h"
 #include "resamp.h"
+#include "resamp_bank.h"
 #include "tx_resamp.h"
 #include "pfb.h"
 #include "pfb_synth.h"
@@ -117,6 +118,7 @@ struct ofdm_handle {
   DdcBankState bank;  // all links of a capture in one pass (ddc_bank.h / engine_ddc_bank.inc)
   DucState duc;  // wideband transmit stage (duc.h / engine_duc.inc)
   ResampState resamp;  // rational-rate front end (resamp.h / engine_resamp.inc)
+  ResampBankState resamp_bank;  // all links of a capture at a rational rate in one pass (resamp_bank.h / engine_resamp_bank.inc)
   TxResampState tx_resamp;  // rational-rate transmit stage (tx_resamp.h / engine_tx_resamp.inc)
   PfbState pfb;  // polyphase-FFT channeliser for links on the k/M grid (pfb.h / engine_pfb.inc)
   PfbSynthState pfb_synth;  // its transmit mirror: the synthesis bank (pfb_synth.h / engine_pfb_synth.inc)
@@ -548,6 +550,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->bank.release();
   h->duc.release();
   h->resamp.release();
+  h->resamp_bank.release();
   h->tx_resamp.release();
   h->pfb.release();
   h->pfb_synth.release();
@@ -987,6 +990,7 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_ddc_bank.inc"
 #include "engine_duc.inc"
 #include "engine_resamp.inc"
+#include "engine_resamp_bank.inc"
 #include "engine_tx_resamp.inc"
 #include "engine_pfb.inc"
 #include "engine_pfb_synth.inc"

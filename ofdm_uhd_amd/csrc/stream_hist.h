@@ -1,4 +1,4 @@
-// stream_hist.h -- the history kernels of the eight wideband stream stages: each keeps the last H input samples of its
+// stream_hist.h -- the history kernels of the nine wideband stream stages: each keeps the last H input samples of its
 // stream (ddc.h, ddc_bank.h, pfb.h, resamp.h, duc.h, tx_resamp.h), or of each of its streams (pfb_synth.h, duc_bank.h),
 // for the next call's oldest taps.  (What the stages' compute kernels share is stream_tile.h.)
 #pragma once

@@ -81,6 +81,7 @@ class Engine(object):
         self.ddc_cfg = None     # the wideband front end's configuration in force (set_ddc), None without one
         self.ddc_bank_cfg = None  # the DDC bank's configuration in force (set_ddc_bank), None without one
         self.resamp_cfg = None  # the rational-rate front end's configuration in force (set_resamp), None without one
+        self.resamp_bank_cfg = None  # the resampler bank's configuration in force (set_resamp_bank), None without one
         self.duc_cfg = None     # the wideband transmit stage's configuration in force (set_duc), None without one
         self.tx_resamp_cfg = None  # the rational-rate transmit stage's configuration in force (set_tx_resamp), None without one
         self.pfb_cfg = None     # the channeliser's configuration in force (set_pfb), None without one
@@ -348,7 +349,7 @@ class Engine(object):
         n = npk.value
         return n, off[:n + 1], ln[:n], ok[:n]
 
-    # -- the eight wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
+    # -- the nine wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
     def _stage_set(self, name, maker, cfg, kw):
         """ofdm_set_<name>: ``cfg`` or, from keywords, what ``maker`` ("module.function" of this package) builds."""
         if cfg is None and kw:
@@ -505,6 +506,47 @@ class Engine(object):
     def resamp_last_ms(self):
         """HIP-event time of k_resamp in the last resamp() / resamp_device() (needs prof_enable())."""
         return self._stage_last_ms("resamp")
+
+    # -- resampler bank: every link of a capture at a rational rate in one pass ----------------
+    def set_resamp_bank(self, cfg=None, **kw):
+        """Configure the bank: an ``ofdm_resamp_bank_cfg`` (resample.bank_cfg) or its keywords (interpolation=,
+        decimation=, center_freqs=, taps= / occupied_fraction=).  ``set_resamp_bank(None)`` with no keywords removes
+        it.  Resets the bank's stream state; the single resampler (set_resamp) is a separate stage and keeps its own."""
+        self._stage_set("resamp_bank", "resample.bank_cfg", cfg, kw)
+
+    def resamp_bank_reset(self, first_sample_index=0):
+        """Start a new wideband stream whose first sample has this absolute index; the filter history is zero."""
+        self._stage_reset("resamp_bank", first_sample_index)
+
+    def resamp_bank_count(self, nin):
+        """Outputs PER LINK the next resamp_bank() call of ``nin`` samples produces, from the current stream state."""
+        return self._stage_count("resamp_bank", nin)
+
+    def resamp_bank(self, iq):
+        """Host mode: the next samples of the wideband stream (in the receive IQ format) -> complex64 of shape
+        (K, nout): row i is what resamp() gives for link i's frequency.  Stateful like resamp()."""
+        assert not self.device_ptrs
+        if self.resamp_bank_cfg is None:
+            raise ValueError("resamp_bank() without set_resamp_bank()")
+        iq = self._rx_samples(iq)
+        K = int(self.resamp_bank_cfg.nlinks)
+        cap = max(self.resamp_bank_count(len(iq)), 1)
+        out = np.zeros((K, cap), np.complex64)
+        return out[:, :self._stage_call("resamp_bank", _ptr(iq) if len(iq) else None, len(iq), _ptr(out), cap, cap)]
+
+    def resamp_bank_device(self, iq_ptr, nin, out_ptr, link_stride, out_cap):
+        """Device mode: both buffers are device pointers; link i's run begins ``link_stride`` samples after link
+        i - 1's and can go straight to rx_device / rx_submit_device.  Returns the number of outputs per link."""
+        return self._stage_device("resamp_bank", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(link_stride),
+                                  int(out_cap))
+
+    def resamp_bank_taps(self, link):
+        """The band-pass table of one link as the kernel multiplies with it (complex64)."""
+        return self._stage_taps("resamp_bank", int(link))
+
+    def resamp_bank_last_ms(self):
+        """HIP-event time of k_resamp_bank in the last resamp_bank() / resamp_bank_device() (needs prof_enable())."""
+        return self._stage_last_ms("resamp_bank")
 
     # -- DDC bank: every link of a wideband capture in one pass ------------------------------
     def set_ddc_bank(self, cfg=None, **kw):

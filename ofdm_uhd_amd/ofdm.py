@@ -912,3 +912,63 @@ class ofdm_demod_channelizer(ofdm_demod_bank):
         if len(iq) == 0:
             return np.zeros((len(self._links), 0), np.complex64)
         return eng.pfb(iq)
+
+
+class ofdm_demod_resamp_bank(ofdm_demod_bank):
+    """
+    Demodulates every link of one wideband capture whose rate is M / L times the modem's, no integer multiple of it
+    (a recorder's 25 MS/s file that holds several 10 MS/s links): K links that share the ratio and the low-pass
+    prototype and differ in their centre frequency.  ofdm_demod_bank with the resampler bank (Engine.resamp_bank) in
+    the DDC bank's place: link i returns what ofdm_demod(options_i, resample=dict(interpolation=, decimation=,
+    center_freq=center_freqs[i], taps=)) returns on the same samples.  work, feed, flush, links and close are the
+    bank's.
+    """
+
+    def __init__(self, options, center_freqs, interpolation, decimation, taps=None, callback=None, iq_format="fc32",
+                 iq_scale=None, device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
+        @param interpolation, decimation: L and M, 1..64 each: the modem's rate is L / M times the capture's
+        @param taps: the shared prototype at L times the wideband rate; None: resample.design for the largest
+            occupied_tones / fft_length of the links
+        @param callback: function of three args: link, ok, payload -- per call fired for link 0's packets, then link
+            1's, and so on
+        @param iq_format, iq_scale: format of the WIDEBAND samples, as for ofdm_demod
+        """
+        # every argument is checked before the first engine exists
+        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != len(fcs):
+                raise ValueError("ofdm_demod_resamp_bank needs one options object, or one per centre frequency")
+        else:
+            opts = [options] * len(fcs)
+        if callback is not None and not callable(callback):
+            raise ValueError("callback must be callable: callback(link, ok, payload)")
+        fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        # ValueError: K, frequencies, L, M, taps
+        cfg = _resample.bank_cfg(interpolation, decimation, fcs, taps=taps, occupied_fraction=occ)
+        self._callback = callback
+        self._links = []
+        self._engine = engine.Engine(opts[0], device_id=device_id)
+        try:
+            if fmt != "fc32":
+                self._engine.set_rx_iq_format(fmt, scale)
+            self._engine.set_resamp_bank(cfg)
+            for i, o in enumerate(opts):
+                cb = (lambda ok, payload, link=i: self._callback(link, ok, payload)) if callback is not None else None
+                self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
+        except Exception:
+            self.close()
+            raise
+        self._streaming = False
+
+    def _tune(self, iq, restart):
+        eng = self._engine
+        if restart:
+            eng.resamp_bank_reset(0)
+        if len(iq) == 0:
+            return np.zeros((len(self._links), 0), np.complex64)
+        return eng.resamp_bank(iq)

@@ -15,6 +15,7 @@ from . import _abi, ddc, firdes
 
 MAX_TAPS = _abi.OFDM_RESAMP_MAX_TAPS
 MAX_RATIO = 64
+MAX_LINKS = _abi.OFDM_RESAMP_BANK_MAX_LINKS
 
 
 def _check_ratio(interpolation, decimation):
@@ -70,4 +71,25 @@ def resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupied_f
     cfg.interpolation = int(interpolation)
     cfg.decimation = int(decimation)
     cfg.center_freq = float(center_freq)
+    return cfg
+
+
+def bank_cfg(interpolation, decimation, center_freqs, taps=None, occupied_fraction=None, transition=None):
+    """ofdm_resamp_bank_cfg for Engine.set_resamp_bank: one ratio and one prototype, one centre frequency per link
+    (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed).  ``taps=None``
+    designs the prototype from ``occupied_fraction`` as resamp_cfg does.  ValueError for a ratio outside 1..64, with
+    given taps too."""
+    L, M = _check_ratio(interpolation, decimation)
+    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    if not 1 <= len(fcs) <= MAX_LINKS:
+        raise ValueError("a resampler bank has 1 to %d links" % MAX_LINKS)
+    if not all(abs(f) <= 0.5 for f in fcs):
+        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
+    cfg = ddc._cfg_with_taps(_abi.ofdm_resamp_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, decimation, occupied_fraction, transition))
+    cfg.interpolation = L
+    cfg.decimation = M
+    cfg.nlinks = len(fcs)
+    for i, f in enumerate(fcs):
+        cfg.center_freq[i] = f
     return cfg
