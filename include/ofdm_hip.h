@@ -912,6 +912,87 @@ int ofdm_tx_resamp(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const of
  * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_tx_resamp_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- wideband transmit: L / M resampler bank, K links onto one band in one pass -------------------------------------
+ * What replaces one ofdm_tx_resamp(..., add = band) pass per link (several 10 MS/s links in a 25 MS/s band): one ratio
+ * L / M, one real prototype h[0..ntaps) and K centre frequencies place K narrowband streams on the band in ONE pass.
+ * K passes of ofdm_tx_resamp evaluate the float64 phasor once per OUTPUT and pass; here the shift moves to the input
+ * side, as in the DUC bank: one phasor per INPUT sample and link (M / L per output), and all links add into one
+ * accumulator pair before a single store.  The order of the additions, hence the last bits, are this stage's own: it
+ * is not bit-identical to K ofdm_tx_resamp passes.  A standalone, stateful stage; additions only: OFDM_ABI_VERSION
+ * stays 6, the OFDM_K_* table is unchanged, and with no bank configured nothing here launches, allocates or copies.
+ * Definition.  K = nlinks links, 1..OFDM_TX_RESAMP_BANK_MAX_LINKS; L = interpolation and M = decimation, any integers
+ * in 1..64, shared (the library does not reduce them); h[k], k in [0, ntaps): real float32 taps at L times the input
+ * rate, shared; fc_i in [-0.5, 0.5] cycles per OUTPUT sample; x_i[m]: link i's narrowband complex64 stream, m an
+ * absolute index counted from the last reset (ofdm_set_tx_resamp_bank, ofdm_tx_resamp_bank_reset), zero before that
+ * reset's first index.  Output n sits at position n M on the L-times grid: i_n = floor(n M / L), p_n = n M mod L, and
+ * a call with the inputs [a, a + nin) produces every output with a <= i_n < a + nin, as in ofdm_tx_resamp.
+ *   phase     G_i = frac(fc_i / M) * 2^64 truncated, 0 where frac rounds up to 1: the phase per step of the L-times
+ *             grid; fc_i / M is ONE double division.  E_i = (L * G_i) mod 2^64 is the advance per INPUT sample,
+ *             D_i = (M * G_i) mod 2^64 the advance per OUTPUT sample.  The effective centre frequency is D_i / 2^64
+ *             cycles per output sample; it can differ from fc_i by up to about M * 2^-54.
+ *   rotation  xr_i[m] = x_i[m] * r_i[m], r_i[m] = complex64(expj(+2 pi (m E_i mod 2^64) / 2^64)): the engine's
+ *             bit-reproducible float64 evaluation of expj, rounded to complex64 once; the product is the gr_complex
+ *             product: two products and one addition per part, separately rounded.  A function of the absolute m and
+ *             the configuration alone.
+ *   table     c_i[k] = complex64(h[k] exp(j 2 pi fc_i k / M)), float64 on the host, rounded once
+ *             (ofdm_tx_resamp_bank_taps): bit for bit the table ofdm_resamp_bank_taps returns for the mirror ratio
+ *             (interpolation = M) with the same (h, fc_i).
+ *   sums      for output n, p = p_n: A and B are each ONE chain of packed fused multiply-adds on the (re, im) pair,
+ *             begun at +0; the links in ascending i, inside a link q ascending while p + q L < ntaps:
+ *               A = fma(re c_i[p + q L], xr_i[i_n - q], A),   B = fma(im c_i[p + q L], xr_i[i_n - q], B)
+ *             v[n] = (A.re - B.im, A.im + B.re), one float32 operation per part.  A phase without a tap
+ *             (ntaps <= p) gives v[n] = 0.  The input-side shift is exact: n M = (p + q L) + (i_n - q) L, so
+ *             k G_i + m E_i = n D_i modulo 2^64 without rounding.  The value depends on n and the configuration (the
+ *             order of the list included), never on where a call, a chunk or a tile starts.
+ *   store     out[n] = store(v[n] + add[n]) when an `add` buffer is given (one float32 addition per part), else
+ *             store(v[n]); complex64, or ofdm_sc16 by the transmit rule of ofdm_tx_resamp (out_format / out_scale are
+ *             the stage's own).
+ *   state     the last Q = (ntaps - 1) / L RAW inputs of every link (rotated when they are used, never stored rotated)
+ *             and the absolute index of the next input: the bank's own, separate from every other stage's.  Any
+ *             segmentation gives the same bits; calls of 0 inputs, calls shorter than Q and calls that produce nothing
+ *             are included.
+ * With K = 1 and fc = 0 the output equals ofdm_tx_resamp's at fc = 0; with K = 1 and h = {1.0} it equals
+ * ofdm_tx_resamp's at the same fc wherever frac(fc) 2^64 = M G exactly.  The stream's input index must stay at or
+ * below 2^56, as a reset value and after a call.  Link i's nin inputs are the contiguous run iq_in + i * link_stride
+ * (samples).  add (may be NULL) is complex64 with as many samples as the call has outputs and may be iq_out itself when
+ * out_format is OFDM_IQ_FC32: each output sample is read before it is written, by the same thread.  Pointers are host
+ * or device as the handle was created.  Like ofdm_duc_bank, the call orders itself behind an ofdm_tx_async still in
+ * flight and returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, interpolation or decimation outside 1..64, bad ntaps, nlinks, out_format or out_scale,
+ * a non-finite tap, any |center_freq[i]| > 0.5 or NaN; ofdm_tx_resamp_bank / _reset / _count / _taps without a
+ * configuration; link >= nlinks; a float32 pointer not 8-byte (ofdm_sc16: 4-byte) aligned; link_stride < nin with
+ * nlinks > 1; the index limit above; a call too long for one grid (split it).  A refused configuration leaves the one
+ * in force (or none) as it was.
+ * OFDM_E_CAPACITY: out_cap smaller than ofdm_tx_resamp_bank_count says (*nout is set); the stream state is then
+ * unchanged. */
+#define OFDM_TX_RESAMP_BANK_MAX_LINKS 8
+typedef struct ofdm_tx_resamp_bank_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_tx_resamp_bank_cfg) */
+  uint32_t interpolation; /* L, 1..64, shared by the links */
+  uint32_t decimation;    /* M, 1..64, shared by the links */
+  uint32_t ntaps;         /* 1..OFDM_TX_RESAMP_MAX_TAPS */
+  uint32_t nlinks;        /* K, 1..OFDM_TX_RESAMP_BANK_MAX_LINKS */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  double center_freq[OFDM_TX_RESAMP_BANK_MAX_LINKS]; /* fc[i], cycles per OUTPUT sample, [-0.5, 0.5]; the first nlinks count */
+  float taps[OFDM_TX_RESAMP_MAX_TAPS]; /* real low-pass prototype at L times the input rate, gain L in its pass band */
+} ofdm_tx_resamp_bank_cfg;
+/* K rational_resampler_ccf ctors + set_center_freq on one band; NULL: none.  Resets the bank's stream state (history
+ * zero, next input index 0). */
+int ofdm_set_tx_resamp_bank(ofdm_handle *h, const ofdm_tx_resamp_bank_cfg *cfg);
+/* a new stream whose first input has this absolute index (at most 2^56): history zero */
+int ofdm_tx_resamp_bank_reset(ofdm_handle *h, uint64_t first_input_index);
+/* outputs the NEXT ofdm_tx_resamp_bank call of nin samples per link produces, from the current state */
+int ofdm_tx_resamp_bank_count(const ofdm_handle *h, uint64_t nin, uint64_t *nout);
+/* the next nin samples of every link in, the samples of the band they complete out (added onto `add` where given) */
+int ofdm_tx_resamp_bank(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t link_stride, uint64_t nin, const ofdm_c32 *add,
+                        void *iq_out, uint64_t out_cap, uint64_t *nout);
+/* the table of one link as the kernel multiplies with it (out NULL: size query) */
+int ofdm_tx_resamp_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int cap, int *n);
+/* HIP-event time of k_tx_resamp_bank in the last ofdm_tx_resamp_bank, which must have run with profiling on
+ * (ofdm_prof_enable) and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_tx_resamp_bank_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -21,6 +21,7 @@ OFDM_RESAMP_BANK_MAX_LINKS = 8
 OFDM_DUC_MAX_TAPS = 1024
 OFDM_DUC_BANK_MAX_LINKS = 8
 OFDM_TX_RESAMP_MAX_TAPS = 1024
+OFDM_TX_RESAMP_BANK_MAX_LINKS = 8
 OFDM_PFB_MAX_CHANNELS = 64
 OFDM_PFB_MAX_TAPS = 1024
 
@@ -244,6 +245,20 @@ class ofdm_tx_resamp_cfg(C.Structure):
     ]
 
 
+class ofdm_tx_resamp_bank_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interpolation", C.c_uint32),
+        ("decimation", C.c_uint32),
+        ("ntaps", C.c_uint32),
+        ("nlinks", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("out_scale", C.c_float),
+        ("center_freq", C.c_double * OFDM_TX_RESAMP_BANK_MAX_LINKS),
+        ("taps", C.c_float * OFDM_TX_RESAMP_MAX_TAPS),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -266,6 +281,8 @@ EXPORTS = (
     "ofdm_set_pfb", "ofdm_pfb_reset", "ofdm_pfb_count", "ofdm_pfb", "ofdm_pfb_last_ms",
     "ofdm_set_pfb_synth", "ofdm_pfb_synth_reset", "ofdm_pfb_synth", "ofdm_pfb_synth_last_ms",
     "ofdm_set_duc_bank", "ofdm_duc_bank_reset", "ofdm_duc_bank", "ofdm_duc_bank_taps", "ofdm_duc_bank_last_ms",
+    "ofdm_set_tx_resamp_bank", "ofdm_tx_resamp_bank_reset", "ofdm_tx_resamp_bank_count", "ofdm_tx_resamp_bank",
+    "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
 )
 
 _LIB = None
@@ -346,6 +363,12 @@ def _declare(lib):
     lib.ofdm_tx_resamp_count.argtypes = [H, C.c_uint64, u64p]
     lib.ofdm_tx_resamp.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
     lib.ofdm_tx_resamp_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_tx_resamp_bank.argtypes = [H, C.POINTER(ofdm_tx_resamp_bank_cfg)]
+    lib.ofdm_tx_resamp_bank_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_tx_resamp_bank_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_tx_resamp_bank.argtypes = [H, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p]
+    lib.ofdm_tx_resamp_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_tx_resamp_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

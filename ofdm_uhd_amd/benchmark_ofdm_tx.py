@@ -55,9 +55,60 @@ def make_parser():
                       help="with --duc-interp: centre of the link in the wideband file, cycles per sample in "
                            "[-0.5, 0.5] (the radio's set_center_freq over the file's rate) [default=%default]")
     _options.add_tx_resamp_options(parser)
+    parser.add_option("", "--tx-resamp-freqs", default=None,
+                      help="with --tx-resamp-interp / --tx-resamp-decim, instead of --tx-resamp-freq: comma-separated "
+                           "centres of ALL links of the band; every link carries the packet stream and they are placed "
+                           "on the band in one pass on the GPU (ofdm_mod_resamp_bank) [default=off]")
     transmit_path.transmit_path.add_options(parser, expert_grp)
     ofdm.ofdm_mod.add_options(parser, expert_grp)
     return parser
+
+
+BANK_BATCH = 16   # packets per link between two flushes of the bank
+
+
+def _main_tx_resamp_bank(parser, options):
+    """--tx-resamp-freqs: the packet stream on every link of one ofdm_mod_resamp_bank, the band to --to-file; returns
+    the packets sent per link."""
+    if options.duc_interp or options.duc_freq:
+        parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
+    if options.tx_resamp_freq:
+        parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
+    if not options.tx_resamp_interp and not options.tx_resamp_decim:
+        parser.error("--tx-resamp-freqs needs --tx-resamp-interp / --tx-resamp-decim")
+    try:
+        freqs = [float(f) for f in options.tx_resamp_freqs.split(",")]
+    except ValueError:
+        parser.error("--tx-resamp-freqs takes comma-separated numbers")
+    L, M = int(options.tx_resamp_interp or 1), int(options.tx_resamp_decim or 1)  # (one of the two alone: the other is 1)
+    try:
+        bank = ofdm.ofdm_mod_resamp_bank(options, freqs, L, M, iq_format=options.iq_format, iq_scale=options.iq_scale)
+    except ValueError as e:
+        parser.error("--tx-resamp-freqs: %s" % e)
+    src = open(options.from_file, 'rb') if options.from_file is not None else None
+    if src is not None:
+        print(os.path.getsize(options.from_file))
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)
+    try:
+        for m in bank.links():
+            m.engine().set_tx_amplitude(min(max(options.tx_amplitude, 0.0), 1))
+        npk = 0
+        for payload in build_payloads(options, src):
+            for i in range(len(freqs)):
+                bank.send_pkt(i, payload)
+            sys.stderr.write('.')
+            npk += 1
+            if npk % BANK_BATCH == 0:
+                sink.write(bank.flush())
+        iq = bank.flush(end=True)
+        if iq is not None:
+            sink.write(iq)
+        symbols = sum(m.symbols_sent for m in bank.links())
+    finally:
+        sink.close()
+        bank.close()
+    sys.stderr.write("\n%d packets on each of %d links, %d symbols -> %s\n" % (npk, len(freqs), symbols, options.to_file))
+    return npk
 
 
 def main(argv=None):
@@ -66,6 +117,8 @@ def main(argv=None):
     if len(args) != 0:
         parser.print_help()
         sys.exit(1)
+    if options.tx_resamp_freqs is not None:
+        return _main_tx_resamp_bank(parser, options)
 
     src = open(options.from_file, 'rb') if options.from_file is not None else None
     if src is not None:

@@ -27,6 +27,7 @@
 #include "resamp.h"
 #include "resamp_bank.h"
 #include "tx_resamp.h"
+#include "tx_resamp_bank.h"
 #include "pfb.h"
 #include "pfb_synth.h"
 
@@ -123,6 +124,7 @@ struct ofdm_handle {
   PfbState pfb;  // polyphase-FFT channeliser for links on the k/M grid (pfb.h / engine_pfb.inc)
   PfbSynthState pfb_synth;  // its transmit mirror: the synthesis bank (pfb_synth.h / engine_pfb_synth.inc)
   DucBankState duc_bank;  // all links of a band at arbitrary centre frequencies in one pass (duc_bank.h / engine_duc_bank.inc)
+  TxResampBankState tx_resamp_bank;  // the same at a rational rate (tx_resamp_bank.h / engine_tx_resamp_bank.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -555,6 +557,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->pfb.release();
   h->pfb_synth.release();
   h->duc_bank.release();
+  h->tx_resamp_bank.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -995,3 +998,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_pfb.inc"
 #include "engine_pfb_synth.inc"
 #include "engine_duc_bank.inc"
+#include "engine_tx_resamp_bank.inc"

@@ -1,7 +1,7 @@
-// engine_stage.inc -- what the host sides of the nine wideband stream stages share (StreamStage, host_util.h): the
+// engine_stage.inc -- what the host sides of the ten wideband stream stages share (StreamStage, host_util.h): the
 // steps of a configure call, reset, the argument checks, host-mode staging, timing, the history roll, the choice of a
 // transmit kernel's <OUT, ADD> and the end of a call.  Included by engine.hip ahead of
-// engine_{ddc,ddc_bank,pfb,resamp,resamp_bank,duc,duc_bank,pfb_synth,tx_resamp}.inc, which keep what is a stage's own: its
+// engine_{ddc,ddc_bank,pfb,resamp,resamp_bank,duc,duc_bank,pfb_synth,tx_resamp,tx_resamp_bank}.inc, which keep what is a stage's own: its
 // configuration checks and messages, its table, its index limits, its output count and its launch.
 
 #define RCCHK(expr)         \

@@ -58,7 +58,7 @@ struct PinBuf {
   }
 };
 
-// What the nine wideband stream stages (DDC, DDC bank, channeliser, DUC, DUC bank, synthesis bank, both resamplers, resampler bank)
+// What the ten wideband stream stages (DDC, DDC bank, channeliser, DUC, DUC bank, synthesis bank, both resamplers, both resampler banks)
 // share on the host: where the stream stands, the carried history and its double buffer, the host-mode staging buffers
 // and the HIP-event pair of the last call.  Each stage's state derives from it and adds its own rates, tables and
 // output format; the code that works on these fields is engine_stage.inc.

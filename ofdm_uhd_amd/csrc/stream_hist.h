@@ -1,5 +1,5 @@
-// stream_hist.h -- the history kernels of the nine wideband stream stages: each keeps the last H input samples of its
-// stream (ddc.h, ddc_bank.h, pfb.h, resamp.h, duc.h, tx_resamp.h), or of each of its streams (pfb_synth.h, duc_bank.h),
+// stream_hist.h -- the history kernels of the ten wideband stream stages: each keeps the last H input samples of its
+// stream (ddc.h, ddc_bank.h, pfb.h, resamp.h, duc.h, tx_resamp.h), or of each of its streams (pfb_synth.h, duc_bank.h, tx_resamp_bank.h),
 // for the next call's oldest taps.  (What the stages' compute kernels share is stream_tile.h.)
 #pragma once
 #include "common.h"

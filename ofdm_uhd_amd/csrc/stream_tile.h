@@ -1,5 +1,5 @@
-// stream_tile.h -- what the tiles of the nine wideband stage kernels share on the device (ddc.h, ddc_bank.h, pfb.h,
-// resamp.h, resamp_bank.h, duc.h, duc_bank.h, pfb_synth.h, tx_resamp.h): the two polyphase layouts a tile is staged in and the
+// stream_tile.h -- what the tiles of the ten wideband stage kernels share on the device (ddc.h, ddc_bank.h, pfb.h,
+// resamp.h, resamp_bank.h, duc.h, duc_bank.h, pfb_synth.h, tx_resamp.h, tx_resamp_bank.h): the two polyphase layouts a tile is staged in and the
 // rotation by an NCO phase.  Small inlined functions only.  (The staging block and the transmit store stay in every
 // kernel's own text: DESIGN.md, "The wideband stages share one host-side skeleton ...", says what a shared
 // template of either did to the compiler's output and the measured times.)

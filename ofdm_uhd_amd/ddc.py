@@ -55,7 +55,7 @@ def bandpass_taps(taps, fc, interpolation=1):
 
 
 def _cfg_with_taps(struct, who, max_taps, taps, occupied_fraction, design_taps):
-    """A zeroed ``struct`` (one of the nine stages' configurations) with struct_size, ntaps and taps filled in: the
+    """A zeroed ``struct`` (one of the ten stages' configurations) with struct_size, ntaps and taps filled in: the
     given taps as float32 or, with ``taps=None``, what ``design_taps()`` makes of ``occupied_fraction``."""
     if taps is None:
         if occupied_fraction is None:

@@ -87,6 +87,7 @@ class Engine(object):
         self.pfb_cfg = None     # the channeliser's configuration in force (set_pfb), None without one
         self.pfb_synth_cfg = None  # the synthesis bank's configuration in force (set_pfb_synth), None without one
         self.duc_bank_cfg = None  # the DUC bank's configuration in force (set_duc_bank), None without one
+        self.tx_resamp_bank_cfg = None  # the transmit resampler bank's configuration in force (set_tx_resamp_bank), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -349,7 +350,7 @@ class Engine(object):
         n = npk.value
         return n, off[:n + 1], ln[:n], ok[:n]
 
-    # -- the nine wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
+    # -- the ten wideband stream stages: one body per kind of call, the stage's name picks the ofdm_* symbols --------
     def _stage_set(self, name, maker, cfg, kw):
         """ofdm_set_<name>: ``cfg`` or, from keywords, what ``maker`` ("module.function" of this package) builds."""
         if cfg is None and kw:
@@ -416,8 +417,9 @@ class Engine(object):
                                      _ptr(add) if add is not None and no else None, _ptr(out), len(out))]
 
     def _tx_bank_stage(self, name, x, add, rows, factor, shape, add_size):
-        """Host mode of a transmit bank, pfb_synth() and duc_bank(): ``x`` is complex64 of shape (rows, nin) and gives
-        nin * factor outputs; ``shape`` and ``add_size`` name the two in the error messages."""
+        """Host mode of a transmit bank, pfb_synth(), duc_bank() and tx_resamp_bank(): ``x`` is complex64 of shape
+        (rows, nin) and gives nin * factor outputs (``factor`` a field of the configuration) or factor(nin) of them
+        (a callable: the stage's count); ``shape`` and ``add_size`` name the two in the error messages."""
         assert not self.device_ptrs
         cfg = getattr(self, name + "_cfg")
         if cfg is None:
@@ -431,7 +433,7 @@ class Engine(object):
         if x.ndim != 2 or x.shape[0] != K:
             raise ValueError("%s() takes complex64 of shape %s" % (name, shape))
         nin = x.shape[1]
-        no = nin * int(getattr(cfg, factor))
+        no = factor(nin) if callable(factor) else nin * int(getattr(cfg, factor))
         if add is not None:
             add = np.ascontiguousarray(add, np.complex64).reshape(-1)
             if len(add) != no:
@@ -747,6 +749,46 @@ class Engine(object):
     def tx_resamp_last_ms(self):
         """HIP-event time of k_tx_resamp in the last tx_resamp() / tx_resamp_device() (needs prof_enable())."""
         return self._stage_last_ms("tx_resamp")
+
+    # -- transmit resampler bank: every link of a band at a rational rate in one pass over it ------------
+    def set_tx_resamp_bank(self, cfg=None, **kw):
+        """Configure the bank: an ``ofdm_tx_resamp_bank_cfg`` (tx_resample.bank_cfg) or its keywords (interpolation=,
+        decimation=, center_freqs=, taps= / occupied_fraction=, out_format=, out_scale=).
+        ``set_tx_resamp_bank(None)`` with no keywords removes it.  Resets the bank's stream state; the single stage
+        (set_tx_resamp) is a separate one and keeps its own."""
+        self._stage_set("tx_resamp_bank", "tx_resample.bank_cfg", cfg, kw)
+
+    def tx_resamp_bank_reset(self, first=0):
+        """Start new narrowband streams whose first samples have this absolute index; the filter history is zero."""
+        self._stage_reset("tx_resamp_bank", first)
+
+    def tx_resamp_bank_count(self, nin):
+        """Outputs the next tx_resamp_bank() call of ``nin`` samples per link produces, from the current stream state."""
+        return self._stage_count("tx_resamp_bank", nin)
+
+    def tx_resamp_bank(self, x, add=None):
+        """Host mode: the next samples of the K narrowband streams, complex64 of shape (K, nin), row i at
+        center_freqs[i] -> the samples of the band at L / M times their rate that they complete (possibly none;
+        complex64, or int16 of shape (n, 2) with out_format "sc16"), added onto the complex64 band ``add`` where one
+        is given.  Stateful: any segmentation gives the same bits."""
+        return self._tx_bank_stage("tx_resamp_bank", x, add, "nlinks", self.tx_resamp_bank_count, "(nlinks, nin)",
+                                   "tx_resamp_bank_count(nin)")
+
+    def tx_resamp_bank_device(self, iq_ptr, link_stride, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; link i's ``nin`` inputs begin ``link_stride`` samples after
+        link i - 1's (what tx_device(wait=False) is filling, same handle), ``add_ptr`` may be ``out_ptr`` itself for
+        complex64 output.  Returns the number of outputs written."""
+        return self._stage_device("tx_resamp_bank", C.c_void_p(iq_ptr), int(link_stride), int(nin),
+                                  C.c_void_p(add_ptr) if add_ptr else None, C.c_void_p(out_ptr), int(out_cap))
+
+    def tx_resamp_bank_taps(self, link):
+        """The band-pass table of one link as the kernel multiplies with it (complex64)."""
+        return self._stage_taps("tx_resamp_bank", int(link))
+
+    def tx_resamp_bank_last_ms(self):
+        """HIP-event time of k_tx_resamp_bank in the last tx_resamp_bank() / tx_resamp_bank_device() (needs
+        prof_enable())."""
+        return self._stage_last_ms("tx_resamp_bank")
 
     # -- chunked streams --------------------------------------------------------------
     def rx_packet_pos(self):

@@ -617,7 +617,7 @@ def _copy_options(options, **overrides):
 
 
 class _ofdm_mod_links(object):
-    """What ofdm_mod_channelizer and ofdm_mod_bank share: K plain ofdm_mod produce the narrowband streams and one engine
+    """What ofdm_mod_channelizer, ofdm_mod_bank and ofdm_mod_resamp_bank share: K plain ofdm_mod produce the narrowband streams and one engine
     owns the stage that places them on the band in one pass.  A subclass checks its arguments, builds the stage's
     configuration and hands both to _open(); ``_stage`` names the engine's stage (Engine.<stage>, <stage>_reset,
     <stage>_cfg) and _history() gives its Q."""
@@ -764,6 +764,45 @@ class ofdm_mod_bank(_ofdm_mod_links):
         cfg = _duc.bank_cfg(interpolation, fcs, taps=taps, occupied_fraction=occ,
                             out_format=iqio.check_format(iq_format), out_scale=iq_scale)   # ValueError: K, fc, L, taps
         self._open(opts, lambda e: e.set_duc_bank(cfg), device_id)
+
+    def _history(self, cfg):
+        return (cfg.ntaps - 1) // cfg.interpolation
+
+
+class ofdm_mod_resamp_bank(_ofdm_mod_links):
+    """
+    Modulates links onto one wideband band whose rate is no integer multiple of the modem's: K links that share the
+    ratio L / M and the low-pass prototype and differ in their centre frequency (the transmit counterpart of
+    ofdm_demod_resamp_bank, which takes such a band apart at the mirror ratio M / L).
+
+    K plain ofdm_mod produce the narrowband streams; one engine owns the transmit resampler bank
+    (Engine.tx_resamp_bank: all K links in one pass over the band, where Engine.tx_resamp(iq, add=band) needs one pass
+    per link).
+    """
+
+    _stage = "tx_resamp_bank"
+
+    def __init__(self, options, center_freqs, interpolation, decimation, taps=None, iq_format="fc32", iq_scale=None,
+                 device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
+        @param interpolation, decimation: L and M, each 1..64: the wideband rate is L / M times the modem's
+        @param taps: the shared prototype; None: tx_resample.design for the largest occupied_tones / fft_length of the links
+        @param iq_format, iq_scale: format of the WIDEBAND samples flush() returns, as for ofdm_mod(duc=)
+        """
+        # every argument is checked before the first engine exists
+        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+        if isinstance(options, (list, tuple)):
+            opts = list(options)
+            if len(opts) != len(fcs):
+                raise ValueError("ofdm_mod_resamp_bank needs one options object, or one per centre frequency")
+        else:
+            opts = [options] * len(fcs)
+        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        cfg = _tx_resample.bank_cfg(interpolation, decimation, fcs, taps=taps, occupied_fraction=occ,
+                                    out_format=iqio.check_format(iq_format), out_scale=iq_scale)   # ValueError: K, fc, L, M, taps
+        self._open(opts, lambda e: e.set_tx_resamp_bank(cfg), device_id)
 
     def _history(self, cfg):
         return (cfg.ntaps - 1) // cfg.interpolation

@@ -78,3 +78,42 @@ def tx_resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupie
     cfg.center_freq = float(center_freq)
     cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
     return cfg
+
+
+MAX_LINKS = _abi.OFDM_TX_RESAMP_BANK_MAX_LINKS
+
+
+def bank_phase_steps(center_freq, interpolation, decimation):
+    """(G, E, D) of the bank's definition, each in units of 2^-64 turn: G = turns(fc / M), the phase per step of the
+    L-times grid (fc / M is ONE double division, the one the table c[k] = h[k] exp(j 2 pi fc k / M) makes),
+    E = L G mod 2^64 per input and D = M G mod 2^64 per output.  With n M = k + m L, k G + m E = n D modulo 2^64."""
+    L, M = _check_ratio(interpolation, decimation)
+    G = phase_step(float(center_freq) / float(M))
+    return G, (L * G) & (2 ** 64 - 1), (M * G) & (2 ** 64 - 1)
+
+
+def bank_cfg(interpolation, decimation, center_freqs, taps=None, occupied_fraction=None, transition=None,
+             out_format="fc32", out_scale=None):
+    """ofdm_tx_resamp_bank_cfg for Engine.set_tx_resamp_bank: one ratio and one prototype, one centre frequency per
+    link (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed), row i of
+    Engine.tx_resamp_bank's input at center_freqs[i].  ``taps=None`` designs the prototype from ``occupied_fraction``
+    as tx_resamp_cfg does; ``out_format`` / ``out_scale`` are tx_resamp_cfg's.  ValueError for a ratio outside 1..64,
+    with given taps too."""
+    L, M = _check_ratio(interpolation, decimation)
+    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    if not 1 <= len(fcs) <= MAX_LINKS:
+        raise ValueError("a transmit resampler bank has 1 to %d links" % MAX_LINKS)
+    if not all(abs(f) <= 0.5 for f in fcs):
+        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
+    cfg = ddc._cfg_with_taps(_abi.ofdm_tx_resamp_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
+                             lambda: design(interpolation, decimation, occupied_fraction, transition))
+    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
+        raise ValueError("taps must be finite")
+    cfg.interpolation = L
+    cfg.decimation = M
+    cfg.nlinks = len(fcs)
+    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
+    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
+    for i, f in enumerate(fcs):
+        cfg.center_freq[i] = f
+    return cfg
