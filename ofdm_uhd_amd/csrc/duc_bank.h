@@ -173,10 +173,9 @@ struct DucBankState : StreamStage {
   float out_scale = 32768.0f;
   uint64_t E[DUC_BANK_MAX_LINKS] = {};
   std::vector<c32> tab;  // link i's table at tab[i * ntaps], as ofdm_duc_bank_taps returns it
-  DevBuf d_tab, d_add;
+  DevBuf d_tab;
   void release() {
     d_tab.release();
-    d_add.release();
     StreamStage::release();
   }
 };

@@ -11,7 +11,7 @@ extern "C" int ofdm_set_ddc(ofdm_handle* h, const ofdm_ddc_cfg* cfg) {
   if (cfg->struct_size != sizeof(ofdm_ddc_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_cfg.struct_size does not match this library");
   if (cfg->decimation < 1 || cfg->decimation > DDC_MAX_DECIM) FAIL(h, OFDM_E_INVAL, "DDC decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_DDC_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "DDC ntaps must be in [1, 1024]");
-  if (!(fabs(cfg->center_freq) <= 0.5)) FAIL(h, OFDM_E_INVAL, "DDC center_freq must be in [-0.5, 0.5] cycles per sample");
+  RCCHK(stage_check_center_freqs(h, "DDC", &cfg->center_freq, 1, "sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "DDC taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.R = (int)cfg->decimation;
@@ -80,14 +80,8 @@ extern "C" int ofdm_ddc(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm_c3
 
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
-    d_in = d.d_in.p;
-    if (no) {
-      HIPCHK(h, d.d_out.ensure(no * sizeof(c32)));
-      d_out = d.d_out.as<c32>();
-    }
-  }
+  RCCHK(stage_rx_in(h, d, iq_in, nin, &d_in));
+  RCCHK(stage_rx_out(h, d, 1, no, &d_out, nullptr));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     const DdcGeom g = ddc_geom(d.R);
@@ -109,7 +103,7 @@ extern "C" int ofdm_ddc(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm_c3
     p.W = ddc_pitch(g.T(), p.Q);
     p.scale = h->rx_scale;
     const uint64_t grid = (no + (uint64_t)g.T() - 1) / (uint64_t)g.T();
-    if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_ddc: call too long (split it)");
+    RCCHK(stage_check_grid(h, "ofdm_ddc", grid));
     const size_t lds = ddc_lds_bytes(d.R, d.ntaps);  // (never more than 64 KB: no hipFuncSetAttribute)
     RCCHK(stage_time_begin(h, d, timing));
     if (h->rx_fmt == OFDM_IQ_SC16) launch_ddc<sc16>(h, p, g, (unsigned)grid, lds);
@@ -117,6 +111,6 @@ extern "C" int ofdm_ddc(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm_c3
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_rx_history(h, d, d_in, nin));
-  if (!h->dev_ptrs && no) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_rx_readback(h, iq_out, 0, 1, no, d_out));
   return stage_finish(h, d, nin, timing);
 }

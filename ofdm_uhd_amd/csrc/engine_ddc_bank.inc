@@ -1,4 +1,4 @@
-// engine_ddc_bank.inc -- host side of the DDC bank (ddc_bank.h): configuration, launches, the per-link copy-back.
+// engine_ddc_bank.inc -- host side of the DDC bank (ddc_bank.h): configuration, launches (the per-link copy-back: stage_rx_readback).
 // Included by engine.hip after engine_stage.inc and engine_ddc.inc (DDC_MAX_INDEX).
 
 /* K gr.freq_xlating_fir_filter_ccf ctors that share decimation and prototype (dual_channel/dual_channel.py tunes one
@@ -10,9 +10,8 @@ extern "C" int ofdm_set_ddc_bank(ofdm_handle* h, const ofdm_ddc_bank_cfg* cfg) {
   if (cfg->struct_size != sizeof(ofdm_ddc_bank_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank_cfg.struct_size does not match this library");
   if (cfg->decimation < 1 || cfg->decimation > DDC_MAX_DECIM) FAIL(h, OFDM_E_INVAL, "DDC bank decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_DDC_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "DDC bank ntaps must be in [1, 1024]");
-  if (cfg->nlinks < 1 || cfg->nlinks > OFDM_DDC_BANK_MAX_LINKS) FAIL(h, OFDM_E_INVAL, "DDC bank nlinks must be in [1, 8]");
-  for (uint32_t i = 0; i < cfg->nlinks; i++)
-    if (!(fabs(cfg->center_freq[i]) <= 0.5)) FAIL(h, OFDM_E_INVAL, "DDC bank center_freq must be in [-0.5, 0.5] cycles per sample");
+  RCCHK(stage_check_nlinks(h, "DDC bank", cfg->nlinks));
+  RCCHK(stage_check_center_freqs(h, "DDC bank", cfg->center_freq, cfg->nlinks, "sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "DDC bank taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.R = (int)cfg->decimation;
@@ -20,14 +19,12 @@ extern "C" int ofdm_set_ddc_bank(ofdm_handle* h, const ofdm_ddc_bank_cfg* cfg) {
   d.K = (int)cfg->nlinks;
   const int KP = (d.K + 1) & ~1;
   // every link's table is the DDC's; the device copy is link-minor
-  d.tab.clear();
+  d.tab = bank_tables(cfg->taps, d.ntaps, cfg->center_freq, d.K, 1);
   std::vector<c32> dev((size_t)d.ntaps * KP, c32{0.f, 0.f});
   for (int i = 0; i < d.K; i++) {
     d.fc[i] = cfg->center_freq[i];
     d.D[i] = ddc_turns(d.fc[i] * (double)d.R);
-    const std::vector<c32> c = bandpass_table(cfg->taps, d.ntaps, d.fc[i], 1);
-    d.tab.insert(d.tab.end(), c.begin(), c.end());
-    for (int k = 0; k < d.ntaps; k++) dev[(size_t)k * KP + i] = c[k];
+    for (int k = 0; k < d.ntaps; k++) dev[(size_t)k * KP + i] = d.tab[(size_t)i * d.ntaps + k];
   }
   HIPCHK(h, upload(d.d_tab, dev.data(), dev.size()));
   return stage_arm(h, d, d.ntaps - 1);
@@ -52,8 +49,7 @@ extern "C" int ofdm_ddc_bank_count(const ofdm_handle* h, uint64_t nin, uint64_t*
 extern "C" int ofdm_ddc_bank_taps(const ofdm_handle* h, int link, ofdm_c32* out, int cap, int* n) {
   if (!h || !n) return OFDM_E_INVAL;
   const DdcBankState& d = h->bank;
-  if (!d.on || link < 0 || link >= d.K) return OFDM_E_INVAL;
-  return stage_taps_out(d.tab.data() + (size_t)link * d.ntaps, d.ntaps, out, cap, n);
+  return stage_bank_taps(d.on, d.tab, d.ntaps, d.K, link, out, cap, n);
 }
 
 extern "C" int ofdm_ddc_bank_last_ms(const ofdm_handle* h, double* ms) {
@@ -61,20 +57,11 @@ extern "C" int ofdm_ddc_bank_last_ms(const ofdm_handle* h, double* ms) {
   return stage_last_ms(h->bank, ms);
 }
 
-template <typename XT, int OPT, int TJ>
-static int launch_ddc_bank_g(ofdm_handle* h, const DdcBankParams& p, unsigned grid, size_t lds) {
-  // the tables of many links and long filters take the workgroup past the default 64 KB of dynamic LDS
-  if (lds > 64 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ddc_bank<XT, OPT, TJ>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ddc_bank<XT, OPT, TJ>), dim3(grid), dim3(DDC_THREADS), lds, h->stream, p);
-  return OFDM_OK;
-}
 template <typename XT>
 static int launch_ddc_bank(ofdm_handle* h, const DdcBankParams& p, const DdcGeom& g, unsigned grid, size_t lds) {
-  if (g.opt == 4 && g.tj == 256) return launch_ddc_bank_g<XT, 4, 256>(h, p, grid, lds);
-  if (g.opt == 4) return launch_ddc_bank_g<XT, 4, 64>(h, p, grid, lds);
-  return launch_ddc_bank_g<XT, 1, 64>(h, p, grid, lds);
+  if (g.opt == 4 && g.tj == 256) return stage_launch(h, &k_ddc_bank<XT, 4, 256>, grid, DDC_THREADS, lds, p);
+  if (g.opt == 4) return stage_launch(h, &k_ddc_bank<XT, 4, 64>, grid, DDC_THREADS, lds, p);
+  return stage_launch(h, &k_ddc_bank<XT, 1, 64>, grid, DDC_THREADS, lds, p);
 }
 
 /* the next nin wideband samples in, the narrowband samples they complete out, for every link: link i's run begins at
@@ -101,15 +88,8 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
   uint64_t stride = link_stride;
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
-    d_in = d.d_in.p;
-    if (no) {
-      HIPCHK(h, d.d_out.ensure(K * no * sizeof(c32)));
-      d_out = d.d_out.as<c32>();
-      stride = no;
-    }
-  }
+  RCCHK(stage_rx_in(h, d, iq_in, nin, &d_in));
+  RCCHK(stage_rx_out(h, d, K, no, &d_out, &stride));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     const DdcGeom g = ddc_geom(d.R);
@@ -134,15 +114,13 @@ extern "C" int ofdm_ddc_bank(ofdm_handle* h, const void* iq_in, uint64_t nin, of
     p.K = d.K;
     p.KP = (d.K + 1) & ~1;
     const uint64_t grid = (no + (uint64_t)g.T() - 1) / (uint64_t)g.T();
-    if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_ddc_bank: call too long (split it)");
+    RCCHK(stage_check_grid(h, "ofdm_ddc_bank", grid));
     const size_t lds = ddc_bank_lds_bytes(d.R, d.ntaps, d.K);
     RCCHK(stage_time_begin(h, d, timing));
     RCCHK(h->rx_fmt == OFDM_IQ_SC16 ? launch_ddc_bank<sc16>(h, p, g, (unsigned)grid, lds) : launch_ddc_bank<c32>(h, p, g, (unsigned)grid, lds));
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_rx_history(h, d, d_in, nin));
-  if (!h->dev_ptrs && no)
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(iq_out + i * link_stride, d_out + i * no, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_rx_readback(h, iq_out, link_stride, K, no, d_out));
   return stage_finish(h, d, nin, timing);
 }

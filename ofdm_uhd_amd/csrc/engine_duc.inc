@@ -13,7 +13,7 @@ extern "C" int ofdm_set_duc(ofdm_handle* h, const ofdm_duc_cfg* cfg) {
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_DUC_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "DUC ntaps must be in [1, 1024]");
   float scale;
   RCCHK(stage_out_scale(h, "DUC", cfg->out_format, cfg->out_scale, &scale));
-  if (!(fabs(cfg->center_freq) <= 0.5)) FAIL(h, OFDM_E_INVAL, "DUC center_freq must be in [-0.5, 0.5] cycles per output sample");
+  RCCHK(stage_check_center_freqs(h, "DUC", &cfg->center_freq, 1, "output sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "DUC taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
@@ -64,23 +64,15 @@ extern "C" int ofdm_duc(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, con
   if (nin == 0) return OFDM_OK;
   const DucGeom g = duc_geom(d.L);
   const uint64_t grid = (no + (uint64_t)g.T() - 1) / (uint64_t)g.T();
-  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_duc: call too long (split it)");
+  RCCHK(stage_check_grid(h, "ofdm_duc", grid));
   RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
   const c32* d_in = reinterpret_cast<const c32*>(iq_in);
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * sizeof(c32)));
-    d_in = d.d_in.as<c32>();
-    if (add) {
-      RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
-      d_add = d.d_add.as<c32>();
-    }
-    HIPCHK(h, d.d_out.ensure(no * oss));
-    d_out = d.d_out.p;
-  }
+  RCCHK(stage_tx_rows_in(h, d, iq_in, 0, 1, nin, &d_in, nullptr));
+  RCCHK(stage_tx_out(h, d, add, no, oss, &d_add, &d_out));  // (nin > 0: the call has outputs)
   const bool timing = h->prof.on;  // (nin > 0: the call has outputs)
   DucParams p;
   memset(&p, 0, sizeof(p));
@@ -103,6 +95,6 @@ extern "C" int ofdm_duc(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, con
   stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_duc<decltype(o), decltype(a)::value>(h, p, g, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
   RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));
-  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_tx_readback(h, iq_out, d_out, no, oss));
   return stage_finish(h, d, nin, timing);
 }

@@ -1,5 +1,5 @@
-// engine_duc_bank.inc -- host side of the DUC bank (duc_bank.h): configuration, index limits, the per-link upload,
-// launch.  Included by engine.hip after engine_stage.inc and engine_duc.inc (DUC_MAX_OUTPUT).
+// engine_duc_bank.inc -- host side of the DUC bank (duc_bank.h): configuration, index limits, launch (the per-link
+// upload: stage_tx_rows_in).  Included by engine.hip after engine_stage.inc and engine_duc.inc (DUC_MAX_OUTPUT).
 
 /* one sink.set_interp + set_center_freq per link (usrp_transmit_path.py:79-88; the two-channel transmitter of
  * dual_channel/dual_channel.py), for K links that share interpolation and prototype */
@@ -10,12 +10,10 @@ extern "C" int ofdm_set_duc_bank(ofdm_handle* h, const ofdm_duc_bank_cfg* cfg) {
   if (cfg->struct_size != sizeof(ofdm_duc_bank_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_duc_bank_cfg.struct_size does not match this library");
   if (cfg->interpolation < 1 || cfg->interpolation > DUC_MAX_INTERP) FAIL(h, OFDM_E_INVAL, "DUC bank interpolation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_DUC_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "DUC bank ntaps must be in [1, 1024]");
-  if (cfg->nlinks < 1 || cfg->nlinks > OFDM_DUC_BANK_MAX_LINKS) FAIL(h, OFDM_E_INVAL, "DUC bank nlinks must be in [1, 8]");
+  RCCHK(stage_check_nlinks(h, "DUC bank", cfg->nlinks));
   float scale;
   RCCHK(stage_out_scale(h, "DUC bank", cfg->out_format, cfg->out_scale, &scale));
-  for (uint32_t i = 0; i < cfg->nlinks; i++)
-    if (!(fabs(cfg->center_freq[i]) <= 0.5))
-      FAIL(h, OFDM_E_INVAL, "DUC bank center_freq must be in [-0.5, 0.5] cycles per output sample");
+  RCCHK(stage_check_center_freqs(h, "DUC bank", cfg->center_freq, cfg->nlinks, "output sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "DUC bank taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
@@ -25,12 +23,8 @@ extern "C" int ofdm_set_duc_bank(ofdm_handle* h, const ofdm_duc_bank_cfg* cfg) {
   d.out_fmt = (int)cfg->out_format;
   d.out_scale = scale;
   // every link's table is the DDC bank's; its phase step per INPUT is L times the DUC's per output, modulo a turn
-  d.tab.clear();
-  for (int i = 0; i < d.K; i++) {
-    d.E[i] = ddc_turns(cfg->center_freq[i]) * (uint64_t)d.L;
-    const std::vector<c32> c = bandpass_table(cfg->taps, d.ntaps, cfg->center_freq[i], 1);
-    d.tab.insert(d.tab.end(), c.begin(), c.end());
-  }
+  d.tab = bank_tables(cfg->taps, d.ntaps, cfg->center_freq, d.K, 1);
+  for (int i = 0; i < d.K; i++) d.E[i] = ddc_turns(cfg->center_freq[i]) * (uint64_t)d.L;
   HIPCHK(h, upload(d.d_tab, d.tab.data(), d.tab.size()));
   return stage_arm(h, d, d.K * d.Q);  // the last Q raw inputs of every link
 }
@@ -46,8 +40,7 @@ extern "C" int ofdm_duc_bank_reset(ofdm_handle* h, uint64_t first_input_index) {
 extern "C" int ofdm_duc_bank_taps(const ofdm_handle* h, int link, ofdm_c32* out, int cap, int* n) {
   if (!h || !n) return OFDM_E_INVAL;
   const DucBankState& d = h->duc_bank;
-  if (!d.on || link < 0 || link >= d.K) return OFDM_E_INVAL;
-  return stage_taps_out(d.tab.data() + (size_t)link * d.ntaps, d.ntaps, out, cap, n);
+  return stage_bank_taps(d.on, d.tab, d.ntaps, d.K, link, out, cap, n);
 }
 
 extern "C" int ofdm_duc_bank_last_ms(const ofdm_handle* h, double* ms) {
@@ -84,7 +77,7 @@ extern "C" int ofdm_duc_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t lin
   if (nin == 0) return OFDM_OK;
   const DucGeom g = duc_geom(d.L);
   const uint64_t grid = (no + (uint64_t)g.T() - 1) / (uint64_t)g.T();
-  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_duc_bank: call too long (split it)");
+  RCCHK(stage_check_grid(h, "ofdm_duc_bank", grid));
   RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
@@ -92,19 +85,8 @@ extern "C" int ofdm_duc_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t lin
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
   uint64_t stride = link_stride;
-  if (!h->dev_ptrs) {
-    HIPCHK(h, d.d_in.ensure(K * nin * sizeof(c32)));
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(d.d_in.as<c32>() + i * nin, iq_in + i * link_stride, nin * sizeof(c32), hipMemcpyHostToDevice, h->stream));
-    d_in = d.d_in.as<c32>();
-    stride = nin;
-    if (add) {
-      RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
-      d_add = d.d_add.as<c32>();
-    }
-    HIPCHK(h, d.d_out.ensure(no * oss));
-    d_out = d.d_out.p;
-  }
+  RCCHK(stage_tx_rows_in(h, d, iq_in, link_stride, K, nin, &d_in, &stride));
+  RCCHK(stage_tx_out(h, d, add, no, oss, &d_add, &d_out));  // (nin > 0: the call has outputs)
   const bool timing = h->prof.on;  // (nin > 0: the call has outputs)
   DucBankParams p;
   memset(&p, 0, sizeof(p));
@@ -128,11 +110,7 @@ extern "C" int ofdm_duc_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t lin
   RCCHK(stage_time_begin(h, d, timing));
   stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_duc_bank<decltype(o), decltype(a)::value>(h, p, g, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
-  if (d.Q > 0) {
-    hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,
-                       d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), d.Q);
-    HIPCHK(h, hipGetLastError());
-  }
-  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_roll_rows_history(h, d, d_in, stride, nin, d.Q, d.K));
+  RCCHK(stage_tx_readback(h, iq_out, d_out, no, oss));
   return stage_finish(h, d, nin, timing);
 }

@@ -1,4 +1,4 @@
-// engine_pfb.inc -- host side of the polyphase-FFT channeliser (pfb.h): configuration, launch, the per-channel copy-back.
+// engine_pfb.inc -- host side of the polyphase-FFT channeliser (pfb.h): configuration, launch (the per-channel copy-back: stage_rx_readback).
 // Included by engine.hip after engine_stage.inc and engine_ddc.inc (DDC_MAX_INDEX).
 
 /* one set_center_freq per radio channel on a uniform grid (dual_channel/dual_channel.py tunes one channel per link; the
@@ -58,23 +58,16 @@ extern "C" int ofdm_pfb_last_ms(const ofdm_handle* h, double* ms) {
   return stage_last_ms(h->pfb, ms);
 }
 
-template <typename XT, int M>
-static int launch_pfb_m(ofdm_handle* h, const PfbParams& p, unsigned grid, size_t lds) {
-  // (no shape of the definition needs it today; a longer filter or a larger tile would)
-  if (lds > 64 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pfb<XT, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pfb<XT, M>), dim3(grid), dim3(PFB_THREADS), lds, h->stream, p);
-  return OFDM_OK;
-}
+// (no shape of the definition takes stage_launch past 64 KB of LDS today; a longer filter or a larger tile would)
 template <typename XT>
 static int launch_pfb(ofdm_handle* h, const PfbParams& p, int M, unsigned grid, size_t lds) {
   switch (M) {
-    case 2: return launch_pfb_m<XT, 2>(h, p, grid, lds);
-    case 4: return launch_pfb_m<XT, 4>(h, p, grid, lds);
-    case 8: return launch_pfb_m<XT, 8>(h, p, grid, lds);
-    case 16: return launch_pfb_m<XT, 16>(h, p, grid, lds);
-    case 32: return launch_pfb_m<XT, 32>(h, p, grid, lds);
-    default: return launch_pfb_m<XT, 64>(h, p, grid, lds);
+    case 2: return stage_launch(h, &k_pfb<XT, 2>, grid, PFB_THREADS, lds, p);
+    case 4: return stage_launch(h, &k_pfb<XT, 4>, grid, PFB_THREADS, lds, p);
+    case 8: return stage_launch(h, &k_pfb<XT, 8>, grid, PFB_THREADS, lds, p);
+    case 16: return stage_launch(h, &k_pfb<XT, 16>, grid, PFB_THREADS, lds, p);
+    case 32: return stage_launch(h, &k_pfb<XT, 32>, grid, PFB_THREADS, lds, p);
+    default: return stage_launch(h, &k_pfb<XT, 64>, grid, PFB_THREADS, lds, p);
   }
 }
 
@@ -103,15 +96,8 @@ extern "C" int ofdm_pfb(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm_c3
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
   uint64_t stride = chan_stride;
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
-    d_in = d.d_in.p;
-    if (no) {
-      HIPCHK(h, d.d_out.ensure(K * no * sizeof(c32)));
-      d_out = d.d_out.as<c32>();
-      stride = no;
-    }
-  }
+  RCCHK(stage_rx_in(h, d, iq_in, nin, &d_in));
+  RCCHK(stage_rx_out(h, d, K, no, &d_out, &stride));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     const int T = pfb_tile_outputs(d.M);
@@ -136,15 +122,13 @@ extern "C" int ofdm_pfb(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm_c3
     memcpy(p.first, d.sel_first, sizeof(p.first));
     memcpy(p.next, d.sel_next, sizeof(p.next));
     const uint64_t grid = (no + (uint64_t)T - 1) / (uint64_t)T;
-    if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_pfb: call too long (split it)");
+    RCCHK(stage_check_grid(h, "ofdm_pfb", grid));
     const size_t lds = pfb_lds_bytes(d.M, d.ntaps);
     RCCHK(stage_time_begin(h, d, timing));
     RCCHK(h->rx_fmt == OFDM_IQ_SC16 ? launch_pfb<sc16>(h, p, d.M, (unsigned)grid, lds) : launch_pfb<c32>(h, p, d.M, (unsigned)grid, lds));
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_rx_history(h, d, d_in, nin));
-  if (!h->dev_ptrs && no)
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(iq_out + i * chan_stride, d_out + i * no, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_rx_readback(h, iq_out, chan_stride, K, no, d_out));
   return stage_finish(h, d, nin, timing);
 }

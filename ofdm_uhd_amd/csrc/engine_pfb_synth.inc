@@ -1,5 +1,5 @@
 // engine_pfb_synth.inc -- host side of the polyphase-FFT synthesis bank (pfb_synth.h): configuration, index limits,
-// the per-channel upload, launch.  Included by engine.hip after engine_stage.inc and engine_duc.inc (DUC_MAX_OUTPUT).
+// launch (the per-channel upload: stage_tx_rows_in).  Included by engine.hip after engine_stage.inc and engine_duc.inc (DUC_MAX_OUTPUT).
 
 /* one set_center_freq per radio channel on a uniform grid, transmit side (the two-channel transmitter of
  * dual_channel/dual_channel.py), for every slot of the band at once */
@@ -88,7 +88,7 @@ extern "C" int ofdm_pfb_synth(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ch
   d.timed = false;
   if (nin == 0) return OFDM_OK;
   const uint64_t T = (uint64_t)pfb_synth_tile_inputs(d.M), grid = (nin + T - 1) / T;
-  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_pfb_synth: call too long (split it)");
+  RCCHK(stage_check_grid(h, "ofdm_pfb_synth", grid));
   RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
@@ -96,19 +96,8 @@ extern "C" int ofdm_pfb_synth(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ch
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
   uint64_t stride = chan_stride;
-  if (!h->dev_ptrs) {
-    HIPCHK(h, d.d_in.ensure(K * nin * sizeof(c32)));
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(d.d_in.as<c32>() + i * nin, iq_in + i * chan_stride, nin * sizeof(c32), hipMemcpyHostToDevice, h->stream));
-    d_in = d.d_in.as<c32>();
-    stride = nin;
-    if (add) {
-      RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
-      d_add = d.d_add.as<c32>();
-    }
-    HIPCHK(h, d.d_out.ensure(no * oss));
-    d_out = d.d_out.p;
-  }
+  RCCHK(stage_tx_rows_in(h, d, iq_in, chan_stride, K, nin, &d_in, &stride));
+  RCCHK(stage_tx_out(h, d, add, no, oss, &d_add, &d_out));  // (nin > 0: the call has outputs)
   const bool timing = h->prof.on;  // (nin > 0: the call has outputs)
   PfbSynthParams p;
   memset(&p, 0, sizeof(p));
@@ -130,11 +119,7 @@ extern "C" int ofdm_pfb_synth(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ch
   RCCHK(stage_time_begin(h, d, timing));
   stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) { launch_pfb_synth<decltype(o), decltype(a)::value>(h, p, d.M, (unsigned)grid, lds); });
   RCCHK(stage_time_end(h, d, timing));
-  if (d.Q > 0) {
-    hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,
-                       d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), d.Q);
-    HIPCHK(h, hipGetLastError());
-  }
-  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_roll_rows_history(h, d, d_in, stride, nin, d.Q, d.K));
+  RCCHK(stage_tx_readback(h, iq_out, d_out, no, oss));
   return stage_finish(h, d, nin, timing);
 }

@@ -12,7 +12,7 @@ extern "C" int ofdm_set_resamp(ofdm_handle* h, const ofdm_resamp_cfg* cfg) {
   if (cfg->interpolation < 1 || cfg->interpolation > RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "resampler interpolation must be in [1, 64]");
   if (cfg->decimation < 1 || cfg->decimation > RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "resampler decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_RESAMP_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "resampler ntaps must be in [1, 1024]");
-  if (!(fabs(cfg->center_freq) <= 0.5)) FAIL(h, OFDM_E_INVAL, "resampler center_freq must be in [-0.5, 0.5] cycles per sample");
+  RCCHK(stage_check_center_freqs(h, "resampler", &cfg->center_freq, 1, "sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "resampler taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
@@ -51,18 +51,9 @@ extern "C" int ofdm_resamp_last_ms(const ofdm_handle* h, double* ms) {
   return stage_last_ms(h->resamp, ms);
 }
 
-template <typename XT, int NG>
-static hipError_t launch_resamp_g(ofdm_handle* h, const ResampParams& p, unsigned grid, size_t lds) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resamp<XT, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resamp<XT, NG>), dim3(grid), dim3(RESAMP_THREADS), lds, h->stream, p);
-  return hipSuccess;
-}
 template <typename XT>
-static hipError_t launch_resamp(ofdm_handle* h, const ResampParams& p, const ResampGeom& g, unsigned grid, size_t lds) {
-  return g.ng == 1 ? launch_resamp_g<XT, 1>(h, p, grid, lds) : launch_resamp_g<XT, 4>(h, p, grid, lds);
+static int launch_resamp(ofdm_handle* h, const ResampParams& p, const ResampGeom& g, unsigned grid, size_t lds) {
+  return stage_launch(h, g.ng == 1 ? &k_resamp<XT, 1> : &k_resamp<XT, 4>, grid, RESAMP_THREADS, lds, p);
 }
 
 /* rational_resampler_ccf::work behind the tuner: the next nin wideband samples in, the samples at L / M times their
@@ -85,14 +76,8 @@ extern "C" int ofdm_resamp(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm
 
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
-    d_in = d.d_in.p;
-    if (no) {
-      HIPCHK(h, d.d_out.ensure(no * sizeof(c32)));
-      d_out = d.d_out.as<c32>();
-    }
-  }
+  RCCHK(stage_rx_in(h, d, iq_in, nin, &d_in));
+  RCCHK(stage_rx_out(h, d, 1, no, &d_out, nullptr));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     const ResampGeom g = resamp_geom(d.L, d.M);
@@ -122,14 +107,13 @@ extern "C" int ofdm_resamp(ofdm_handle* h, const void* iq_in, uint64_t nin, ofdm
     p.scale = h->rx_scale;
     const uint64_t periods = (n0 + no + L - 1) / L - p.J0;
     const uint64_t grid = (periods + TJ - 1) / TJ;
-    if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_resamp: call too long (split it)");
+    RCCHK(stage_check_grid(h, "ofdm_resamp", grid));
     const size_t lds = resamp_lds_bytes(d.L, d.M, d.ntaps);
     RCCHK(stage_time_begin(h, d, timing));
-    if (h->rx_fmt == OFDM_IQ_SC16) HIPCHK(h, launch_resamp<sc16>(h, p, g, (unsigned)grid, lds));
-    else HIPCHK(h, launch_resamp<c32>(h, p, g, (unsigned)grid, lds));
+    RCCHK(h->rx_fmt == OFDM_IQ_SC16 ? launch_resamp<sc16>(h, p, g, (unsigned)grid, lds) : launch_resamp<c32>(h, p, g, (unsigned)grid, lds));
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_rx_history(h, d, d_in, nin));
-  if (!h->dev_ptrs && no) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_rx_readback(h, iq_out, 0, 1, no, d_out));
   return stage_finish(h, d, nin, timing);
 }

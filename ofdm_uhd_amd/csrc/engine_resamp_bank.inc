@@ -1,5 +1,5 @@
-// engine_resamp_bank.inc -- host side of the resampler bank (resamp_bank.h): configuration, launches, the per-link
-// copy-back.  Included by engine.hip after engine_stage.inc and engine_resamp.inc (RESAMP_MAX_INDEX).
+// engine_resamp_bank.inc -- host side of the resampler bank (resamp_bank.h): configuration, launches (the per-link
+// copy-back: stage_rx_readback).  Included by engine.hip after engine_stage.inc and engine_resamp.inc (RESAMP_MAX_INDEX).
 
 /* K blks2.rational_resampler_ccf ctors behind K tuners that share ratio and prototype (a recorder's capture holding
  * several links at a rate that is no integer multiple of theirs) */
@@ -11,9 +11,8 @@ extern "C" int ofdm_set_resamp_bank(ofdm_handle* h, const ofdm_resamp_bank_cfg* 
   if (cfg->interpolation < 1 || cfg->interpolation > RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "resampler bank interpolation must be in [1, 64]");
   if (cfg->decimation < 1 || cfg->decimation > RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "resampler bank decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_RESAMP_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "resampler bank ntaps must be in [1, 1024]");
-  if (cfg->nlinks < 1 || cfg->nlinks > OFDM_RESAMP_BANK_MAX_LINKS) FAIL(h, OFDM_E_INVAL, "resampler bank nlinks must be in [1, 8]");
-  for (uint32_t i = 0; i < cfg->nlinks; i++)
-    if (!(fabs(cfg->center_freq[i]) <= 0.5)) FAIL(h, OFDM_E_INVAL, "resampler bank center_freq must be in [-0.5, 0.5] cycles per sample");
+  RCCHK(stage_check_nlinks(h, "resampler bank", cfg->nlinks));
+  RCCHK(stage_check_center_freqs(h, "resampler bank", cfg->center_freq, cfg->nlinks, "sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "resampler bank taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
@@ -22,14 +21,12 @@ extern "C" int ofdm_set_resamp_bank(ofdm_handle* h, const ofdm_resamp_bank_cfg* 
   d.K = (int)cfg->nlinks;
   const int KP = (d.K + 1) & ~1;
   // every link's table is the resampler's; the device copy is link-minor
-  d.tab.clear();
+  d.tab = bank_tables(cfg->taps, d.ntaps, cfg->center_freq, d.K, d.L);
   std::vector<c32> dev((size_t)d.ntaps * KP, c32{0.f, 0.f});
   for (int i = 0; i < d.K; i++) {
     d.fc[i] = cfg->center_freq[i];
     d.D[i] = ddc_turns(d.fc[i] * (double)d.M / (double)d.L);
-    const std::vector<c32> c = bandpass_table(cfg->taps, d.ntaps, d.fc[i], d.L);
-    d.tab.insert(d.tab.end(), c.begin(), c.end());
-    for (int k = 0; k < d.ntaps; k++) dev[(size_t)k * KP + i] = c[k];
+    for (int k = 0; k < d.ntaps; k++) dev[(size_t)k * KP + i] = d.tab[(size_t)i * d.ntaps + k];
   }
   HIPCHK(h, upload(d.d_tab, dev.data(), dev.size()));
   return stage_arm(h, d, (d.ntaps - 1) / d.L);
@@ -54,8 +51,7 @@ extern "C" int ofdm_resamp_bank_count(const ofdm_handle* h, uint64_t nin, uint64
 extern "C" int ofdm_resamp_bank_taps(const ofdm_handle* h, int link, ofdm_c32* out, int cap, int* n) {
   if (!h || !n) return OFDM_E_INVAL;
   const ResampBankState& d = h->resamp_bank;
-  if (!d.on || link < 0 || link >= d.K) return OFDM_E_INVAL;
-  return stage_taps_out(d.tab.data() + (size_t)link * d.ntaps, d.ntaps, out, cap, n);
+  return stage_bank_taps(d.on, d.tab, d.ntaps, d.K, link, out, cap, n);
 }
 
 extern "C" int ofdm_resamp_bank_last_ms(const ofdm_handle* h, double* ms) {
@@ -63,18 +59,9 @@ extern "C" int ofdm_resamp_bank_last_ms(const ofdm_handle* h, double* ms) {
   return stage_last_ms(h->resamp_bank, ms);
 }
 
-template <typename XT, int NG>
-static int launch_resamp_bank_g(ofdm_handle* h, const ResampBankParams& p, unsigned grid, size_t lds) {
-  // the tables of many links and long filters take the workgroup past the default 64 KB of dynamic LDS
-  if (lds > 64 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_resamp_bank<XT, NG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resamp_bank<XT, NG>), dim3(grid), dim3(RESAMP_THREADS), lds, h->stream, p);
-  return OFDM_OK;
-}
 template <typename XT>
 static int launch_resamp_bank(ofdm_handle* h, const ResampBankParams& p, const ResampGeom& g, unsigned grid, size_t lds) {
-  return g.ng == 1 ? launch_resamp_bank_g<XT, 1>(h, p, grid, lds) : launch_resamp_bank_g<XT, 4>(h, p, grid, lds);
+  return stage_launch(h, g.ng == 1 ? &k_resamp_bank<XT, 1> : &k_resamp_bank<XT, 4>, grid, RESAMP_THREADS, lds, p);
 }
 
 /* the next nin wideband samples in, the samples at L / M times their rate that they complete out, for every link:
@@ -100,15 +87,8 @@ extern "C" int ofdm_resamp_bank(ofdm_handle* h, const void* iq_in, uint64_t nin,
   const void* d_in = iq_in;
   c32* d_out = reinterpret_cast<c32*>(iq_out);
   uint64_t stride = link_stride;
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
-    d_in = d.d_in.p;
-    if (no) {
-      HIPCHK(h, d.d_out.ensure(K * no * sizeof(c32)));
-      d_out = d.d_out.as<c32>();
-      stride = no;
-    }
-  }
+  RCCHK(stage_rx_in(h, d, iq_in, nin, &d_in));
+  RCCHK(stage_rx_out(h, d, K, no, &d_out, &stride));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     const ResampGeom g = resamp_geom(d.L, d.M);
@@ -142,7 +122,7 @@ extern "C" int ofdm_resamp_bank(ofdm_handle* h, const void* iq_in, uint64_t nin,
     p.NB = resamp_bank_sum_links(d.L, d.M, d.ntaps, d.K);
     const uint64_t periods = (n0 + no + L - 1) / L - p.b.J0;
     const uint64_t grid = (periods + TJ - 1) / TJ;
-    if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_resamp_bank: call too long (split it)");
+    RCCHK(stage_check_grid(h, "ofdm_resamp_bank", grid));
     const size_t lds = resamp_bank_lds_bytes(d.L, d.M, d.ntaps, d.K, p.NB);
     RCCHK(stage_time_begin(h, d, timing));
     RCCHK(h->rx_fmt == OFDM_IQ_SC16 ? launch_resamp_bank<sc16>(h, p, g, (unsigned)grid, lds)
@@ -150,8 +130,6 @@ extern "C" int ofdm_resamp_bank(ofdm_handle* h, const void* iq_in, uint64_t nin,
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_rx_history(h, d, d_in, nin));
-  if (!h->dev_ptrs && no)
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(iq_out + i * link_stride, d_out + i * no, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_rx_readback(h, iq_out, link_stride, K, no, d_out));
   return stage_finish(h, d, nin, timing);
 }

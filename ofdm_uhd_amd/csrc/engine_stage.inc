@@ -1,8 +1,16 @@
 // engine_stage.inc -- what the host sides of the ten wideband stream stages share (StreamStage, host_util.h): the
-// steps of a configure call, reset, the argument checks, host-mode staging, timing, the history roll, the choice of a
-// transmit kernel's <OUT, ADD> and the end of a call.  Included by engine.hip ahead of
-// engine_{ddc,ddc_bank,pfb,resamp,resamp_bank,duc,duc_bank,pfb_synth,tx_resamp,tx_resamp_bank}.inc, which keep what is a stage's own: its
-// configuration checks and messages, its table, its index limits, its output count and its launch.
+// steps of a configure call and its per-link checks and tables, reset, the argument checks, timing, the launch, the
+// history roll, the choice of a transmit kernel's <OUT, ADD>, the end of a call, and host-mode staging, one function
+// per step of the four call shapes:
+//   receive single (ddc, resamp) and bank (ddc_bank, resamp_bank, pfb; `rows` runs at the caller's stride):
+//     stage_rx_in, stage_rx_out, [launch], stage_roll_rx_history, stage_rx_readback
+//   transmit single (duc, tx_resamp) and bank (duc_bank, tx_resamp_bank, pfb_synth; `rows` runs in):
+//     stage_tx_rows_in, stage_tx_out, [launch], stage_roll_history / stage_roll_rows_history, stage_tx_readback
+// A staging step leaves the caller's pointers (device mode) as they are and, in host mode, puts the stage's device
+// copy in their place.  Included by engine.hip ahead of engine_{ddc,ddc_bank,duc,resamp,resamp_bank,tx_resamp,pfb,
+// pfb_synth,duc_bank,tx_resamp_bank}.inc (in that order: a bank uses its single stage's index limit), which keep what
+// is a stage's own: its configuration checks and messages, its index limits, its output count, its Params and its
+// template dispatch.
 
 #define RCCHK(expr)         \
   do {                      \
@@ -26,6 +34,15 @@ static std::vector<c32> bandpass_table(const float* taps, int ntaps, double fc, 
   }
   return tab;
 }
+// the tables of a bank's K links, one after the other (link i's at [i * ntaps], as ofdm_*_bank_taps returns it)
+static std::vector<c32> bank_tables(const float* taps, int ntaps, const double* fcs, int K, int L) {
+  std::vector<c32> tab;
+  for (int i = 0; i < K; i++) {
+    const std::vector<c32> c = bandpass_table(taps, ntaps, fcs[i], L);
+    tab.insert(tab.end(), c.begin(), c.end());
+  }
+  return tab;
+}
 
 // the first output n whose newest input floor(n M / L) is at or behind a: ceil(a L / M).  (L = 1, M = R: the DDC's
 // outputs m with m R >= a.)  Nothing overflows: the DDC and the bank have L = 1, so a L is a for every a; the
@@ -40,6 +57,21 @@ static bool taps_finite(const float* taps, uint32_t ntaps) {
   for (uint32_t k = 0; k < ntaps; k++)
     if (!std::isfinite(taps[k])) return false;
   return true;
+}
+
+// nlinks and the n centre frequencies of a configuration (`who` begins the messages, `per` ends the second: the
+// receive stages count cycles per "sample", the transmit stages per "output sample")
+static int stage_check_nlinks(ofdm_handle* h, const char* who, uint32_t nlinks) {
+  static_assert(OFDM_DDC_BANK_MAX_LINKS == 8 && OFDM_RESAMP_BANK_MAX_LINKS == 8 && OFDM_DUC_BANK_MAX_LINKS == 8 &&
+                    OFDM_TX_RESAMP_BANK_MAX_LINKS == 8,
+                "the message below names the limit");
+  if (nlinks < 1 || nlinks > 8) FAIL(h, OFDM_E_INVAL, std::string(who) + " nlinks must be in [1, 8]");
+  return OFDM_OK;
+}
+static int stage_check_center_freqs(ofdm_handle* h, const char* who, const double* fc, uint32_t n, const char* per) {
+  for (uint32_t i = 0; i < n; i++)
+    if (!(fabs(fc[i]) <= 0.5)) FAIL(h, OFDM_E_INVAL, std::string(who) + " center_freq must be in [-0.5, 0.5] cycles per " + per);
+  return OFDM_OK;
 }
 
 // out_format / out_scale of the transmit stages (`who` begins their messages): the full scale in force
@@ -110,6 +142,12 @@ static int stage_taps_out(const c32* tab, int ntaps, ofdm_c32* out, int cap, int
   return OFDM_OK;
 }
 
+// the table of one link of a bank (tab: bank_tables)
+static int stage_bank_taps(bool on, const std::vector<c32>& tab, int ntaps, int K, int link, ofdm_c32* out, int cap, int* n) {
+  if (!on || link < 0 || link >= K) return OFDM_E_INVAL;
+  return stage_taps_out(tab.data() + (size_t)link * ntaps, ntaps, out, cap, n);
+}
+
 // the caller's input of a receive stage, in the handle's receive format
 static int stage_check_rx_in(ofdm_handle* h, const void* iq_in, uint64_t nin) {
   const bool s16 = h->rx_fmt == OFDM_IQ_SC16;
@@ -150,6 +188,76 @@ static int stage_upload(ofdm_handle* h, DevBuf& b, const void* src, size_t bytes
   return OFDM_OK;
 }
 
+// host mode of a receive stage: the call's input into d.d_in
+static int stage_rx_in(ofdm_handle* h, StreamStage& d, const void* iq_in, uint64_t nin, const void** d_in) {
+  if (h->dev_ptrs) return OFDM_OK;
+  RCCHK(stage_upload(h, d.d_in, iq_in, nin * rx_ss(h)));
+  *d_in = d.d_in.p;
+  return OFDM_OK;
+}
+// ... its `rows` runs of `no` outputs into d.d_out, one behind the other (rows = 1: stride may be NULL) ...
+static int stage_rx_out(ofdm_handle* h, StreamStage& d, uint64_t rows, uint64_t no, c32** d_out, uint64_t* stride) {
+  if (h->dev_ptrs || !no) return OFDM_OK;
+  HIPCHK(h, d.d_out.ensure(rows * no * sizeof(c32)));
+  *d_out = d.d_out.as<c32>();
+  if (stride) *stride = no;
+  return OFDM_OK;
+}
+// ... and from there into the caller's buffer, run i at iq_out + i * caller_stride
+static int stage_rx_readback(ofdm_handle* h, ofdm_c32* iq_out, uint64_t caller_stride, uint64_t rows, uint64_t no, const c32* d_out) {
+  if (h->dev_ptrs || !no) return OFDM_OK;
+  for (uint64_t i = 0; i < rows; i++)
+    HIPCHK(h, hipMemcpyAsync(iq_out + i * caller_stride, d_out + i * no, no * sizeof(c32), hipMemcpyDeviceToHost, h->stream));
+  return OFDM_OK;
+}
+
+// host mode of a transmit stage: the `rows` runs of `nin` inputs, run i at iq_in + i * caller_stride, into d.d_in one
+// behind the other (rows = 1: stride may be NULL)
+static int stage_tx_rows_in(ofdm_handle* h, StreamStage& d, const ofdm_c32* iq_in, uint64_t caller_stride, uint64_t rows, uint64_t nin,
+                            const c32** d_in, uint64_t* stride) {
+  if (h->dev_ptrs) return OFDM_OK;
+  HIPCHK(h, d.d_in.ensure(rows * nin * sizeof(c32)));
+  for (uint64_t i = 0; i < rows; i++)
+    HIPCHK(h, hipMemcpyAsync(d.d_in.as<c32>() + i * nin, iq_in + i * caller_stride, nin * sizeof(c32), hipMemcpyHostToDevice, h->stream));
+  *d_in = d.d_in.as<c32>();
+  if (stride) *stride = nin;
+  return OFDM_OK;
+}
+// ... the band to add onto, where one is given, into d.d_add, and room for the `no` outputs of `oss` bytes in d.d_out
+// (a stage whose call may complete no output asks for this step only where no > 0) ...
+static int stage_tx_out(ofdm_handle* h, StreamStage& d, const ofdm_c32* add, uint64_t no, size_t oss, const c32** d_add, void** d_out) {
+  if (h->dev_ptrs) return OFDM_OK;
+  if (add) {
+    RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
+    *d_add = d.d_add.as<c32>();
+  }
+  HIPCHK(h, d.d_out.ensure(no * oss));
+  *d_out = d.d_out.p;
+  return OFDM_OK;
+}
+// ... and the outputs into the caller's buffer (asked for as stage_tx_out is)
+static int stage_tx_readback(ofdm_handle* h, void* iq_out, const void* d_out, uint64_t no, size_t oss) {
+  if (h->dev_ptrs) return OFDM_OK;
+  HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  return OFDM_OK;
+}
+
+// a launch may have 2^31 - 1 workgroups (`who`: the entry point)
+static int stage_check_grid(ofdm_handle* h, const char* who, uint64_t grid) {
+  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, std::string(who) + ": call too long (split it)");
+  return OFDM_OK;
+}
+
+// a stage's compute kernel; tables of many links and long filters take a workgroup past the default 64 KB of dynamic
+// LDS, and the limit is raised first
+template <typename P>
+static int stage_launch(ofdm_handle* h, void (*kernel)(P), unsigned grid, unsigned threads, size_t lds, const P& p) {
+  if (lds > 64 * 1024)
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, h->stream, p);
+  return OFDM_OK;
+}
+
 // the HIP-event pair around a stage's compute kernel, created with the first timed call
 static int stage_time_begin(ofdm_handle* h, StreamStage& d, bool timing) {
   if (!timing) return OFDM_OK;
@@ -179,6 +287,15 @@ static int stage_roll_history(ofdm_handle* h, StreamStage& d, const XT* x, uint6
 static int stage_roll_rx_history(ofdm_handle* h, StreamStage& d, const void* x, uint64_t nin) {
   if (h->rx_fmt == OFDM_IQ_SC16) return stage_roll_history(h, d, static_cast<const sc16*>(x), nin, h->rx_scale);
   return stage_roll_history(h, d, static_cast<const c32*>(x), nin, h->rx_scale);
+}
+
+// a transmit bank: the last Q inputs of each of the `rows` runs at x + i * stride
+static int stage_roll_rows_history(ofdm_handle* h, StreamStage& d, const c32* x, uint64_t stride, uint64_t nin, int Q, int rows) {
+  if (Q <= 0) return OFDM_OK;
+  hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((Q + 255) / 256), (unsigned)rows), dim3(256), 0, h->stream, x, stride, nin,
+                     d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), Q);
+  HIPCHK(h, hipGetLastError());
+  return OFDM_OK;
 }
 
 // the end of a call: everything queued is done, the new history is the current one, the stream has moved on

@@ -14,7 +14,7 @@ extern "C" int ofdm_set_tx_resamp(ofdm_handle* h, const ofdm_tx_resamp_cfg* cfg)
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_TX_RESAMP_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "transmit resampler ntaps must be in [1, 1024]");
   float scale;
   RCCHK(stage_out_scale(h, "transmit resampler", cfg->out_format, cfg->out_scale, &scale));
-  if (!(fabs(cfg->center_freq) <= 0.5)) FAIL(h, OFDM_E_INVAL, "transmit resampler center_freq must be in [-0.5, 0.5] cycles per output sample");
+  RCCHK(stage_check_center_freqs(h, "transmit resampler", &cfg->center_freq, 1, "output sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "transmit resampler taps must be finite");
   RCCHK(stage_disarm(h, d));
   d.L = (int)cfg->interpolation;
@@ -48,16 +48,6 @@ extern "C" int ofdm_tx_resamp_last_ms(const ofdm_handle* h, double* ms) {
   return stage_last_ms(h->tx_resamp, ms);
 }
 
-template <typename OUT, bool ADD>
-static hipError_t launch_tx_resamp(ofdm_handle* h, const TxResampParams& p, unsigned grid, size_t lds) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tx_resamp<OUT, ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_resamp<OUT, ADD>), dim3(grid), dim3(TX_RESAMP_THREADS), lds, h->stream, p);
-  return hipSuccess;
-}
-
 /* the next nin narrowband samples in, the wideband samples at L / M times their rate that they complete out (optionally
  * added onto a band that is there) */
 extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, const ofdm_c32* add, void* iq_out, uint64_t out_cap,
@@ -79,25 +69,15 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
   const TxResampGeom g = tx_resamp_geom(d.L, d.M);
   const uint64_t TJ = (uint64_t)g.TJ(), J0 = n0 / L;
   const uint64_t grid = no ? ((n0 + no + L - 1) / L - J0 + TJ - 1) / TJ : 0;
-  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp: call too long (split it)");
+  RCCHK(stage_check_grid(h, "ofdm_tx_resamp", grid));
   RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
   const c32* d_in = reinterpret_cast<const c32*>(iq_in);
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
-  if (!h->dev_ptrs) {
-    RCCHK(stage_upload(h, d.d_in, iq_in, nin * sizeof(c32)));
-    d_in = d.d_in.as<c32>();
-    if (no) {
-      if (add) {
-        RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
-        d_add = d.d_add.as<c32>();
-      }
-      HIPCHK(h, d.d_out.ensure(no * oss));
-      d_out = d.d_out.p;
-    }
-  }
+  RCCHK(stage_tx_rows_in(h, d, iq_in, 0, 1, nin, &d_in, nullptr));
+  if (no) RCCHK(stage_tx_out(h, d, add, no, oss, &d_add, &d_out));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     TxResampParams p;
@@ -126,12 +106,12 @@ extern "C" int ofdm_tx_resamp(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t ni
     p.scale = d.out_scale;
     const size_t lds = tx_resamp_lds_bytes(d.L, d.M, d.ntaps);
     RCCHK(stage_time_begin(h, d, timing));
-    HIPCHK(h, stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) {
-      return launch_tx_resamp<decltype(o), decltype(a)::value>(h, p, (unsigned)grid, lds);
+    RCCHK(stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) {
+      return stage_launch(h, &k_tx_resamp<decltype(o), decltype(a)::value>, (unsigned)grid, TX_RESAMP_THREADS, lds, p);
     }));
     RCCHK(stage_time_end(h, d, timing));
   }
   RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));
-  if (!h->dev_ptrs && no) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  if (no) RCCHK(stage_tx_readback(h, iq_out, d_out, no, oss));
   return stage_finish(h, d, nin, timing);
 }

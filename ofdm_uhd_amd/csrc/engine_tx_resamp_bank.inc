@@ -1,5 +1,5 @@
 // engine_tx_resamp_bank.inc -- host side of the transmit resampler bank (tx_resamp_bank.h): configuration, index
-// limits, the per-link upload, launch.  Included by engine.hip after engine_stage.inc and engine_tx_resamp.inc
+// limits, launch (the per-link upload: stage_tx_rows_in).  Included by engine.hip after engine_stage.inc and engine_tx_resamp.inc
 // (TX_RESAMP_MAX_INDEX).
 
 /* K blks2.rational_resampler_ccf(interpolation, decimation, taps) + set_center_freq that share ratio and prototype,
@@ -12,12 +12,10 @@ extern "C" int ofdm_set_tx_resamp_bank(ofdm_handle* h, const ofdm_tx_resamp_bank
   if (cfg->interpolation < 1 || cfg->interpolation > TX_RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "transmit resampler bank interpolation must be in [1, 64]");
   if (cfg->decimation < 1 || cfg->decimation > TX_RESAMP_MAX_RATIO) FAIL(h, OFDM_E_INVAL, "transmit resampler bank decimation must be in [1, 64]");
   if (cfg->ntaps < 1 || cfg->ntaps > OFDM_TX_RESAMP_MAX_TAPS) FAIL(h, OFDM_E_INVAL, "transmit resampler bank ntaps must be in [1, 1024]");
-  if (cfg->nlinks < 1 || cfg->nlinks > OFDM_TX_RESAMP_BANK_MAX_LINKS) FAIL(h, OFDM_E_INVAL, "transmit resampler bank nlinks must be in [1, 8]");
+  RCCHK(stage_check_nlinks(h, "transmit resampler bank", cfg->nlinks));
   float scale;
   RCCHK(stage_out_scale(h, "transmit resampler bank", cfg->out_format, cfg->out_scale, &scale));
-  for (uint32_t i = 0; i < cfg->nlinks; i++)
-    if (!(fabs(cfg->center_freq[i]) <= 0.5))
-      FAIL(h, OFDM_E_INVAL, "transmit resampler bank center_freq must be in [-0.5, 0.5] cycles per output sample");
+  RCCHK(stage_check_center_freqs(h, "transmit resampler bank", cfg->center_freq, cfg->nlinks, "output sample"));
   if (!taps_finite(cfg->taps, cfg->ntaps)) FAIL(h, OFDM_E_INVAL, "transmit resampler bank taps must be finite");
   // (holds for every ratio and length accepted above; the launch relies on it)
   if (tx_resamp_bank_lds_bytes((int)cfg->interpolation, (int)cfg->decimation, (int)cfg->ntaps) > TX_RESAMP_BANK_MAX_LDS)
@@ -32,12 +30,8 @@ extern "C" int ofdm_set_tx_resamp_bank(ofdm_handle* h, const ofdm_tx_resamp_bank
   d.out_scale = scale;
   // G = turns(fc / M), the phase per step of the L-times grid (ONE double division: the table below divides the same
   // way); a link's step per INPUT is L G modulo a turn.  Its table is the receive bank's at interpolation = M.
-  d.tab.clear();
-  for (int i = 0; i < d.K; i++) {
-    d.E[i] = ddc_turns(cfg->center_freq[i] / (double)d.M) * (uint64_t)d.L;
-    const std::vector<c32> c = bandpass_table(cfg->taps, d.ntaps, cfg->center_freq[i], d.M);
-    d.tab.insert(d.tab.end(), c.begin(), c.end());
-  }
+  d.tab = bank_tables(cfg->taps, d.ntaps, cfg->center_freq, d.K, d.M);
+  for (int i = 0; i < d.K; i++) d.E[i] = ddc_turns(cfg->center_freq[i] / (double)d.M) * (uint64_t)d.L;
   HIPCHK(h, upload(d.d_tab, d.tab.data(), d.tab.size()));
   return stage_arm(h, d, d.K * d.Q);  // the last Q raw inputs of every link
 }
@@ -61,23 +55,12 @@ extern "C" int ofdm_tx_resamp_bank_count(const ofdm_handle* h, uint64_t nin, uin
 extern "C" int ofdm_tx_resamp_bank_taps(const ofdm_handle* h, int link, ofdm_c32* out, int cap, int* n) {
   if (!h || !n) return OFDM_E_INVAL;
   const TxResampBankState& d = h->tx_resamp_bank;
-  if (!d.on || link < 0 || link >= d.K) return OFDM_E_INVAL;
-  return stage_taps_out(d.tab.data() + (size_t)link * d.ntaps, d.ntaps, out, cap, n);
+  return stage_bank_taps(d.on, d.tab, d.ntaps, d.K, link, out, cap, n);
 }
 
 extern "C" int ofdm_tx_resamp_bank_last_ms(const ofdm_handle* h, double* ms) {
   if (!h) return OFDM_E_INVAL;
   return stage_last_ms(h->tx_resamp_bank, ms);
-}
-
-template <typename OUT, bool ADD>
-static hipError_t launch_tx_resamp_bank(ofdm_handle* h, const TxResampBankParams& p, unsigned grid, size_t lds) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tx_resamp_bank<OUT, ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tx_resamp_bank<OUT, ADD>), dim3(grid), dim3(TX_RESAMP_THREADS), lds, h->stream, p);
-  return hipSuccess;
 }
 
 /* the next nin samples of every link in (link i's run begins at iq_in + i * link_stride), the samples of the band at
@@ -102,7 +85,7 @@ extern "C" int ofdm_tx_resamp_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64
   const TxResampGeom g = tx_resamp_geom(d.L, d.M);
   const uint64_t TJ = (uint64_t)g.TJ(), J0 = n0 / L;
   const uint64_t grid = no ? ((n0 + no + L - 1) / L - J0 + TJ - 1) / TJ : 0;
-  if (grid > 0x7FFFFFFFull) FAIL(h, OFDM_E_INVAL, "ofdm_tx_resamp_bank: call too long (split it)");
+  RCCHK(stage_check_grid(h, "ofdm_tx_resamp_bank", grid));
   RCCHK(stage_enter(h));
 
   const size_t oss = s16 ? sizeof(sc16) : sizeof(c32);
@@ -110,21 +93,8 @@ extern "C" int ofdm_tx_resamp_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64
   const c32* d_add = reinterpret_cast<const c32*>(add);
   void* d_out = iq_out;
   uint64_t stride = link_stride;
-  if (!h->dev_ptrs) {
-    HIPCHK(h, d.d_in.ensure(K * nin * sizeof(c32)));
-    for (uint64_t i = 0; i < K; i++)
-      HIPCHK(h, hipMemcpyAsync(d.d_in.as<c32>() + i * nin, iq_in + i * link_stride, nin * sizeof(c32), hipMemcpyHostToDevice, h->stream));
-    d_in = d.d_in.as<c32>();
-    stride = nin;
-    if (no) {
-      if (add) {
-        RCCHK(stage_upload(h, d.d_add, add, no * sizeof(c32)));
-        d_add = d.d_add.as<c32>();
-      }
-      HIPCHK(h, d.d_out.ensure(no * oss));
-      d_out = d.d_out.p;
-    }
-  }
+  RCCHK(stage_tx_rows_in(h, d, iq_in, link_stride, K, nin, &d_in, &stride));
+  if (no) RCCHK(stage_tx_out(h, d, add, no, oss, &d_add, &d_out));
   const bool timing = h->prof.on && no > 0;
   if (no) {
     TxResampBankParams p;
@@ -155,16 +125,12 @@ extern "C" int ofdm_tx_resamp_bank(ofdm_handle* h, const ofdm_c32* iq_in, uint64
     p.scale = d.out_scale;
     const size_t lds = tx_resamp_bank_lds_bytes(d.L, d.M, d.ntaps);
     RCCHK(stage_time_begin(h, d, timing));
-    HIPCHK(h, stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) {
-      return launch_tx_resamp_bank<decltype(o), decltype(a)::value>(h, p, (unsigned)grid, lds);
+    RCCHK(stage_tx_variant(s16, add != nullptr, [&](auto o, auto a) {
+      return stage_launch(h, &k_tx_resamp_bank<decltype(o), decltype(a)::value>, (unsigned)grid, TX_RESAMP_THREADS, lds, p);
     }));
     RCCHK(stage_time_end(h, d, timing));
   }
-  if (d.Q > 0) {
-    hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((d.Q + 255) / 256), (unsigned)d.K), dim3(256), 0, h->stream, d_in, stride, nin,
-                       d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), d.Q);
-    HIPCHK(h, hipGetLastError());
-  }
-  if (!h->dev_ptrs && no) HIPCHK(h, hipMemcpyAsync(iq_out, d_out, no * oss, hipMemcpyDeviceToHost, h->stream));
+  RCCHK(stage_roll_rows_history(h, d, d_in, stride, nin, d.Q, d.K));
+  if (no) RCCHK(stage_tx_readback(h, iq_out, d_out, no, oss));
   return stage_finish(h, d, nin, timing);
 }

@@ -68,6 +68,7 @@ struct StreamStage {
   int cur = 0;        // d_hist[cur] holds the `hist` samples before `next`
   int hist = 0;       // samples of history a call reaches back: ntaps - 1 (DDC, bank), Q = (ntaps - 1) / L (the others)
   DevBuf d_hist[2], d_in, d_out;
+  DevBuf d_add;        // the transmit stages: host mode's copy of the band a call adds onto
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   double last_ms = 0.0;
   bool timed = false;  // last_ms is of the stage's last call
@@ -76,6 +77,7 @@ struct StreamStage {
     d_hist[1].release();
     d_in.release();
     d_out.release();
+    d_add.release();
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);
     ev_a = ev_b = nullptr;

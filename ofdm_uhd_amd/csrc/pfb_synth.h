@@ -197,11 +197,10 @@ struct PfbSynthState : StreamStage {
   int out_fmt = OFDM_IQ_FC32;
   float out_scale = 32768.0f;
   signed char pos[PFB_MAX_CHANNELS] = {};  // PfbSynthParams::pos
-  DevBuf d_taps, d_w, d_add;
+  DevBuf d_taps, d_w;
   void release() {
     d_taps.release();
     d_w.release();
-    d_add.release();
     StreamStage::release();
   }
 };

@@ -155,10 +155,9 @@ struct TxResampState : StreamStage {
   int out_fmt = OFDM_IQ_FC32;
   float out_scale = 32768.0f;
   uint64_t D = 0;     // frac(fc) in 2^-64 turn
-  DevBuf d_taps, d_add;
+  DevBuf d_taps;
   void release() {
     d_taps.release();
-    d_add.release();
     StreamStage::release();
   }
 };

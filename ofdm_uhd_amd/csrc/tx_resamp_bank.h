@@ -209,10 +209,9 @@ struct TxResampBankState : StreamStage {
   float out_scale = 32768.0f;
   uint64_t E[TX_RESAMP_BANK_MAX_LINKS] = {};
   std::vector<c32> tab;  // link i's table at tab[i * ntaps], as ofdm_tx_resamp_bank_taps returns it
-  DevBuf d_tab, d_add;
+  DevBuf d_tab;
   void release() {
     d_tab.release();
-    d_add.release();
     StreamStage::release();
   }
 };

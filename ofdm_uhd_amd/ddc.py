@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, firdes
+from . import _abi, firdes, iqio
 
 MAX_TAPS = _abi.OFDM_DDC_MAX_TAPS
 MAX_DECIM = 64
@@ -54,9 +54,10 @@ def bandpass_taps(taps, fc, interpolation=1):
     return (h * np.cos(a) + 1j * (h * np.sin(a))).astype(np.complex64)
 
 
-def _cfg_with_taps(struct, who, max_taps, taps, occupied_fraction, design_taps):
+def _cfg_with_taps(struct, who, max_taps, taps, occupied_fraction, design_taps, finite=False):
     """A zeroed ``struct`` (one of the ten stages' configurations) with struct_size, ntaps and taps filled in: the
-    given taps as float32 or, with ``taps=None``, what ``design_taps()`` makes of ``occupied_fraction``."""
+    given taps as float32 or, with ``taps=None``, what ``design_taps()`` makes of ``occupied_fraction``.  ``finite``:
+    the builder refuses taps that are not finite itself (the others leave that to the library)."""
     if taps is None:
         if occupied_fraction is None:
             raise ValueError("%s needs taps or occupied_fraction" % who)
@@ -64,10 +65,42 @@ def _cfg_with_taps(struct, who, max_taps, taps, occupied_fraction, design_taps):
     taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
     if not 1 <= len(taps) <= max_taps:
         raise ValueError("ntaps must be in [1, %d]" % max_taps)
+    if finite and not np.all(np.isfinite(taps)):
+        raise ValueError("taps must be finite")
     cfg = struct()
     cfg.struct_size = C.sizeof(struct)
     cfg.ntaps = len(taps)
     C.memmove(cfg.taps, taps.ctypes.data, 4 * len(taps))
+    return cfg
+
+
+def _bank_cfg_with_taps(struct, bank, max_links, center_freqs, max_taps, taps, occupied_fraction, design_taps,
+                        finite=False):
+    """_cfg_with_taps for the four banks of links at arbitrary centre frequencies (``bank`` names the stage in the
+    message): the list is normalised and checked first, against ``max_links`` and [-0.5, 0.5], and fills nlinks and
+    center_freq[]."""
+    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    if not 1 <= len(fcs) <= max_links:
+        raise ValueError("a %s has 1 to %d links" % (bank, max_links))
+    if not all(abs(f) <= 0.5 for f in fcs):
+        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
+    cfg = _cfg_with_taps(struct, "bank_cfg", max_taps, taps, occupied_fraction, design_taps, finite)
+    cfg.nlinks = len(fcs)
+    for i, f in enumerate(fcs):
+        cfg.center_freq[i] = f
+    return cfg
+
+
+_NO_FC = object()
+
+
+def _set_out_format(cfg, out_format, out_scale, center_freq=_NO_FC):
+    """out_format ("fc32" or "sc16") and out_scale (None: the library's 2^15) of a transmit stage's configuration.
+    The single stages hand their ``center_freq`` in as well: it is converted between the two checks, as ever."""
+    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
+    if center_freq is not _NO_FC:
+        cfg.center_freq = float(center_freq)
+    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
     return cfg
 
 
@@ -84,15 +117,7 @@ def bank_cfg(decimation, center_freqs, taps=None, occupied_fraction=None, transi
     """ofdm_ddc_bank_cfg for Engine.set_ddc_bank: one decimation and one prototype, one centre frequency per link
     (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed).  ``taps=None``
     designs the prototype from ``occupied_fraction`` as ddc_cfg does."""
-    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
-    if not 1 <= len(fcs) <= MAX_LINKS:
-        raise ValueError("a DDC bank has 1 to %d links" % MAX_LINKS)
-    if not all(abs(f) <= 0.5 for f in fcs):
-        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
-    cfg = _cfg_with_taps(_abi.ofdm_ddc_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
-                         lambda: design(decimation, occupied_fraction, transition))
+    cfg = _bank_cfg_with_taps(_abi.ofdm_ddc_bank_cfg, "DDC bank", MAX_LINKS, center_freqs, MAX_TAPS, taps,
+                              occupied_fraction, lambda: design(decimation, occupied_fraction, transition))
     cfg.decimation = int(decimation)
-    cfg.nlinks = len(fcs)
-    for i, f in enumerate(fcs):
-        cfg.center_freq[i] = f
     return cfg

@@ -10,7 +10,7 @@ Frequencies are in cycles per OUTPUT (wideband) sample.
 """
 import numpy as np
 
-from . import _abi, ddc, iqio
+from . import _abi, ddc
 
 MAX_TAPS = _abi.OFDM_DUC_MAX_TAPS
 MAX_INTERP = 64
@@ -37,10 +37,7 @@ def duc_cfg(interpolation, center_freq, taps=None, occupied_fraction=None, trans
     cfg = ddc._cfg_with_taps(_abi.ofdm_duc_cfg, "duc_cfg", MAX_TAPS, taps, occupied_fraction,
                              lambda: design(interpolation, occupied_fraction, transition))
     cfg.interpolation = int(interpolation)
-    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
-    cfg.center_freq = float(center_freq)
-    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    return cfg
+    return ddc._set_out_format(cfg, out_format, out_scale, center_freq)
 
 
 def bank_cfg(interpolation, center_freqs, taps=None, occupied_fraction=None, transition=None, out_format="fc32",
@@ -49,21 +46,10 @@ def bank_cfg(interpolation, center_freqs, taps=None, occupied_fraction=None, tra
     (1 to MAX_LINKS of them, each in [-0.5, 0.5] cycles per wideband sample; equal ones are allowed), row i of
     Engine.duc_bank's input at center_freqs[i].  ``taps=None`` designs the prototype from ``occupied_fraction`` as
     duc_cfg does; ``out_format`` / ``out_scale`` are duc_cfg's."""
-    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
-    if not 1 <= len(fcs) <= MAX_LINKS:
-        raise ValueError("a DUC bank has 1 to %d links" % MAX_LINKS)
-    if not all(abs(f) <= 0.5 for f in fcs):
-        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
-    cfg = ddc._cfg_with_taps(_abi.ofdm_duc_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
-                             lambda: design(interpolation, occupied_fraction, transition))
-    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
-        raise ValueError("taps must be finite")
+    cfg = ddc._bank_cfg_with_taps(_abi.ofdm_duc_bank_cfg, "DUC bank", MAX_LINKS, center_freqs, MAX_TAPS, taps,
+                                  occupied_fraction, lambda: design(interpolation, occupied_fraction, transition),
+                                  finite=True)
     cfg.interpolation = int(interpolation)
     if not 1 <= cfg.interpolation <= MAX_INTERP:
         raise ValueError("interpolation must be in [1, %d]" % MAX_INTERP)
-    cfg.nlinks = len(fcs)
-    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
-    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    for i, f in enumerate(fcs):
-        cfg.center_freq[i] = f
-    return cfg
+    return ddc._set_out_format(cfg, out_format, out_scale)

@@ -808,47 +808,39 @@ class ofdm_mod_resamp_bank(_ofdm_mod_links):
         return (cfg.ntaps - 1) // cfg.interpolation
 
 
-class ofdm_demod_bank(object):
-    """
-    Demodulates every link of one wideband capture: K links that share the decimation and the low-pass prototype and
-    differ in their centre frequency (the receive-side counterpart of adding links onto one band with Engine.duc).
+class _ofdm_demod_links(object):
+    """What ofdm_demod_bank, ofdm_demod_channelizer and ofdm_demod_resamp_bank share, the receive mirror of
+    _ofdm_mod_links: one engine owns the stage that takes the K narrowband streams out of the capture in one pass, and
+    each stream goes to a plain ofdm_demod of its own.  A subclass checks its arguments with _check(), builds the
+    stage's configuration and hands both to _open(); ``_stage`` names the engine's stage (Engine.<stage>,
+    set_<stage>, <stage>_reset)."""
 
-    One engine owns the DDC bank (Engine.ddc_bank: all K narrowband streams from one pass over the wideband samples);
-    each stream goes to a plain ofdm_demod of its own.  Link i returns what ofdm_demod(options_i, ddc=dict(decimation=,
-    center_freq=center_freqs[i], taps=)) returns on the same samples.
-    """
+    _stage = None
 
-    def __init__(self, options, center_freqs, decimation, taps=None, callback=None, iq_format="fc32", iq_scale=None,
-                 device_id=0):
-        """
-        @param options: one options object for all links, or a list of K for links that differ in modulation
-        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
-        @param decimation: wideband rate over the modem's rate, 1..64
-        @param taps: the shared prototype; None: ddc.design for the largest occupied_tones / fft_length of the links
-        @param callback: function of three args: link, ok, payload -- per call fired for link 0's packets, then link
-            1's, and so on
-        @param iq_format, iq_scale: format of the WIDEBAND samples, as for ofdm_demod
-        """
-        # every argument is checked before the first engine exists
-        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+    def _check(self, options, K, per, callback, position, iq_format, iq_scale):
+        """The checks the three classes share, in their order: ``options`` is one object or a list of K (``per``
+        names what a list holds one for), ``callback`` a function of (``position``, ok, payload).  Returns the K
+        options, the wideband format and scale and the largest occupied fraction."""
         if isinstance(options, (list, tuple)):
             opts = list(options)
-            if len(opts) != len(fcs):
-                raise ValueError("ofdm_demod_bank needs one options object, or one per centre frequency")
+            if len(opts) != K:
+                raise ValueError("%s needs one options object, or one per %s" % (type(self).__name__, per))
         else:
-            opts = [options] * len(fcs)
+            opts = [options] * K
         if callback is not None and not callable(callback):
-            raise ValueError("callback must be callable: callback(link, ok, payload)")
+            raise ValueError("callback must be callable: callback(%s, ok, payload)" % position)
         fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
         occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
-        cfg = _ddc.bank_cfg(decimation, fcs, taps=taps, occupied_fraction=occ)   # ValueError: K, frequencies, R, taps
+        return opts, fmt, scale, occ
+
+    def _open(self, opts, cfg, callback, fmt, scale, device_id):
         self._callback = callback
         self._links = []
         self._engine = engine.Engine(opts[0], device_id=device_id)
         try:
             if fmt != "fc32":
                 self._engine.set_rx_iq_format(fmt, scale)
-            self._engine.set_ddc_bank(cfg)
+            getattr(self._engine, "set_" + self._stage)(cfg)
             for i, o in enumerate(opts):
                 cb = (lambda ok, payload, link=i: self._callback(link, ok, payload)) if callback is not None else None
                 self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
@@ -868,10 +860,10 @@ class ofdm_demod_bank(object):
     def _tune(self, iq, restart):
         eng = self._engine
         if restart:
-            eng.ddc_bank_reset(0)
+            getattr(eng, self._stage + "_reset")(0)
         if len(iq) == 0:
             return np.zeros((len(self._links), 0), np.complex64)
-        return eng.ddc_bank(iq)
+        return getattr(eng, self._stage)(iq)
 
     def work(self, iq):
         """Demodulate one contiguous wideband stream: a list of K packet lists."""
@@ -896,6 +888,36 @@ class ofdm_demod_bank(object):
         self._engine.close()
 
 
+class ofdm_demod_bank(_ofdm_demod_links):
+    """
+    Demodulates every link of one wideband capture: K links that share the decimation and the low-pass prototype and
+    differ in their centre frequency (the receive-side counterpart of adding links onto one band with Engine.duc).
+
+    One engine owns the DDC bank (Engine.ddc_bank: all K narrowband streams from one pass over the wideband samples);
+    each stream goes to a plain ofdm_demod of its own.  Link i returns what ofdm_demod(options_i, ddc=dict(decimation=,
+    center_freq=center_freqs[i], taps=)) returns on the same samples.
+    """
+
+    _stage = "ddc_bank"
+
+    def __init__(self, options, center_freqs, decimation, taps=None, callback=None, iq_format="fc32", iq_scale=None,
+                 device_id=0):
+        """
+        @param options: one options object for all links, or a list of K for links that differ in modulation
+        @param center_freqs: K centre frequencies, cycles per wideband sample, each in [-0.5, 0.5]
+        @param decimation: wideband rate over the modem's rate, 1..64
+        @param taps: the shared prototype; None: ddc.design for the largest occupied_tones / fft_length of the links
+        @param callback: function of three args: link, ok, payload -- per call fired for link 0's packets, then link
+            1's, and so on
+        @param iq_format, iq_scale: format of the WIDEBAND samples, as for ofdm_demod
+        """
+        # every argument is checked before the first engine exists
+        fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
+        opts, fmt, scale, occ = self._check(options, len(fcs), "centre frequency", callback, "link", iq_format, iq_scale)
+        cfg = _ddc.bank_cfg(decimation, fcs, taps=taps, occupied_fraction=occ)   # ValueError: K, frequencies, R, taps
+        self._open(opts, cfg, callback, fmt, scale, device_id)
+
+
 class ofdm_demod_channelizer(ofdm_demod_bank):
     """
     Demodulates links that sit on a uniform grid of one wideband capture: M channels at centre frequencies c/M cycles
@@ -903,6 +925,8 @@ class ofdm_demod_channelizer(ofdm_demod_bank):
     polyphase-FFT channeliser (Engine.pfb) in the DDC bank's place: one real-tap filter and one M-point transform serve
     all channels, up to 64 of them.  work, feed, flush, links and close are the bank's.
     """
+
+    _stage = "pfb"
 
     def __init__(self, options, nchannels, channels=None, taps=None, callback=None, iq_format="fc32", iq_scale=None,
                  device_id=0):
@@ -918,39 +942,9 @@ class ofdm_demod_channelizer(ofdm_demod_bank):
         # every argument is checked before the first engine exists
         channels = None if channels is None else list(channels)
         K = int(nchannels) if channels is None else len(channels)
-        if isinstance(options, (list, tuple)):
-            opts = list(options)
-            if len(opts) != K:
-                raise ValueError("ofdm_demod_channelizer needs one options object, or one per kept channel")
-        else:
-            opts = [options] * K
-        if callback is not None and not callable(callback):
-            raise ValueError("callback must be callable: callback(channel_position, ok, payload)")
-        fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
-        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        opts, fmt, scale, occ = self._check(options, K, "kept channel", callback, "channel_position", iq_format, iq_scale)
         cfg = _pfb.pfb_cfg(nchannels, channels, taps=taps, occupied_fraction=occ)   # ValueError: M, K, channels, taps
-        self._callback = callback
-        self._links = []
-        self._engine = engine.Engine(opts[0], device_id=device_id)
-        try:
-            if fmt != "fc32":
-                self._engine.set_rx_iq_format(fmt, scale)
-            self._engine.set_pfb(cfg)
-            for i, o in enumerate(opts):
-                cb = (lambda ok, payload, pos=i: self._callback(pos, ok, payload)) if callback is not None else None
-                self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
-        except Exception:
-            self.close()
-            raise
-        self._streaming = False
-
-    def _tune(self, iq, restart):
-        eng = self._engine
-        if restart:
-            eng.pfb_reset(0)
-        if len(iq) == 0:
-            return np.zeros((len(self._links), 0), np.complex64)
-        return eng.pfb(iq)
+        self._open(opts, cfg, callback, fmt, scale, device_id)
 
 
 class ofdm_demod_resamp_bank(ofdm_demod_bank):
@@ -962,6 +956,8 @@ class ofdm_demod_resamp_bank(ofdm_demod_bank):
     center_freq=center_freqs[i], taps=)) returns on the same samples.  work, feed, flush, links and close are the
     bank's.
     """
+
+    _stage = "resamp_bank"
 
     def __init__(self, options, center_freqs, interpolation, decimation, taps=None, callback=None, iq_format="fc32",
                  iq_scale=None, device_id=0):
@@ -977,37 +973,7 @@ class ofdm_demod_resamp_bank(ofdm_demod_bank):
         """
         # every argument is checked before the first engine exists
         fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
-        if isinstance(options, (list, tuple)):
-            opts = list(options)
-            if len(opts) != len(fcs):
-                raise ValueError("ofdm_demod_resamp_bank needs one options object, or one per centre frequency")
-        else:
-            opts = [options] * len(fcs)
-        if callback is not None and not callable(callback):
-            raise ValueError("callback must be callable: callback(link, ok, payload)")
-        fmt, scale = iqio.check_format(iq_format), iqio.check_scale(iq_scale, iqio.RX_SCALE)
-        occ = max([o.occupied_tones / float(o.fft_length) for o in opts] or [1.0])
+        opts, fmt, scale, occ = self._check(options, len(fcs), "centre frequency", callback, "link", iq_format, iq_scale)
         # ValueError: K, frequencies, L, M, taps
         cfg = _resample.bank_cfg(interpolation, decimation, fcs, taps=taps, occupied_fraction=occ)
-        self._callback = callback
-        self._links = []
-        self._engine = engine.Engine(opts[0], device_id=device_id)
-        try:
-            if fmt != "fc32":
-                self._engine.set_rx_iq_format(fmt, scale)
-            self._engine.set_resamp_bank(cfg)
-            for i, o in enumerate(opts):
-                cb = (lambda ok, payload, link=i: self._callback(link, ok, payload)) if callback is not None else None
-                self._links.append(ofdm_demod(o, callback=cb, device_id=device_id))
-        except Exception:
-            self.close()
-            raise
-        self._streaming = False
-
-    def _tune(self, iq, restart):
-        eng = self._engine
-        if restart:
-            eng.resamp_bank_reset(0)
-        if len(iq) == 0:
-            return np.zeros((len(self._links), 0), np.complex64)
-        return eng.resamp_bank(iq)
+        self._open(opts, cfg, callback, fmt, scale, device_id)

@@ -12,7 +12,7 @@ Channel c in [0, M) sits at c/M; c >= M/2 is the negative frequency (c - M)/M.
 """
 import numpy as np
 
-from . import _abi, ddc, duc, iqio
+from . import _abi, ddc, duc
 
 MAX_CHANNELS = _abi.OFDM_PFB_MAX_CHANNELS
 MAX_TAPS = _abi.OFDM_PFB_MAX_TAPS
@@ -40,9 +40,7 @@ def pfb_cfg(nchannels, channels=None, taps=None, occupied_fraction=None, transit
     if not all(-(M // 2) <= c < M for c in chans):
         raise ValueError("channels must lie in [-M/2, M)")
     cfg = ddc._cfg_with_taps(_abi.ofdm_pfb_cfg, "pfb_cfg", MAX_TAPS, taps, occupied_fraction,
-                             lambda: design(M, occupied_fraction, transition))
-    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
-        raise ValueError("taps must be finite")
+                             lambda: design(M, occupied_fraction, transition), finite=True)
     cfg.nchannels = M
     cfg.nsel = len(chans)
     for i, c in enumerate(chans):
@@ -76,13 +74,9 @@ def synth_cfg(nchannels, channels, taps=None, occupied_fraction=None, transition
     if len(set(chans)) != len(chans):
         raise ValueError("a synthesis bank's channels must all be different (mod nchannels)")
     cfg = ddc._cfg_with_taps(_abi.ofdm_pfb_synth_cfg, "synth_cfg", MAX_TAPS, taps, occupied_fraction,
-                             lambda: synth_design(M, occupied_fraction, transition))
-    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
-        raise ValueError("taps must be finite")
+                             lambda: synth_design(M, occupied_fraction, transition), finite=True)
     cfg.nchannels = M
     cfg.nsel = len(chans)
-    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
-    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
     for i, c in enumerate(chans):
         cfg.channel[i] = c
-    return cfg
+    return ddc._set_out_format(cfg, out_format, out_scale)

@@ -80,16 +80,9 @@ def bank_cfg(interpolation, decimation, center_freqs, taps=None, occupied_fracti
     designs the prototype from ``occupied_fraction`` as resamp_cfg does.  ValueError for a ratio outside 1..64, with
     given taps too."""
     L, M = _check_ratio(interpolation, decimation)
-    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
-    if not 1 <= len(fcs) <= MAX_LINKS:
-        raise ValueError("a resampler bank has 1 to %d links" % MAX_LINKS)
-    if not all(abs(f) <= 0.5 for f in fcs):
-        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
-    cfg = ddc._cfg_with_taps(_abi.ofdm_resamp_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
-                             lambda: design(interpolation, decimation, occupied_fraction, transition))
+    cfg = ddc._bank_cfg_with_taps(_abi.ofdm_resamp_bank_cfg, "resampler bank", MAX_LINKS, center_freqs, MAX_TAPS, taps,
+                                  occupied_fraction,
+                                  lambda: design(interpolation, decimation, occupied_fraction, transition))
     cfg.interpolation = L
     cfg.decimation = M
-    cfg.nlinks = len(fcs)
-    for i, f in enumerate(fcs):
-        cfg.center_freq[i] = f
     return cfg

@@ -13,7 +13,7 @@ import math
 
 import numpy as np
 
-from . import _abi, ddc, duc, firdes, iqio, resample
+from . import _abi, ddc, duc, firdes, resample
 
 MAX_TAPS = _abi.OFDM_TX_RESAMP_MAX_TAPS
 MAX_RATIO = resample.MAX_RATIO
@@ -74,10 +74,7 @@ def tx_resamp_cfg(interpolation, decimation, center_freq=0.0, taps=None, occupie
                              lambda: design(interpolation, decimation, occupied_fraction, transition))
     cfg.interpolation = int(interpolation)
     cfg.decimation = int(decimation)
-    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
-    cfg.center_freq = float(center_freq)
-    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    return cfg
+    return ddc._set_out_format(cfg, out_format, out_scale, center_freq)
 
 
 MAX_LINKS = _abi.OFDM_TX_RESAMP_BANK_MAX_LINKS
@@ -100,20 +97,9 @@ def bank_cfg(interpolation, decimation, center_freqs, taps=None, occupied_fracti
     as tx_resamp_cfg does; ``out_format`` / ``out_scale`` are tx_resamp_cfg's.  ValueError for a ratio outside 1..64,
     with given taps too."""
     L, M = _check_ratio(interpolation, decimation)
-    fcs = [float(f) for f in np.asarray(center_freqs, np.float64).reshape(-1)]
-    if not 1 <= len(fcs) <= MAX_LINKS:
-        raise ValueError("a transmit resampler bank has 1 to %d links" % MAX_LINKS)
-    if not all(abs(f) <= 0.5 for f in fcs):
-        raise ValueError("center_freqs must lie in [-0.5, 0.5] cycles per sample")
-    cfg = ddc._cfg_with_taps(_abi.ofdm_tx_resamp_bank_cfg, "bank_cfg", MAX_TAPS, taps, occupied_fraction,
-                             lambda: design(interpolation, decimation, occupied_fraction, transition))
-    if not np.all(np.isfinite(np.ctypeslib.as_array(cfg.taps)[:cfg.ntaps])):
-        raise ValueError("taps must be finite")
+    cfg = ddc._bank_cfg_with_taps(_abi.ofdm_tx_resamp_bank_cfg, "transmit resampler bank", MAX_LINKS, center_freqs,
+                                  MAX_TAPS, taps, occupied_fraction,
+                                  lambda: design(interpolation, decimation, occupied_fraction, transition), finite=True)
     cfg.interpolation = L
     cfg.decimation = M
-    cfg.nlinks = len(fcs)
-    cfg.out_format = iqio.FORMATS.index(iqio.check_format(out_format))
-    cfg.out_scale = 0.0 if out_scale is None else iqio.check_scale(out_scale, iqio.TX_SCALE)
-    for i, f in enumerate(fcs):
-        cfg.center_freq[i] = f
-    return cfg
+    return ddc._set_out_format(cfg, out_format, out_scale)

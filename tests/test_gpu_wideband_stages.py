@@ -2,10 +2,14 @@
 bank, DUC bank) live on ONE handle.  They share one host-side skeleton (StreamStage, csrc/engine_stage.inc); each must
 still own its history buffers, its staging buffers, its stream position and its HIP-event pair.  The per-stage files
 check the receive stages together and the transmit stages together; this is the only place that has all eight
-interleaved."""
+interleaved.  The last test is about a buffer that StreamStage holds for the five transmit stages: the host-mode copy
+of the band a call adds onto."""
 import numpy as np
 import pytest
 
+import duc_cases
+import pfb_synth_cases
+import tx_resamp_cases
 from helpers import make_cfg
 from ofdm_uhd_amd import ddc, duc, engine, pfb, resample, tx_resample
 
@@ -102,5 +106,78 @@ def test_eight_stages_interleaved_on_one_handle():
         for s in STAGES:
             y = _join(s, got[s])
             assert y.shape == want[s].shape and np.array_equal(y, want[s]), s
+    finally:
+        eng.close()
+
+
+# (stage, L, M): the five transmit stages, the resamplers on both sides of 1
+ADD_CASES = [("duc", 4, 1), ("duc_bank", 4, 1), ("pfb_synth", 4, 1), ("tx_resamp", 3, 2), ("tx_resamp", 2, 3),
+             ("tx_resamp_bank", 3, 2), ("tx_resamp_bank", 2, 3)]
+
+
+def _add_case(stage, L, M, rng):
+    """(cfg, rows, inputs of one workgroup tile, count(eng, nin)) of a transmit stage with 9 taps, K = 3 for the
+    banks; the tile is the stage's own geometry as its test module restates it."""
+    h = (rng.standard_normal(9) / 3.0).astype(np.float32)
+    fcs = [0.21, -0.3, 0.0]
+    fixed = lambda eng, n: n * L
+    if stage == "duc":
+        return duc.duc_cfg(L, fcs[0], taps=h), None, duc_cases.tile_outputs(L) // L, fixed
+    if stage == "duc_bank":
+        return duc.bank_cfg(L, fcs, taps=h), 3, duc_cases.tile_outputs(L) // L, fixed
+    if stage == "pfb_synth":
+        return pfb.synth_cfg(L, [1, 3, 0], taps=h), 3, pfb_synth_cases.tile_inputs(L), fixed
+    counted = lambda eng, n: getattr(eng, stage + "_count")(n)
+    if stage == "tx_resamp":
+        return tx_resample.tx_resamp_cfg(L, M, fcs[0], taps=h), None, tx_resamp_cases.tile_inputs(L, M), counted
+    return tx_resample.bank_cfg(L, M, fcs, taps=h), 3, tx_resamp_cases.tile_inputs(L, M), counted
+
+
+@pytest.mark.parametrize("stage,L,M", ADD_CASES)
+def test_add_after_reconfiguration_sees_no_stale_band(stage, L, M):
+    """Host mode with ``add``: the band reaches the kernel through the stage's own device copy (StreamStage::d_add).
+    On a handle that has added onto a long band, was switched off (set_<stage>(None)) and configured afresh, nothing
+    of that band reaches the kernel with a shorter one: the stream in segments of 1, 0 and 3 samples and the rest
+    gives, bit for bit, what a handle that never saw the first band gives in one call.  (Whether the copy's memory is
+    reused cannot be seen from here.)  The stream begins at index 2, where at L < M the one-sample call completes no
+    output (the history rolls, nothing is launched or copied back), and spans two workgroup tiles and a ragged
+    tail."""
+    rng = np.random.default_rng(300 + 10 * ADD_CASES.index((stage, L, M)))
+    cfg, rows, tile, count = _add_case(stage, L, M, rng)
+    call = lambda e, what, *args, **kw: getattr(e, what % stage)(*args, **kw)
+    n1, n2 = 3 * tile + 101, 2 * tile + 37
+    shape = lambda n: (n,) if rows is None else (rows, n)
+    draw = lambda sh: (0.1 * (rng.standard_normal(sh) + 1j * rng.standard_normal(sh))).astype(np.complex64)
+    x1, x2 = draw(shape(n1)), draw(shape(n2))
+
+    fresh = engine.Engine(cfg=make_cfg())
+    try:
+        call(fresh, "set_%s", cfg)
+        call(fresh, "%s_reset", 2)
+        band2 = draw((count(fresh, n2),))
+        want = call(fresh, "%s", x2, add=band2).copy()
+    finally:
+        fresh.close()
+    assert len(want) == len(band2) > 2 * tile * L // M
+
+    eng = engine.Engine(cfg=make_cfg())
+    try:
+        call(eng, "set_%s", cfg)
+        band1 = draw((count(eng, n1),)) + np.complex64(8.0)              # a stale band would show
+        assert len(call(eng, "%s", x1, add=band1)) == len(band1) > len(band2)
+        call(eng, "set_%s", None)
+        call(eng, "set_%s", cfg)
+        call(eng, "%s_reset", 2)
+        parts, a, o, empty = [], 0, 0, 0
+        for n in (1, 0, 3, n2 - 4):
+            cnt = count(eng, n)
+            y = call(eng, "%s", x2[..., a:a + n], add=band2[o:o + cnt])
+            assert len(y) == cnt
+            empty += n > 0 and cnt == 0
+            parts.append(y.copy())
+            a, o = a + n, o + cnt
+        assert empty == (1 if L < M else 0)
+        got = np.concatenate(parts)
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
     finally:
         eng.close()
