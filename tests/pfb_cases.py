@@ -2,6 +2,8 @@
 include/ofdm_hip.h, restated in NumPy in its polyphase form), its derived error bound and the shapes the tests use."""
 import numpy as np
 
+import ddc_bank_cases
+
 EPS = 2.0 ** -24
 CHANNEL_COUNTS = (2, 4, 8, 16, 32, 64)
 # ntaps per M: from {1, M - 1, M, M + 1, 31, 155, 1024}, at most three, 1024 wherever Q or the branch count is largest
@@ -65,8 +67,7 @@ def bound(ntaps, M, s):
     return (Q + 1 + 8 * int(np.log2(M))) * EPS * np.asarray(s)
 
 
-def taps_for(rng, ntaps):
-    return (rng.standard_normal(ntaps) / np.sqrt(ntaps)).astype(np.float32)
+taps_for = ddc_bank_cases.taps_for
 
 
 def chunk_sizes(rng, n, M, ntaps):

@@ -1,10 +1,12 @@
 """Shared by test_resamp_bank_host.py and test_gpu_resamp_bank.py: the geometry of k_resamp_bank the tests pick their
 sizes around, and the grids of the bit-identity and segmentation tests."""
-import numpy as np
-
+import ddc_bank_cases
 import resamp_cases
 
 MAX_LINKS = 8
+# eight centre frequencies (the fixed ones of the single stage's tests, 0.0 and 0.5 among them, three random ones and one
+# duplicate), the K-link lists the grid picks from them, and the taps: the DDC bank's
+frequencies, pick, taps_for = ddc_bank_cases.frequencies, ddc_bank_cases.pick, ddc_bank_cases.taps_for
 
 
 def tile_inputs(L, M, K=1):
@@ -34,18 +36,6 @@ SEG_SHAPES = [(2, 5, 39, 2), (4, 3, 23, 4), (8, 25, 481, 3), (64, 63, 1024, 8), 
               (3, 2, 2, 7), (5, 7, 1, 6)]
 
 
-def frequencies(rng, fixed):
-    """Eight centre frequencies: the fixed ones of the resampler's tests (0.0 and 0.5 among them), three random ones,
-    and one duplicate."""
-    f = list(fixed) + [float(v) for v in rng.uniform(-0.5, 0.5, MAX_LINKS - 1 - len(fixed))]
-    return f + [f[2]]
-
-
-def pick(freqs, K):
-    """The K-link list the grid uses: K = 3 holds the duplicate pair, K = 1 a random frequency."""
-    return {1: [freqs[5]], 3: [freqs[2], freqs[4], freqs[7]], 8: list(freqs)}[K]
-
-
 def stream_length(L, M):
     """min(2 tile + tile / 3 + 5, 60000) inputs, moved up to the next length that is a multiple of neither M nor the
     tile."""
@@ -59,7 +49,3 @@ def stream_length(L, M):
 def far_start(M):
     """A stream origin near 10^6 that is no multiple of M."""
     return 1000003 if 1000003 % M else 1000004
-
-
-def taps_for(rng, ntaps):
-    return (rng.standard_normal(ntaps) / np.sqrt(ntaps)).astype(np.float32)

@@ -1,17 +1,14 @@
 """Host side of the DDC bank (ddc.bank_cfg, the ofdm_ddc_bank_* part of the C ABI, ofdm_demod_bank's argument checks):
 no GPU needed."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import ddc_bank_cases
-from ofdm_uhd_amd import _abi, ddc, ofdm, options
+import stage_harness as sh
+from ofdm_uhd_amd import _abi, ddc, ofdm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BANK_FUNCS = ("ofdm_set_ddc_bank", "ofdm_ddc_bank_reset", "ofdm_ddc_bank_count", "ofdm_ddc_bank", "ofdm_ddc_bank_taps",
               "ofdm_ddc_bank_last_ms")
 
@@ -36,35 +33,14 @@ def test_bank_cfg_builder():
 
 
 def test_bank_cfg_layout_matches_header(tmp_path):
-    st = _abi.ofdm_ddc_bank_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_ddc_bank_cfg));', 'printf("links %d\\n", OFDM_DDC_BANK_MAX_LINKS);']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_ddc_bank_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 16 + 8 * 8 + 4 * 1024
+    got = sh.check_cfg_layout_matches_header(tmp_path, _abi.ofdm_ddc_bank_cfg, 16 + 8 * 8 + 4 * 1024,
+                                             macros=[("links", "OFDM_DDC_BANK_MAX_LINKS")])
     assert int(got["links"]) == _abi.OFDM_DDC_BANK_MAX_LINKS == ddc.MAX_LINKS == ddc_bank_cases.MAX_LINKS == 8
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
 
 
 def test_header_declares_the_bank_and_the_library_exports_it():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in BANK_FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
-        assert hasattr(lib, name), name
-    # additions only: the version, the kernel table and the single DDC's struct are what they were
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and lib.ofdm_abi_version() == 6
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
+    sh.check_header_declares_and_library_exports(BANK_FUNCS)
+    # additions only: the single DDC's struct is what it was
     assert ctypes.sizeof(_abi.ofdm_ddc_cfg) == 24 + 4 * 1024
 
 
@@ -95,24 +71,11 @@ def test_tile_geometry_helper():
     assert len(ddc_bank_cases.pick(f, 3)) == 3 and ddc_bank_cases.pick(f, 3)[0] == ddc_bank_cases.pick(f, 3)[2]
 
 
-def _opt():
-    return options.default_options(modulation="qpsk")
-
-
 @pytest.mark.parametrize("kw", [
     dict(center_freqs=[]), dict(center_freqs=[0.0] * 9), dict(center_freqs=[0.1, 0.6]), dict(center_freqs=[0.1], decimation=0),
     dict(center_freqs=[0.1], decimation=65), dict(center_freqs=[0.1], taps=[]), dict(center_freqs=[0.1], iq_format="u8"),
     dict(center_freqs=[0.1], iq_scale=-1.0), dict(center_freqs=[0.1], callback=3), dict(center_freqs=[0.1, 0.2], options=3),
 ])
 def test_demod_bank_checks_its_arguments_before_any_engine_exists(kw, monkeypatch):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", no_engine)
-    args = dict(options=_opt(), center_freqs=[0.25], decimation=4)
-    args.update(kw)
-    if args["options"] == 3:
-        args["options"] = [_opt()] * 3            # three option sets for two links
-    with pytest.raises(ValueError):
-        ofdm.ofdm_demod_bank(args.pop("options"), args.pop("center_freqs"), args.pop("decimation"), **args)
+    sh.check_arguments_are_checked_before_any_engine_exists(
+        monkeypatch, ofdm.ofdm_demod_bank, ("options", "center_freqs", "decimation"), dict(center_freqs=[0.25], decimation=4), kw)

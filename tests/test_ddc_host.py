@@ -2,17 +2,15 @@
 tests use: no GPU needed.  The float64 model of the definition (ddc_cases.model) is applied to the two-link wideband
 captures and its output is fed to the CPU oracle: every sent packet must come back."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import ddc_cases
+import stage_harness as sh
 from ofdm_uhd_amd import _abi, ddc, firdes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DDC_FUNCS = ("ofdm_set_ddc", "ofdm_ddc_reset", "ofdm_ddc_count", "ofdm_ddc", "ofdm_ddc_taps", "ofdm_ddc_last_ms")
 
 
@@ -64,39 +62,15 @@ def test_phase_step_and_count_follow_the_definition():
 
 
 def test_header_declares_the_ddc_entry_points_and_python_mirrors_them():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    for name in DDC_FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
+    hdr, code = sh.check_header_declares_and_library_exports(DDC_FUNCS)
     assert re.search(r"#define\s+OFDM_DDC_MAX_TAPS\s+1024\b", code) and _abi.OFDM_DDC_MAX_TAPS == 1024
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code)
     # each entry point names what it replaces
     for word in ("set_decim", "set_center_freq", "freq_xlating_fir_filter_ccf"):
         assert word in hdr, word
-    lib = _abi.load()
-    for name in DDC_FUNCS:
-        assert hasattr(lib, name), name
-    # no kernel id was added for it: Engine.prof() and bench.py --full iterate over the same table as before
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
 
 
 def test_ddc_cfg_layout_matches_header(tmp_path):
-    st = _abi.ofdm_ddc_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_ddc_cfg));']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_ddc_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 24 + 4 * 1024
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
+    sh.check_cfg_layout_matches_header(tmp_path, _abi.ofdm_ddc_cfg, 24 + 4 * 1024)
 
 
 def test_ddc_cfg_builder():

@@ -1,31 +1,21 @@
 """Host side of the DUC bank (duc.bank_cfg, the float64 model and the float32 emulation of duc_bank_cases, the
 ofdm_duc_bank_* part of the C ABI, ofdm_mod_bank's argument checks): no GPU needed."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import duc_bank_cases as bc
 import duc_cases
-from ofdm_uhd_amd import _abi, ddc, duc, ofdm, options
+import stage_harness as sh
+from ofdm_uhd_amd import _abi, ddc, duc, ofdm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BANK_FUNCS = ("ofdm_set_duc_bank", "ofdm_duc_bank_reset", "ofdm_duc_bank", "ofdm_duc_bank_taps", "ofdm_duc_bank_last_ms")
 
 
 def test_header_declares_the_bank_and_the_library_exports_it():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in BANK_FUNCS:
-        assert name in declared and name in _abi.EXPORTS and hasattr(lib, name), name
-    # additions only: the version and the kernel table are what they were
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and lib.ofdm_abi_version() == 6
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
+    _, code = sh.check_header_declares_and_library_exports(BANK_FUNCS)
     assert re.search(r"#define\s+OFDM_DUC_BANK_MAX_LINKS\s+8\b", code) and _abi.OFDM_DUC_BANK_MAX_LINKS == 8 == bc.MAX_LINKS
 
 
@@ -34,19 +24,7 @@ def test_struct_layout_matches_the_header(tmp_path):
     st = _abi.ofdm_duc_bank_cfg
     assert [f for f, _ in st._fields_] == ["struct_size", "interpolation", "ntaps", "nlinks", "out_format", "out_scale",
                                           "center_freq", "taps"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_duc_bank_cfg));']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_duc_bank_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 24 + 8 * 8 + 4 * 1024
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
+    sh.check_cfg_layout_matches_header(tmp_path, st, 24 + 8 * 8 + 4 * 1024)
 
 
 def test_bank_cfg_builder_and_its_refusals():
@@ -166,53 +144,20 @@ def test_entry_points_refuse_a_null_handle_without_a_gpu():
     assert (n.value, k.value, ms.value) == (7, 7, 7.0)            # nothing was written
 
 
-def _opt():
-    return options.default_options(modulation="qpsk")
-
-
 @pytest.mark.parametrize("kw", [
     dict(center_freqs=[]), dict(center_freqs=[0.0] * 9), dict(center_freqs=[0.1, 0.6]), dict(center_freqs=[float("nan")]),
     dict(interpolation=0), dict(interpolation=65), dict(taps=[]), dict(taps=[float("nan")]), dict(iq_format="u8"),
     dict(iq_scale=-1.0), dict(options=3),
 ])
 def test_mod_bank_checks_its_arguments_before_any_engine_exists(kw, monkeypatch):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", no_engine)
-    args = dict(options=_opt(), center_freqs=[0.2, -0.1], interpolation=4)
-    args.update(kw)
-    if args["options"] == 3:
-        args["options"] = [_opt()] * 3                # three option sets for two links
-    with pytest.raises(ValueError):
-        ofdm.ofdm_mod_bank(args.pop("options"), args.pop("center_freqs"), args.pop("interpolation"), **args)
+    sh.check_arguments_are_checked_before_any_engine_exists(
+        monkeypatch, ofdm.ofdm_mod_bank, ("options", "center_freqs", "interpolation"),
+        dict(center_freqs=[0.2, -0.1], interpolation=4), kw)
 
 
 def test_mod_bank_drops_a_failing_batch_on_every_link():
-    """flush() modulates every link before the band moves; a link that fails takes the whole batch with it."""
-    class Link(object):
-        def __init__(self, fail):
-            self._pending, self.fail = [b"p"], fail
-
-        def flush(self):
-            self._pending = []
-            if self.fail:
-                raise RuntimeError("link failed")
-            return np.ones(4, np.complex64)
-
-    class Bank(object):
-        calls = 0
-
-        def duc_bank(self, x):
-            Bank.calls += 1
-    tx = ofdm.ofdm_mod_bank.__new__(ofdm.ofdm_mod_bank)
-    tx._links, tx._engine, tx._live = [Link(False), Link(True), Link(False)], Bank(), False
-    tx._engine.duc_bank_cfg = duc.bank_cfg(4, [0.0, 0.1, 0.2], taps=[1.0])
-    with pytest.raises(RuntimeError):
-        tx.flush()
-    assert Bank.calls == 0 and not tx._live and all(not m._pending for m in tx._links)
-    assert tx.flush() is None
+    sh.check_mod_links_drops_a_failing_batch_on_every_link(ofdm.ofdm_mod_bank, "duc_bank",
+                                                           duc.bank_cfg(4, [0.0, 0.1, 0.2], taps=[1.0]))
 
 
 def test_the_two_multi_link_modulators_share_one_flush():

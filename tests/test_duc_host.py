@@ -2,53 +2,28 @@
 model the GPU tests use: no GPU needed.  The model of the definition (duc_cases.model) builds the two-link wideband
 band, the model of the receive stage (ddc_cases.model) tunes to each link and the CPU oracle must recover every packet."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import ddc_cases
 import duc_cases
+import stage_harness as sh
 from ofdm_uhd_amd import _abi, ddc, duc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DUC_FUNCS = ("ofdm_set_duc", "ofdm_duc_reset", "ofdm_duc", "ofdm_duc_last_ms")
 
 
 def test_duc_cfg_layout_matches_header(tmp_path):
-    st = _abi.ofdm_duc_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_duc_cfg));']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_duc_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 32 + 4 * 1024
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
+    sh.check_cfg_layout_matches_header(tmp_path, _abi.ofdm_duc_cfg, 32 + 4 * 1024)
 
 
 def test_header_declares_the_duc_entry_points_and_python_mirrors_them():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    for name in DUC_FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
+    hdr, code = sh.check_header_declares_and_library_exports(DUC_FUNCS)
     assert re.search(r"#define\s+OFDM_DUC_MAX_TAPS\s+1024\b", code) and _abi.OFDM_DUC_MAX_TAPS == 1024
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code)
     for word in ("set_interp", "set_center_freq"):
         assert word in hdr, word
-    lib = _abi.load()
-    for name in DUC_FUNCS:
-        assert hasattr(lib, name), name
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
 
 
 @pytest.mark.parametrize("L", [1, 2, 3, 4, 8, 64])

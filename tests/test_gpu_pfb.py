@@ -9,28 +9,15 @@ import pytest
 import ddc_cases
 import duc_cases
 import pfb_cases as pc
+import stage_harness as sh
 from helpers import make_cfg, make_payloads
-from ofdm_uhd_amd import _abi, ddc, duc, engine, iqio, ofdm, options, pfb, resample, tx_resample
+from ofdm_uhd_amd import _abi, ddc, duc, engine, ofdm, pfb, resample, tx_resample
+from stage_harness import EPS, eng   # noqa: F401 (eng: one handle per file)
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = engine.Engine(cfg=make_cfg())
-    yield e
-    e.close()
-
-
-def _stream(rng, n, fmt):
-    """(samples in the receive format, the same samples converted to complex64)"""
-    if fmt == "sc16":
-        q = rng.integers(-32768, 32768, (n, 2)).astype(np.int16)
-        return q, iqio.from_sc16(q)
-    x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
-    return x, x
+STAGE = sh.STAGES["pfb"]
+_stream, _options, _engine_tx, _wide_sc16 = sh.rx_stream, sh.options_of, sh.engine_tx, sh.wide_sc16
 
 
 def _check_against_model(y, x, h, M, chans, first, what):
@@ -185,28 +172,6 @@ def test_against_the_ddc_bank_on_the_grid(eng, M, ntaps):
         eng.set_ddc_bank(None)
 
 
-def _options(k):
-    return options.default_options(modulation=k["mod"], fft_length=k["N"], occupied_tones=k["occ"], cp_length=k["CP"])
-
-
-def _engine_tx(e):
-    def tx(cfg, payloads, lead, tail):
-        e.set_channel(sigma=0.0, lead=lead, tail=tail)
-        try:
-            return e.tx(payloads)
-        finally:
-            e.set_channel(enable=False)
-    return tx
-
-
-def _wide_sc16(wide):
-    """The capture as 16-bit IQ with its peak at half scale; nothing may saturate."""
-    peak = float(max(np.max(np.abs(wide.real)), np.max(np.abs(wide.imag))))
-    q = iqio.to_sc16(wide * np.float32(0.5 / peak))
-    assert int(np.max(np.abs(q.astype(np.int32)))) < 32767, "a sample saturated"
-    return q
-
-
 @pytest.mark.parametrize("name,fmt", [("qpsk512_r4", "fc32"), ("qpsk512_r4", "sc16"), ("qam16_2048_r2", "fc32"),
                                       ("bpsk64_r8", "fc32")])
 def test_two_links_end_to_end(orc, name, fmt):
@@ -265,176 +230,49 @@ def test_two_links_end_to_end(orc, name, fmt):
     assert ch.engine()._h.value is None and all(d.engine()._h.value is None for d in ch.links())
 
 
-def _raw_pfb(lib, h, x, out, stride, cap, n=None):
-    nn = C.c_uint64(0)
-    rc = lib.ofdm_pfb(h, x.ctypes.data_as(C.c_void_p), len(x) if n is None else n, out.ctypes.data_as(C.c_void_p), stride, cap,
-                      C.byref(nn))
-    return rc, nn.value
-
-
 def test_layout_and_capacity(eng):
-    lib = _abi.load()
-    rng = np.random.default_rng(5)
-    raw, _ = _stream(rng, 5000, "fc32")
-    h = pfb.design(4, 0.4)
-    eng.set_pfb(pfb.pfb_cfg(4, [3, 0, 1], taps=h))
-    try:
-        want = eng.pfb(raw).copy()
-        no = want.shape[1]
-        # chan_stride > nout: the gaps keep what they held
-        eng.pfb_reset(0)
-        sentinel = np.complex64(-7.5 + 3.25j)
-        out = np.full((3, no + 13), sentinel, np.complex64)
-        assert _raw_pfb(lib, eng._h, raw, out, no + 13, no) == (_abi.OFDM_OK, no)
-        assert np.array_equal(out[:, :no], want) and np.all(out[:, no:] == sentinel)
-        # out_cap one short: refused with *nout set, and the stream does not move
-        eng.pfb_reset(0)
-        first = eng.pfb(raw[:1001]).copy()
-        need = eng.pfb_count(3999)
-        out = np.full((3, need), sentinel, np.complex64)
-        rest_in = np.ascontiguousarray(raw[1001:])
-        assert _raw_pfb(lib, eng._h, rest_in, out, need, need - 1) == (_abi.OFDM_E_CAPACITY, need)
-        assert np.all(out == sentinel) and eng.pfb_count(3999) == need
-        # chan_stride < nout with more than one channel
-        assert _raw_pfb(lib, eng._h, rest_in, out, need - 1, need) == (_abi.OFDM_E_INVAL, need)
-        assert eng.pfb_count(3999) == need
-        rest = eng.pfb(rest_in)
-        assert np.array_equal(np.concatenate([first, rest], axis=1), want)     # the stream continues bit for bit
-        # one channel: the stride does not matter
-        eng.set_pfb(pfb.pfb_cfg(4, [0], taps=h))
-        out = np.zeros(no, np.complex64)
-        assert _raw_pfb(lib, eng._h, raw, out, 0, no) == (_abi.OFDM_OK, no)
-        assert np.array_equal(out, want[1])
-    finally:
-        eng.set_pfb(None)
-
-
-def _raw_cfg(**kw):
-    c = pfb.pfb_cfg(4, [1, 3], taps=np.ones(5, np.float32))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+    sh.check_rx_layout_and_capacity(eng, STAGE, (4,), [3, 0, 1], pfb.design(4, 0.4), one_sel=[0])
 
 
 def test_invalid_arguments_are_refused(eng):
-    lib = _abi.load()
-    eng.set_pfb(None)
     x = np.zeros(64, np.complex64)
     x[::3] = 1.0
-    out = np.zeros((2, 64), np.complex64)
-    assert _raw_pfb(lib, eng._h, x, out, 64, 64)[0] == _abi.OFDM_E_INVAL            # no configuration
-    for call in (lambda: eng.pfb(x), lambda: eng.pfb_reset(0), lambda: eng.pfb_count(4), lambda: eng.pfb_last_ms()):
-        with pytest.raises(ValueError):
-            call()
-    good = _raw_cfg()
-    eng.set_pfb(good)
-    assert _raw_pfb(lib, eng._h, x, out, 64, 64) == (_abi.OFDM_OK, 16)
-    y = out[:, :16].copy()
-    bad_chan = _raw_cfg()
-    bad_chan.channel[1] = 4
-    bad_tap = []
-    for v in (float("nan"), float("inf")):
-        c = _raw_cfg()
-        c.taps[3] = v
-        bad_tap.append(c)
-    refused = [_raw_cfg(**b) for b in (dict(struct_size=12), dict(nchannels=0), dict(nchannels=1), dict(nchannels=3),
-                                       dict(nchannels=128), dict(ntaps=0), dict(ntaps=1025), dict(nsel=0), dict(nsel=5))]
-    refused += [bad_chan] + bad_tap
-    for c in refused:
-        with pytest.raises(ValueError):
-            eng.set_pfb(c)
-        assert eng.pfb_cfg is good
-    # the same through the raw ABI, and a channel beyond nsel is not looked at
-    for c in refused:
-        assert lib.ofdm_set_pfb(eng._h, C.byref(c)) == _abi.OFDM_E_INVAL
-    c = _raw_cfg()
-    c.channel[2] = 200
-    eng.set_pfb(c)
-    eng.set_pfb(good)
-    # ... a refused configuration leaves the one in force untouched: same stream position, same outputs
-    eng.pfb(x[:62])
-    with pytest.raises(ValueError):
-        eng.set_pfb(refused[3])
-    assert eng.pfb_count(2) == 0 and eng.pfb_count(3) == 1                           # still 62 samples into the stream
-    eng.pfb_reset(0)
-    assert np.array_equal(eng.pfb(x), y)
-    # index limits: the DDC bank's
-    eng.pfb_reset(1 << 62)
-    assert eng.pfb_count(8) == 2
-    with pytest.raises(ValueError):
-        eng.pfb_reset((1 << 62) + 1)
-    assert eng.pfb_count(8) == 2                          # the refused reset left the stream where it was
-    nn = C.c_uint64(0)
-    assert lib.ofdm_pfb(eng._h, x.ctypes.data_as(C.c_void_p), (1 << 62) + 1, out.ctypes.data_as(C.c_void_p), 64, 64,
-                        C.byref(nn)) == _abi.OFDM_E_INVAL
-    eng.pfb_reset(0)
-    # misaligned buffers: complex64 in and out on 8 bytes, 16-bit in on 4
-    f = np.zeros(2 * 64 + 2, np.float32)
-    assert lib.ofdm_pfb(eng._h, C.c_void_p(f.ctypes.data + 4), 64, out.ctypes.data_as(C.c_void_p), 64, 64,
-                        C.byref(nn)) == _abi.OFDM_E_INVAL
-    assert lib.ofdm_pfb(eng._h, x.ctypes.data_as(C.c_void_p), 64, C.c_void_p(f.ctypes.data + 4), 16, 16,
-                        C.byref(nn)) == _abi.OFDM_E_INVAL
-    eng.set_rx_iq_format("sc16")
-    try:
-        q = np.zeros(2 * 64 + 2, np.int16)
-        rc = lib.ofdm_pfb(eng._h, C.c_void_p(q.ctypes.data + 2), 64, out.ctypes.data_as(C.c_void_p), 64, 64, C.byref(nn))
-        assert rc == _abi.OFDM_E_INVAL
-        assert eng.pfb_count(64) == 16                    # ... and the stream did not move
-    finally:
-        eng.set_rx_iq_format("fc32")
-        eng.set_pfb(None)
-    assert _raw_pfb(lib, eng._h, x, out, 64, 64)[0] == _abi.OFDM_E_INVAL            # ... and after it was dropped
 
-
-def _release(torch, *tensors):
-    """Hand the test's device buffers back zeroed and drop torch's cache: a later test's torch.empty() must not inherit
-    this file's bytes."""
-    for t in tensors:
-        t.zero_()
-    torch.cuda.synchronize()
-    del tensors
-    torch.cuda.empty_cache()
+    def index_limits_and_misaligned_buffers(lib, x, out):
+        # index limits: the DDC bank's
+        eng.pfb_reset(1 << 62)
+        assert eng.pfb_count(8) == 2
+        with pytest.raises(ValueError):
+            eng.pfb_reset((1 << 62) + 1)
+        assert eng.pfb_count(8) == 2                          # the refused reset left the stream where it was
+        nn = C.c_uint64(0)
+        assert lib.ofdm_pfb(eng._h, x.ctypes.data_as(C.c_void_p), (1 << 62) + 1, out.ctypes.data_as(C.c_void_p), 64, 64,
+                            C.byref(nn)) == _abi.OFDM_E_INVAL
+        eng.pfb_reset(0)
+        # misaligned buffers: complex64 in and out on 8 bytes (16-bit in on 4: the harness)
+        f = np.zeros(2 * 64 + 2, np.float32)
+        assert lib.ofdm_pfb(eng._h, C.c_void_p(f.ctypes.data + 4), 64, out.ctypes.data_as(C.c_void_p), 64, 64,
+                            C.byref(nn)) == _abi.OFDM_E_INVAL
+        assert lib.ofdm_pfb(eng._h, x.ctypes.data_as(C.c_void_p), 64, C.c_void_p(f.ctypes.data + 4), 16, 16,
+                            C.byref(nn)) == _abi.OFDM_E_INVAL
+    base = lambda: pfb.pfb_cfg(4, [1, 3], taps=np.ones(5, np.float32))
+    sh.check_rx_bank_invalid_arguments(eng, STAGE, (4,), base, x, nout=16, after62=(0, 1), still_refused=3, edge_sel=None,
+                                       middle=index_limits_and_misaligned_buffers)
 
 
 @pytest.mark.parametrize("fmt", ["fc32", "sc16"])
 def test_device_pointers(fmt):
     import torch
-    dev = torch.device("cuda", 0)
     M, sel = 8, [5, 0, 7, 2, 5]
-    K = len(sel)
     rng = np.random.default_rng(31)
     n = 3 * pc.tile_outputs(M) * M + 77
     raw, _ = _stream(rng, n, fmt)
-    taps = pfb.design(M, 0.75)
     host = engine.Engine(cfg=make_cfg())
     devE = engine.Engine(cfg=make_cfg(device_ptrs=True))
     try:
-        for e in (host, devE):
-            e.set_rx_iq_format(fmt)
-            e.set_pfb(pfb.pfb_cfg(M, sel, taps=taps))
-            e.prof_enable(True)
-        with pytest.raises(ValueError):
-            devE.pfb_last_ms()                            # no profiled call yet
-        want = host.pfb(raw)
-        no = want.shape[1]
-        stride = no + 3
-        x = torch.from_numpy(np.ascontiguousarray(raw)).to(dev)
-        y = torch.full((K, stride), -2.0 + 1.0j, dtype=torch.complex64, device=dev)
-        got = devE.pfb_device(x.data_ptr(), n, y.data_ptr(), stride, no)
-        torch.cuda.synchronize()
-        assert got == no
-        out = y.cpu().numpy()
-        assert np.array_equal(out[:, :no], want) and np.all(out[:, no:] == np.complex64(-2.0 + 1.0j))
-        assert devE.pfb_last_ms() > 0.0 and host.pfb_last_ms() > 0.0
-        # two halves through device pointers continue the stream
-        devE.pfb_reset(0)
-        h1 = n // 2 + 1
-        n1 = devE.pfb_device(x.data_ptr(), h1, y.data_ptr(), stride, stride)
-        off = h1 * (4 if fmt == "sc16" else 8)            # bytes per wideband sample
-        n2 = devE.pfb_device(x.data_ptr() + off, n - h1, y.data_ptr() + 8 * n1, stride, stride - n1)
-        torch.cuda.synchronize()
-        assert n1 + n2 == no and np.array_equal(y.cpu().numpy()[:, :no], want)
-        _release(torch, x, y)
+        x, y = sh.check_rx_device_pointers(torch, STAGE, host, devE, pfb.pfb_cfg(M, sel, taps=pfb.design(M, 0.75)), raw,
+                                           len(sel), fmt)[:2]
+        sh.release(torch, x, y)
     finally:
         host.close()
         devE.close()
@@ -471,7 +309,7 @@ def test_device_pointer_path_behind_an_asynchronous_transmit():
         assert dev.pfb_device(d_wide.data_ptr(), nsamp * M, d_out.data_ptr(), no, no) == no
         assert np.array_equal(d_wide.cpu().numpy(), wide)
         assert np.array_equal(d_out.cpu().numpy(), want)
-        _release(torch, d_pay, d_iq, d_wide, d_out)
+        sh.release(torch, d_pay, d_iq, d_wide, d_out)
     finally:
         host.close()
         dev.close()
@@ -497,23 +335,7 @@ def test_the_other_stages_and_the_channeliser_do_not_disturb_each_other(eng):
     off = dict(pfb=eng.set_pfb, ddc=eng.set_ddc, ddc_bank=eng.set_ddc_bank, resamp=eng.set_resamp, duc=eng.set_duc,
                tx_resamp=eng.set_tx_resamp)
     try:
-        alone = {}
-        for name, (cfg, run, total, _) in stages.items():
-            cfg()
-            alone[name] = run(0, total).copy()
-            off[name](None)
-        # all six configured, their calls interleaved, each with its own chunking
-        for cfg, _, _, _ in stages.values():
-            cfg()
-        parts = {name: [] for name in stages}
-        pos = {name: 0 for name in stages}
-        while any(pos[name] < stages[name][2] for name in stages):
-            for name, (_, run, total, step) in stages.items():
-                if pos[name] < total:
-                    parts[name].append(run(pos[name], min(pos[name] + step, total)).copy())
-                    pos[name] += step
-        for name in stages:
-            assert np.array_equal(np.concatenate(parts[name], axis=1), alone[name]), name
+        alone = sh.check_interleaved(stages, off)
         # dropping or resetting another stage leaves the channeliser's stream where it was, and the other way round
         eng.pfb(raw[:100])
         eng.ddc_bank_reset(0)

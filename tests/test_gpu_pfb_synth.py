@@ -2,7 +2,6 @@
 model of its definition within the derived bound, exact where it must be (channel 0 alone is the DUC at fc = 0),
 independent of the order of the selection and of the segmentation, against K DUC passes, end to end into the
 channeliser, at its edges, and beside the other stages."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -12,36 +11,15 @@ import ddc_cases
 import duc_cases
 import pfb_cases as pc
 import pfb_synth_cases as sc
+import stage_harness as sh
 from helpers import make_cfg, make_payloads
-from ofdm_uhd_amd import _abi, duc, engine, iqio, ofdm, options, pfb
+from ofdm_uhd_amd import _abi, duc, engine, iqio, ofdm, pfb
+from stage_harness import SCALE, START, eng   # noqa: F401 (eng: one handle per file)
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24
-SCALE = 32768.0
-AMP = 1.0 / 16.0           # keeps every band of these tests inside the 16-bit range (asserted where it matters)
-START = 1000003            # a first input index that is a multiple of no tile
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = engine.Engine(cfg=make_cfg())
-    yield e
-    e.close()
-
-
-def _rows(rng, K, n, amp=AMP):
-    return (amp * (rng.standard_normal((K, n)) + 1j * rng.standard_normal((K, n)))).astype(np.complex64)
-
-
-def _bits(a):
-    """The stored bits: -0 and +0 differ (int16 samples compare as they are)."""
-    return a.view(np.uint32) if a.dtype == np.complex64 else a
-
-
-def _c64(out, fmt):
-    """The stage's output as complex128 samples."""
-    return (iqio.from_sc16(out) if fmt == "sc16" else out).astype(np.complex128)
+STAGE = sh.STAGES["pfb_synth"]
+_rows, _bits, _c64, _options = sh.rows, sh.bits, sh.c64, sh.options_of
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,22 +85,7 @@ def test_against_float64_model(eng, M, fmt, with_add):
 @pytest.mark.parametrize("fmt", ["fc32", "sc16"])
 @pytest.mark.parametrize("M,ntaps", [(2, 1024), (4, 31), (8, 155), (16, 17), (32, 31), (64, 65)])
 def test_channel_zero_alone_is_the_duc_at_zero_frequency(eng, M, ntaps, fmt):
-    rng = np.random.default_rng(100 * M + ntaps)
-    x = _rows(rng, 1, sc.stream_inputs(M))
-    h = sc.taps_for(rng, ntaps)
-    try:
-        eng.set_pfb_synth(pfb.synth_cfg(M, [0], taps=h, out_format=fmt))
-        eng.set_duc(duc.duc_cfg(M, 0.0, taps=h, out_format=fmt))
-        for first in (0, START):
-            eng.pfb_synth_reset(first)
-            eng.duc_reset(first)
-            a, b = eng.pfb_synth(x), eng.duc(x[0])
-            assert a.shape == b.shape and a.dtype == b.dtype
-            assert np.array_equal(a, b), (M, ntaps, fmt, first)          # as numbers: the sign of a zero may differ
-        assert np.any(a != 0)
-    finally:
-        eng.set_pfb_synth(None)
-        eng.set_duc(None)
+    sh.check_one_row_at_zero_frequency_is_the_single_stage(eng, STAGE, (M,), ntaps, fmt, seed=100 * M + ntaps, sel=[0])
 
 
 @pytest.mark.parametrize("M,ntaps", [(8, 155), (32, 31), (64, 65)])
@@ -157,34 +120,8 @@ SEG_SHAPES = [(M, t) for M in (2, 8, 64) for t in (min(sc.TAP_GRID[M]), max(sc.T
 @pytest.mark.parametrize("fmt", ["fc32", "sc16"])
 @pytest.mark.parametrize("M,ntaps", SEG_SHAPES)
 def test_any_segmentation_gives_the_same_bits(eng, M, ntaps, fmt):
-    rng = np.random.default_rng(53 * M + ntaps)
-    T, Q = sc.tile_inputs(M), sc.history(ntaps, M)
-    nin = 3 * T + 100 + 3 * Q
-    sel = [M - 1, 0, M // 2][:min(M, 3)]
-    K = len(sel)
-    x = _rows(rng, K, nin)
-    h = sc.taps_for(rng, ntaps)
-    band = _rows(rng, 1, nin * M)[0]
-    try:
-        eng.set_pfb_synth(pfb.synth_cfg(M, sel, taps=h, out_format=fmt))
-        for first, add in ((0, None), (7 * 1024 + 5, band)):
-            eng.pfb_synth_reset(first)
-            whole = eng.pfb_synth(x, add=add).copy()
-            assert len(whole) == nin * M
-            eng.pfb_synth_reset(first)
-            sizes = sc.chunk_inputs(rng, nin, M, ntaps)
-            assert sum(sizes) == nin and {0, 1, Q + 1, T - 1, T + 1} <= set(sizes)
-            assert (Q in sizes or Q == 0) and (Q - 1 in sizes or Q <= 1)
-            parts, a = [], 0
-            for n in sizes:
-                y = eng.pfb_synth(x[:, a:a + n], add=None if add is None else add[a * M:(a + n) * M])
-                assert len(y) == n * M
-                parts.append(y.copy())
-                a += n
-            got = np.concatenate(parts)
-            assert got.dtype == whole.dtype and np.array_equal(_bits(got), _bits(whole)), (M, ntaps, first, fmt)
-    finally:
-        eng.set_pfb_synth(None)
+    sh.check_tx_bank_segmentation(eng, STAGE, (M,), ntaps, [M - 1, 0, M // 2][:min(M, 3)], fmt, seed=53 * M + ntaps,
+                                  far=7 * 1024 + 5)
 
 
 @pytest.mark.parametrize("M,ntaps", [(4, 31), (8, 155), (64, 155)])
@@ -213,14 +150,6 @@ def test_against_k_duc_passes_on_the_grid(eng, M, ntaps):
     finally:
         eng.set_pfb_synth(None)
         eng.set_duc(None)
-
-
-def _zero(torch, *tensors):
-    """Zero the test's device buffers before they are released: a later test's torch.empty() must not inherit this
-    file's bytes."""
-    for t in tensors:
-        t.zero_()
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("M,ntaps", [(4, 31), (32, 155)])
@@ -252,48 +181,7 @@ def test_add_is_one_float32_addition_per_part(eng, M, ntaps):
 
 def test_in_device_mode_add_may_be_the_output_buffer():
     import torch
-    M, sel, ntaps = 8, [5, 0, 7], 155
-    rng = np.random.default_rng(31)
-    nin = 2 * sc.tile_inputs(M) + 77
-    stride = nin + 5
-    x = np.zeros((3, stride), np.complex64)
-    x[:, :nin] = _rows(rng, 3, nin)
-    band = _rows(rng, 1, nin * M)[0]
-    h = sc.taps_for(rng, ntaps)
-    host = engine.Engine(cfg=make_cfg())
-    dev = engine.Engine(cfg=make_cfg(device_ptrs=True))
-    try:
-        for e in (host, dev):
-            e.set_pfb_synth(pfb.synth_cfg(M, sel, taps=h))
-            e.prof_enable(True)
-        with pytest.raises(ValueError):
-            dev.pfb_synth_last_ms()                       # no profiled call yet
-        want = host.pfb_synth(x[:, :nin], add=band)
-        d_x = torch.from_numpy(x).cuda()
-        d_out = torch.from_numpy(band.copy()).cuda()
-        torch.cuda.synchronize()
-        assert dev.pfb_synth_device(d_x.data_ptr(), stride, nin, d_out.data_ptr(), nin * M, add_ptr=d_out.data_ptr()) == nin * M
-        assert np.array_equal(d_out.cpu().numpy(), want)
-        assert dev.pfb_synth_last_ms() > 0.0 and host.pfb_synth_last_ms() > 0.0
-        # two halves through device pointers continue the stream
-        dev.pfb_synth_reset(0)
-        d_out.copy_(torch.from_numpy(band))
-        torch.cuda.synchronize()
-        n1 = nin // 2 + 1
-        a = dev.pfb_synth_device(d_x.data_ptr(), stride, n1, d_out.data_ptr(), nin * M, add_ptr=d_out.data_ptr())
-        b = dev.pfb_synth_device(d_x.data_ptr() + 8 * n1, stride, nin - n1, d_out.data_ptr() + 8 * a, nin * M - a,
-                                 add_ptr=d_out.data_ptr() + 8 * a)
-        assert a + b == nin * M and np.array_equal(d_out.cpu().numpy(), want)
-        _zero(torch, d_x, d_out)
-        del d_x, d_out
-        torch.cuda.empty_cache()
-    finally:
-        host.close()
-        dev.close()
-
-
-def _options(k):
-    return options.default_options(modulation=k["mod"], fft_length=k["N"], occupied_tones=k["occ"], cp_length=k["CP"])
+    sh.check_in_device_mode_add_may_be_the_output_buffer(torch, STAGE, (8,), [5, 0, 7], ntaps=155, nin=2 * sc.tile_inputs(8) + 77)
 
 
 ROUND_TRIPS = [(name, M, chans, "fc32") for name, (M, chans) in sorted(pc.ON_GRID.items())] + [("bpsk64_r8", 8, (1, 6, 3), "sc16")]
@@ -388,149 +276,13 @@ def test_round_trip_into_the_channeliser(name, M, chans, fmt):
         rx.close()
 
 
-def _raw(lib, h, x, stride, nin, out, cap, add=None):
-    nn = C.c_uint64(0)
-    rc = lib.ofdm_pfb_synth(h, x.ctypes.data_as(C.c_void_p), stride, nin, None if add is None else add.ctypes.data_as(C.c_void_p),
-                            out.ctypes.data_as(C.c_void_p), cap, C.byref(nn))
-    return rc, nn.value
-
-
 def test_layout_and_capacity(eng):
-    lib = _abi.load()
-    rng = np.random.default_rng(5)
-    M, sel, nin = 4, [3, 0, 1], 1500
-    x = _rows(rng, 3, nin)
-    h = pfb.synth_design(M, 0.4)
-    Q = (len(h) - 1) // M
-    eng.set_pfb_synth(pfb.synth_cfg(M, sel, taps=h))
-    try:
-        want = eng.pfb_synth(x).copy()
-        # chan_stride > nin: the gaps are not read
-        eng.pfb_synth_reset(0)
-        wide = np.full((3, nin + 13), np.complex64(np.nan), np.complex64)
-        wide[:, :nin] = x
-        out = np.zeros(nin * M, np.complex64)
-        assert _raw(lib, eng._h, wide, nin + 13, nin, out, nin * M) == (_abi.OFDM_OK, nin * M)
-        assert np.array_equal(out, want)
-        # out_cap one short: refused with *nout set, and the stream does not move
-        eng.pfb_synth_reset(0)
-        n1 = 401
-        first = eng.pfb_synth(x[:, :n1]).copy()
-        rest_in = np.ascontiguousarray(x[:, n1:])
-        n2 = nin - n1
-        sentinel = np.complex64(-7.5 + 3.25j)
-        out = np.full(n2 * M, sentinel, np.complex64)
-        assert _raw(lib, eng._h, rest_in, n2, n2, out, n2 * M - 1) == (_abi.OFDM_E_CAPACITY, n2 * M)
-        assert np.all(out == sentinel)
-        # chan_stride < nin with more than one channel
-        assert _raw(lib, eng._h, rest_in, n2 - 1, n2, out, n2 * M)[0] == _abi.OFDM_E_INVAL
-        assert np.all(out == sentinel)
-        rest = eng.pfb_synth(rest_in)
-        assert np.array_equal(np.concatenate([first, rest]), want)        # the stream continues bit for bit
-        # calls of 0 and calls shorter than Q are part of the stream
-        eng.pfb_synth_reset(0)
-        assert Q >= 2
-        parts = [eng.pfb_synth(x[:, a:b]).copy() for a, b in ((0, 0), (0, 1), (1, Q), (Q, Q), (Q, nin))]
-        assert [len(p) for p in parts[:4]] == [0, M, (Q - 1) * M, 0] and np.array_equal(np.concatenate(parts), want)
-        # one channel: the stride does not matter
-        eng.set_pfb_synth(pfb.synth_cfg(M, [0], taps=h))
-        one = eng.pfb_synth(x[1]).copy()
-        eng.pfb_synth_reset(0)
-        out = np.zeros(nin * M, np.complex64)
-        assert _raw(lib, eng._h, np.ascontiguousarray(x[1]), 0, nin, out, nin * M) == (_abi.OFDM_OK, nin * M)
-        assert np.array_equal(out, one)
-    finally:
-        eng.set_pfb_synth(None)
-
-
-def _raw_cfg(**kw):
-    c = pfb.synth_cfg(4, [1, 3], taps=np.ones(5, np.float32))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+    sh.check_tx_bank_layout_and_capacity(eng, STAGE, (4,), [3, 0, 1], pfb.synth_design(4, 0.4), nin=1500, one_sel=[0])
 
 
 def test_invalid_arguments_are_refused(eng):
-    lib = _abi.load()
-    eng.set_pfb_synth(None)
-    x = np.zeros((2, 16), np.complex64)
-    x[:, ::3] = 1.0
-    out = np.zeros(64, np.complex64)
-    assert _raw(lib, eng._h, x, 16, 16, out, 64)[0] == _abi.OFDM_E_INVAL            # no configuration
-    for call in (lambda: eng.pfb_synth(x), lambda: eng.pfb_synth_reset(0), lambda: eng.pfb_synth_last_ms()):
-        with pytest.raises(ValueError):
-            call()
-    good = _raw_cfg()
-    eng.set_pfb_synth(good)
-    assert _raw(lib, eng._h, x, 16, 16, out, 64) == (_abi.OFDM_OK, 64)
-    y = out.copy()
-    bad_chan, twice = _raw_cfg(), _raw_cfg()
-    bad_chan.channel[1] = 4
-    twice.channel[1] = 1
-    bad_tap = []
-    for v in (float("nan"), float("inf")):
-        c = _raw_cfg()
-        c.taps[3] = v
-        bad_tap.append(c)
-    refused = [_raw_cfg(**b) for b in (dict(struct_size=12), dict(nchannels=0), dict(nchannels=1), dict(nchannels=3),
-                                       dict(nchannels=128), dict(ntaps=0), dict(ntaps=1025), dict(nsel=0), dict(nsel=5),
-                                       dict(out_format=2), dict(out_format=1, out_scale=-1.0),
-                                       dict(out_format=1, out_scale=float("inf")))]
-    refused += [bad_chan, twice] + bad_tap
-    for c in refused:
-        with pytest.raises(ValueError) as info:
-            eng.set_pfb_synth(c)
-        assert str(info.value)                            # each refusal has its message
-        assert eng.pfb_synth_cfg is good
-    for c in refused:
-        assert lib.ofdm_set_pfb_synth(eng._h, C.byref(c)) == _abi.OFDM_E_INVAL
-    c = _raw_cfg()
-    c.channel[2] = 200                                    # a channel beyond nsel is not looked at
-    eng.set_pfb_synth(c)
-    eng.set_pfb_synth(good)
-    # a refused configuration leaves the one in force untouched: same stream position, same outputs
-    a = eng.pfb_synth(x[:, :7]).copy()
-    with pytest.raises(ValueError):
-        eng.set_pfb_synth(twice)
-    b = eng.pfb_synth(x[:, 7:])
-    assert np.array_equal(np.concatenate([a, b]), y)
-    # index limits: the DUC's, no output index past 2^63
-    lim = (1 << 63) // 4
-    eng.pfb_synth_reset(lim)
-    with pytest.raises(ValueError):
-        eng.pfb_synth_reset(lim + 1)
-    assert _raw(lib, eng._h, x, 16, 1, out, 64)[0] == _abi.OFDM_E_INVAL              # one input more would pass it
-    assert _raw(lib, eng._h, x, 16, 0, out, 64) == (_abi.OFDM_OK, 0)
-    eng.pfb_synth_reset(lim - 16)
-    assert _raw(lib, eng._h, x, 16, 16, out, 64) == (_abi.OFDM_OK, 64) and np.array_equal(out, y)
-    eng.pfb_synth_reset(0)
-    assert _raw(lib, eng._h, x, 1 << 62, 1 << 62, out, 64)[0] == _abi.OFDM_E_INVAL
-    # a call too long for one grid (more than 2^31 - 1 tiles of 4096 / M input indices): refused before anything is
-    # read or written, the stream stays where it was
-    long_n = (1 << 31) * sc.tile_inputs(4) + 1
-    assert _raw(lib, eng._h, x, long_n, long_n, out, 1 << 62) == (_abi.OFDM_E_INVAL, long_n * 4)
-    assert b"too long" in lib.ofdm_last_error(eng._h)
-    assert _raw(lib, eng._h, x, 16, 16, out, 64) == (_abi.OFDM_OK, 64) and np.array_equal(out, y)
-    eng.pfb_synth_reset(0)
-    # misaligned buffers: complex64 in, add and out on 8 bytes, 16-bit out on 4
-    f = np.zeros(2 * 64 + 2, np.float32)
-    nn = C.c_uint64(0)
-    xp, op, odd = x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.c_void_p(f.ctypes.data + 4)
-    assert lib.ofdm_pfb_synth(eng._h, odd, 0, 16, None, op, 64, C.byref(nn)) == _abi.OFDM_E_INVAL
-    assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, odd, op, 64, C.byref(nn)) == _abi.OFDM_E_INVAL
-    assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, None, odd, 64, C.byref(nn)) == _abi.OFDM_E_INVAL
-    assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, None, None, 64, C.byref(nn)) == _abi.OFDM_E_INVAL       # null iq_out
-    assert lib.ofdm_pfb_synth(eng._h, None, 16, 16, None, op, 64, C.byref(nn)) == _abi.OFDM_E_INVAL       # null iq_in
-    assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, None, op, 64, None) == _abi.OFDM_E_INVAL
-    eng.set_pfb_synth(_raw_cfg(out_format=1))
-    try:
-        q = np.zeros(2 * 64 + 2, np.int16)
-        assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, None, C.c_void_p(q.ctypes.data + 2), 64, C.byref(nn)) == _abi.OFDM_E_INVAL
-        assert lib.ofdm_pfb_synth(eng._h, xp, 16, 16, None, C.c_void_p(q.ctypes.data + 4), 64, C.byref(nn)) == _abi.OFDM_OK
-        assert np.array_equal(q[2:130].reshape(-1, 2), iqio.to_sc16(y))               # ... and the stream had not moved
-    finally:
-        eng.set_pfb_synth(None)
-    assert _raw(lib, eng._h, x, 16, 16, out, 64)[0] == _abi.OFDM_E_INVAL            # ... and after it was dropped
+    base = lambda: pfb.synth_cfg(4, [1, 3], taps=np.ones(5, np.float32))
+    sh.check_tx_bank_invalid_arguments(eng, STAGE, (4,), base, nout=64, still_refused=1, edge_sel=None)
 
 
 def test_device_pointer_path_behind_an_asynchronous_transmit():
@@ -564,7 +316,7 @@ def test_device_pointer_path_behind_an_asynchronous_transmit():
         assert dev.pfb_device(d_wide.data_ptr(), nsamp * M, d_out.data_ptr(), nsamp, nsamp) == nsamp
         assert np.array_equal(d_wide.cpu().numpy(), wide)
         assert np.array_equal(d_out.cpu().numpy(), want)
-        _zero(torch, d_pay, d_iq, d_wide, d_out)
+        sh.zero(torch, d_pay, d_iq, d_wide, d_out)
         del d_pay, d_iq, d_wide, d_out
         torch.cuda.empty_cache()
     finally:
@@ -586,22 +338,7 @@ def test_the_channeliser_the_duc_and_the_bank_do_not_disturb_each_other(eng):
     }
     off = dict(pfb=eng.set_pfb, duc=eng.set_duc, pfb_synth=eng.set_pfb_synth)
     try:
-        alone = {}
-        for name, (cfg, run, total, _) in stages.items():
-            cfg()
-            alone[name] = run(0, total).copy()
-            off[name](None)
-        for cfg, _, _, _ in stages.values():
-            cfg()
-        parts = {name: [] for name in stages}
-        pos = {name: 0 for name in stages}
-        while any(pos[name] < stages[name][2] for name in stages):
-            for name, (_, run, total, step) in stages.items():
-                if pos[name] < total:
-                    parts[name].append(run(pos[name], min(pos[name] + step, total)).copy())
-                    pos[name] += step
-        for name in stages:
-            assert np.array_equal(np.concatenate(parts[name], axis=1), alone[name]), name
+        alone = sh.check_interleaved(stages, off)
         # dropping or resetting another stage leaves the bank's stream where it was, and the other way round
         eng.pfb_synth_reset(0)
         a = eng.pfb_synth(nb[:, :500]).copy()

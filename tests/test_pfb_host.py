@@ -1,7 +1,6 @@
 """Host side of the polyphase-FFT channeliser (pfb.design, pfb.pfb_cfg, the float64 model of pfb_cases, the ofdm_pfb_*
 part of the C ABI): no GPU needed."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -9,9 +8,9 @@ import pytest
 
 import ddc_cases
 import pfb_cases
-from ofdm_uhd_amd import _abi, ddc, ofdm, options, pfb
+import stage_harness as sh
+from ofdm_uhd_amd import _abi, ddc, ofdm, pfb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PFB_FUNCS = ("ofdm_set_pfb", "ofdm_pfb_reset", "ofdm_pfb_count", "ofdm_pfb", "ofdm_pfb_last_ms")
 
 
@@ -78,17 +77,9 @@ def test_on_grid_captures_decode_through_the_float64_model(orc, name):
 
 
 def test_header_declares_the_channeliser_and_the_library_exports_it():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in PFB_FUNCS:
-        assert name in declared and name in _abi.EXPORTS and hasattr(lib, name), name
+    _, code = sh.check_header_declares_and_library_exports(PFB_FUNCS)
     assert re.search(r"#define\s+OFDM_PFB_MAX_CHANNELS\s+64\b", code) and _abi.OFDM_PFB_MAX_CHANNELS == pfb.MAX_CHANNELS == 64
     assert re.search(r"#define\s+OFDM_PFB_MAX_TAPS\s+1024\b", code) and _abi.OFDM_PFB_MAX_TAPS == pfb.MAX_TAPS == 1024
-    # additions only: the version and the kernel table are what they were
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and lib.ofdm_abi_version() == 6
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
 
 
 def test_entry_points_refuse_a_null_handle_without_a_gpu():
@@ -118,24 +109,11 @@ def test_shapes_of_the_gpu_tests():
         assert sum(sizes) == 3 * tile + 1234 + 3 * 1024
 
 
-def _opt():
-    return options.default_options(modulation="qpsk")
-
-
 @pytest.mark.parametrize("kw", [
     dict(nchannels=3), dict(nchannels=128), dict(channels=[]), dict(channels=[4]), dict(channels=[0, 1, 2, 3, 0]),
     dict(taps=[]), dict(taps=[float("nan")]), dict(iq_format="u8"), dict(iq_scale=-1.0), dict(callback=3), dict(options=3),
 ])
 def test_demod_channelizer_checks_its_arguments_before_any_engine_exists(kw, monkeypatch):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", no_engine)
-    args = dict(options=_opt(), nchannels=4, channels=[1, 3])
-    args.update(kw)
-    if args["options"] == 3:
-        args["options"] = [_opt()] * 3                # three option sets for two channels
-    with pytest.raises(ValueError):
-        ofdm.ofdm_demod_channelizer(args.pop("options"), args.pop("nchannels"), **args)
+    sh.check_arguments_are_checked_before_any_engine_exists(
+        monkeypatch, ofdm.ofdm_demod_channelizer, ("options", "nchannels"), dict(nchannels=4, channels=[1, 3]), kw)
     assert issubclass(ofdm.ofdm_demod_channelizer, ofdm.ofdm_demod_bank)

@@ -10,22 +10,15 @@ import pytest
 import duc_cases
 import pfb_cases
 import pfb_synth_cases as sc
-from ofdm_uhd_amd import _abi, duc, ofdm, options, pfb
+import stage_harness as sh
+from ofdm_uhd_amd import _abi, duc, ofdm, pfb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYNTH_FUNCS = ("ofdm_set_pfb_synth", "ofdm_pfb_synth_reset", "ofdm_pfb_synth", "ofdm_pfb_synth_last_ms")
 
 
 def test_header_declares_the_synthesis_bank_and_the_library_exports_it():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in SYNTH_FUNCS:
-        assert name in declared and name in _abi.EXPORTS and hasattr(lib, name), name
-    # additions only: the version and the kernel table are what they were
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and lib.ofdm_abi_version() == 6
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
+    sh.check_header_declares_and_library_exports(SYNTH_FUNCS)
 
 
 def test_struct_layout_matches_the_header():
@@ -146,50 +139,16 @@ def test_entry_points_refuse_a_null_handle_without_a_gpu():
     assert (n.value, ms.value) == (7, 7.0)            # nothing was written
 
 
-def _opt():
-    return options.default_options(modulation="qpsk")
-
-
 @pytest.mark.parametrize("kw", [
     dict(nchannels=3), dict(nchannels=128), dict(channels=[]), dict(channels=[4]), dict(channels=[1, 1]),
     dict(channels=[-1, 3]), dict(taps=[]), dict(taps=[float("nan")]), dict(iq_format="u8"), dict(iq_scale=-1.0),
     dict(options=3),
 ])
 def test_mod_channelizer_checks_its_arguments_before_any_engine_exists(kw, monkeypatch):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", no_engine)
-    args = dict(options=_opt(), nchannels=4, channels=[1, 3])
-    args.update(kw)
-    if args["options"] == 3:
-        args["options"] = [_opt()] * 3                # three option sets for two channels
-    with pytest.raises(ValueError):
-        ofdm.ofdm_mod_channelizer(args.pop("options"), args.pop("nchannels"), **args)
+    sh.check_arguments_are_checked_before_any_engine_exists(
+        monkeypatch, ofdm.ofdm_mod_channelizer, ("options", "nchannels"), dict(nchannels=4, channels=[1, 3]), kw)
 
 
 def test_mod_channelizer_drops_a_failing_batch_on_every_link():
-    """flush() modulates every link before the band moves; a link that fails takes the whole batch with it."""
-    class Link(object):
-        def __init__(self, fail):
-            self._pending, self.fail = [b"p"], fail
-
-        def flush(self):
-            self._pending = []
-            if self.fail:
-                raise RuntimeError("link failed")
-            return np.ones(4, np.complex64)
-
-    class Bank(object):
-        calls = 0
-
-        def pfb_synth(self, x):
-            Bank.calls += 1
-    tx = ofdm.ofdm_mod_channelizer.__new__(ofdm.ofdm_mod_channelizer)
-    tx._links, tx._engine, tx._live = [Link(False), Link(True), Link(False)], Bank(), False
-    tx._engine.pfb_synth_cfg = pfb.synth_cfg(4, [0, 1, 2], taps=[1.0])
-    with pytest.raises(RuntimeError):
-        tx.flush()
-    assert Bank.calls == 0 and not tx._live and all(not m._pending for m in tx._links)
-    assert tx.flush() is None
+    sh.check_mod_links_drops_a_failing_batch_on_every_link(ofdm.ofdm_mod_channelizer, "pfb_synth",
+                                                           pfb.synth_cfg(4, [0, 1, 2], taps=[1.0]))

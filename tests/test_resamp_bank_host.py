@@ -1,18 +1,15 @@
 """Host side of the resampler bank (resample.bank_cfg, the ofdm_resamp_bank_* part of the C ABI, the argument checks of
 ofdm_demod_resamp_bank and of the command line): no GPU needed."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import resamp_bank_cases as bc
 import resamp_cases
-from ofdm_uhd_amd import _abi, benchmark_ofdm_rx, ofdm, options, resample
+import stage_harness as sh
+from ofdm_uhd_amd import _abi, benchmark_ofdm_rx, ofdm, resample
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BANK_FUNCS = ("ofdm_set_resamp_bank", "ofdm_resamp_bank_reset", "ofdm_resamp_bank_count", "ofdm_resamp_bank",
               "ofdm_resamp_bank_taps", "ofdm_resamp_bank_last_ms")
 
@@ -49,37 +46,16 @@ def test_bank_cfg_builder():
 
 
 def test_bank_cfg_layout_matches_header(tmp_path):
-    st = _abi.ofdm_resamp_bank_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_resamp_bank_cfg));', 'printf("links %d\\n", OFDM_RESAMP_BANK_MAX_LINKS);',
-             'printf("maxtaps %d\\n", OFDM_RESAMP_MAX_TAPS);']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_resamp_bank_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 24 + 8 * 8 + 4 * 1024      # five uint32, padded to the doubles
+    got = sh.check_cfg_layout_matches_header(        # five uint32, padded to the doubles
+        tmp_path, _abi.ofdm_resamp_bank_cfg, 24 + 8 * 8 + 4 * 1024,
+        macros=[("links", "OFDM_RESAMP_BANK_MAX_LINKS"), ("maxtaps", "OFDM_RESAMP_MAX_TAPS")])
     assert int(got["links"]) == _abi.OFDM_RESAMP_BANK_MAX_LINKS == resample.MAX_LINKS == bc.MAX_LINKS == 8
     assert int(got["maxtaps"]) == _abi.OFDM_RESAMP_MAX_TAPS == resample.MAX_TAPS
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
 
 
 def test_header_declares_the_bank_and_the_library_exports_it():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in BANK_FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
-        assert hasattr(lib, name), name
-    # additions only: the version, the kernel table and the single resampler's struct are what they were
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and lib.ofdm_abi_version() == 6
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
+    sh.check_header_declares_and_library_exports(BANK_FUNCS)
+    # additions only: the single resampler's struct is what it was
     assert ctypes.sizeof(_abi.ofdm_resamp_cfg) == 24 + 4 * 1024
 
 
@@ -116,10 +92,6 @@ def test_grids_cover_what_they_claim():
     assert all(1 <= K <= 8 for _, _, _, K in bc.SEG_SHAPES)
 
 
-def _opt():
-    return options.default_options(modulation="qpsk")
-
-
 @pytest.mark.parametrize("kw", [
     dict(center_freqs=[]), dict(center_freqs=[0.0] * 9), dict(center_freqs=[0.1, 0.6]), dict(center_freqs=[0.1], decimation=0),
     dict(center_freqs=[0.1], decimation=65), dict(center_freqs=[0.1], interpolation=0), dict(center_freqs=[0.1], interpolation=65),
@@ -129,18 +101,9 @@ def _opt():
     dict(center_freqs=[0.1], iq_scale=-1.0), dict(center_freqs=[0.1], callback=3), dict(center_freqs=[0.1, 0.2], options=3),
 ])
 def test_demod_resamp_bank_checks_its_arguments_before_any_engine_exists(kw, monkeypatch):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created before the arguments were checked")
-    monkeypatch.setattr(engine, "Engine", no_engine)
-    args = dict(options=_opt(), center_freqs=[0.25], interpolation=2, decimation=5)
-    args.update(kw)
-    if args["options"] == 3:
-        args["options"] = [_opt()] * 3            # three option sets for two links
-    with pytest.raises(ValueError):
-        ofdm.ofdm_demod_resamp_bank(args.pop("options"), args.pop("center_freqs"), args.pop("interpolation"),
-                                    args.pop("decimation"), **args)
+    sh.check_arguments_are_checked_before_any_engine_exists(
+        monkeypatch, ofdm.ofdm_demod_resamp_bank, ("options", "center_freqs", "interpolation", "decimation"),
+        dict(center_freqs=[0.25], interpolation=2, decimation=5), kw)
 
 
 @pytest.mark.parametrize("extra", [
@@ -148,17 +111,9 @@ def test_demod_resamp_bank_checks_its_arguments_before_any_engine_exists(kw, mon
     ["--resamp-freq", "0.1"], ["--link-quality"], ["--csi-report", "csi.txt"], ["--suggest-map", "10"],
 ])
 def test_command_line_refuses_what_the_bank_does_not_combine_with(extra, tmp_path, monkeypatch, capsys):
-    from ofdm_uhd_amd import engine
-
-    def no_engine(*a, **k):
-        raise AssertionError("an engine was created for a refused command line")
-    monkeypatch.setattr(engine, "Engine", no_engine)
     base = ["-m", "qpsk", "--from-file", str(tmp_path / "none.dat"), "--to-file", str(tmp_path / "rx.txt"),
             "--resamp-interp", "2", "--resamp-decim", "5", "--resamp-freqs", "0.22,-0.21"]
-    with pytest.raises(SystemExit) as e:
-        benchmark_ofdm_rx.main(base + extra)
-    assert e.value.code == 2 and "--resamp-freqs" in capsys.readouterr().err
-    assert not list(tmp_path.iterdir())           # refused before a file was opened
+    sh.check_command_line_refuses(monkeypatch, capsys, tmp_path, benchmark_ofdm_rx.main, base + extra, "--resamp-freqs")
 
 
 def test_command_line_needs_a_ratio_and_numbers(tmp_path, capsys):

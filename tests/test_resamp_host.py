@@ -2,17 +2,15 @@
 fixtures the GPU tests use: no GPU needed.  The float64 model of the definition (resamp_cases.model) is applied to the
 wideband captures and its output is fed to the CPU oracle: every sent packet must come back."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import resamp_cases
+import stage_harness as sh
 from ofdm_uhd_amd import _abi, ddc, firdes, ofdm, options, resample
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RESAMP_FUNCS = ("ofdm_set_resamp", "ofdm_resamp_reset", "ofdm_resamp_count", "ofdm_resamp", "ofdm_resamp_taps",
                 "ofdm_resamp_last_ms")
 
@@ -96,36 +94,13 @@ def test_bandpass_taps_is_the_float64_evaluation_rounded_once(fc):
 
 
 def test_header_declares_the_entry_points_and_the_library_exports_them():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    lib = _abi.load()
-    for name in RESAMP_FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
-        assert hasattr(lib, name), name
+    hdr, code = sh.check_header_declares_and_library_exports(RESAMP_FUNCS)
     assert re.search(r"#define\s+OFDM_RESAMP_MAX_TAPS\s+1024\b", code) and _abi.OFDM_RESAMP_MAX_TAPS == 1024
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and _abi.OFDM_ABI_VERSION == 6
     assert "rational_resampler_ccf" in hdr
-    # no kernel id was added for it
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
 
 
 def test_resamp_cfg_layout_matches_header(tmp_path):
-    st = _abi.ofdm_resamp_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_resamp_cfg));']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_resamp_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 24 + 4 * 1024
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
+    sh.check_cfg_layout_matches_header(tmp_path, _abi.ofdm_resamp_cfg, 24 + 4 * 1024)
 
 
 def test_resamp_cfg_builder():

@@ -3,55 +3,31 @@ and the float64 model the GPU tests use: no GPU needed.  The model of the defini
 wideband band of each case, the model of the receive stage (resamp_cases.model) tunes to each link and brings it back to
 the modem's rate, and the CPU oracle must recover every packet."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import duc_cases
 import resamp_cases
+import stage_harness as sh
 import tx_resamp_cases as cases
 from ofdm_uhd_amd import _abi, benchmark_ofdm_tx, ddc, duc, firdes, ofdm, options, resample, transmit_path, tx_resample
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCS = ("ofdm_set_tx_resamp", "ofdm_tx_resamp_reset", "ofdm_tx_resamp_count", "ofdm_tx_resamp", "ofdm_tx_resamp_last_ms")
 RATIOS = ((1, 1), (2, 1), (5, 2), (3, 4), (4, 3), (25, 8), (8, 25), (64, 63), (64, 1), (1, 64), (7, 64))
 
 
 def test_cfg_layout_matches_header(tmp_path):
     st = _abi.ofdm_tx_resamp_cfg
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ofdm_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(ofdm_tx_resamp_cfg));']
-    for f, _ in st._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(ofdm_tx_resamp_cfg, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
-    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
-    assert int(got["size"]) == ctypes.sizeof(st) == 40 + 4 * 1024
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
+    sh.check_cfg_layout_matches_header(tmp_path, st, 40 + 4 * 1024)
     assert [f for f, _ in st._fields_] == ["struct_size", "interpolation", "decimation", "ntaps", "out_format", "center_freq",
                                            "out_scale", "reserved", "taps"]
 
 
 def test_header_declares_the_entry_points_and_python_mirrors_them():
-    hdr = open(os.path.join(ROOT, "include", "ofdm_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(ofdm_[a-z_0-9]+)\s*\(", code))
-    for name in FUNCS:
-        assert name in declared, name
-        assert name in _abi.EXPORTS, name
+    _, code = sh.check_header_declares_and_library_exports(FUNCS)
     assert re.search(r"#define\s+OFDM_TX_RESAMP_MAX_TAPS\s+1024\b", code) and _abi.OFDM_TX_RESAMP_MAX_TAPS == 1024
-    assert re.search(r"#define\s+OFDM_ABI_VERSION\s+6\b", code) and _abi.OFDM_ABI_VERSION == 6
-    lib = _abi.load()
-    for name in FUNCS:
-        assert hasattr(lib, name), name
-    assert _abi.K_COUNT == 11 and re.search(r"OFDM_K_COUNT\s*=\s*11\b", code)
 
 
 @pytest.mark.parametrize("occ_frac", [200 / 512.0, 48 / 64.0, 1200 / 2048.0])
