@@ -788,9 +788,10 @@ struct orc_rx_result {
 #define QINV (1.0 / 1099511627776.0)
 
 static inline int64_t q40(float v) {
-  /* |v| is clamped so that 2048-term windows stay inside int64 */
-  if (v > 511.0f) v = 511.0f;
-  if (v < -511.0f) v = -511.0f;
+  /* |v| is clamped so that 2048-term windows stay inside int64.  fmaxf / fminf, not comparisons: a NaN term becomes
+   * -511 (IEEE maxNum returns the operand that is a number) -- the engine's q40_clamped, DESIGN.md section 2.  A NaN
+   * let through to llrint would be undefined. */
+  v = fminf(fmaxf(v, -511.0f), 511.0f);
   return (int64_t)llrint((double)v * QSCALE);
 }
 

@@ -253,7 +253,10 @@ class RxResult(object):
             self._h = None
 
     def __del__(self):
-        self.close()
+        try:
+            self.close()
+        except TypeError:       # interpreter shutdown: this module's globals are already gone (results cached by a test module)
+            pass
 
 
 def rx(cfg, iq, tap_mask=0):

@@ -33,10 +33,10 @@ run("period-256 sequence 300k", np.tile(rng.standard_normal(256) + 1j * rng.stan
 run("white noise 1M", (rng.standard_normal(1000000) + 1j * rng.standard_normal(1000000)) * 0.01)
 x = (rng.standard_normal(200000) + 1j * rng.standard_normal(200000)).astype(np.complex64) * 0.01
 x[1000] = np.nan
-run("noise with one NaN", x, compare=False)
+run("noise with one NaN", x)            # (defined on both sides: a NaN term of a window sum is -511)
 x[1000] = np.inf
-run("noise with one Inf", x, compare=False)
-run("huge amplitude 1e30", (rng.standard_normal(200000) + 1j * rng.standard_normal(200000)) * 1e30, compare=False)
+run("noise with one Inf", x)
+run("huge amplitude 1e30", (rng.standard_normal(200000) + 1j * rng.standard_normal(200000)) * 1e30)
 run("denormal amplitude 1e-42", (rng.standard_normal(200000) + 1j * rng.standard_normal(200000)) * 1e-42)
 # sensing on hostile input
 sc = config.make_sense_cfg(256, 1, 3, 2, 1)
