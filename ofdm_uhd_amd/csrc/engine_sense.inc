@@ -80,6 +80,7 @@ static int sense_enqueue(ofdm_handle* h, const ofdm_sense_cfg* sc, const c32* d_
   const uint32_t G = (uint32_t)std::max(1, 256 / (S / 8));
   const uint32_t max_split = (sc->dwell_delay + G - 1) / G;
   uint32_t want = (uint32_t)((2048 + nm - 1) / nm);
+  if (const char* e = getenv("OFDM_SENSE_SPLIT")) want = (uint32_t)std::max(1, atoi(e));  // tuning knob: workgroups per message
   p.nsplit = std::max(1u, std::min(max_split, want));
   h->prof.begin(OFDM_K_SENSE, s);
   switch (S) {

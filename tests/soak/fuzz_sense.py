@@ -15,7 +15,11 @@ t_end = time.time() + budget
 ncase = nbad = 0
 while time.time() < t_end:
     S = int(rng.choice([64, 128, 256, 256, 512, 1024, 2048, 4096]))
-    tune, dwell = int(rng.integers(0, 6)), int(rng.integers(1, 40))
+    tune, dwell = int(rng.integers(0, 6)), int(rng.integers(1, 40 if rng.random() < 0.7 else 300))
+    split = None if rng.random() < 0.5 else int(rng.integers(1, 6))     # OFDM_SENSE_SPLIT: several rounds per dwell
+    os.environ.pop("OFDM_SENSE_SPLIT", None)
+    if split is not None:
+        os.environ["OFDM_SENSE_SPLIT"] = str(split)
     avg, skip = int(rng.integers(1, 12)), int(rng.integers(0, 3))
     thr = float(rng.choice([1e-4, 1e-3, 0.2]))
     win = None if rng.random() < 0.7 else (0.5 + rng.random(S)).tolist()
@@ -29,7 +33,7 @@ while time.time() < t_end:
     for _ in range(int(rng.integers(0, 4))):
         f, a = rng.random(), 10 ** rng.uniform(-3, -0.5)
         iq += (a / (0.36 * S) * np.exp(2j * np.pi * f * t)).astype(np.complex64)
-    desc = dict(S=S, tune=tune, dwell=dwell, avg=avg, skip=skip, thr=thr, n=n, window=win is not None)
+    desc = dict(S=S, tune=tune, dwell=dwell, avg=avg, skip=skip, thr=thr, n=n, window=win is not None, split=split)
     ncase += 1
     try:
         g, o = eng.sense(sc, iq), orc.sense(sc, iq)

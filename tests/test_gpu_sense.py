@@ -97,6 +97,7 @@ def test_sense_edge_cases(eng, orc):
     got2 = eng.sense(sc, iq2)
     ref2 = orc.sense(sc, iq2)
     assert np.isfinite(got2["msgs"]).all() and np.isfinite(ref2["msgs"]).all()
+    assert np.array_equal(got2["msgs"], ref2["msgs"])
     with pytest.raises(ValueError):
         bad = config.make_sense_cfg(256)
         bad.dwell_delay = 0

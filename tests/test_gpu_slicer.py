@@ -15,7 +15,8 @@ from test_gpu_parity import _check_rx, check_rx_tap_free, check_rx_untapped
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("OFDM_DEMOD_LDS", "OFDM_SYNC_W", "OFDM_SYNC_STATIC", "OFDM_EXACT_SMALL", "OFDM_RX_SYNCS", "OFDM_FRONT")
+KNOBS = ("OFDM_DEMOD_LDS", "OFDM_SYNC_W", "OFDM_SYNC_STATIC", "OFDM_EXACT_SMALL", "OFDM_RX_SYNCS", "OFDM_FRONT",
+         "OFDM_SENSE_SPLIT")
 LDS_ERROR = "configuration needs more than 160 KiB of LDS in k_rx_demod"
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from ofdm_uhd_amd import config, predictive_sense, window
+from sense_cases import np_sense_msgs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -99,17 +100,6 @@ def test_sense_count(orc):
     bad = config.make_sense_cfg()
     bad.fft_size = 100
     assert lib.ofdm_sense_count(C.byref(bad), 1000, None, None) == _abi.OFDM_E_INVAL
-
-
-def np_sense_msgs(sc, iq):
-    """Independent float64 model of the sensor graph."""
-    S = sc.fft_size
-    w = np.array(sc.window[:S], np.float64)
-    per = sc.tune_delay + sc.dwell_delay
-    nm = (len(iq) // S) // per
-    v = iq[:nm * per * S].astype(np.complex128).reshape(nm, per, S)[:, sc.tune_delay:, :]
-    pw = np.abs(np.fft.fft(v * w, axis=2)) ** 2
-    return pw.max(axis=1)
 
 
 @pytest.mark.parametrize("S,tune,dwell", [(64, 0, 3), (256, 2, 5), (1024, 1, 4), (4096, 0, 2)])
