@@ -993,6 +993,74 @@ int ofdm_tx_resamp_bank_taps(const ofdm_handle *h, int link, ofdm_c32 *out, int 
  * (ofdm_prof_enable) and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_tx_resamp_bank_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- propagation channel: multipath, Doppler, tones, carrier offset and noise between ofdm_tx and ofdm_rx ------------
+ * The reference puts a radio pair and the air between its transmitter and its receiver (usrp_transmit_path.py ->
+ * usrp_receive_path.py); ofdm_chan above is the flat stand-in for it.  This stage is the frequency-selective and
+ * time-varying one: P delayed paths, each with a complex gain and a Doppler shift, J continuous tones (a primary user
+ * for the sensor), then ofdm_chan's carrier rotation and noise.  It has the call shape of ofdm_duc at L = 1.
+ * Definition.  n is the absolute stream index; x[n] is indexed from the last reset (ofdm_set_multipath,
+ * ofdm_multipath_reset) and zero before that reset's first index.
+ *   c_p[n] = g_p                                                        where D_p == 0
+ *          = g_p * complex64(expj(2 pi ((n D_p) mod 2^64) / 2^64))      otherwise: the gr_complex product
+ *   v[n]   = sum over p in [0, P) of c_p[n] * x[n - d_p]                gr_complex products, added in float32 per part
+ *                                                                       in ascending p, begun at +0
+ *   t[n]   = sum over j in [0, J) of a_j * complex64(expj(2 pi ((Psi_j + n F_j) mod 2^64) / 2^64))
+ *                                                                       real times complex; ascending j, begun at +0
+ *   z[n]   = channel(v[n] + t[n]) at stream index n: ofdm_chan's definition with (sigma, cfo, seed, stream_id) -- the
+ *            rotation by cfo * n where cfo != 0, then the noise word of index n where sigma > 0
+ *   out[n] = store(z[n] + add[n])  when an `add` buffer is given: one float32 addition per part
+ *          = store(z[n])           otherwise; complex64, or ofdm_sc16 by the transmit rule of ofdm_duc
+ *   phases    D_p = frac(doppler_p) * 2^64, F_j = frac(tone_freq_j) * 2^64, Psi_j = frac(tone_phase_j) * 2^64,
+ *             truncated, 0 where frac rounds up to 1 (the DDC's convention); the phasors are the engine's
+ *             bit-reproducible float64 evaluation of expj at (int64)phase * 2 pi / 2^64, rounded to complex64 once.
+ *   state     the last Dmax = max d_p inputs and the absolute index of the next input.  A call with nin inputs
+ *             produces exactly nin outputs.  Every term is a function of n alone: a stream fed in any segmentation
+ *             gives bit-identical outputs; calls of 0 inputs and calls shorter than Dmax are included.
+ * With P = 1, d = 0, g = 1, J = 0 the output equals ofdm_channel's on the same samples at index0 = the stream's first
+ * index, as numbers.  The stream index stays at or below 2^53: the rotation's float64 product cfo * n is exact only
+ * below it.
+ * Pointers are host or device as the handle was created.  iq_in and add are complex64; add (may be NULL) holds nin
+ * samples and may be iq_out itself when out_format is OFDM_IQ_FC32.  iq_in must not overlap iq_out: a workgroup reads
+ * the inputs of its neighbours' outputs.  Like ofdm_duc, the call orders itself behind an ofdm_tx_async still in
+ * flight and returns after the stream drained.
+ * OFDM_E_INVAL: bad struct_size, npaths, ntones, out_format or out_scale; a delay above OFDM_MULTIPATH_MAX_DELAY; a
+ * non-finite gain; |doppler| or |tone_freq| > 0.5 or NaN; a tone_amp negative or not finite; a non-finite tone_phase;
+ * sigma negative or not finite; a non-finite cfo (entries beyond npaths / ntones are not looked at);
+ * ofdm_multipath / ofdm_multipath_reset without a configuration; a float32 pointer not 8-byte (ofdm_sc16: 4-byte)
+ * aligned; iq_in overlapping iq_out; a first_index above 2^53, or a call that would take the stream past it.  A
+ * refused configuration leaves the one in force (or none), stream state included, as it was.
+ * OFDM_E_CAPACITY: out_cap < nin (*nout is set); the stream state is then unchanged. */
+#define OFDM_MULTIPATH_MAX_PATHS 16
+#define OFDM_MULTIPATH_MAX_TONES 4
+#define OFDM_MULTIPATH_MAX_DELAY 1023
+typedef struct ofdm_multipath_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_multipath_cfg) */
+  uint32_t npaths;        /* P, 1..OFDM_MULTIPATH_MAX_PATHS */
+  uint32_t ntones;        /* J, 0..OFDM_MULTIPATH_MAX_TONES */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  float sigma;            /* ofdm_chan.sigma: finite, >= 0 */
+  float cfo;              /* ofdm_chan.cfo, radians per sample: finite */
+  uint64_t seed;          /* ofdm_chan.seed */
+  uint64_t stream_id;     /* ofdm_chan.stream_id */
+  uint32_t delay[OFDM_MULTIPATH_MAX_PATHS];   /* d_p in samples, 0..OFDM_MULTIPATH_MAX_DELAY; equal ones are allowed */
+  ofdm_c32 gain[OFDM_MULTIPATH_MAX_PATHS];    /* g_p, finite */
+  double doppler[OFDM_MULTIPATH_MAX_PATHS];   /* cycles per sample, [-0.5, 0.5] */
+  float tone_amp[OFDM_MULTIPATH_MAX_TONES];   /* a_j: finite, >= 0 */
+  double tone_freq[OFDM_MULTIPATH_MAX_TONES]; /* cycles per sample, [-0.5, 0.5] */
+  double tone_phase[OFDM_MULTIPATH_MAX_TONES]; /* phase at stream index 0, cycles: finite */
+} ofdm_multipath_cfg;
+/* NULL: none (touches no device memory).  Resets the stream state (history zero, next index 0). */
+int ofdm_set_multipath(ofdm_handle *h, const ofdm_multipath_cfg *cfg);
+/* a new stream whose first sample has this absolute index (at most 2^53): history zero */
+int ofdm_multipath_reset(ofdm_handle *h, uint64_t first_index);
+/* the next nin samples of the stream in, nin samples out (added onto `add` where given) */
+int ofdm_multipath(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const ofdm_c32 *add, void *iq_out, uint64_t out_cap,
+                   uint64_t *nout);
+/* HIP-event time of k_multipath in the last ofdm_multipath, which must have run with profiling on (ofdm_prof_enable)
+ * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
+int ofdm_multipath_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

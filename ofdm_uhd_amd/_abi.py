@@ -24,6 +24,9 @@ OFDM_TX_RESAMP_MAX_TAPS = 1024
 OFDM_TX_RESAMP_BANK_MAX_LINKS = 8
 OFDM_PFB_MAX_CHANNELS = 64
 OFDM_PFB_MAX_TAPS = 1024
+OFDM_MULTIPATH_MAX_PATHS = 16
+OFDM_MULTIPATH_MAX_TONES = 4
+OFDM_MULTIPATH_MAX_DELAY = 1023
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -259,6 +262,26 @@ class ofdm_tx_resamp_bank_cfg(C.Structure):
     ]
 
 
+class ofdm_multipath_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("npaths", C.c_uint32),
+        ("ntones", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("out_scale", C.c_float),
+        ("sigma", C.c_float),
+        ("cfo", C.c_float),
+        ("seed", C.c_uint64),
+        ("stream_id", C.c_uint64),
+        ("delay", C.c_uint32 * OFDM_MULTIPATH_MAX_PATHS),
+        ("gain", ofdm_c32 * OFDM_MULTIPATH_MAX_PATHS),
+        ("doppler", C.c_double * OFDM_MULTIPATH_MAX_PATHS),
+        ("tone_amp", C.c_float * OFDM_MULTIPATH_MAX_TONES),
+        ("tone_freq", C.c_double * OFDM_MULTIPATH_MAX_TONES),
+        ("tone_phase", C.c_double * OFDM_MULTIPATH_MAX_TONES),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -283,6 +306,7 @@ EXPORTS = (
     "ofdm_set_duc_bank", "ofdm_duc_bank_reset", "ofdm_duc_bank", "ofdm_duc_bank_taps", "ofdm_duc_bank_last_ms",
     "ofdm_set_tx_resamp_bank", "ofdm_tx_resamp_bank_reset", "ofdm_tx_resamp_bank_count", "ofdm_tx_resamp_bank",
     "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
+    "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
 )
 
 _LIB = None
@@ -369,6 +393,10 @@ def _declare(lib):
     lib.ofdm_tx_resamp_bank.argtypes = [H, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p]
     lib.ofdm_tx_resamp_bank_taps.argtypes = [H, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_tx_resamp_bank_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_multipath.argtypes = [H, C.POINTER(ofdm_multipath_cfg)]
+    lib.ofdm_multipath_reset.argtypes = [H, C.c_uint64]
+    lib.ofdm_multipath.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+    lib.ofdm_multipath_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

@@ -30,6 +30,7 @@
 #include "tx_resamp_bank.h"
 #include "pfb.h"
 #include "pfb_synth.h"
+#include "multipath.h"
 
 static std::string g_create_error;
 
@@ -125,6 +126,7 @@ struct ofdm_handle {
   PfbSynthState pfb_synth;  // its transmit mirror: the synthesis bank (pfb_synth.h / engine_pfb_synth.inc)
   DucBankState duc_bank;  // all links of a band at arbitrary centre frequencies in one pass (duc_bank.h / engine_duc_bank.inc)
   TxResampBankState tx_resamp_bank;  // the same at a rational rate (tx_resamp_bank.h / engine_tx_resamp_bank.inc)
+  MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -558,6 +560,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->pfb_synth.release();
   h->duc_bank.release();
   h->tx_resamp_bank.release();
+  h->multipath.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -999,3 +1002,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_pfb_synth.inc"
 #include "engine_duc_bank.inc"
 #include "engine_tx_resamp_bank.inc"
+#include "engine_multipath.inc"

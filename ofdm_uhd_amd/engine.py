@@ -88,6 +88,7 @@ class Engine(object):
         self.pfb_synth_cfg = None  # the synthesis bank's configuration in force (set_pfb_synth), None without one
         self.duc_bank_cfg = None  # the DUC bank's configuration in force (set_duc_bank), None without one
         self.tx_resamp_bank_cfg = None  # the transmit resampler bank's configuration in force (set_tx_resamp_bank), None without one
+        self.multipath_cfg = None  # the propagation channel's configuration in force (set_multipath), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -791,6 +792,34 @@ class Engine(object):
         return self._stage_last_ms("tx_resamp_bank")
 
     # -- chunked streams --------------------------------------------------------------
+    # -- propagation channel (multipath, Doppler, tones, carrier offset and noise between tx and rx) ---------------
+    def set_multipath(self, cfg=None, **kw):
+        """Configure the propagation channel stage: an ``ofdm_multipath_cfg`` (multipath.multipath_cfg) or its keywords
+        (paths=, tones=, sigma=, cfo=, seed=, stream_id=, out_format=, out_scale=).  ``set_multipath(None)`` with no
+        keywords removes it.  Resets the stream state."""
+        self._stage_set("multipath", "multipath.multipath_cfg", cfg, kw)
+
+    def multipath_reset(self, first=0):
+        """Start a new stream whose first sample has this absolute index (at most 2^53); the echo history is zero."""
+        self._stage_reset("multipath", first)
+
+    def multipath(self, iq, add=None):
+        """Host mode: the next complex64 samples of the stream -> as many received samples (complex64, or int16 of
+        shape (n, 2) with out_format "sc16"), added onto the complex64 band ``add`` where one is given.  Stateful: any
+        segmentation of a stream gives the same bits."""
+        return self._tx_stage("multipath", iq, add, lambda n: n, "len(iq)")
+
+    def multipath_device(self, iq_ptr, nin, out_ptr, out_cap, add_ptr=None):
+        """Device mode: all buffers are device pointers; ``iq_ptr`` can be what tx_device(wait=False) is filling (same
+        handle) and must not overlap ``out_ptr``; ``add_ptr`` may be ``out_ptr`` itself for complex64 output.  Returns
+        the number of outputs written."""
+        return self._stage_device("multipath", C.c_void_p(iq_ptr), int(nin), C.c_void_p(add_ptr) if add_ptr else None,
+                                  C.c_void_p(out_ptr), int(out_cap))
+
+    def multipath_last_ms(self):
+        """HIP-event time of k_multipath in the last multipath() / multipath_device() (needs prof_enable())."""
+        return self._stage_last_ms("multipath")
+
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""
         n = C.c_int(0)
