@@ -150,8 +150,9 @@ __device__ __forceinline__ long long q40_clamped(float v) {
 __device__ __forceinline__ double q40_to_double(long long s) { return (double)s * Q40_INV; }
 
 // ---- complex_to_arg for the sample-and-held fine-frequency estimate ------------------------
-// Plain float32 operations (Cephes-style atanf, ~2 ulp), NOT ocml's atan2f: the CPU restatement
-// evaluates the same operations and gets the same bits.  The NCO integrates this angle over
+// Plain float32 operations (Cephes-style atanf; the CPU restatement of it is within 3 * 2^-23 of atan2, about
+// 3 ulp near pi / 2: tests/test_capture_edges_host.py), NOT ocml's atan2f: the CPU restatement evaluates the same
+// operations and gets the same bits.  The NCO integrates this angle over
 // thousands of samples; a 1-ulp difference between two libm's would grow to 1e-4 rad.
 __device__ __forceinline__ float det_atanf_pos(float x) {
   float y0;

@@ -388,6 +388,12 @@ class ofdm_demod(object):
         self._streaming = False
         self._log_samples = 0
 
+    def stream_position(self):
+        """Where the chunked stream stands, read-only: (absolute index of the first carried sample, samples carried,
+        last absolute index up to which every flag is final).  The next feed() demodulates the carried samples plus its
+        chunk; flag f of that call (engine().rx_nco_state()) is sample ``first carried + f`` of the stream."""
+        return self._s_abs, len(self._s_tail), self._s_final
+
     def _stream_symbol(self, p):
         """Ordinal, among the sampled symbols of the whole capture, of the preamble of the next final flag p (absolute):
         the sampler's bookkeeping (k_frames) restated over the final flags -- the frame of the flag before takes

@@ -73,7 +73,8 @@ static inline ofdm_c32 cdiv(ofdm_c32 a, ofdm_c32 b) {
 static inline float cnorm(ofdm_c32 a) { return a.re * a.re + a.im * a.im; }
 
 /* complex_to_arg for the sample-and-held fine-frequency estimate.  Written out in plain float32
- * operations (Cephes-style atanf: two range reductions + a degree-9 odd polynomial, ~2 ulp) so
+ * operations (Cephes-style atanf: two range reductions + a degree-9 odd polynomial, within
+ * 3 * 2^-23 absolute, about 3 ulp near pi / 2: tests/test_capture_edges_host.py) so
  * that the GPU evaluates the very same operations and gets the same bits: the NCO integrates this
  * angle over thousands of samples, which would turn a 1-ulp libm/ocml difference into 1e-4 rad. */
 static inline float det_atanf_pos(float x) {

@@ -34,11 +34,16 @@ def pad_symbol(seed, pkt, slot, arity):
     return (z >> 32) % arity
 
 
+def carriers_of(cfg):
+    """The configuration's carrier map string (empty: the built-in FE7F)."""
+    return cfg.carrier_map.decode("ascii") or "FE7F"
+
+
 def tx_freq(cfg, payloads):
     """Mapper + insert_preamble output: list of N-vectors (complex128)."""
     N, occ, CP, const, ks, _ = cfg_arrays(cfg)
     nb = nbits_of(cfg)
-    cmap = np.array(config.carrier_map(occ, N))
+    cmap = np.array(config.carrier_map(occ, N, carriers_of(cfg)))
     zl = config.zeros_on_left(N, occ)
     pre = np.zeros(N, complex)
     pre[zl:zl + occ] = ks
@@ -70,6 +75,8 @@ def tx_time(cfg, freq):
 
 def chan_filter(cfg, x):
     taps = cfg_arrays(cfg)[5]
+    if len(x) == 0:
+        return np.zeros(0, np.complex128)
     return np.convolve(x.astype(np.complex128), taps)[:len(x)]
 
 
@@ -260,17 +267,21 @@ def frame_acq(cfg, symbols):
     return out
 
 
-def frame_sink(cfg, acq):
-    """Returns (messages, derotated-symbol list)."""
+def frame_sink(cfg, acq, origins=None):
+    """Returns (messages, derotated-symbol list).  origins: a list that receives, per message, the ordinal among the
+    flagged symbols (= the frame) of the preamble the message's header search began at."""
     N, occ, CP, const, ks, _ = cfg_arrays(cfg)
     nb = nbits_of(cfg)
-    smap = np.array(config.carrier_map(occ, occ))
+    smap = np.array(config.carrier_map(occ, occ, carriers_of(cfg)))
     msgs, derots = [], []
     state = 0
+    nflag, opened = 0, 0
     for flag, sym in acq:
+        nflag += 1 if flag else 0
         if state == 0:
             if flag:
                 state = 1
+                opened = nflag - 1
                 bitbuf = []
                 header_bytes = []
                 phase = freq = 0.0
@@ -310,6 +321,8 @@ def frame_sink(cfg, acq):
                         pkt = bytearray()
                         if plen == 0:
                             msgs.append(bytes(pkt))
+                            if origins is not None:
+                                origins.append(opened)
                             state = 0
                     else:
                         state = 0
@@ -317,6 +330,8 @@ def frame_sink(cfg, acq):
                 pkt.append(byte)
                 if len(pkt) == plen:
                     msgs.append(bytes(pkt))
+                    if origins is not None:
+                        origins.append(opened)
                     state = 0
             # state 0: remaining bytes of the symbol are dropped
     return msgs, derots
@@ -331,10 +346,12 @@ def rx(cfg, iq):
     frames = sampler_frames(peaks, len(y), cfg.fft_length, cfg.cp_length, cfg.sampler_timeout)
     syms = rx_symbols(cfg, y, peaks, angles, frames)
     acq = frame_acq(cfg, syms)
-    msgs, derots = frame_sink(cfg, acq)
+    origins = []
+    msgs, derots = frame_sink(cfg, acq, origins)
     packets = [ofdm_packet_utils.unmake_packet(m) for m in msgs]
+    # pos: the flag each packet belongs to (what the engine reports as rx_packet_pos)
     return dict(y=y, u=u, peaks=peaks, angles=angles, frames=frames, fft=syms, acq=acq, sink=derots,
-                msgs=msgs, packets=packets)
+                msgs=msgs, packets=packets, pos=[frames[i][0] for i in origins])
 
 
 # --- the peak detector's running average at run starts (OFDM_TAP_RX_RUN_AVG) ------------------------------------
