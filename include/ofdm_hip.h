@@ -1061,6 +1061,60 @@ int ofdm_multipath(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const of
  * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_multipath_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- coded links: rate-1/2, K = 7 convolutional code over the payload, Viterbi decoder on the GPU --------------------
+ * A forward-error-correcting layer at the payload boundary: ofdm_fec_encode turns payloads into coded blocks that go
+ * to ofdm_tx / ofdm_make_packets as payloads; ofdm_fec_decode takes the payloads ofdm_rx delivered (CRC-failed ones
+ * included) and returns what was sent.  Additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and
+ * without a call to these functions nothing here launches, allocates or copies.  All arithmetic is integer: results
+ * are defined bit for bit.
+ *
+ * Definition.  Info bytes of an n-byte payload (0 <= n <= OFDM_FEC_MAX_PAYLOAD): payload | CRC-32(payload) big-endian
+ * (the packet CRC); info bits u[0 .. 8(n+4)) MSB first, six zero tail bits behind them, u[t] = 0 for t < 0;
+ * T = 8(n+4) + 6 steps.  Generators 133 / 171 octal:  A[t] = u[t]^u[t-2]^u[t-3]^u[t-5]^u[t-6],
+ * B[t] = u[t]^u[t-1]^u[t-2]^u[t-3]^u[t-6];  coded bits c[2t] = A[t], c[2t+1] = B[t], then 4 zero pad bits:
+ * 16n + 80 bits = 2n + 10 bytes.  Interleaver with C = interleave_cols columns, R = (16n + 80) / C: sent bit j =
+ * c[(j mod R) * C + j / R], packed MSB first (C = 1: identity).
+ * Decoder input: one signed value v per sent bit, v > 0 means 1, v = 0 is an erasure, -128 reads as -127; a hard byte
+ * is v = +1 / -1 per bit.  The last 4 (deinterleaved) positions are ignored.  Full-sequence maximum-correlation
+ * Viterbi: state bit k = u[t-1-k]; start and end in state 0; int32 path metric = sum of (2c-1) * v; a path is
+ * replaced only by a strictly larger metric (on a tie the predecessor with u[t-6] = 0 stays); full traceback.
+ * Per block: the n payload bytes, ok = 1 when the decoded CRC matches, corrected = positions among the first 2T
+ * deinterleaved ones with v != 0 whose sign disagrees with the decoded sequence encoded again.
+ * A coded length that is odd, under 10 or over OFDM_FEC_MAX_CODED is no block: ok = 0, no payload bytes,
+ * corrected = 0 for that entry, and no error for the batch; nothing of it is read.
+ *
+ * Pointers as for ofdm_make_packets: the blobs (payloads, coded, soft) are host or device pointers by the handle's
+ * mode; the offset, length, ok and corrected arrays are always host memory.  coded_off / payload_off OUT have
+ * nblk + 1 entries and are set before the capacity check.  cfg NULL: interleave_cols 16.
+ * OFDM_E_INVAL: bad struct_size, interleave_cols not one of 1, 2, 4, 8, 16, a payload longer than
+ * OFDM_FEC_MAX_PAYLOAD (encode), a null argument.  OFDM_E_CAPACITY: the output blob is too small.
+ * The decision workspace (8 bytes per trellis step and block in flight) belongs to the handle and is bounded; a large
+ * batch is decoded in slices. */
+#define OFDM_FEC_MAX_PAYLOAD 2040
+#define OFDM_FEC_MAX_CODED 4090
+typedef struct ofdm_fec_cfg {
+  uint32_t struct_size;      /* = sizeof(ofdm_fec_cfg) */
+  uint32_t interleave_cols;  /* 1, 2, 4, 8 or 16 */
+  uint32_t reserved[6];      /* 0 */
+} ofdm_fec_cfg;
+
+/* pure host functions, usable without a GPU: 2n + 10, and its inverse (OFDM_E_INVAL for a length that is no block) */
+int ofdm_fec_coded_len(uint32_t payload_len, uint32_t *coded_len);
+int ofdm_fec_payload_len(uint32_t coded_len, uint32_t *payload_len);
+int ofdm_fec_encode(ofdm_handle *h, const ofdm_fec_cfg *cfg, const uint8_t *payloads, const uint64_t *payload_off,
+                    const uint32_t *payload_len, int nblk, uint8_t *coded, uint64_t coded_cap, uint64_t *coded_off);
+int ofdm_fec_decode(ofdm_handle *h, const ofdm_fec_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,
+                    const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap, uint64_t *payload_off,
+                    uint8_t *ok, uint32_t *corrected);
+/* the same from int8 values, 8 per coded byte: block k holds 8 * coded_len[k] values from soft + soft_off[k] */
+int ofdm_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, const int8_t *soft, const uint64_t *soft_off,
+                         const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap,
+                         uint64_t *payload_off, uint8_t *ok, uint32_t *corrected);
+/* HIP-event time of k_fec_encode / k_fec_decode (all slices) in the last of the three calls above, which must have run
+ * with profiling on (ofdm_prof_enable) and launched; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table
+ * is unchanged. */
+int ofdm_fec_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

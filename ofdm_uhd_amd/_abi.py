@@ -27,6 +27,8 @@ OFDM_PFB_MAX_TAPS = 1024
 OFDM_MULTIPATH_MAX_PATHS = 16
 OFDM_MULTIPATH_MAX_TONES = 4
 OFDM_MULTIPATH_MAX_DELAY = 1023
+OFDM_FEC_MAX_PAYLOAD = 2040
+OFDM_FEC_MAX_CODED = 4090
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -282,6 +284,14 @@ class ofdm_multipath_cfg(C.Structure):
     ]
 
 
+class ofdm_fec_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("interleave_cols", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -307,6 +317,8 @@ EXPORTS = (
     "ofdm_set_tx_resamp_bank", "ofdm_tx_resamp_bank_reset", "ofdm_tx_resamp_bank_count", "ofdm_tx_resamp_bank",
     "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
+    "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
+    "ofdm_fec_last_ms",
 )
 
 _LIB = None
@@ -397,6 +409,13 @@ def _declare(lib):
     lib.ofdm_multipath_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_multipath.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
     lib.ofdm_multipath_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    FC = C.POINTER(ofdm_fec_cfg)
+    lib.ofdm_fec_coded_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_fec_payload_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_fec_encode.argtypes = [H, FC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
+    lib.ofdm_fec_decode.argtypes = [H, FC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p]
+    lib.ofdm_fec_decode_soft.argtypes = lib.ofdm_fec_decode.argtypes
+    lib.ofdm_fec_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

@@ -66,6 +66,10 @@ def make_parser():
                       help="with --ddc-decim, instead of --ddc-freq: comma-separated centres of ALL links in the capture; "
                            "they are extracted in one pass on the GPU (ofdm_demod_bank), one account per link, and "
                            "--to-file gets .linkN appended [default=off]")
+    parser.add_option("", "--fec", action="store_true", default=False,
+                      help="coded link: the file was written by benchmark_ofdm_tx --fec; every delivered packet, the "
+                           "CRC-failed ones included, goes through the Viterbi decoder on the GPU and is accounted by "
+                           "the CRC inside the code [default=%default]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -147,6 +151,8 @@ def main(argv=None):
     if len(args) != 0:
         parser.print_help(sys.stderr)
         sys.exit(1)
+    if options.fec and (options.resamp_freqs is not None or options.ddc_freqs is not None):
+        parser.error("--fec does not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:
         return _main_resamp_bank(parser, options)
     if options.ddc_freqs is not None:
@@ -159,7 +165,7 @@ def main(argv=None):
         rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
         rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
-    # (receive_path takes --iq-format / --iq-scale, --ddc-decim / --ddc-freq and --resamp-* from the options)
+    # (receive_path takes --iq-format / --iq-scale, --fec, --ddc-decim / --ddc-freq and --resamp-* from the options)
     rxpath.run(iqio.file_source(options.from_file, fmt=options.iq_format), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     if options.csi_report is not None:

@@ -54,6 +54,10 @@ def make_parser():
     parser.add_option("", "--duc-freq", type="eng_float", default=0.0,
                       help="with --duc-interp: centre of the link in the wideband file, cycles per sample in "
                            "[-0.5, 0.5] (the radio's set_center_freq over the file's rate) [default=%default]")
+    parser.add_option("", "--fec", action="store_true", default=False,
+                      help="coded link: protect every payload (at most 2040 bytes) with the rate-1/2 K=7 convolutional "
+                           "code and interleaver, encoded on the GPU; demodulate with benchmark_ofdm_rx --fec "
+                           "[default=%default]")
     _options.add_tx_resamp_options(parser)
     parser.add_option("", "--tx-resamp-freqs", default=None,
                       help="with --tx-resamp-interp / --tx-resamp-decim, instead of --tx-resamp-freq: comma-separated "
@@ -72,6 +76,8 @@ def _main_tx_resamp_bank(parser, options):
     the packets sent per link."""
     if options.duc_interp or options.duc_freq:
         parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
+    if options.fec:
+        parser.error("--tx-resamp-freqs does not combine with --fec")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -125,7 +131,7 @@ def main(argv=None):
         print(os.path.getsize(options.from_file))
 
     txpath = transmit_path.transmit_path(options)
-    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format and --duc-interp / --duc-freq, --tx-resamp-* from the options)
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format, --fec and --duc-interp / --duc-freq, --tx-resamp-* from the options)
     txpath.connect(sink)
     npk = 0
     for payload in build_payloads(options, src):

@@ -31,6 +31,7 @@
 #include "pfb.h"
 #include "pfb_synth.h"
 #include "multipath.h"
+#include "fec.h"
 
 static std::string g_create_error;
 
@@ -127,6 +128,7 @@ struct ofdm_handle {
   DucBankState duc_bank;  // all links of a band at arbitrary centre frequencies in one pass (duc_bank.h / engine_duc_bank.inc)
   TxResampBankState tx_resamp_bank;  // the same at a rational rate (tx_resamp_bank.h / engine_tx_resamp_bank.inc)
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
+  FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -561,6 +563,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->duc_bank.release();
   h->tx_resamp_bank.release();
   h->multipath.release();
+  h->fec.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -1003,3 +1006,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_duc_bank.inc"
 #include "engine_tx_resamp_bank.inc"
 #include "engine_multipath.inc"
+#include "engine_fec.inc"

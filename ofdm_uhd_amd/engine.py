@@ -820,6 +820,91 @@ class Engine(object):
         """HIP-event time of k_multipath in the last multipath() / multipath_device() (needs prof_enable())."""
         return self._stage_last_ms("multipath")
 
+    # -- coded links (convolutional encoder and Viterbi decoder over the payloads) ---------------------------------
+    def _fec_cfg(self, fec):
+        from . import fec as _fec
+        cfg = _fec.as_cfg(True if fec is None else fec)
+        if cfg is None:
+            raise ValueError("fec=False names no code")
+        return cfg
+
+    def fec_encode(self, payloads, fec=None):
+        """Host mode: list of payloads (0 .. 2040 bytes each) -> list of coded blocks (2 n + 10 bytes each), the
+        payloads tx() then takes.  ``fec``: None / True (16 interleaver columns), a column count, a dict of
+        fec.fec_cfg's keywords or an ``ofdm_fec_cfg``."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        blob, offs, lens = pack_payloads(payloads)
+        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 10 * len(payloads), 1), np.uint8)
+        coff = np.zeros(len(payloads) + 1, np.uint64)
+        self._check(self._lib.ofdm_fec_encode(self._h, C.byref(cfg), _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
+                                              coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+
+    def fec_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap, fec=None):
+        """Device mode: payload bytes and coded blocks are device pointers; offs / lens are NumPy host arrays.
+        Returns the nblk + 1 block offsets (uint64)."""
+        assert self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        coff = np.zeros(len(lens) + 1, np.uint64)
+        self._check(self._lib.ofdm_fec_encode(self._h, C.byref(cfg), C.c_void_p(payload_ptr),
+                                              offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
+                                              int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return coff
+
+    def _fec_decode(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap):
+        n = len(lens)
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr = np.zeros(max(n, 1), np.uint32)
+        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
+                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return poff, ok[:n], corr[:n]
+
+    def fec_decode(self, blocks, fec=None):
+        """Host mode: list of received blocks (hard bytes of any length, e.g. the payloads rx() delivered whatever
+        their CRC said) -> list of (ok, payload, corrected): the decoded payload, whether its inner CRC matches, and
+        the number of coded bits the decoder changed.  A length that is no block gives (False, b"", 0)."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        blob, offs, lens = pack_payloads(blocks)
+        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode, cfg, _ptr(blob), offs, lens, _ptr(out), len(out))
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(blocks))]
+
+    def fec_decode_soft(self, values, fec=None):
+        """Host mode: list of int8 arrays, one value per transmitted bit (v > 0 means 1, 0 is an erasure, -128 reads
+        as -127), 8 per coded byte -> list of (ok, payload, corrected) as fec_decode.  An array whose length is no
+        multiple of 8, or no block's, gives (False, b"", 0)."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
+        # (a length that is no multiple of 8 is handed on as the odd length 1: no block)
+        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
+        offs = np.zeros(max(len(vals), 1), np.uint64)
+        if len(vals) > 1:
+            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
+        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
+        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode_soft, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out),
+                                          len(out))
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(vals))]
+
+    def fec_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, fec=None, soft=False):
+        """Device mode: the blocks (hard bytes, or int8 values with ``soft``: 8 per coded byte, offsets in values) and
+        the payloads are device pointers; offs / lens (coded bytes) are NumPy host arrays.  Returns (payload offsets
+        uint64[nblk + 1], ok uint8[nblk], corrected uint32[nblk]) as host arrays."""
+        assert self.device_ptrs
+        fn = self._lib.ofdm_fec_decode_soft if soft else self._lib.ofdm_fec_decode
+        return self._fec_decode(fn, self._fec_cfg(fec), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+
+    def fec_last_ms(self):
+        """HIP-event time of k_fec_encode / k_fec_decode in the last fec call (needs prof_enable())."""
+        return self._stage_last_ms("fec")
+
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""
         n = C.c_int(0)

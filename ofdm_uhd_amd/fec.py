@@ -1,0 +1,55 @@
+"""Coded links: the configuration and length arithmetic of the forward-error-correcting layer over the payload.
+
+A rate-1/2, K = 7 convolutional code (133 / 171 octal) with a block interleaver, decoded by a full-sequence Viterbi
+decoder on the GPU (include/ofdm_hip.h, "coded links").  The work is ``Engine.fec_encode`` /
+``Engine.fec_decode`` / ``Engine.fec_decode_soft``; ``ofdm_mod(fec=...)`` and ``ofdm_demod(fec=...)`` put it on a
+link.
+"""
+import ctypes as C
+
+from . import _abi
+
+MAX_PAYLOAD = _abi.OFDM_FEC_MAX_PAYLOAD
+MAX_CODED = _abi.OFDM_FEC_MAX_CODED
+INTERLEAVE_COLS = (1, 2, 4, 8, 16)
+
+
+def fec_cfg(interleave=16):
+    """An ``ofdm_fec_cfg``: ``interleave`` is the interleaver's column count, one of 1 (none), 2, 4, 8, 16."""
+    if isinstance(interleave, bool) or int(interleave) != interleave or int(interleave) not in INTERLEAVE_COLS:
+        raise ValueError("fec interleave must be 1, 2, 4, 8 or 16")
+    cfg = _abi.ofdm_fec_cfg()
+    cfg.struct_size = C.sizeof(_abi.ofdm_fec_cfg)
+    cfg.interleave_cols = int(interleave)
+    return cfg
+
+
+def as_cfg(fec):
+    """What ``ofdm_mod`` / ``ofdm_demod`` / the Engine methods accept as ``fec``: None or False (no coding), True
+    (defaults), a dict of fec_cfg's keywords, an int (the column count) or an ``ofdm_fec_cfg``."""
+    if fec is None or fec is False:
+        return None
+    if fec is True:
+        return fec_cfg()
+    if isinstance(fec, _abi.ofdm_fec_cfg):
+        return fec
+    if isinstance(fec, dict):
+        return fec_cfg(**fec)
+    return fec_cfg(fec)
+
+
+def coded_len(payload_len):
+    """Bytes of the coded block of a ``payload_len``-byte payload: 2 n + 10.  ValueError above MAX_PAYLOAD."""
+    n = C.c_uint32(0)
+    if payload_len < 0 or payload_len > 0xffffffff or _abi.load().ofdm_fec_coded_len(int(payload_len), C.byref(n)) != _abi.OFDM_OK:
+        raise ValueError("fec: len(payload) must be in [0, %d]" % MAX_PAYLOAD)
+    return n.value
+
+
+def payload_len(coded_len):
+    """Payload bytes of a coded block of ``coded_len`` bytes, None for a length that is no block (odd, under 10, over
+    MAX_CODED)."""
+    n = C.c_uint32(0)
+    if coded_len < 0 or coded_len > 0xffffffff or _abi.load().ofdm_fec_payload_len(int(coded_len), C.byref(n)) != _abi.OFDM_OK:
+        return None
+    return n.value

@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -27,7 +27,7 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None):
+                 resample=None, fec=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
@@ -47,6 +47,10 @@ class ofdm_mod(object):
                ``dict(interpolation=, decimation=, center_freq=0.0, taps=None)``, the engine's rational-rate transmit
                stage (tx_resample.py, Engine.tx_resamp) in the DUC's place; ``taps=None``: tx_resample.design.  Not
                together with ``duc``
+        @param fec: coded link: ``True`` or ``dict(interleave=16)`` (fec.py).  send_pkt then takes up to 2040 bytes and
+               flush() encodes the batch on the GPU (Engine.fec_encode: payload | CRC-32 through the rate-1/2, K = 7
+               convolutional code and a block interleaver, 2 n + 10 bytes) ahead of the modulator; the receiving end
+               is ofdm_demod(fec=) with the same setting.  None: the payloads go out as they are and nothing new runs
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
@@ -83,6 +87,7 @@ class ofdm_mod(object):
             self._duc = "tx_resamp"
         elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
+        self._fec = _fec.as_cfg(fec)
         self._pending = []
         self._sink = None
         self.symbols_sent = 0
@@ -124,6 +129,12 @@ class ofdm_mod(object):
         payload = bytes(payload)
         # same limit and exception as make_packet (ofdm_packet_utils.py:123-126) -- and, like it, raised HERE for
         # the offending packet only: the padded, whitened body must fit the mask too (whiten(), :84-87)
+        if self._fec is not None:
+            if len(payload) > _fec.MAX_PAYLOAD:
+                raise ValueError("len(payload) must be in [0, %d]" % (_fec.MAX_PAYLOAD,))
+            self._engine.framed_len(_fec.coded_len(len(payload)))   # the coded block is what gets framed
+            self._pending.append(payload)
+            return
         if len(payload) + 4 > len(ofdm_packet_utils.random_mask_tuple):
             raise ValueError("len(payload) must be in [0, %d]" % (len(ofdm_packet_utils.random_mask_tuple),))
         self._engine.framed_len(len(payload))        # ValueError when the whitening mask is exhausted
@@ -146,6 +157,8 @@ class ofdm_mod(object):
         iq = None
         if self._pending:
             pending, self._pending = self._pending, []   # a failing batch never poisons the queue
+            if self._fec is not None:
+                pending = self._engine.fec_encode(pending, self._fec)
             iq = self._engine.tx(pending)
             self.symbols_sent += self._engine.last_stats.get("symbols", 0)
             self.packets_sent += len(pending)
@@ -214,7 +227,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None, resample=None):
+                 iq_scale=None, ddc=None, resample=None, fec=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -234,6 +247,11 @@ class ofdm_demod(object):
         @param resample: the same for a capture whose rate is M / L times the modem's, no integer multiple of it:
             ``dict(interpolation=, decimation=, center_freq=0.0, taps=None)``, the engine's rational-rate stage
             (resample.py, Engine.resamp) in the DDC's place; ``taps=None``: resample.design.  Not together with ``ddc``
+        @param fec: coded link, as for ofdm_mod: every packet work() / feed() delivers, the CRC-failed ones included, is
+            decoded in one batch (Engine.fec_decode) before the callbacks fire.  ``callback(ok, payload)`` and the
+            returned list then carry the decoded payload and the verdict of the CRC inside the code; ``last_fec`` holds
+            (outer_ok, corrected) per packet -- what the packet CRC said and how many coded bits the decoder changed;
+            ``n_ok`` counts decoded verdicts.  Link quality and channel state describe the packets as received
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -244,6 +262,8 @@ class ofdm_demod(object):
         self._snr = getattr(options, "snr", 30)
         self._callback = callback
         self._quality_callback = quality_callback
+        self._fec = _fec.as_cfg(fec)
+        self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec only)
 
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
@@ -329,8 +349,17 @@ class ofdm_demod(object):
             self._csi_accumulate(pkts)
         if self._log:
             self._write_logs()
+        pkts = self._decode(pkts)
         self._deliver(pkts)
         return pkts
+
+    def _decode(self, pkts):
+        """The coded link's receiving end: the delivered packets' bytes, whatever their CRC said, through the decoder."""
+        if self._fec is None:
+            return pkts
+        dec = self._engine.fec_decode([p for _, p in pkts], self._fec) if pkts else []
+        self.last_fec = [(bool(ok), c) for (ok, _), (_, _, c) in zip(pkts, dec)]
+        return [(ok, p) for ok, p, _ in dec]
 
     def _deliver(self, pkts):
         for i, (ok, payload) in enumerate(pkts):
@@ -479,6 +508,7 @@ class ofdm_demod(object):
         if self._csi:
             self.last_csi = self._csi_rows(rows, sel)
             self._csi_accumulate(out)
+        out = self._decode(out)
         self._deliver(out)
         return out
 

@@ -6,15 +6,18 @@ from . import ofdm, options as _options
 
 class receive_path(object):
     def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
-                 ddc=None, resample=None):
+                 ddc=None, resample=None, fec=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
         ``ddc_decim`` / ``ddc_freq`` (--ddc-decim / --ddc-freq), no front end where ddc_decim is unset or 0 (what the
         reference sets on its radio: set_decim / set_center_freq, usrp_receive_path.py).
         ``resample``: rational-rate front end of ofdm_demod, ``dict(interpolation=, decimation=, center_freq=0.0,
-        taps=None)``; None: the options' ``resamp_interp`` / ``resamp_decim`` / ``resamp_freq`` (--resamp-*)."""
+        taps=None)``; None: the options' ``resamp_interp`` / ``resamp_decim`` / ``resamp_freq`` (--resamp-*).
+        ``fec``: coded link of ofdm_demod, ``True`` or ``dict(interleave=16)``; None: the options' ``fec`` (--fec)."""
         options = copy.copy(options)    # make a copy so we can destructively modify
+        if fec is None:
+            fec = getattr(options, "fec", None) or None
         if iq_format is None:
             iq_format = getattr(options, "iq_format", None) or "fc32"
         if iq_scale is None:
@@ -32,7 +35,7 @@ class receive_path(object):
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
                                        quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
-                                       ddc=ddc, resample=resample)
+                                       ddc=ddc, resample=resample, fec=fec)
 
         if self._verbose:
             self._print_verbage()
