@@ -1115,6 +1115,56 @@ int ofdm_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, const int8_t *
  * is unchanged. */
 int ofdm_fec_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- soft-decision receive: per-bit reliabilities of the delivered packets (no reference counterpart) -----------------
+ * Off by default; ofdm_set_rx_soft(h, &cfg) holds for the following ofdm_rx calls, ofdm_set_rx_soft(h, NULL) turns it
+ * off and frees its buffer.  With it on, every packet ofdm_rx delivers (CRC failures included) also gets
+ * 8 * payload_len int8 values in a buffer the handle owns, in the order ofdm_fec_decode_soft reads: value 8 m + k
+ * belongs to bit 7 - k of payload byte m, v > 0 means the bit is 1, 0 is an erasure, -128 never occurs.
+ * ofdm_rx_fec_decode_soft decodes them where they lie.  Additions only: OFDM_ABI_VERSION and the OFDM_K_* table are
+ * unchanged, with the option off nothing new launches, allocates or copies, and no existing kernel changes: a call
+ * with it on runs the demodulator's tap pass with the sink's rows requested internally, the CSI instantiation for the
+ * equaliser rows, and one kernel more (k_soft_demap).  Independent of ofdm_set_taps, ofdm_set_rx_quality and
+ * ofdm_set_rx_csi, which keep answering exactly as set (ofdm_tap(OFDM_TAP_RX_SINK) still needs the caller's own mask).
+ *
+ * Definition.  nmap data carriers per symbol, sink column c at occupied index smap[c]; nbits bits per carrier,
+ * constellation cst[j], j < arity; the bit label of point j is j itself.  For one delivered packet: plen payload bytes
+ * (message length minus the 4 CRC bytes); s = 0, 1, ... numbers the symbols the frame sink demapped for it (the rows
+ * first_symbol + 1 ... first_symbol + nsym of the sampled symbols: the rows OFDM_TAP_RX_SINK holds for the packet);
+ * eq is the packet's ofdm_rx_csi row hinv.  All arithmetic is float32, every operation rounded separately.
+ *   carrier weight  m_i = eq[i].re^2 + eq[i].im^2;  w_i = 1 / m_i if m_i is finite and > 0, else 0
+ *   mean weight     wbar = (sum of w_smap[c] for c = 0 ... nmap-1, one sequential chain in that order) / nmap
+ *   gain            g = scale / (wbar * dmin2), dmin2 the smallest |cst[a] - cst[b]|^2 over a != b;
+ *                   if wbar is 0 or not finite, every value of the packet is 0
+ *   distances       for carrier (s, c) with x the slicer's input there: d_j = |x - cst[j]|^2, the slicer's own expression
+ *   bit b < nbits   D0 = min d_j over the points with bit b of j clear, D1 over those with it set (+inf for an empty
+ *                   class);  l = (D0 - D1) * (w_smap[c] * g);  v = rint(l) clamped to [-127, 127], NaN gives 0
+ *   placement       the sink packs LSB first: stream bit beta = (s * nmap + c) * nbits + b lies in frame byte beta >> 3
+ *                   with bit weight e = beta & 7; frame bytes 0-3 are the header; message byte mb = (beta >> 3) - 4 with
+ *                   0 <= mb < plen receives the value at index 8 mb + 7 - e, negated where bit e of whitening_mask[mb]
+ *                   is 1 (the mask ofdm_rx removes, offset 0).  Nothing is produced for the CRC bytes or beyond.
+ * Packets the deframer does not deliver get no values.  Wherever the slicer's input has no two equidistant nearest
+ * points with opposite bit b, v != 0 implies (v > 0) == the delivered payload's bit.
+ * scale sets the value of a bit at the constellation's decision distance on a carrier of mean weight (default 32).
+ *
+ * ofdm_rx_soft: the last call's values, `out` a host or device pointer by the handle's mode, cap in values; off (host,
+ * may be NULL) receives *n + 1 value offsets, packet k at [off[k], off[k+1]); out == NULL: size query.  OFDM_E_INVAL if
+ * that call ran without soft values; OFDM_E_CAPACITY (with *n and off set) if cap < off[*n].
+ * ofdm_rx_fec_decode_soft: the last call's packets through ofdm_fec_decode_soft's decoder, the values read from the
+ * handle's buffer; payloads by the handle's mode, payload_off (max_pkts + 1), ok and corrected (max_pkts) host arrays.
+ * A packet whose length is no block gives ok = 0 and no bytes.  OFDM_E_CAPACITY (with *n set) if max_pkts < *n.
+ * ofdm_rx_soft_last_ms: HIP-event time of k_soft_demap in the last ofdm_rx, which must have run with profiling on and
+ * launched it; OFDM_E_INVAL otherwise.  As ofdm_fec_last_ms: the OFDM_K_* table is unchanged. */
+typedef struct ofdm_soft_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_soft_cfg) */
+  float scale;          /* > 0, finite; 32 is the usual choice */
+} ofdm_soft_cfg;
+
+int ofdm_set_rx_soft(ofdm_handle *h, const ofdm_soft_cfg *cfg);
+int ofdm_rx_soft(ofdm_handle *h, int8_t *out, uint64_t cap, uint64_t *off, int *n);
+int ofdm_rx_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, uint8_t *payloads, uint64_t payload_cap,
+                            uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, int max_pkts, int *n);
+int ofdm_rx_soft_last_ms(ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -292,6 +292,13 @@ class ofdm_fec_cfg(C.Structure):
     ]
 
 
+class ofdm_soft_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("scale", C.c_float),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -319,6 +326,7 @@ EXPORTS = (
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms",
+    "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
 )
 
 _LIB = None
@@ -416,6 +424,10 @@ def _declare(lib):
     lib.ofdm_fec_decode.argtypes = [H, FC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p]
     lib.ofdm_fec_decode_soft.argtypes = lib.ofdm_fec_decode.argtypes
     lib.ofdm_fec_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_rx_soft.argtypes = [H, C.POINTER(ofdm_soft_cfg)]
+    lib.ofdm_rx_soft.argtypes = [H, vp, C.c_uint64, u64p, C.POINTER(C.c_int)]
+    lib.ofdm_rx_fec_decode_soft.argtypes = [H, FC, u8p, C.c_uint64, u64p, vp, u32p, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_rx_soft_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

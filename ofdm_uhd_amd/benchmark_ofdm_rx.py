@@ -70,6 +70,10 @@ def make_parser():
                       help="coded link: the file was written by benchmark_ofdm_tx --fec; every delivered packet, the "
                            "CRC-failed ones included, goes through the Viterbi decoder on the GPU and is accounted by "
                            "the CRC inside the code [default=%default]")
+    parser.add_option("", "--fec-soft", action="store_true", default=False,
+                      help="--fec with soft decisions: the receiver hands the decoder one reliability per coded bit, "
+                           "weighted by each carrier's channel gain, where --fec hands it the sliced bytes "
+                           "[default=%default]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -151,6 +155,8 @@ def main(argv=None):
     if len(args) != 0:
         parser.print_help(sys.stderr)
         sys.exit(1)
+    if options.fec_soft:
+        options.fec = True
     if options.fec and (options.resamp_freqs is not None or options.ddc_freqs is not None):
         parser.error("--fec does not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:

@@ -17,6 +17,7 @@
 #include "rx_sync.h"
 #include "rx_demod.h"
 #include "rx_deframe.h"
+#include "rx_soft.h"
 #include "rx_state.h"
 #include "sense.h"
 #include "stream_hist.h"
@@ -1007,3 +1008,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_tx_resamp_bank.inc"
 #include "engine_multipath.inc"
 #include "engine_fec.inc"
+#include "engine_soft.inc"

@@ -89,10 +89,12 @@ extern "C" int ofdm_fec_encode(ofdm_handle* h, const ofdm_fec_cfg* cfg, const ui
   return fec_finish(h, f, st, timing);  // (synchronises: the staged block table is the caller's again)
 }
 
-// `unit` input items per coded byte: 1 (hard bytes) or 8 (int8 values)
+// `unit` input items per coded byte: 1 (hard bytes) or 8 (int8 values).  in_on_device: the input blob is device memory
+// whatever the handle's pointer mode (the handle's own soft values: ofdm_rx_fec_decode_soft)
 template <bool SOFT>
 static int fec_decode_impl(ofdm_handle* h, const ofdm_fec_cfg* cfg, const uint8_t* in, const uint64_t* in_off, const uint32_t* coded_len,
-                           int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off, uint8_t* ok, uint32_t* corrected) {
+                           int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off, uint8_t* ok, uint32_t* corrected,
+                           bool in_on_device = false) {
   if (!h) return OFDM_E_INVAL;
   FecState& f = h->fec;
   if (nblk < 0 || (nblk && (!in || !in_off || !coded_len || !ok || !corrected)) || !payload_off) FAIL(h, OFDM_E_INVAL, "null argument");
@@ -120,10 +122,12 @@ static int fec_decode_impl(ofdm_handle* h, const ofdm_fec_cfg* cfg, const uint8_
   HIPCHK(h, f.d_ok.ensure((size_t)nblk));
   HIPCHK(h, f.d_corr.ensure(sizeof(uint32_t) * (size_t)nblk));
   if (!h->dev_ptrs) {
-    HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
-    HIPCHK(h, hipMemcpyAsync(f.d_in.p, in, extent, hipMemcpyHostToDevice, st));
+    if (!in_on_device) {
+      HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
+      HIPCHK(h, hipMemcpyAsync(f.d_in.p, in, extent, hipMemcpyHostToDevice, st));
+      d_in = f.d_in.as<uint8_t>();
+    }
     HIPCHK(h, f.d_out.ensure(std::max<uint64_t>(total, 1)));
-    d_in = f.d_in.as<uint8_t>();
     d_out = f.d_out.as<uint8_t>();
   }
   // every block in flight owns `stride` decision words; the workspace is bounded, a larger batch goes in slices

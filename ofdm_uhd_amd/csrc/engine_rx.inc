@@ -819,7 +819,7 @@ static int make_demod_params(RxCall& c) {
     HIPCHK(h, rx.qual_frame.ensure(c.nframes * sizeof(FrameQuality)));
     dq.qual = rx.qual_frame.as<FrameQuality>();
   }
-  if (rx.csi_on) {
+  if (rx.csi_on || rx.soft_on) {  // (soft-decision receive weighs the carriers by the frame's own equaliser row)
     rx.csi_stride = (h->occ + 3) & ~3;
     HIPCHK(h, rx.csi_frame.ensure(csi_bytes(c.nframes, (uint64_t)rx.csi_stride)));
     c.csi_fr = csi_carve(rx.csi_frame, c.nframes, (uint64_t)rx.csi_stride);  // per-frame rows
@@ -900,7 +900,8 @@ static int rx_chains(RxCall& c) {
 static int rx_tap_pass(RxCall& c) {
   ofdm_handle* h = c.h;
   RxState& rx = h->rx;
-  const uint32_t tapm = h->tap_mask;
+  // (soft-decision receive reads the sink's rows: it asks for them whatever the caller's mask says)
+  const uint32_t tapm = h->tap_mask | (rx.soft_on ? (1u << OFDM_TAP_RX_SINK) : 0u);
   auto on = [&](int tap) { return (tapm >> tap) & 1u; };
   const uint64_t nsamples = c.nsamples, nsym = c.nsym;
   if (on(OFDM_TAP_RX_SIGMIX) || on(OFDM_TAP_RX_NCO)) {
@@ -1065,6 +1066,56 @@ static int rx_outputs(RxCall& c) {
   return OFDM_OK;
 }
 
+// Soft-decision receive: the values of the packets k_deframe_write kept, 8 per payload byte at 8 times the payload's
+// offset, from the tap pass's sink rows and the frames' equaliser rows (rx_soft.h).  Such a call reads its counts as it
+// goes (rx_counts_on_device), so the packet list is final here.
+static int rx_soft_values(RxCall& c) {
+  ofdm_handle* h = c.h;
+  RxState& rx = h->rx;
+  if (!rx.soft_on || c.npk_ub == 0) return OFDM_OK;
+  HIPCHK(h, rx.soft_vals.ensure(std::max<uint64_t>(soft_values(c.nbytes), 16)));
+  SoftParams sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.sink = rx.tap_sink.as<c32>();
+  sp.sink_rows = c.nsym;
+  sp.sym_base = rx.sym_base.as<uint64_t>();
+  sp.eq = c.csi_fr.eq;
+  sp.eq_stride = rx.csi_stride;
+  sp.smap = h->d_smap.as<int16_t>();
+  sp.cst = h->d_const.as<c32>();
+  sp.occ = h->occ;
+  sp.nmap = h->nmap;
+  sp.nbits = h->nbits;
+  sp.arity = (int)h->cfg.arity;
+  sp.scale = rx.soft_scale;
+  sp.dmin2 = rx.soft_dmin2;
+  sp.out = rx.soft_vals.as<int8_t>();
+  if (sp.nbits < 1 || sp.nbits > (int)SOFT_MAX_BITS || sp.arity > (1 << SOFT_MAX_BITS) || sp.nmap < 1)
+    FAIL(h, OFDM_E_INVAL, "soft-decision receive needs 1 to 8 bits per carrier");
+  const bool timing = h->prof.on;
+  if (timing) {
+    if (!rx.soft_ev_a) {
+      HIPCHK(h, hipEventCreate(&rx.soft_ev_a));
+      HIPCHK(h, hipEventCreate(&rx.soft_ev_b));
+    }
+    HIPCHK(h, hipEventRecord(rx.soft_ev_a, h->stream));
+  }
+  const dim3 grid((unsigned)c.nframes), block(SOFT_THREADS);
+  const size_t shmem = (size_t)sp.nmap * sizeof(float);
+  switch (sp.nbits) {  // (the kernel unrolls its per-bit work to the constellation's bits)
+#define SOFT_LAUNCH(NB) \
+  case NB: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_soft_demap<NB>), grid, block, shmem, h->stream, c.fq, sp); break;
+    SOFT_LAUNCH(1) SOFT_LAUNCH(2) SOFT_LAUNCH(3) SOFT_LAUNCH(4) SOFT_LAUNCH(5) SOFT_LAUNCH(6) SOFT_LAUNCH(7) SOFT_LAUNCH(8)
+#undef SOFT_LAUNCH
+  }
+  HIPCHK(h, hipGetLastError());
+  if (timing) {
+    HIPCHK(h, hipEventRecord(rx.soft_ev_b, h->stream));
+    rx.soft_timed = true;  // (read after the call's final synchronisation: ofdm_rx_soft_last_ms)
+  }
+  return OFDM_OK;
+}
+
 // The final read-back (dyn: the first time the host learns the frame and packet counts, hence the capacity check and
 // the payload copy here) and what the call leaves for its accessors.
 static int rx_finish(RxCall& c) {
@@ -1090,6 +1141,11 @@ static int rx_finish(RxCall& c) {
   if (rx.csi_on) {
     rx.csi_n = npk;
     rx.csi_ok.assign(c.crc_ok, c.crc_ok + npk);
+  }
+  if (rx.soft_on && npk > 0) {
+    rx.soft_off.resize(npk + 1);
+    soft_plan_offsets(c.payload_off, npk, rx.soft_off.data());
+    rx.soft_len.assign(c.payload_len, c.payload_len + npk);
   }
   if (c.stats) {
     uint64_t nok = 0;
@@ -1118,6 +1174,10 @@ static int rx_begin(RxCall& c) {
   rx.csi_valid = rx.csi_on;
   rx.csi_n = 0;
   rx.csi_ok.clear();
+  rx.soft_valid = rx.soft_on;
+  rx.soft_timed = false;
+  rx.soft_off.assign(1, 0);
+  rx.soft_len.clear();
   if (c.stats) c.stats->samples = c.nsamples;
   return OFDM_OK;
 }
@@ -1152,7 +1212,7 @@ static int rx_input(RxCall& c) {
 static bool rx_counts_on_device(const ofdm_handle* h) {
   const uint32_t probes = (1u << OFDM_TAP_RX_SIGMIX) | (1u << OFDM_TAP_RX_NCO) | (1u << OFDM_TAP_RX_FFT) | (1u << OFDM_TAP_RX_ACQ) |
                           (1u << OFDM_TAP_RX_SINK) | (1u << OFDM_TAP_RX_SAMPLER) | (1u << OFDM_TAP_RX_PACKETS);
-  return !h->rx.nco_ref_on && !(h->tap_mask & probes) && !getenv("OFDM_RX_SYNCS");
+  return !h->rx.nco_ref_on && !(h->tap_mask & probes) && !h->rx.soft_on && !getenv("OFDM_RX_SYNCS");
 }
 
 static int rx_impl(RxCall& c) {
@@ -1177,6 +1237,7 @@ static int rx_impl(RxCall& c) {
     if (!c.dyn && ((rc = rx_read_counts(c)) || (rc = rx_check_capacity(c)))) return rc;
     if ((rc = rx_outputs(c))) return rc;
   }
+  if ((rc = rx_soft_values(c))) return rc;
   return rx_finish(c);
 }
 

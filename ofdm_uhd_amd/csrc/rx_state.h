@@ -10,7 +10,7 @@
   X(sym_base) X(res) X(raw) X(invalid) X(chain_list) X(key) X(pos) X(out_payload) X(out_off) X(out_len) X(out_ok)          \
   X(out_pos) X(inc_acc) X(Phi_u) X(peaks2) X(peak_P2) X(fstep) X(pre_inv) X(stash_peaks) X(stash_P) X(tap_fft) X(tap_acq)  \
   X(tap_sink) X(tap_demapped) X(raw_tap) X(raw_lens) X(raw_pos) X(tap_sampler) X(tap_sigmix) X(tap_nco) X(qual_frame)      \
-  X(qual_out) X(csi_frame) X(csi_rows) X(csi_part) X(csi_sum) X(run_rows)
+  X(qual_out) X(csi_frame) X(csi_rows) X(csi_part) X(csi_sum) X(run_rows) X(soft_vals)
 
 struct RxState {
 #define X(name) DevBuf name;
@@ -47,7 +47,19 @@ struct RxState {
   uint64_t csi_n = 0, csi_rows_cap = 0;
   int csi_stride = 0;
   std::vector<uint8_t> csi_ok;
+  // soft-decision receive (ofdm_set_rx_soft): on for the following calls; whether the last call ran with it, and where
+  // its packets' values lie in soft_vals (device; intact until the next call): value offsets [n + 1], payload lengths [n]
+  bool soft_on = false, soft_valid = false;
+  float soft_scale = 32.0f, soft_dmin2 = 0.0f;
+  std::vector<uint64_t> soft_off;
+  std::vector<uint32_t> soft_len;
+  hipEvent_t soft_ev_a = nullptr, soft_ev_b = nullptr;
+  double soft_ms = 0.0;
+  bool soft_timed = false;  // soft_ms is of the last call's k_soft_demap
   void release() {
+    if (soft_ev_a) (void)hipEventDestroy(soft_ev_a);
+    if (soft_ev_b) (void)hipEventDestroy(soft_ev_b);
+    soft_ev_a = soft_ev_b = nullptr;
 #define X(name) name.release();
     RX_DEVBUFS(X)
 #undef X

@@ -905,6 +905,78 @@ class Engine(object):
         """HIP-event time of k_fec_encode / k_fec_decode in the last fec call (needs prof_enable())."""
         return self._stage_last_ms("fec")
 
+    # -- soft-decision receive: per-bit reliabilities of the delivered packets, decoded where they lie ---------------
+    def set_rx_soft(self, soft=True):
+        """Soft values for the following rx() / rx_device() calls: ``True`` (scale 32), ``dict(scale=)`` or a number
+        (the scale); ``None`` / ``False`` turns them off and frees their buffer."""
+        if soft is None or soft is False:
+            self._check(self._lib.ofdm_set_rx_soft(self._h, None))
+            return
+        if isinstance(soft, dict):
+            unknown = set(soft) - {"scale"}
+            if unknown:
+                raise ValueError("unknown soft option(s): %s" % ", ".join(sorted(unknown)))
+            scale = soft.get("scale", 32.0)
+        else:
+            scale = 32.0 if soft is True else soft
+        cfg = _abi.ofdm_soft_cfg(struct_size=C.sizeof(_abi.ofdm_soft_cfg), scale=float(scale))
+        self._check(self._lib.ofdm_set_rx_soft(self._h, C.byref(cfg)))
+
+    def _rx_soft_offsets(self):
+        n = C.c_int(0)
+        self._check(self._lib.ofdm_rx_soft(self._h, None, 0, None, C.byref(n)))
+        off = np.zeros(n.value + 1, np.uint64)
+        self._check(self._lib.ofdm_rx_soft(self._h, None, 0, off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        return n.value, off
+
+    def rx_soft(self):
+        """Host mode: the soft values of the packets the last rx() returned, in the same order: a list of int8 arrays,
+        8 * len(payload) values each, MSB first (v > 0: the bit is 1; 0: an erasure).  ValueError if that call ran
+        without set_rx_soft()."""
+        assert not self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        vals = np.zeros(max(int(off[n]), 1), np.int8)
+        if off[n]:
+            self._check(self._lib.ofdm_rx_soft(self._h, _ptr(vals), len(vals), None, C.byref(C.c_int(0))))
+        return [vals[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+
+    def rx_soft_device(self, out_ptr, cap):
+        """Device mode: copies the last call's values to the device buffer ``out_ptr`` (``cap`` values); returns the
+        n + 1 value offsets (uint64, host)."""
+        assert self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        self._check(self._lib.ofdm_rx_soft(self._h, C.c_void_p(out_ptr), int(cap), None, C.byref(C.c_int(0))))
+        return off
+
+    def _rx_fec_decode_soft(self, fec, out_ptr, out_cap, n):
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr = np.zeros(max(n, 1), np.uint32)
+        self._check(self._lib.ofdm_rx_fec_decode_soft(self._h, C.byref(self._fec_cfg(fec)), out_ptr, int(out_cap),
+                                                      poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
+                                                      corr.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(C.c_int(0))))
+        return poff, ok[:n], corr[:n]
+
+    def rx_fec_decode_soft(self, fec=None):
+        """Host mode: the packets the last rx() returned, decoded from the handle's own soft values (they never visit
+        the host) -> list of (ok, payload, corrected) as fec_decode_soft.  Needs set_rx_soft() before that rx()."""
+        assert not self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        out = np.zeros(max(int(off[n]) // 16, 1), np.uint8)
+        poff, ok, corr = self._rx_fec_decode_soft(fec, _ptr(out), len(out), n)
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(n)]
+
+    def rx_fec_decode_soft_device(self, payload_ptr, payload_cap, fec=None):
+        """Device mode: the same into the device buffer ``payload_ptr``; returns (payload offsets uint64[n + 1],
+        ok uint8[n], corrected uint32[n]) as host arrays."""
+        assert self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._rx_fec_decode_soft(fec, C.c_void_p(payload_ptr), payload_cap, n)
+
+    def rx_soft_last_ms(self):
+        """HIP-event time of k_soft_demap in the last rx() / rx_device() (needs prof_enable())."""
+        return self._stage_last_ms("rx_soft")
+
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""
         n = C.c_int(0)

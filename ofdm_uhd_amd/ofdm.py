@@ -227,7 +227,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None, resample=None, fec=None):
+                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -252,6 +252,10 @@ class ofdm_demod(object):
             returned list then carry the decoded payload and the verdict of the CRC inside the code; ``last_fec`` holds
             (outer_ok, corrected) per packet -- what the packet CRC said and how many coded bits the decoder changed;
             ``n_ok`` counts decoded verdicts.  Link quality and channel state describe the packets as received
+        @param soft: soft-decision receive, ``True`` or ``dict(scale=32)`` (Engine.set_rx_soft): ``last_soft`` holds one
+            int8 array per packet the last work() / feed() / flush() returned, 8 values per payload byte.  With ``fec``
+            set as well the decoder takes those values on the GPU (Engine.rx_fec_decode_soft) in place of the hard
+            bytes; ``last_fec`` keeps its meaning.  Without ``fec`` it only fills ``last_soft``
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -264,6 +268,8 @@ class ofdm_demod(object):
         self._quality_callback = quality_callback
         self._fec = _fec.as_cfg(fec)
         self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec only)
+        self._soft = None if (soft is None or soft is False) else soft
+        self.last_soft = []          # int8 values of the packets the last work() / feed() returned (soft only)
 
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
@@ -296,6 +302,8 @@ class ofdm_demod(object):
             self._engine.set_rx_csi(True)
         self.last_csi = self._csi_rows(None, [])
         self.reset_carrier_report()
+        if self._soft is not None:
+            self._engine.set_rx_soft(self._soft)
         self._log = bool(getattr(options, "log", False))
         if self._log:
             self._engine.set_taps(engine._abi.TAP_RX_FFT, engine._abi.TAP_RX_ACQ, engine._abi.TAP_RX_SINK,
@@ -349,15 +357,24 @@ class ofdm_demod(object):
             self._csi_accumulate(pkts)
         if self._log:
             self._write_logs()
+        if self._soft is not None:
+            self.last_soft = self._engine.rx_soft()
         pkts = self._decode(pkts)
         self._deliver(pkts)
         return pkts
 
-    def _decode(self, pkts):
-        """The coded link's receiving end: the delivered packets' bytes, whatever their CRC said, through the decoder."""
+    def _decode(self, pkts, sel=None):
+        """The coded link's receiving end: the delivered packets' bytes, whatever their CRC said, through the decoder
+        (``soft``: their soft values, on the GPU where the last rx() left them; ``sel`` picks the delivered ones among
+        that call's packets)."""
         if self._fec is None:
             return pkts
-        dec = self._engine.fec_decode([p for _, p in pkts], self._fec) if pkts else []
+        if self._soft is not None:
+            dec = self._engine.rx_fec_decode_soft(self._fec) if pkts else []
+            if sel is not None:
+                dec = [dec[i] for i in sel]
+        else:
+            dec = self._engine.fec_decode([p for _, p in pkts], self._fec) if pkts else []
         self.last_fec = [(bool(ok), c) for (ok, _), (_, _, c) in zip(pkts, dec)]
         return [(ok, p) for ok, p, _ in dec]
 
@@ -457,6 +474,7 @@ class ofdm_demod(object):
         out = []
         qual = []
         sel, rows = [], None    # packets of this call that are delivered now (rows of its channel state)
+        soft = []
         if len(buf) and horizon > self._s_final:
             eng = self._engine
             # the settled past: flags inside this buffer keep their known steps (whatever the call re-detects
@@ -478,6 +496,7 @@ class ofdm_demod(object):
                 first_sym[int(fl[j])] = self._stream_symbol(int(fl[j]))
             recs = eng.rx_quality() if self._quality_callback is not None else None
             rows = eng.rx_csi() if self._csi else None
+            soft = eng.rx_soft() if self._soft is not None else []
             for i, ((ok, payload), p) in enumerate(zip(pkts, pos)):
                 if self._s_final < p <= horizon:
                     out.append((ok, payload))
@@ -508,7 +527,9 @@ class ofdm_demod(object):
         if self._csi:
             self.last_csi = self._csi_rows(rows, sel)
             self._csi_accumulate(out)
-        out = self._decode(out)
+        if self._soft is not None:
+            self.last_soft = [soft[i] for i in sel]
+        out = self._decode(out, sel)
         self._deliver(out)
         return out
 
