@@ -1089,13 +1089,35 @@ int ofdm_multipath_last_ms(const ofdm_handle *h, double *ms);
  * OFDM_E_INVAL: bad struct_size, interleave_cols not one of 1, 2, 4, 8, 16, a payload longer than
  * OFDM_FEC_MAX_PAYLOAD (encode), a null argument.  OFDM_E_CAPACITY: the output blob is too small.
  * The decision workspace (8 bytes per trellis step and block in flight) belongs to the handle and is bounded; a large
- * batch is decoded in slices. */
+ * batch is decoded in slices.
+ *
+ * Punctured rates (ofdm_fec_cfg.rate, both ends configured alike).  rate = OFDM_FEC_RATE_1_2 (0) is everything above,
+ * unchanged: the same kernels and launches, nothing new allocates or copies.  Any value above OFDM_FEC_RATE_5_6 is
+ * OFDM_E_INVAL.  Otherwise the mother coded bits c[0 .. 2T), 2T = 16n + 76 (without the pad), are thinned by the 802.11
+ * patterns: bit i is kept when (i mod period) lies in the keep set,
+ *   2/3: period 4, keep {0, 1, 2};   3/4: period 6, keep {0, 1, 2, 5};   5/6: period 10, keep {0, 1, 2, 5, 6, 9}.
+ * Kept stream p[q] = c[i_q], i_q the q-th kept index in ascending order, K kept bits; the block has P = ceil(K / 8)
+ * bytes, p[q] = 0 for K <= q < 8P.  P is strictly increasing in n, so a received length names at most one n; a length
+ * P never reaches (or above P(OFDM_FEC_MAX_PAYLOAD)) is no block.  Interleaver of the punctured block: C' = the largest
+ * power of two that is <= interleave_cols and divides 8P (8 where interleave_cols is 16 and P is odd, interleave_cols
+ * otherwise), R' = 8P / C', sent bit j = p[(j mod R') * C' + j / R'], packed MSB first.
+ * Decoding: one signed value v per sent bit of the punctured block; the C' interleaver is undone, mother value
+ * d[i_q] = v_q for q < K, every other mother position (punctured ones and the pad) is 0, the values v_q, q >= K, are
+ * ignored; then the decoder defined above runs on d, unchanged (corrected counts positions with d != 0 only).
+ * All lengths and offsets of coded blocks, in and out, are those of the punctured blocks.  The mother values of the
+ * blocks in flight (8 bytes per mother byte) live in a buffer the handle owns, cut into the same slices as the decision
+ * workspace. */
 #define OFDM_FEC_MAX_PAYLOAD 2040
 #define OFDM_FEC_MAX_CODED 4090
+#define OFDM_FEC_RATE_1_2 0
+#define OFDM_FEC_RATE_2_3 1
+#define OFDM_FEC_RATE_3_4 2
+#define OFDM_FEC_RATE_5_6 3
 typedef struct ofdm_fec_cfg {
   uint32_t struct_size;      /* = sizeof(ofdm_fec_cfg) */
   uint32_t interleave_cols;  /* 1, 2, 4, 8 or 16 */
-  uint32_t reserved[6];      /* 0 */
+  uint32_t rate;             /* OFDM_FEC_RATE_*; 0 = rate 1/2, the mother code */
+  uint32_t reserved[5];      /* 0 */
 } ofdm_fec_cfg;
 
 /* pure host functions, usable without a GPU: 2n + 10, and its inverse (OFDM_E_INVAL for a length that is no block) */
@@ -1114,6 +1136,16 @@ int ofdm_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, const int8_t *
  * with profiling on (ofdm_prof_enable) and launched; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table
  * is unchanged. */
 int ofdm_fec_last_ms(const ofdm_handle *h, double *ms);
+/* The two length functions at a rate, usable without a GPU: P(n) and its inverse (OFDM_E_INVAL for a rate above
+ * OFDM_FEC_RATE_5_6, a payload above OFDM_FEC_MAX_PAYLOAD, a length that is no block at that rate, a null pointer).
+ * With rate 0 they are ofdm_fec_coded_len / ofdm_fec_payload_len. */
+int ofdm_fec_coded_len_rate(uint32_t rate, uint32_t payload_len, uint32_t *coded_len);
+int ofdm_fec_payload_len_rate(uint32_t rate, uint32_t coded_len, uint32_t *payload_len);
+/* HIP-event time of k_fec_puncture / k_fec_depuncture (all slices) alone in the last fec call, which must have run at a
+ * punctured rate with profiling on and launched; OFDM_E_INVAL otherwise.  ofdm_fec_last_ms keeps reporting the encoder /
+ * decoder: k_fec_decode's slices in a punctured decode; in a punctured encode k_fec_puncture is the encoder, and both
+ * functions report it. */
+int ofdm_fec_punct_last_ms(const ofdm_handle *h, double *ms);
 
 /* --- soft-decision receive: per-bit reliabilities of the delivered packets (no reference counterpart) -----------------
  * Off by default; ofdm_set_rx_soft(h, &cfg) holds for the following ofdm_rx calls, ofdm_set_rx_soft(h, NULL) turns it

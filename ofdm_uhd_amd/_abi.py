@@ -29,6 +29,7 @@ OFDM_MULTIPATH_MAX_TONES = 4
 OFDM_MULTIPATH_MAX_DELAY = 1023
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
+OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -288,7 +289,8 @@ class ofdm_fec_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("interleave_cols", C.c_uint32),
-        ("reserved", C.c_uint32 * 6),
+        ("rate", C.c_uint32),
+        ("reserved", C.c_uint32 * 5),
     ]
 
 
@@ -325,7 +327,7 @@ EXPORTS = (
     "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
-    "ofdm_fec_last_ms",
+    "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
 )
 
@@ -424,6 +426,9 @@ def _declare(lib):
     lib.ofdm_fec_decode.argtypes = [H, FC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p]
     lib.ofdm_fec_decode_soft.argtypes = lib.ofdm_fec_decode.argtypes
     lib.ofdm_fec_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_fec_coded_len_rate.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    lib.ofdm_fec_payload_len_rate.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    lib.ofdm_fec_punct_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_rx_soft.argtypes = [H, C.POINTER(ofdm_soft_cfg)]
     lib.ofdm_rx_soft.argtypes = [H, vp, C.c_uint64, u64p, C.POINTER(C.c_int)]
     lib.ofdm_rx_fec_decode_soft.argtypes = [H, FC, u8p, C.c_uint64, u64p, vp, u32p, C.c_int, C.POINTER(C.c_int)]

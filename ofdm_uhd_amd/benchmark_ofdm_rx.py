@@ -74,6 +74,9 @@ def make_parser():
                       help="--fec with soft decisions: the receiver hands the decoder one reliability per coded bit, "
                            "weighted by each carrier's channel gain, where --fec hands it the sliced bytes "
                            "[default=%default]")
+    parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
+                      help="coded link at this rate, as benchmark_ofdm_tx --fec-rate wrote it (implies --fec; works "
+                           "with --fec-soft) [default=1/2]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -157,6 +160,8 @@ def main(argv=None):
         sys.exit(1)
     if options.fec_soft:
         options.fec = True
+    if options.fec_rate:
+        options.fec = dict(rate=options.fec_rate)   # (what receive_path hands to ofdm_demod(fec=))
     if options.fec and (options.resamp_freqs is not None or options.ddc_freqs is not None):
         parser.error("--fec does not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:

@@ -58,6 +58,9 @@ def make_parser():
                       help="coded link: protect every payload (at most 2040 bytes) with the rate-1/2 K=7 convolutional "
                            "code and interleaver, encoded on the GPU; demodulate with benchmark_ofdm_rx --fec "
                            "[default=%default]")
+    parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
+                      help="coded link at this rate: the K=7 code punctured by the 802.11 patterns (implies --fec; "
+                           "demodulate with the same benchmark_ofdm_rx --fec-rate) [default=1/2]")
     _options.add_tx_resamp_options(parser)
     parser.add_option("", "--tx-resamp-freqs", default=None,
                       help="with --tx-resamp-interp / --tx-resamp-decim, instead of --tx-resamp-freq: comma-separated "
@@ -123,6 +126,8 @@ def main(argv=None):
     if len(args) != 0:
         parser.print_help()
         sys.exit(1)
+    if options.fec_rate:
+        options.fec = dict(rate=options.fec_rate)   # (what transmit_path hands to ofdm_mod(fec=))
     if options.tx_resamp_freqs is not None:
         return _main_tx_resamp_bank(parser, options)
 

@@ -33,6 +33,7 @@
 #include "pfb_synth.h"
 #include "multipath.h"
 #include "fec.h"
+#include "fec_punct.h"
 
 static std::string g_create_error;
 
@@ -130,6 +131,7 @@ struct ofdm_handle {
   TxResampBankState tx_resamp_bank;  // the same at a rational rate (tx_resamp_bank.h / engine_tx_resamp_bank.inc)
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
+  FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -565,6 +567,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->tx_resamp_bank.release();
   h->multipath.release();
   h->fec.release();
+  h->fec_punct.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);

@@ -1,0 +1,134 @@
+// fec_punct.h -- the punctured rates 2/3, 3/4 and 5/6 of the coded-link layer (fec.h): the layer that leaves coded bits
+// out on the way to the air and puts erasures back in front of the decoder.  k_fec_encode and k_fec_decode are not
+// touched: the encoder here forms only the kept parities, the decoder reads the expanded block as any other soft block.
+// Definition: include/ofdm_hip.h ("punctured rates"), arithmetic: punct_plan.h, DESIGN.md section 7.
+//
+//   kept bit q   = mother bit punct_unrank(q), q < K; zero for K <= q < 8P
+//   sent bit j   = kept bit (j mod R') * C' + j / R', R' = 8P / C'
+#pragma once
+#include "fec.h"
+#include "punct_plan.h"
+
+#define FEC_DEPUNCT_THREADS 256
+
+// what the punctured rates keep on a handle next to FecState: nothing of it exists until a call at such a rate
+struct FecPunctState {
+  DevBuf d_pblk, d_mother;        // k_fec_depuncture's block table; the mother values of one slice
+  std::vector<FecBlk> pblk;
+  std::vector<hipEvent_t> ev;     // three per slice of a timed decode
+  double last_ms = 0.0;
+  bool timed = false;             // last_ms is of the last fec call
+  void release() {
+    d_pblk.release();
+    d_mother.release();
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    ev.clear();
+  }
+};
+
+// ---------------------------------------------------------------------------------
+// Punctured encoder: one workgroup per block, as k_fec_encode and with its helpers -- the payload goes to LDS once, the
+// CRC is summed there, then every thread composes whole output bytes.  A sent bit is found through the C' interleaver
+// and the pattern's unrank, and is one parity over seven info bits: the mother block is never formed, a dropped bit
+// costs nothing.  No atomics: each output byte has one writer.  blk: {payload offset, block offset, payload bytes}.
+// ---------------------------------------------------------------------------------
+template <uint32_t RATE>
+__global__ void __launch_bounds__(FEC_ENC_THREADS) k_fec_puncture(const uint8_t* __restrict__ payloads, const FecBlk* __restrict__ blk,
+                                                                  uint8_t* __restrict__ coded, const uint32_t* __restrict__ crc_table,
+                                                                  const uint32_t* __restrict__ xp8, uint32_t lgC) {
+  __shared__ uint8_t info[FEC_INFO_LDS];
+  __shared__ uint32_t red[FEC_ENC_THREADS / WAVE];
+  const FecBlk b = blk[blockIdx.x];
+  const uint32_t n = b.len;  // <= OFDM_FEC_MAX_PAYLOAD (the host refuses longer ones)
+  const uint8_t* src = payloads + b.in_off;
+  uint8_t* out = coded + b.out_off;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < FEC_INFO_LDS; i += FEC_ENC_THREADS) {
+    const int k = i - 8;
+    info[i] = (k >= 0 && (uint32_t)k < n) ? src[k] : (uint8_t)0;
+  }
+  __syncthreads();
+  uint32_t acc = fec_crc_part<8>(info, n, tid, crc_table, xp8);
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) acc ^= __shfl_xor(acc, d, WAVE);
+  if (lane_id() == 0) red[wave_id()] = acc;
+  __syncthreads();
+  if (tid < 4) {
+    uint32_t crc32 = 0;
+#pragma unroll
+    for (int w = 0; w < FEC_ENC_THREADS / WAVE; w++) crc32 ^= red[w];
+    info[8u + n + (uint32_t)tid] = (uint8_t)(crc32 >> (8 * (3 - tid)));  // struct.pack(">I", crc)
+  }
+  __syncthreads();
+
+  const uint32_t K = punct_kept_bits<RATE>(n);
+  const uint32_t nout = (K + 7u) >> 3;
+  const uint32_t lgc = punct_log2_cols(lgC, nout);
+  const uint32_t R = (8u * nout) >> lgc;
+  for (uint32_t ob = (uint32_t)tid; ob < nout; ob += FEC_ENC_THREADS) {
+    uint32_t col = (8u * ob) / R, row = 8u * ob - col * R;
+    uint32_t by = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t q = (row << lgc) + col;
+      uint32_t bit = 0;
+      if (q < K) {
+        const uint32_t i = punct_unrank<RATE>(q);
+        bit = (uint32_t)__popc(fec_register(info, i >> 1) & ((i & 1u) ? FEC_MASK_B : FEC_MASK_A)) & 1u;
+      }
+      by = (by << 1) | bit;
+      if (++row == R) {
+        row = 0;
+        col++;
+      }
+    }
+    out[ob] = (uint8_t)by;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Depuncture: one workgroup per block.  Expands a punctured block into the 8 (2n + 10) int8 mother values, in coded
+// order, that k_fec_decode<true> reads at one column.  Every thread owns whole 16-byte groups of the output: mother
+// position i is zero where the pattern dropped it or the pad lies, else the value of kept bit rank(i), fetched from
+// where the C' interleaver sent it; a group leaves in one 16-byte store.  The divisions by the period are by
+// compile-time constants.  blk: {input offset (bytes hard, values soft), offset into the mother values, punctured
+// bytes P, mother bytes 2n + 10 or 0}: a block whose length is no block at this rate (pad = 0) writes nothing, and the
+// decoder's own table calls it no block.
+// ---------------------------------------------------------------------------------
+template <uint32_t RATE, bool SOFT>
+__global__ void __launch_bounds__(FEC_DEPUNCT_THREADS) k_fec_depuncture(const uint8_t* __restrict__ in_all, const FecBlk* __restrict__ blk,
+                                                                        int8_t* __restrict__ mother, uint32_t lgC) {
+  const FecBlk b = blk[blockIdx.x];
+  const uint32_t mlen = b.pad;
+  if (mlen == 0) return;
+  const uint32_t P = b.len;                // = punct_block_len<RATE>(n) (the host found n from it)
+  const uint32_t ncoded = 8u * mlen - 4u;  // 2T; the four positions behind are the pad
+  const uint32_t lgc = punct_log2_cols(lgC, P);
+  const uint32_t R = (8u * P) >> lgc;
+  const uint8_t* in = in_all + b.in_off;
+  uint4* out = reinterpret_cast<uint4*>(mother + b.out_off);  // 16-byte aligned: the host's strides are multiples of 16
+  const uint32_t ngroups = mlen >> 1;                          // 8 mlen / 16, mlen is even
+  for (uint32_t g = threadIdx.x; g < ngroups; g += FEC_DEPUNCT_THREADS) {
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const uint32_t i = 16u * g + 4u * (uint32_t)k + (uint32_t)e;
+        int v = 0;
+        if (i < ncoded && punct_kept<RATE>(i)) {
+          const uint32_t q = punct_rank<RATE>(i);                      // < K <= 8P
+          const uint32_t j = (q & ((1u << lgc) - 1u)) * R + (q >> lgc);  // where kept bit q was sent, < 8P
+          if (SOFT)
+            v = (int)(int8_t)in[j];
+          else
+            v = ((in[j >> 3] >> (7u - (j & 7u))) & 1u) ? 1 : -1;
+        }
+        word |= ((uint32_t)v & 0xFFu) << (8 * e);
+      }
+      w[k] = word;
+    }
+    out[g] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}

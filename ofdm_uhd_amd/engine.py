@@ -828,6 +828,13 @@ class Engine(object):
             raise ValueError("fec=False names no code")
         return cfg
 
+    @staticmethod
+    def _fec_payload_room(cfg, lens):
+        """Bytes that hold the payloads of blocks of these lengths: half a block at rate 1/2, under a whole one at the
+        punctured rates."""
+        total = int(np.asarray(lens).astype(np.int64).sum())
+        return max(total if cfg.rate else total // 2, 1)
+
     def fec_encode(self, payloads, fec=None):
         """Host mode: list of payloads (0 .. 2040 bytes each) -> list of coded blocks (2 n + 10 bytes each), the
         payloads tx() then takes.  ``fec``: None / True (16 interleaver columns), a column count, a dict of
@@ -835,7 +842,7 @@ class Engine(object):
         assert not self.device_ptrs
         cfg = self._fec_cfg(fec)
         blob, offs, lens = pack_payloads(payloads)
-        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 10 * len(payloads), 1), np.uint8)
+        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 10 * len(payloads), 1), np.uint8)   # (covers every rate)
         coff = np.zeros(len(payloads) + 1, np.uint64)
         self._check(self._lib.ofdm_fec_encode(self._h, C.byref(cfg), _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
                                               lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
@@ -871,7 +878,7 @@ class Engine(object):
         assert not self.device_ptrs
         cfg = self._fec_cfg(fec)
         blob, offs, lens = pack_payloads(blocks)
-        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
         poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode, cfg, _ptr(blob), offs, lens, _ptr(out), len(out))
         return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(blocks))]
 
@@ -888,7 +895,7 @@ class Engine(object):
         if len(vals) > 1:
             offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
         blob = np.concatenate(vals + [np.zeros(8, np.int8)])
-        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
         poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode_soft, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out),
                                           len(out))
         return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(vals))]
@@ -904,6 +911,11 @@ class Engine(object):
     def fec_last_ms(self):
         """HIP-event time of k_fec_encode / k_fec_decode in the last fec call (needs prof_enable())."""
         return self._stage_last_ms("fec")
+
+    def fec_punct_last_ms(self):
+        """HIP-event time of k_fec_puncture / k_fec_depuncture alone in the last fec call, which ran at a punctured
+        rate (needs prof_enable())."""
+        return self._stage_last_ms("fec_punct")
 
     # -- soft-decision receive: per-bit reliabilities of the delivered packets, decoded where they lie ---------------
     def set_rx_soft(self, soft=True):
@@ -962,7 +974,7 @@ class Engine(object):
         the host) -> list of (ok, payload, corrected) as fec_decode_soft.  Needs set_rx_soft() before that rx()."""
         assert not self.device_ptrs
         n, off = self._rx_soft_offsets()
-        out = np.zeros(max(int(off[n]) // 16, 1), np.uint8)
+        out = np.zeros(self._fec_payload_room(self._fec_cfg(fec), [int(off[n]) // 8]), np.uint8)
         poff, ok, corr = self._rx_fec_decode_soft(fec, _ptr(out), len(out), n)
         return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(n)]
 

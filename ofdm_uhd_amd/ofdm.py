@@ -47,10 +47,11 @@ class ofdm_mod(object):
                ``dict(interpolation=, decimation=, center_freq=0.0, taps=None)``, the engine's rational-rate transmit
                stage (tx_resample.py, Engine.tx_resamp) in the DUC's place; ``taps=None``: tx_resample.design.  Not
                together with ``duc``
-        @param fec: coded link: ``True`` or ``dict(interleave=16)`` (fec.py).  send_pkt then takes up to 2040 bytes and
-               flush() encodes the batch on the GPU (Engine.fec_encode: payload | CRC-32 through the rate-1/2, K = 7
-               convolutional code and a block interleaver, 2 n + 10 bytes) ahead of the modulator; the receiving end
-               is ofdm_demod(fec=) with the same setting.  None: the payloads go out as they are and nothing new runs
+        @param fec: coded link: ``True`` or ``dict(interleave=16, rate="1/2")`` (fec.py).  send_pkt then takes up to 2040
+               bytes and flush() encodes the batch on the GPU (Engine.fec_encode: payload | CRC-32 through the rate-1/2,
+               K = 7 convolutional code and a block interleaver, 2 n + 10 bytes; ``rate`` "2/3", "3/4" or "5/6" punctures
+               it to fec.coded_len(n, rate) bytes) ahead of the modulator; the receiving end is ofdm_demod(fec=) with
+               the same setting.  None: the payloads go out as they are and nothing new runs
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
@@ -132,7 +133,7 @@ class ofdm_mod(object):
         if self._fec is not None:
             if len(payload) > _fec.MAX_PAYLOAD:
                 raise ValueError("len(payload) must be in [0, %d]" % (_fec.MAX_PAYLOAD,))
-            self._engine.framed_len(_fec.coded_len(len(payload)))   # the coded block is what gets framed
+            self._engine.framed_len(_fec.coded_len(len(payload), self._fec))   # the coded block (at the link's rate) is what gets framed
             self._pending.append(payload)
             return
         if len(payload) + 4 > len(ofdm_packet_utils.random_mask_tuple):

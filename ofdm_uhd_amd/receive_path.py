@@ -14,13 +14,13 @@ class receive_path(object):
         reference sets on its radio: set_decim / set_center_freq, usrp_receive_path.py).
         ``resample``: rational-rate front end of ofdm_demod, ``dict(interpolation=, decimation=, center_freq=0.0,
         taps=None)``; None: the options' ``resamp_interp`` / ``resamp_decim`` / ``resamp_freq`` (--resamp-*).
-        ``fec``: coded link of ofdm_demod, ``True`` or ``dict(interleave=16)``; None: the options' ``fec`` (--fec).
+        ``fec``: coded link of ofdm_demod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
         ``soft``: soft-decision receive of ofdm_demod, ``True`` or ``dict(scale=32)``; None: the options' ``fec_soft``
         (--fec-soft), which turns the coded link on as well."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
-            fec = True if fec is None else fec
+            fec = (getattr(options, "fec", None) or True) if fec is None else fec   # (a dict where --fec-rate set one)
         if fec is None:
             fec = getattr(options, "fec", None) or None
         if iq_format is None:

@@ -29,7 +29,7 @@ class transmit_path(object):
         ``resample``: rational-rate transmit stage of ofdm_mod, ``dict(interpolation=, decimation=, center_freq=0.0,
         taps=None)``; None: the options' ``tx_resamp_interp`` / ``tx_resamp_decim`` / ``tx_resamp_freq``
         (--tx-resamp-*).
-        ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16)``; None: the options' ``fec`` (--fec)."""
+        ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec)."""
         opts = copy.copy(options)
         if fec is None:
             fec = getattr(opts, "fec", None) or None
