@@ -15,8 +15,18 @@ the rate): 16-QAM, N 512 / occ 200 / CP 128, packets of 300, 301, 257, 400, 333,
     13 dB  rate 3/4  000000 | 000000  (23 040)
     17 dB  rate 3/4  100000 | 111111
 (no decoder reported ok for a wrong payload).  At rate 5/6 the receiver's packet list on this capture is not the six
-packets at any level from 14 to 24 dB, so the CPU chain, whose bookkeeping assumes them, has no candidate: 5/6 is left
-to the clean and flip tests here."""
+packets at any level from 14 to 24 dB with noise seed 7.  A bounded search with the same chain and channel -- noise
+seeds 7 .. 12, 14 .. 24 dB in 1 dB steps, these lengths and two further sets of six (250, 399, 312, 275, 350, 288 and
+400, 260, 377, 301, 264, 345) -- found 41 of the 198 points at which the oracle delivers the six packets; soft decoding
+returned at least as many as hard at every one of them, and no decoder reported ok for a wrong payload.  With the
+lengths above:
+    seed 8   14, 15 dB        000000 | 100101, 100111
+    seed 10  14 .. 18 dB      000000 | 100101 (14 .. 16), 101111 (17, 18)
+    seed 12  14 .. 19 dB      000000 | 110001, 110101, 111101 (16 .. 18); 19 dB 010000 | 111101
+    seeds 7, 9, 11            no level
+(the second set has two points, both at 14 dB; the third has 26, among them seed 9 at 16 .. 23 dB with all six soft).
+The case taken is seed 12 at 17 dB with the lengths of the other cases: the middle of three levels with the same result,
+hard 0 of 6, soft 5 of 6.  From 20 dB up the packet list is not the six packets there."""
 import ctypes as C
 import functools
 
@@ -352,10 +362,14 @@ def test_the_command_line_takes_the_rate(tmp_path):
         assert open(out, "rb").read() == data
 
 
+def link_case(snr_db, rate, seed=sc.LINK_SEED):
+    return _link_case(snr_db, rate, seed)
+
+
 @functools.lru_cache(maxsize=None)
-def link_case(snr_db, rate):
-    """The link of soft_cases at one level and rate: one receive call with everything the soft model needs, the model's
-    values and both model decoders on them, and what ofdm_demod(fec=) returns hard and soft."""
+def _link_case(snr_db, rate, seed):
+    """The link of soft_cases at one level, rate and noise seed: one receive call with everything the soft model needs,
+    the model's values and both model decoders on them, and what ofdm_demod(fec=) returns hard and soft."""
     opt = options.default_options(modulation=sc.LINK_MOD, fft_length=sc.LINK_N, occupied_tones=sc.LINK_OCC, cp_length=sc.LINK_CP)
     pay = list(sc.link_payloads())
     fcfg = dict(rate=rate)
@@ -369,7 +383,7 @@ def link_case(snr_db, rate):
         iq = mod.flush()
         psig = float(np.mean(np.abs(iq.astype(np.complex128)) ** 2))
         ch = mod.engine()
-        ch.set_multipath(sc.link_channel_cfg(snr_db, psig))
+        ch.set_multipath(sc.link_channel_cfg(snr_db, psig, seed))
         y = ch.multipath(sc.link_air(iq))
         eng.set_taps(*TAPS)
         eng.set_rx_quality(True)
@@ -392,15 +406,16 @@ def _ok_count(r, key):
     return sum(1 for ok, _ in r[key] if ok)
 
 
-LINK_CASES = [(13.0, "1/2"), (13.0, "2/3"), (13.0, "3/4"), (17.0, "3/4")]
+LINK_CASES = [(13.0, "1/2", sc.LINK_SEED), (13.0, "2/3", sc.LINK_SEED), (13.0, "3/4", sc.LINK_SEED), (17.0, "3/4", sc.LINK_SEED),
+              (17.0, "5/6", 12)]
 
 
-@pytest.mark.parametrize("snr_db,rate", LINK_CASES)
-def test_impaired_link_equals_the_model(snr_db, rate):
+@pytest.mark.parametrize("snr_db,rate,seed", LINK_CASES, ids=["%.1f-%s" % c[:2] for c in LINK_CASES])
+def test_impaired_link_equals_the_model(snr_db, rate, seed):
     """Exact part, per level and rate: the soft values equal the soft model fed with the same call's taps, records and
     eq rows; rx_fec_decode_soft, ofdm_demod(fec=, soft=) and ofdm_demod(fec=) equal the model decoders at the rate in every
     field.  Every ok payload is one that was sent."""
-    r = link_case(snr_db, rate)
+    r = link_case(snr_db, rate, seed)
     pk, want = r["pk"], r["want"]
     assert len(r["got_vals"]) == len(want) == len(pk) == len(r["pay"])
     for i, (a, b) in enumerate(zip(r["got_vals"], want)):
