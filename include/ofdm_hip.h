@@ -1197,6 +1197,60 @@ int ofdm_rx_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, uint8_t *pa
                             uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, int max_pkts, int *n);
 int ofdm_rx_soft_last_ms(ofdm_handle *h, double *ms);
 
+/* --- outer code: Reed-Solomon over GF(2^8) on the GPU, the outer half of a concatenated link -----------------------------
+ * A byte-oriented code at the payload boundary, above the coded links and independent of them (it also works on an
+ * uncoded link): ofdm_rs_encode turns payloads into RS blocks that go to ofdm_fec_encode, or straight to ofdm_tx /
+ * ofdm_make_packets, as payloads; ofdm_rs_decode takes what ofdm_fec_decode (whatever its CRC said) or ofdm_rx
+ * delivered and returns what was sent.  Its correction unit is the Viterbi decoder's failure unit: a short burst of
+ * wrong bytes.  Additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, and without a call to these
+ * functions nothing here launches, allocates or copies.  All arithmetic is integer: results are defined bit for bit.
+ * The code has no parameters, hence no configuration struct.
+ *
+ * Field and generator.  GF(2^8) modulo x^8 + x^4 + x^3 + x^2 + 1 (0x11d), alpha = 0x02 (alpha^8 = 0x1d,
+ * alpha^255 = 1).  g(x) = product over i = 0 .. 31 of (x - alpha^i): OFDM_RS_PARITY = 32 parity bytes per codeword,
+ * t = 16.
+ * Block layout.  Info bytes of an n-byte payload (0 <= n <= OFDM_RS_MAX_PAYLOAD): payload | CRC-32(payload)
+ * big-endian, k = n + 4 bytes.  W = ceil(k / 223) codewords, byte-interleaved to depth W: info byte i is symbol i / W
+ * (rounded down) of codeword i mod W, so codeword w has k_w = ceil((k - w) / W) <= 223 info symbols and is the
+ * RS(255, 223) code shortened to k_w + 32 symbols.  The first symbol is the highest-degree coefficient; the parity is
+ * m_w(x) x^32 mod g(x), parity byte j the coefficient of x^(31 - j).  Coded block: the k info bytes verbatim
+ * (systematic), then the parity, byte j of codeword w at position k + j W + w.  Its length is
+ * f(k) = k + 32 ceil(k / 223), strictly increasing in steps of 1 or 33: f(4) = 36, f(223) = 255, f(224) = 288,
+ * f(1784) = 2040, f(1785) = 2073, f(3568) = 4080.  A length f never reaches, below 36 or above OFDM_RS_MAX_CODED is
+ * no block: ok = 0, no payload bytes, corrected = failed = 0 for that entry, nothing of it is read, and no error for
+ * the batch (as the coded links treat an odd length).  OFDM_RS_MAX_PAYLOAD = 3564 gives W = 16 and the largest block a
+ * frame takes; under an inner code the RS block must fit OFDM_FEC_MAX_PAYLOAD, so n <= 1780 (W = 8, block 2040).
+ * Decoding.  Per codeword bounded-distance: if a codeword of the shortened code lies within 16 symbol differences of
+ * the received word it is unique, and the output is that codeword; otherwise the received symbols stay as they are and
+ * the codeword counts as failed.  (An error locator with a root in the shortened, implicitly zero, region, with fewer
+ * roots than its degree, or of degree above 16 is a failure, not a correction.)  Per block: the n payload bytes after
+ * correction; ok = 1 when the CRC-32 of the corrected payload matches the corrected CRC bytes; corrected = symbols
+ * changed, summed over the codewords that decoded; failed = codewords that failed.  Any burst of at most 15 W + 1
+ * consecutive wrong bytes is corrected wherever it lies, up to 16 W where it stays inside the info part or inside the
+ * parity part (across the boundary the interleaving phase jumps by k mod W).
+ *
+ * Pointers, offsets, capacities and errors exactly as ofdm_fec_encode / ofdm_fec_decode: the blobs (payloads, coded)
+ * are host or device pointers by the handle's mode; the offset, length, ok, corrected and failed arrays are always host
+ * memory.  coded_off / payload_off OUT have nblk + 1 entries and are set before the capacity check.  OFDM_E_INVAL: a
+ * payload longer than OFDM_RS_MAX_PAYLOAD (encode), a null argument.  OFDM_E_CAPACITY: the output blob is too small.
+ * In device-pointer mode the payload blob and payload_off of ofdm_fec_decode are the coded blob and coded_off of
+ * ofdm_rs_decode (coded_len[k] = payload_off[k + 1] - payload_off[k]), and the coded blob and coded_off of
+ * ofdm_rs_encode are the payloads of ofdm_fec_encode: the two layers chain without a host round trip.
+ * ofdm_rs_last_ms: HIP-event time of k_rs_encode / k_rs_decode in the last of the two calls, which must have run with
+ * profiling on (ofdm_prof_enable) and launched; OFDM_E_INVAL otherwise.  As ofdm_fec_last_ms. */
+#define OFDM_RS_PARITY 32
+#define OFDM_RS_MAX_PAYLOAD 3564
+#define OFDM_RS_MAX_CODED 4080
+/* pure host functions, usable without a GPU: f(n + 4), and its inverse (OFDM_E_INVAL for a length that is no block) */
+int ofdm_rs_coded_len(uint32_t payload_len, uint32_t *coded_len);
+int ofdm_rs_payload_len(uint32_t coded_len, uint32_t *payload_len);
+int ofdm_rs_encode(ofdm_handle *h, const uint8_t *payloads, const uint64_t *payload_off, const uint32_t *payload_len,
+                   int nblk, uint8_t *coded, uint64_t coded_cap, uint64_t *coded_off);
+int ofdm_rs_decode(ofdm_handle *h, const uint8_t *coded, const uint64_t *coded_off, const uint32_t *coded_len, int nblk,
+                   uint8_t *payloads, uint64_t payload_cap, uint64_t *payload_off, uint8_t *ok, uint32_t *corrected,
+                   uint32_t *failed);
+int ofdm_rs_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

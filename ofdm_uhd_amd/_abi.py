@@ -30,6 +30,9 @@ OFDM_MULTIPATH_MAX_DELAY = 1023
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
+OFDM_RS_PARITY = 32
+OFDM_RS_MAX_PAYLOAD = 3564
+OFDM_RS_MAX_CODED = 4080
 
 OFDM_OK = 0
 OFDM_E_INVAL = -1
@@ -329,6 +332,7 @@ EXPORTS = (
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
+    "ofdm_rs_coded_len", "ofdm_rs_payload_len", "ofdm_rs_encode", "ofdm_rs_decode", "ofdm_rs_last_ms",
 )
 
 _LIB = None
@@ -433,6 +437,11 @@ def _declare(lib):
     lib.ofdm_rx_soft.argtypes = [H, vp, C.c_uint64, u64p, C.POINTER(C.c_int)]
     lib.ofdm_rx_fec_decode_soft.argtypes = [H, FC, u8p, C.c_uint64, u64p, vp, u32p, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_rx_soft_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_rs_coded_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_rs_payload_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_rs_encode.argtypes = [H, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
+    lib.ofdm_rs_decode.argtypes = [H, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p, u32p]
+    lib.ofdm_rs_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

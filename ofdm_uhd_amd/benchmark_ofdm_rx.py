@@ -77,6 +77,11 @@ def make_parser():
     parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
                       help="coded link at this rate, as benchmark_ofdm_tx --fec-rate wrote it (implies --fec; works "
                            "with --fec-soft) [default=1/2]")
+    parser.add_option("", "--rs", action="store_true", default=False,
+                      help="outer code: the file was written by benchmark_ofdm_tx --rs; every delivered packet goes "
+                           "through the Reed-Solomon decoder on the GPU, behind the inner decoder where --fec, "
+                           "--fec-rate or --fec-soft is given, and is accounted by the CRC inside the RS block "
+                           "[default=%default]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -162,8 +167,8 @@ def main(argv=None):
         options.fec = True
     if options.fec_rate:
         options.fec = dict(rate=options.fec_rate)   # (what receive_path hands to ofdm_demod(fec=))
-    if options.fec and (options.resamp_freqs is not None or options.ddc_freqs is not None):
-        parser.error("--fec does not combine with --ddc-freqs or --resamp-freqs")
+    if (options.fec or options.rs) and (options.resamp_freqs is not None or options.ddc_freqs is not None):
+        parser.error("--fec and --rs do not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:
         return _main_resamp_bank(parser, options)
     if options.ddc_freqs is not None:
@@ -176,7 +181,7 @@ def main(argv=None):
         rxpath = receive_path.receive_path(None, options, quality_callback=acct.rx_callback, csi=want_csi)
     else:
         rxpath = receive_path.receive_path(acct.rx_callback, options, csi=want_csi)
-    # (receive_path takes --iq-format / --iq-scale, --fec, --ddc-decim / --ddc-freq and --resamp-* from the options)
+    # (receive_path takes --iq-format / --iq-scale, --fec, --rs, --ddc-decim / --ddc-freq and --resamp-* from the options)
     rxpath.run(iqio.file_source(options.from_file, fmt=options.iq_format), chunk_samples=int(options.chunk_samples))
     packet_file.close()
     if options.csi_report is not None:

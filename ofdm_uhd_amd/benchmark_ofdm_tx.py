@@ -61,6 +61,10 @@ def make_parser():
     parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
                       help="coded link at this rate: the K=7 code punctured by the 802.11 patterns (implies --fec; "
                            "demodulate with the same benchmark_ofdm_rx --fec-rate) [default=1/2]")
+    parser.add_option("", "--rs", action="store_true", default=False,
+                      help="outer code: wrap every payload (at most 3564 bytes, 1780 with --fec / --fec-rate) in a "
+                           "Reed-Solomon block, 32 parity bytes per 223, encoded on the GPU ahead of the inner code; "
+                           "demodulate with benchmark_ofdm_rx --rs [default=%default]")
     _options.add_tx_resamp_options(parser)
     parser.add_option("", "--tx-resamp-freqs", default=None,
                       help="with --tx-resamp-interp / --tx-resamp-decim, instead of --tx-resamp-freq: comma-separated "
@@ -79,8 +83,8 @@ def _main_tx_resamp_bank(parser, options):
     the packets sent per link."""
     if options.duc_interp or options.duc_freq:
         parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
-    if options.fec:
-        parser.error("--tx-resamp-freqs does not combine with --fec")
+    if options.fec or options.rs:
+        parser.error("--tx-resamp-freqs does not combine with --fec or --rs")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -136,7 +140,7 @@ def main(argv=None):
         print(os.path.getsize(options.from_file))
 
     txpath = transmit_path.transmit_path(options)
-    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format, --fec and --duc-interp / --duc-freq, --tx-resamp-* from the options)
+    sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format, --fec, --rs and --duc-interp / --duc-freq, --tx-resamp-* from the options)
     txpath.connect(sink)
     npk = 0
     for payload in build_payloads(options, src):

@@ -34,6 +34,7 @@
 #include "multipath.h"
 #include "fec.h"
 #include "fec_punct.h"
+#include "rs.h"
 
 static std::string g_create_error;
 
@@ -132,6 +133,7 @@ struct ofdm_handle {
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
+  RsState rs;  // outer code: Reed-Solomon over the payloads, above the coded links (rs.h / engine_rs.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -568,6 +570,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->multipath.release();
   h->fec.release();
   h->fec_punct.release();
+  h->rs.release();
   {
     SenseState& ss = h->sense;
     if (ss.side) (void)hipStreamSynchronize(ss.side);
@@ -1012,3 +1015,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_multipath.inc"
 #include "engine_fec.inc"
 #include "engine_soft.inc"
+#include "engine_rs.inc"

@@ -917,6 +917,64 @@ class Engine(object):
         rate (needs prof_enable())."""
         return self._stage_last_ms("fec_punct")
 
+    # -- outer code (Reed-Solomon over the payloads, above the coded links) -------------------------------------------
+    def rs_encode(self, payloads):
+        """Host mode: list of payloads (0 .. 3564 bytes each) -> list of RS blocks (rs.coded_len(n) bytes each), the
+        payloads fec_encode() or tx() then takes."""
+        assert not self.device_ptrs
+        blob, offs, lens = pack_payloads(payloads)
+        k = lens.astype(np.int64) + 4
+        out = np.zeros(max(int((k + 32 * ((k + 222) // 223)).sum()), 1), np.uint8)
+        coff = np.zeros(len(payloads) + 1, np.uint64)
+        self._check(self._lib.ofdm_rs_encode(self._h, _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
+                                             coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+
+    def rs_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap):
+        """Device mode: payload bytes and RS blocks are device pointers; offs / lens are NumPy host arrays.  Returns
+        the nblk + 1 block offsets (uint64), which fec_encode_device() takes as its payload offsets."""
+        assert self.device_ptrs
+        coff = np.zeros(len(lens) + 1, np.uint64)
+        self._check(self._lib.ofdm_rs_encode(self._h, C.c_void_p(payload_ptr), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
+                                             int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return coff
+
+    def _rs_decode(self, in_ptr, offs, lens, out_ptr, out_cap):
+        n = len(lens)
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr = np.zeros(max(n, 1), np.uint32)
+        fail = np.zeros(max(n, 1), np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self._lib.ofdm_rs_decode(self._h, in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(u32p),
+                                             n, out_ptr, int(out_cap), poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
+                                             corr.ctypes.data_as(u32p), fail.ctypes.data_as(u32p)))
+        return poff, ok[:n], corr[:n], fail[:n]
+
+    def rs_decode(self, blocks):
+        """Host mode: list of received RS blocks (bytes of any length, e.g. what fec_decode() returned whatever its
+        CRC said) -> list of (ok, payload, corrected, failed): the corrected payload, whether its CRC matches, the
+        symbols changed and the codewords that could not be decoded.  A length that is no block gives
+        (False, b"", 0, 0)."""
+        assert not self.device_ptrs
+        blob, offs, lens = pack_payloads(blocks)
+        out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
+        poff, ok, corr, fail = self._rs_decode(_ptr(blob), offs, lens, _ptr(out), len(out))
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(fail[i])) for i in range(len(blocks))]
+
+    def rs_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap):
+        """Device mode: the blocks and the payloads are device pointers (the blocks can be what fec_decode_device()
+        wrote, with its payload offsets); offs / lens are NumPy host arrays.  Returns (payload offsets uint64[nblk + 1],
+        ok uint8[nblk], corrected uint32[nblk], failed uint32[nblk]) as host arrays."""
+        assert self.device_ptrs
+        return self._rs_decode(C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+
+    def rs_last_ms(self):
+        """HIP-event time of k_rs_encode / k_rs_decode in the last rs call (needs prof_enable())."""
+        return self._stage_last_ms("rs")
+
     # -- soft-decision receive: per-bit reliabilities of the delivered packets, decoded where they lie ---------------
     def set_rx_soft(self, soft=True):
         """Soft values for the following rx() / rx_device() calls: ``True`` (scale 32), ``dict(scale=)`` or a number

@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -27,7 +27,7 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None):
+                 resample=None, fec=None, rs=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
@@ -52,6 +52,11 @@ class ofdm_mod(object):
                K = 7 convolutional code and a block interleaver, 2 n + 10 bytes; ``rate`` "2/3", "3/4" or "5/6" punctures
                it to fec.coded_len(n, rate) bytes) ahead of the modulator; the receiving end is ofdm_demod(fec=) with
                the same setting.  None: the payloads go out as they are and nothing new runs
+        @param rs: outer code: ``True`` wraps every payload in a Reed-Solomon block (rs.py, Engine.rs_encode: payload |
+               CRC-32, 32 parity bytes per 223, byte-interleaved) before the inner code, if any, and the modulator:
+               flush() encodes outer, then inner, then modulates.  send_pkt then takes up to 3564 bytes, or 1780 with
+               ``fec`` (the RS block must fit the inner code); the receiving end is ofdm_demod(rs=True).  None /
+               False: nothing new runs
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
@@ -89,6 +94,7 @@ class ofdm_mod(object):
         elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
         self._fec = _fec.as_cfg(fec)
+        self._rs = bool(rs)
         self._pending = []
         self._sink = None
         self.symbols_sent = 0
@@ -130,6 +136,15 @@ class ofdm_mod(object):
         payload = bytes(payload)
         # same limit and exception as make_packet (ofdm_packet_utils.py:123-126) -- and, like it, raised HERE for
         # the offending packet only: the padded, whitened body must fit the mask too (whiten(), :84-87)
+        if self._rs:
+            limit = _rs.MAX_PAYLOAD if self._fec is None else _rs.MAX_PAYLOAD_UNDER_FEC
+            if len(payload) > limit:
+                raise ValueError("len(payload) must be in [0, %d]" % (limit,))
+            block = _rs.coded_len(len(payload))
+            # what gets framed: the RS block, or the inner code's block around it
+            self._engine.framed_len(block if self._fec is None else _fec.coded_len(block, self._fec))
+            self._pending.append(payload)
+            return
         if self._fec is not None:
             if len(payload) > _fec.MAX_PAYLOAD:
                 raise ValueError("len(payload) must be in [0, %d]" % (_fec.MAX_PAYLOAD,))
@@ -158,6 +173,8 @@ class ofdm_mod(object):
         iq = None
         if self._pending:
             pending, self._pending = self._pending, []   # a failing batch never poisons the queue
+            if self._rs:
+                pending = self._engine.rs_encode(pending)
             if self._fec is not None:
                 pending = self._engine.fec_encode(pending, self._fec)
             iq = self._engine.tx(pending)
@@ -228,7 +245,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None):
+                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None, rs=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -257,6 +274,12 @@ class ofdm_demod(object):
             int8 array per packet the last work() / feed() / flush() returned, 8 values per payload byte.  With ``fec``
             set as well the decoder takes those values on the GPU (Engine.rx_fec_decode_soft) in place of the hard
             bytes; ``last_fec`` keeps its meaning.  Without ``fec`` it only fills ``last_soft``
+        @param rs: outer code, as for ofdm_mod: the Reed-Solomon decoder (Engine.rs_decode) runs on every delivered
+            packet whatever its CRC said -- behind the inner decoder where ``fec`` is set, hard decisions and ``soft``
+            alike.  ``callback(ok, payload)`` and the returned list then carry the corrected payload and the verdict of
+            the CRC inside the RS block; ``last_rs`` holds (inner_ok, corrected, failed) per packet -- what the stage
+            below said (the inner code's CRC with ``fec``, the packet CRC without), the symbols changed and the
+            codewords that could not be decoded; ``last_fec`` keeps its meaning; ``n_ok`` counts outer verdicts
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -271,6 +294,8 @@ class ofdm_demod(object):
         self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec only)
         self._soft = None if (soft is None or soft is False) else soft
         self.last_soft = []          # int8 values of the packets the last work() / feed() returned (soft only)
+        self._rs = bool(rs)
+        self.last_rs = []            # (inner_ok, corrected, failed) of the packets the last work() / feed() returned (rs only)
 
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
@@ -368,8 +393,15 @@ class ofdm_demod(object):
         """The coded link's receiving end: the delivered packets' bytes, whatever their CRC said, through the decoder
         (``soft``: their soft values, on the GPU where the last rx() left them; ``sel`` picks the delivered ones among
         that call's packets)."""
-        if self._fec is None:
-            return pkts
+        if self._fec is not None:
+            pkts = self._decode_inner(pkts, sel)
+        if self._rs:
+            dec = self._engine.rs_decode([p for _, p in pkts]) if pkts else []
+            self.last_rs = [(bool(ok), c, f) for (ok, _), (_, _, c, f) in zip(pkts, dec)]
+            pkts = [(ok, p) for ok, p, _, _ in dec]
+        return pkts
+
+    def _decode_inner(self, pkts, sel=None):
         if self._soft is not None:
             dec = self._engine.rx_fec_decode_soft(self._fec) if pkts else []
             if sel is not None:

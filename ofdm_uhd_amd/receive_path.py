@@ -6,7 +6,7 @@ from . import ofdm, options as _options
 
 class receive_path(object):
     def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
-                 ddc=None, resample=None, fec=None, soft=None):
+                 ddc=None, resample=None, fec=None, soft=None, rs=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
@@ -16,13 +16,16 @@ class receive_path(object):
         taps=None)``; None: the options' ``resamp_interp`` / ``resamp_decim`` / ``resamp_freq`` (--resamp-*).
         ``fec``: coded link of ofdm_demod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
         ``soft``: soft-decision receive of ofdm_demod, ``True`` or ``dict(scale=32)``; None: the options' ``fec_soft``
-        (--fec-soft), which turns the coded link on as well."""
+        (--fec-soft), which turns the coded link on as well.
+        ``rs``: outer code of ofdm_demod, ``True``; None: the options' ``rs`` (--rs)."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
             fec = (getattr(options, "fec", None) or True) if fec is None else fec   # (a dict where --fec-rate set one)
         if fec is None:
             fec = getattr(options, "fec", None) or None
+        if rs is None:
+            rs = bool(getattr(options, "rs", None))
         if iq_format is None:
             iq_format = getattr(options, "iq_format", None) or "fc32"
         if iq_scale is None:
@@ -40,7 +43,7 @@ class receive_path(object):
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
                                        quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
-                                       ddc=ddc, resample=resample, fec=fec, soft=soft)
+                                       ddc=ddc, resample=resample, fec=fec, soft=soft, rs=rs)
 
         if self._verbose:
             self._print_verbage()

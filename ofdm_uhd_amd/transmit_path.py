@@ -18,7 +18,7 @@ _FLAGS = (
 
 class transmit_path(object):
     def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
-                 resample=None, fec=None):
+                 resample=None, fec=None, rs=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
@@ -29,8 +29,11 @@ class transmit_path(object):
         ``resample``: rational-rate transmit stage of ofdm_mod, ``dict(interpolation=, decimation=, center_freq=0.0,
         taps=None)``; None: the options' ``tx_resamp_interp`` / ``tx_resamp_decim`` / ``tx_resamp_freq``
         (--tx-resamp-*).
-        ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec)."""
+        ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
+        ``rs``: outer code of ofdm_mod, ``True``; None: the options' ``rs`` (--rs)."""
         opts = copy.copy(options)
+        if rs is None:
+            rs = bool(getattr(opts, "rs", None))
         if fec is None:
             fec = getattr(opts, "fec", None) or None
         if iq_format is None:
@@ -46,7 +49,7 @@ class transmit_path(object):
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
-                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec)
+                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
