@@ -1251,6 +1251,52 @@ int ofdm_rs_decode(ofdm_handle *h, const uint8_t *coded, const uint64_t *coded_o
                    uint32_t *failed);
 int ofdm_rs_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- outer code, decoding with reliabilities: errors-and-erasures, the erased symbols chosen per codeword --------------
+ * ofdm_rs_decode_rel is ofdm_rs_decode with one reliability byte per received byte: a codeword the rule above fails is
+ * tried once more with its least reliable symbols erased; an erased symbol costs half an error (2 e + f <= 32).
+ * ofdm_rs_rel_from_soft makes the reliabilities of an RS link without an inner code from the soft demapper's values.
+ * Additions only, as above: without a call to these two nothing new launches, allocates or copies, ofdm_rs_decode returns
+ * what it returned, k_rs_encode and k_rs_decode are unchanged.  All arithmetic is integer.
+ *
+ * Inputs.  rel holds one uint8_t per byte of each coded block, block k at rel + rel_off[k]; rel_off == NULL means
+ * coded_off.  0 is the least reliable value, 255 means "never erase".  rel is a host or device pointer by the handle's
+ * mode, like coded.  M = cfg->max_erasures in 0 .. 32; cfg == NULL means M = 28 (chosen, not measured: it leaves four
+ * parity symbols as a check on what the erasures fill in; the CRC-32 inside the block still decides ok).  rel == NULL or
+ * M = 0 gives exactly ofdm_rs_decode's result.  second (host, may be NULL) receives, per block, the number of codewords
+ * decoded by the second pass.
+ * First pass.  Every codeword first gets ofdm_rs_decode's rule, unchanged: a codeword that decodes there gives that
+ * result whatever rel says.
+ * Second pass, for a codeword the first pass fails, with symbols r_p and reliabilities q_p over its real positions p (the
+ * shortened region has none).  c(tau) = #{p : q_p <= tau}; tau* = the largest tau in 0 .. 254 with c(tau) <= M.  If
+ * there is none (c(0) > M) or c(tau*) = 0 the codeword stays failed.  Otherwise J = {p : q_p <= tau*}, f = |J|.  If a
+ * codeword of the shortened code differs from r in e positions outside J with 2 e + f <= 32 it is unique (two such would
+ * differ in at most 32 < 33 positions) and is the output; corrected gains the number of symbols changed, inside J or
+ * not, and second gains 1.  If there is none the symbols stay as received and the codeword counts as failed.  (An
+ * errata locator with a root in the shortened region, with fewer roots among the real positions than its degree, or
+ * with an error part of degree above (32 - f) / 2 is a failure.)  No smaller tau is tried after a failure.
+ * ofdm_rs_rel_from_soft.  The reliability of byte m is the minimum of |v| over its eight values soft[8 m .. 8 m + 7],
+ * -128 read as 127: 0 .. 127, and a byte holding an erased bit gets 0.  Value layout and offsets as
+ * ofdm_fec_decode_soft (block k: 8 * coded_len[k] values from soft + soft_off[k], soft_off[k] a multiple of 8); every
+ * entry is converted whatever its length; rel_off (OUT, nblk + 1 entries) is the running sum of coded_len.
+ * Errors as ofdm_rs_decode.  OFDM_E_INVAL: a bad struct_size, M > 32, a non-zero reserved word, a null argument, a value
+ * offset that is no multiple of 8.  OFDM_E_CAPACITY: rel_cap or payload_cap too small, the offsets set first.  A length
+ * that is no block gives ok = 0 and zeros, and nothing of it, or of its reliabilities, is read.
+ * ofdm_rs_last_ms reports the decode kernel (k_rs_decode_rel, or k_rs_decode where rel == NULL or M = 0) of the last call;
+ * ofdm_rs_rel_last_ms: HIP-event time of k_rs_rel_soft in the last ofdm_rs_rel_from_soft, which must have run with
+ * profiling on and launched; OFDM_E_INVAL otherwise. */
+typedef struct ofdm_rs_rel_cfg {
+  uint32_t struct_size;  /* = sizeof(ofdm_rs_rel_cfg) */
+  uint32_t max_erasures; /* M: 0 .. 32 */
+  uint32_t reserved[6];  /* 0 */
+} ofdm_rs_rel_cfg;       /* 32 bytes */
+int ofdm_rs_decode_rel(ofdm_handle *h, const ofdm_rs_rel_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,
+                       const uint32_t *coded_len, int nblk, const uint8_t *rel, const uint64_t *rel_off, uint8_t *payloads,
+                       uint64_t payload_cap, uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint32_t *failed,
+                       uint32_t *second);
+int ofdm_rs_rel_from_soft(ofdm_handle *h, const int8_t *soft, const uint64_t *soft_off, const uint32_t *coded_len, int nblk,
+                          uint8_t *rel, uint64_t rel_cap, uint64_t *rel_off);
+int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -304,6 +304,14 @@ class ofdm_soft_cfg(C.Structure):
     ]
 
 
+class ofdm_rs_rel_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_erasures", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -333,6 +341,7 @@ EXPORTS = (
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
     "ofdm_rs_coded_len", "ofdm_rs_payload_len", "ofdm_rs_encode", "ofdm_rs_decode", "ofdm_rs_last_ms",
+    "ofdm_rs_decode_rel", "ofdm_rs_rel_from_soft", "ofdm_rs_rel_last_ms",
 )
 
 _LIB = None
@@ -442,6 +451,10 @@ def _declare(lib):
     lib.ofdm_rs_encode.argtypes = [H, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
     lib.ofdm_rs_decode.argtypes = [H, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p, u32p]
     lib.ofdm_rs_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_rs_decode_rel.argtypes = [H, C.POINTER(ofdm_rs_rel_cfg), u8p, u64p, u32p, C.c_int, u8p, u64p, u8p, C.c_uint64, u64p, vp, u32p,
+                                       u32p, u32p]
+    lib.ofdm_rs_rel_from_soft.argtypes = [H, vp, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
+    lib.ofdm_rs_rel_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

@@ -39,6 +39,16 @@ class rx_accounting(object):
                 print(line)
 
 
+def _rs_erasures(option, opt, value, parser):
+    """--rs-erasures [M]: takes the next argument where it is a number."""
+    m = 28
+    if parser.rargs and parser.rargs[0].isdigit():
+        m = int(parser.rargs.pop(0))
+    if m > 32:
+        parser.error("--rs-erasures takes at most 32")
+    setattr(parser.values, option.dest, m)
+
+
 def make_parser():
     parser = OptionParser(option_class=_options.eng_option, conflict_handler="resolve")
     expert_grp = parser.add_option_group("Expert")
@@ -82,6 +92,11 @@ def make_parser():
                            "through the Reed-Solomon decoder on the GPU, behind the inner decoder where --fec, "
                            "--fec-rate or --fec-soft is given, and is accounted by the CRC inside the RS block "
                            "[default=%default]")
+    parser.add_option("", "--rs-erasures", action="callback", callback=_rs_erasures, dest="rs_erasures", default=None,
+                      help="--rs, decoding with reliabilities: --rs-erasures [M] erases the weakest symbols, at most M "
+                           "(0 .. 32, 28 if not given), of every codeword that fails, chosen by the soft demapper's "
+                           "values; for an RS link without an inner code (not with --fec, --fec-rate or --fec-soft) "
+                           "[default=off]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -167,6 +182,10 @@ def main(argv=None):
         options.fec = True
     if options.fec_rate:
         options.fec = dict(rate=options.fec_rate)   # (what receive_path hands to ofdm_demod(fec=))
+    if options.rs_erasures is not None:
+        if options.fec:
+            parser.error("--rs-erasures needs an RS link without an inner code: not with --fec, --fec-rate or --fec-soft")
+        options.rs = True
     if (options.fec or options.rs) and (options.resamp_freqs is not None or options.ddc_freqs is not None):
         parser.error("--fec and --rs do not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:

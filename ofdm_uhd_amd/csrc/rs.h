@@ -27,12 +27,20 @@ struct RsState {
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   double last_ms = 0.0;
   bool timed = false;  // last_ms is of the last rs call
+  // decoding with reliabilities (ofdm_rs_decode_rel, ofdm_rs_rel_from_soft): nothing of it exists before their first call
+  DevBuf d_rel, d_reloff, d_sec, d_soft;
+  std::vector<uint64_t> reloff;
+  hipEvent_t ev_ra = nullptr, ev_rb = nullptr;
+  double rel_last_ms = 0.0;
+  bool rel_timed = false;  // rel_last_ms is of the last ofdm_rs_rel_from_soft
   void release() {
-    DevBuf* bufs[] = {&d_in, &d_out, &d_blk, &d_ok, &d_corr, &d_fail};
+    DevBuf* bufs[] = {&d_in, &d_out, &d_blk, &d_ok, &d_corr, &d_fail, &d_rel, &d_reloff, &d_sec, &d_soft};
     for (DevBuf* b : bufs) b->release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    hipEvent_t* evs[] = {&ev_a, &ev_b, &ev_ra, &ev_rb};
+    for (hipEvent_t* e : evs) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
+    }
   }
 };
 
@@ -112,6 +120,14 @@ __device__ __forceinline__ uint32_t rs_half_sum(uint32_t v) {
 #pragma unroll
   for (int d = 16; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 32);
   return v;
+}
+
+// LDS written and then read by lanes of ONE wave: DS instructions of a wave execute in issue order, so no s_barrier is
+// needed; the fences and the scheduling barrier keep the compiler's accesses on their side (as FftWaveSync, fft.h)
+__device__ __forceinline__ void rs_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- staging --------------------------------------------------------------------------------------------------------
@@ -372,5 +388,357 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode(const uint8_t* __restr
     ok[blockIdx.x] = crc32 == got ? 1 : 0;
     corrected[blockIdx.x] = c;
     failed[blockIdx.x] = f;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Decoder with reliabilities (include/ofdm_hip.h, "decoding with reliabilities").  k_rs_decode's layout and, as the first
+// pass, k_rs_decode's steps, restated here so that k_rs_decode's own text stays what it is; the block's reliability
+// bytes are staged next to it.  Two wave-uniform exits: clean input, and no half of the wave failing the first pass.
+// A half whose codeword failed goes on:
+//   threshold  tau* by an 8-step search upwards bit by bit; each step counts over the lane's <= 8 positions and sums over
+//              the half.  f = c(tau*) positions are erased
+//   erasures   their X = alpha^deg, compacted by ballot ranks into 32 bytes of LDS per half (written and read by the
+//              half's own wave: rs_wave_sync)
+//   Gamma      prod (1 - X_j x) by f steps of shift-and-multiply.  A polynomial of degree <= 32 lies on a half with
+//              coefficient i + 1 in lane i and coefficient 0 in a register of its own, equal in every lane
+//   Psi        Berlekamp-Massey without inversion started from lambda = B = Gamma, L = f, rounds f .. 31: always a
+//              multiple of Gamma, so the erased positions are roots by construction
+//   roots      as the first pass with Psi_0 .. Psi_32 and Omega_0 .. Omega_31 = S Psi mod x^32 copied to every lane; the
+//              eight positions of a lane in a loop that is not unrolled, the eight errata values packed in two registers
+//   verdict    2 (L - f) + f <= 32 and L roots found: the non-zero errata values are applied, one writer per byte
+// ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(RS_THREADS) k_rs_decode_rel(const uint8_t* __restrict__ coded, const uint8_t* __restrict__ rel,
+                                                              const RsBlk* __restrict__ blk, const uint64_t* __restrict__ rel_off,
+                                                              uint32_t M, uint8_t* __restrict__ payloads, uint8_t* __restrict__ ok,
+                                                              uint32_t* __restrict__ corrected, uint32_t* __restrict__ failed,
+                                                              uint32_t* __restrict__ second, const uint32_t* __restrict__ crc_table,
+                                                              const uint32_t* __restrict__ xp8) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[RS_LDS_BLOCK];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_rel[RS_LDS_BLOCK];
+  __shared__ uint32_t red[RS_THREADS / WAVE];
+  __shared__ uint32_t s_corr[RS_MAX_WORDS], s_fail[RS_MAX_WORDS], s_sec[RS_MAX_WORDS];
+  __shared__ uint8_t s_x[RS_HALVES][32];
+  const RsBlk b = blk[blockIdx.x];
+  const int tid = threadIdx.x;
+  uint32_t k;
+  if (!rs_info_len(b.len, &k)) {  // (uniform over the workgroup)
+    if (tid == 0) {
+      ok[blockIdx.x] = 0;
+      corrected[blockIdx.x] = 0;
+      failed[blockIdx.x] = 0;
+      second[blockIdx.x] = 0;
+    }
+    return;
+  }
+  const uint32_t n = k - 4u, W = rs_words(k);
+  const uint32_t a = rs_stage_in(lds, coded + b.in_off, b.len, tid);
+  const uint32_t ar = rs_stage_in(lds_rel, rel + rel_off[blockIdx.x], b.len, tid);
+  uint8_t* blkb = lds + a;
+  const uint8_t* relb = lds_rel + ar;
+  __syncthreads();
+
+  const uint32_t i = (uint32_t)tid & 31u, half = (uint32_t)tid >> 5;
+  const RsCols ai = rs_cols(rs_tab.exp[i]);
+  for (uint32_t base = 0; base < W; base += RS_HALVES) {
+    const uint32_t w = base + half;
+    const bool active = w < W;
+    const uint32_t kw = active ? rs_cw_info(k, W, w) : 0u;  // (a half without a codeword sees the empty word: clean)
+    const uint32_t len = active ? kw + OFDM_RS_PARITY : 0u;
+    // ---- first pass: k_rs_decode's steps ----
+    uint32_t S = 0;
+    for (uint32_t s = 0; s < kw; s++) S = rs_mulc(ai, S) ^ (uint32_t)blkb[s * W + w];
+    for (uint32_t s = kw; s < len; s++) S = rs_mulc(ai, S) ^ (uint32_t)blkb[k + (s - kw) * W + w];
+    if (__ballot(S != 0) == 0ull) {  // clean input, the common case: wave-uniform
+      if (active && i == 0) {
+        s_corr[w] = 0;
+        s_fail[w] = 0;
+        s_sec[w] = 0;
+      }
+      continue;
+    }
+    const bool dirty = rs_half_sum(S != 0 ? 1u : 0u) != 0;
+    uint32_t lam = i == 0 ? 1u : 0u, B = lam, L = 0, gam = 1;
+    for (uint32_t r = 0; r < OFDM_RS_PARITY; r++) {
+      uint32_t sv = (uint32_t)__shfl((int)S, (int)((r - i) & 31u), 32);
+      sv = i <= r ? sv : 0u;
+      const uint32_t d = rs_half_xor(rs_mul(lam, sv));
+      uint32_t Bs = (uint32_t)__shfl_up((int)B, 1, 32);
+      if (i == 0) Bs = 0;
+      const uint32_t T = rs_mul(gam, lam) ^ rs_mul(d, Bs);
+      const bool upd = d != 0 && 2u * L <= r;
+      B = upd ? lam : Bs;
+      gam = upd ? d : gam;
+      L = upd ? r + 1u - L : L;
+      lam = T;
+    }
+    bool good;
+    {
+      uint32_t lm[17], om[16];
+#pragma unroll
+      for (int j = 0; j < 17; j++) lm[j] = (uint32_t)__shfl((int)lam, j, 32);
+      uint32_t acc = 0;
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const uint32_t sv = (uint32_t)__shfl((int)S, (int)((i - (uint32_t)j) & 31u), 32);
+        acc ^= (uint32_t)j <= i ? rs_mul(lm[j], sv) : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < 16; j++) om[j] = (uint32_t)__shfl((int)acc, j, 32);
+      const bool tryit = L >= 1u && L <= 16u;
+      uint32_t err[8], nroot = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        err[q] = 0;
+        const uint32_t p = i + 32u * (uint32_t)q;
+        if (tryit && p < len) {
+          const uint32_t deg = len - 1u - p;
+          const uint32_t z = rs_tab.exp[deg ? 255u - deg : 0u];
+          const RsCols cz = rs_cols(z);
+          const RsCols cy = rs_cols(rs_mulc(cz, z));
+          uint32_t E = lm[16], O = lm[15];
+#pragma unroll
+          for (int j = 6; j >= 0; j--) {
+            E = rs_mulc(cy, E) ^ lm[2 * j + 2];
+            O = rs_mulc(cy, O) ^ lm[2 * j + 1];
+          }
+          E = rs_mulc(cy, E) ^ lm[0];
+          const uint32_t zO = rs_mulc(cz, O);
+          if ((E ^ zO) == 0u) {
+            nroot++;
+            uint32_t v = om[15];
+#pragma unroll
+            for (int j = 14; j >= 0; j--) v = rs_mulc(cz, v) ^ om[j];
+            err[q] = rs_mul(v, rs_inv(zO));
+          }
+        }
+      }
+      nroot = rs_half_sum(nroot);
+      good = tryit && nroot == L;
+      if (good) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+          const uint32_t p = i + 32u * (uint32_t)q;
+          if (err[q]) {
+            const uint32_t at = p < kw ? p * W + w : k + (p - kw) * W + w;
+            blkb[at] = (uint8_t)((uint32_t)blkb[at] ^ err[q]);
+          }
+        }
+      }
+    }
+    const bool fail1 = dirty && !good;
+    if (__ballot(fail1) == 0ull) {  // the first pass decoded every codeword of the wave: wave-uniform
+      if (active && i == 0) {
+        s_corr[w] = good ? L : 0u;
+        s_fail[w] = 0;
+        s_sec[w] = 0;
+      }
+      continue;
+    }
+
+    // ---- second pass.  Both halves of the wave run every step, the lane exchanges stay inside a half; a half that
+    // did not fail computes on nothing and changes nothing (sec is false) ----
+    uint32_t rq[8];  // reliabilities of the lane's positions, 256 where there is none
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const uint32_t p = i + 32u * (uint32_t)q;
+      rq[q] = p < len ? (uint32_t)relb[p < kw ? p * W + w : k + (p - kw) * W + w] : 256u;
+    }
+    uint32_t tau = 0, f = 0, c0;
+    {
+      uint32_t c = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) c += rq[q] == 0u ? 1u : 0u;
+      c0 = f = rs_half_sum(c);
+    }
+#pragma unroll 1
+    for (int bit = 7; bit >= 0; bit--) {  // the largest tau in 0 .. 254 with c(tau) <= M, given c(0) <= M
+      const uint32_t cand = tau | (1u << bit);
+      uint32_t c = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) c += rq[q] <= cand ? 1u : 0u;
+      c = rs_half_sum(c);
+      const bool take = cand <= 254u && c <= M;
+      tau = take ? cand : tau;
+      f = take ? c : f;
+    }
+    const bool sec = fail1 && c0 <= M && f >= 1u;  // (f <= M <= 32)
+    {
+      uint32_t at = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const bool er = sec && rq[q] <= tau;
+        const uint32_t m = (uint32_t)(__ballot(er) >> (32u * (half & 1u)));
+        if (er) s_x[half][at + (uint32_t)__popc(m & ((1u << i) - 1u))] = rs_tab.exp[len - 1u - (i + 32u * (uint32_t)q)];  // rank < f <= 32
+        at += (uint32_t)__popc(m);
+      }
+    }
+    rs_wave_sync();
+    uint32_t ps = 0, ps0 = 1;  // Gamma: coefficient i + 1 here, coefficient 0 is 1
+#pragma unroll 1
+    for (uint32_t j = 0; j < OFDM_RS_PARITY; j++) {
+      const uint32_t X = s_x[half][j];  // (beyond f: whatever lies there, unused)
+      uint32_t dn = (uint32_t)__shfl_up((int)ps, 1, 32);
+      if (i == 0) dn = 1u;
+      const uint32_t t = ps ^ rs_mul(X, dn);
+      ps = j < f ? t : ps;
+    }
+    rs_wave_sync();  // (the next pass of the loop writes s_x again)
+    uint32_t Bp = ps, Bp0 = 1, L2 = f, gam2 = 1;
+#pragma unroll 1
+    for (uint32_t r = 0; r < OFDM_RS_PARITY; r++) {
+      uint32_t sv = (uint32_t)__shfl((int)S, (int)((r - 1u - i) & 31u), 32);
+      sv = i + 1u <= r ? sv : 0u;
+      const uint32_t Sr = (uint32_t)__shfl((int)S, (int)r, 32);
+      const uint32_t d = rs_half_xor(rs_mul(ps, sv)) ^ rs_mul(ps0, Sr);
+      uint32_t Bs = (uint32_t)__shfl_up((int)Bp, 1, 32);
+      if (i == 0) Bs = Bp0;  // x B: its coefficient i + 1 is B's coefficient i
+      const uint32_t T = rs_mul(gam2, ps) ^ rs_mul(d, Bs);
+      const uint32_t T0 = rs_mul(gam2, ps0);
+      const bool run = r >= f;
+      const bool upd = run && d != 0 && 2u * L2 <= r + f;
+      Bp = run ? (upd ? ps : Bs) : Bp;
+      Bp0 = run ? (upd ? ps0 : 0u) : Bp0;
+      gam2 = upd ? d : gam2;
+      L2 = upd ? r + 1u - L2 + f : L2;
+      ps = run ? T : ps;
+      ps0 = run ? T0 : ps0;
+    }
+    uint32_t pc[33], om[32];
+    pc[0] = ps0;
+#pragma unroll
+    for (int j = 1; j < 33; j++) pc[j] = (uint32_t)__shfl((int)ps, j - 1, 32);
+    {
+      uint32_t acc = 0;  // Omega_i = sum_{j <= i} Psi_j S_(i - j), in lane i
+#pragma unroll
+      for (int j = 0; j < 32; j++) {
+        const uint32_t sv = (uint32_t)__shfl((int)S, (int)((i - (uint32_t)j) & 31u), 32);
+        acc ^= (uint32_t)j <= i ? rs_mul(pc[j], sv) : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < 32; j++) om[j] = (uint32_t)__shfl((int)acc, j, 32);
+    }
+    const bool try2 = sec && 2u * L2 <= OFDM_RS_PARITY + f;  // 2 e + f <= 32 with e = L - f
+    uint32_t elo = 0, ehi = 0, nroot2 = 0;
+#pragma unroll 1
+    for (uint32_t q = 0; q < 8u; q++) {
+      const uint32_t p = i + 32u * q;
+      if (try2 && p < len) {
+        const uint32_t deg = len - 1u - p;
+        const uint32_t z = rs_tab.exp[deg ? 255u - deg : 0u];
+        const RsCols cz = rs_cols(z);
+        const RsCols cy = rs_cols(rs_mulc(cz, z));
+        uint32_t E = pc[32], O = pc[31];
+#pragma unroll
+        for (int j = 14; j >= 0; j--) {
+          E = rs_mulc(cy, E) ^ pc[2 * j + 2];
+          O = rs_mulc(cy, O) ^ pc[2 * j + 1];
+        }
+        E = rs_mulc(cy, E) ^ pc[0];
+        const uint32_t zO = rs_mulc(cz, O);
+        if ((E ^ zO) == 0u) {
+          nroot2++;
+          uint32_t v = om[31];
+#pragma unroll
+          for (int j = 30; j >= 0; j--) v = rs_mulc(cz, v) ^ om[j];
+          const uint32_t e = rs_mul(v, rs_inv(zO)) << (8u * (q & 3u));
+          elo |= q < 4u ? e : 0u;
+          ehi |= q < 4u ? 0u : e;
+        }
+      }
+    }
+    nroot2 = rs_half_sum(nroot2);
+    const bool good2 = try2 && nroot2 == L2;
+    uint32_t changed = 0;
+#pragma unroll 1
+    for (uint32_t q = 0; q < 8u; q++) {
+      const uint32_t e = ((q < 4u ? elo : ehi) >> (8u * (q & 3u))) & 0xFFu;
+      if (good2 && e) {  // (only where p < len) one writer per byte: position p of codeword w is this lane's alone
+        const uint32_t p = i + 32u * q;
+        const uint32_t at = p < kw ? p * W + w : k + (p - kw) * W + w;
+        blkb[at] = (uint8_t)((uint32_t)blkb[at] ^ e);
+        changed++;
+      }
+    }
+    changed = rs_half_sum(changed);
+    if (active && i == 0) {
+      s_corr[w] = fail1 ? changed : (good ? L : 0u);
+      s_fail[w] = (fail1 && !good2) ? 1u : 0u;
+      s_sec[w] = good2 ? 1u : 0u;
+    }
+  }
+  __syncthreads();
+
+  rs_stage_out(payloads + b.out_off, blkb, n, tid);
+  const uint32_t crc32 = rs_crc(blkb, n, tid, red, crc_table, xp8);
+  if (tid == 0) {
+    const uint32_t got = ((uint32_t)blkb[n] << 24) | ((uint32_t)blkb[n + 1u] << 16) | ((uint32_t)blkb[n + 2u] << 8) | (uint32_t)blkb[n + 3u];
+    uint32_t c = 0, f = 0, s2 = 0;
+    for (uint32_t w = 0; w < W; w++) {
+      c += s_corr[w];
+      f += s_fail[w];
+      s2 += s_sec[w];
+    }
+    ok[blockIdx.x] = crc32 == got ? 1 : 0;
+    corrected[blockIdx.x] = c;
+    failed[blockIdx.x] = f;
+    second[blockIdx.x] = s2;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Reliabilities from soft values: byte m of a block gets the smallest |v| of its eight values (rs_rel_of_values).  One
+// workgroup per block; a thread turns 32 values into the 4 bytes of one aligned word of the output: two 16-byte loads
+// where the values lie on a 16-byte boundary (four 8-byte loads where on an 8-byte one), one 4-byte store.  The up to
+// three bytes before the first aligned word and behind the last one go by bytes.  Value offsets are multiples of 8 (the
+// host refuses others).  Nothing outside the blocks is read or written.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rs_rel_of_words(uint32_t lo, uint32_t hi) {
+  uint32_t m = 127u;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int x = (int)(int8_t)(lo >> (8 * j)), y = (int)(int8_t)(hi >> (8 * j));
+    const uint32_t ax = (uint32_t)(x < 0 ? -x : x), ay = (uint32_t)(y < 0 ? -y : y);
+    m = min(m, min(ax, ay));
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(RS_THREADS) k_rs_rel_soft(const int8_t* __restrict__ soft, const RsBlk* __restrict__ blk,
+                                                            uint8_t* __restrict__ rel) {
+  const RsBlk b = blk[blockIdx.x];
+  const int8_t* v = soft + b.in_off;
+  uint8_t* out = rel + b.out_off;
+  const uint32_t n = b.len;
+  const uint32_t lead = (uint32_t)((4u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 3u)) & 3u);
+  const uint32_t head = lead < n ? lead : n;
+  const uint32_t nword = (n - head) >> 2, tail = (n - head) & 3u;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t g = tid; g < nword; g += RS_THREADS) {
+    const uint32_t m = head + 4u * g;
+    const int8_t* s = v + 8ull * m;
+    uint32_t q[8];
+    const uintptr_t al = reinterpret_cast<uintptr_t>(s);
+    if ((al & 15u) == 0) {
+      const uint4 x = *reinterpret_cast<const uint4*>(s), y = *reinterpret_cast<const uint4*>(s + 16);
+      q[0] = x.x, q[1] = x.y, q[2] = x.z, q[3] = x.w, q[4] = y.x, q[5] = y.y, q[6] = y.z, q[7] = y.w;
+    } else if ((al & 7u) == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint2 x = *reinterpret_cast<const uint2*>(s + 8 * j);
+        q[2 * j] = x.x, q[2 * j + 1] = x.y;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        q[j] = (uint32_t)(uint8_t)s[4 * j] | ((uint32_t)(uint8_t)s[4 * j + 1] << 8) | ((uint32_t)(uint8_t)s[4 * j + 2] << 16) |
+               ((uint32_t)(uint8_t)s[4 * j + 3] << 24);
+    }
+    *reinterpret_cast<uint32_t*>(out + m) = rs_rel_of_words(q[0], q[1]) | (rs_rel_of_words(q[2], q[3]) << 8) |
+                                            (rs_rel_of_words(q[4], q[5]) << 16) | (rs_rel_of_words(q[6], q[7]) << 24);
+  }
+  if (tid < head + tail) {  // at most six bytes at the two edges
+    const uint32_t m = tid < head ? tid : head + 4u * nword + (tid - head);
+    out[m] = (uint8_t)rs_rel_of_values(v + 8ull * m);
   }
 }

@@ -112,3 +112,69 @@ static inline uint64_t rs_plan_decode(const uint64_t* in_off, const uint32_t* co
   *in_extent = ext;
   return o;
 }
+
+// ---- reliability-driven errors-and-erasures decoding (ofdm_rs_decode_rel, ofdm_rs_rel_from_soft) ---------------------
+constexpr uint32_t RS_REL_DEFAULT_ERASURES = 28;  // M of cfg == NULL: four parity symbols stay a check on what the erasures fill in
+
+// M of a call: the default for cfg == NULL; false for a cfg the call refuses (size, M > 32, a non-zero reserved word)
+static inline bool rs_rel_max_erasures(const ofdm_rs_rel_cfg* cfg, uint32_t* M) {
+  if (!cfg) {
+    *M = RS_REL_DEFAULT_ERASURES;
+    return true;
+  }
+  if (cfg->struct_size != sizeof(ofdm_rs_rel_cfg) || cfg->max_erasures > OFDM_RS_PARITY) return false;
+  for (uint32_t r : cfg->reserved)
+    if (r) return false;
+  *M = cfg->max_erasures;
+  return true;
+}
+
+// reliability of one byte from its eight values: the smallest |v|, -128 read as 127 (0 .. 127)
+RS_HD static inline uint32_t rs_rel_of_values(const int8_t* v) {
+  uint32_t m = 127u;
+  for (int j = 0; j < 8; j++) {
+    const int x = v[j];
+    const uint32_t a = (uint32_t)(x < 0 ? -x : x);
+    m = a < m ? a : m;
+  }
+  return m;
+}
+
+// Where the reliabilities of a decode batch lie (rel_off == NULL: where the blocks lie) and the bytes of `rel` that the
+// blocks among the entries reach.
+static inline void rs_plan_rel(const uint64_t* coded_off, const uint64_t* rel_off, const uint32_t* coded_len, uint64_t nblk, uint64_t* out,
+                               uint64_t* rel_extent) {
+  uint64_t ext = 0;
+  for (uint64_t b = 0; b < nblk; b++) {
+    out[b] = rel_off ? rel_off[b] : coded_off[b];
+    uint32_t k;
+    if (rs_info_len(coded_len[b], &k)) {
+      const uint64_t e = out[b] + coded_len[b];
+      if (e > ext) ext = e;
+    }
+  }
+  *rel_extent = ext;
+}
+
+// Layout of an ofdm_rs_rel_from_soft batch: entry b reads 8 coded_len[b] values from soft_off[b] (a multiple of 8) and
+// writes coded_len[b] bytes at rel_off[b], the running sum.  Returns the total bytes, ~0 for an offset that is no
+// multiple of 8; *in_extent is the number of values the batch reaches.
+static inline uint64_t rs_plan_rel_soft(const uint64_t* soft_off, const uint32_t* coded_len, uint64_t nblk, RsBlk* blk, uint64_t* rel_off,
+                                        uint64_t* in_extent) {
+  uint64_t o = 0, ext = 0;
+  for (uint64_t b = 0; b < nblk; b++)
+    if (soft_off[b] & 7u) return ~0ull;
+  for (uint64_t b = 0; b < nblk; b++) {
+    blk[b].in_off = soft_off[b];
+    blk[b].out_off = o;
+    blk[b].len = coded_len[b];
+    blk[b].pad = 0;
+    rel_off[b] = o;
+    o += coded_len[b];
+    const uint64_t e = soft_off[b] + 8ull * coded_len[b];
+    if (coded_len[b] && e > ext) ext = e;
+  }
+  rel_off[nblk] = o;
+  *in_extent = ext;
+  return o;
+}

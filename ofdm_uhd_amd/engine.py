@@ -975,6 +975,84 @@ class Engine(object):
         """HIP-event time of k_rs_encode / k_rs_decode in the last rs call (needs prof_enable())."""
         return self._stage_last_ms("rs")
 
+    # -- outer code, decoding with reliabilities (errors-and-erasures, the erased symbols chosen per codeword) ---------
+    def _rs_rel_from_soft(self, soft_ptr, offs, lens, rel_ptr, rel_cap):
+        roff = np.zeros(len(lens) + 1, np.uint64)
+        self._check(self._lib.ofdm_rs_rel_from_soft(self._h, soft_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), rel_ptr, int(rel_cap),
+                                                    roff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return roff
+
+    def rs_rel_from_soft(self, values):
+        """Host mode: list of int8 arrays, 8 values per byte (what rx_soft() returns for the packets of an RS link
+        without an inner code) -> list of uint8 arrays, one reliability per byte (rs.rel_from_values on the GPU)."""
+        assert not self.device_ptrs
+        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
+        if any(len(v) % 8 for v in vals):
+            raise ValueError("rs: 8 values per byte")
+        lens = np.array([len(v) // 8 for v in vals], np.uint32)
+        offs = np.zeros(max(len(vals), 1), np.uint64)
+        if len(vals) > 1:
+            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
+        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
+        out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
+        roff = self._rs_rel_from_soft(_ptr(blob), offs[:len(vals)], lens, _ptr(out), len(out))
+        return [out[int(roff[i]):int(roff[i + 1])].copy() for i in range(len(vals))]
+
+    def rs_rel_from_soft_device(self, soft_ptr, offs, lens, rel_ptr, rel_cap):
+        """Device mode: the values (e.g. what rx_soft_device() wrote, with its offsets; lens in bytes = values / 8) and
+        the reliabilities are device pointers; offs / lens are NumPy host arrays.  Returns the nblk + 1 reliability
+        offsets (uint64), which rs_decode_rel_device() takes as ``rel_offs``."""
+        assert self.device_ptrs
+        return self._rs_rel_from_soft(C.c_void_p(soft_ptr), offs, lens, C.c_void_p(rel_ptr), rel_cap)
+
+    def _rs_decode_rel(self, cfg, in_ptr, offs, lens, rel_ptr, rel_offs, out_ptr, out_cap):
+        n = len(lens)
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr, fail, sec = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        self._check(self._lib.ofdm_rs_decode_rel(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(u64p), lens.ctypes.data_as(u32p), n,
+                                                 rel_ptr, None if rel_offs is None else rel_offs.ctypes.data_as(u64p), out_ptr,
+                                                 int(out_cap), poff.ctypes.data_as(u64p), _ptr(ok), corr.ctypes.data_as(u32p),
+                                                 fail.ctypes.data_as(u32p), sec.ctypes.data_as(u32p)))
+        return poff, ok[:n], corr[:n], fail[:n], sec[:n]
+
+    def rs_decode_rel(self, blocks, rel, rs=None):
+        """Host mode: rs_decode() with reliabilities: ``rel`` holds one uint8 array (or bytes) per block, one value per
+        byte of it, 0 the least reliable, 255 never erased; None decodes without.  ``rs``: None / True (at most 28
+        erasures per codeword), a dict of rs.rs_cfg's keywords or an ``ofdm_rs_rel_cfg``.  Returns a list of
+        (ok, payload, corrected, failed, second): as rs_decode(), and the codewords the second pass decoded."""
+        assert not self.device_ptrs
+        from . import rs as _rs
+        cfg = _rs.as_cfg(rs)
+        blob, offs, lens = pack_payloads(blocks)
+        rblob = None
+        if rel is not None:
+            rel = [np.frombuffer(bytes(r), np.uint8) if isinstance(r, (bytes, bytearray)) else np.ascontiguousarray(r, np.uint8).reshape(-1)
+                   for r in rel]
+            if [len(r) for r in rel] != [len(b) for b in blocks]:
+                raise ValueError("rs: one reliability per byte of every block")
+            rblob = np.concatenate(rel + [np.zeros(1, np.uint8)])     # laid out like the blocks: rel_off = coded_off
+        out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
+        poff, ok, corr, fail, sec = self._rs_decode_rel(cfg, _ptr(blob), offs, lens, None if rblob is None else _ptr(rblob), None,
+                                                        _ptr(out), len(out))
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(fail[i]), int(sec[i]))
+                for i in range(len(blocks))]
+
+    def rs_decode_rel_device(self, in_ptr, offs, lens, rel_ptr, rel_offs, payload_ptr, payload_cap, rs=None):
+        """Device mode: blocks, reliabilities (``rel_ptr`` 0 / None: none; ``rel_offs`` None: at the blocks' offsets)
+        and payloads are device pointers; offs / lens / rel_offs are NumPy host arrays.  Returns (payload offsets
+        uint64[nblk + 1], ok uint8[nblk], corrected, failed, second uint32[nblk]) as host arrays."""
+        assert self.device_ptrs
+        from . import rs as _rs
+        return self._rs_decode_rel(_rs.as_cfg(rs), C.c_void_p(in_ptr), offs, lens, C.c_void_p(rel_ptr) if rel_ptr else None, rel_offs,
+                                   C.c_void_p(payload_ptr), payload_cap)
+
+    def rs_rel_last_ms(self):
+        """HIP-event time of k_rs_rel_soft in the last rs_rel_from_soft call (needs prof_enable())."""
+        return self._stage_last_ms("rs_rel")
+
     # -- soft-decision receive: per-bit reliabilities of the delivered packets, decoded where they lie ---------------
     def set_rx_soft(self, soft=True):
         """Soft values for the following rx() / rx_device() calls: ``True`` (scale 32), ``dict(scale=)`` or a number

@@ -279,7 +279,12 @@ class ofdm_demod(object):
             alike.  ``callback(ok, payload)`` and the returned list then carry the corrected payload and the verdict of
             the CRC inside the RS block; ``last_rs`` holds (inner_ok, corrected, failed) per packet -- what the stage
             below said (the inner code's CRC with ``fec``, the packet CRC without), the symbols changed and the
-            codewords that could not be decoded; ``last_fec`` keeps its meaning; ``n_ok`` counts outer verdicts
+            codewords that could not be decoded; ``last_fec`` keeps its meaning; ``n_ok`` counts outer verdicts.
+            ``dict(erasures=True, max_erasures=28)`` decodes with reliabilities (Engine.rs_decode_rel): a codeword that
+            fails is tried once more with its weakest symbols, ``max_erasures`` at the most, erased; the reliabilities
+            come from ``last_soft`` (Engine.rs_rel_from_soft), so it needs ``soft`` and no ``fec`` -- behind the inner
+            decoder there is no source of reliabilities yet (ValueError).  ``last_rs`` keeps its three fields,
+            ``last_rs_second`` holds the codewords per packet that the second pass decoded
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -296,6 +301,19 @@ class ofdm_demod(object):
         self.last_soft = []          # int8 values of the packets the last work() / feed() returned (soft only)
         self._rs = bool(rs)
         self.last_rs = []            # (inner_ok, corrected, failed) of the packets the last work() / feed() returned (rs only)
+        self._rs_rel = None          # ofdm_rs_rel_cfg: decode with reliabilities from last_soft
+        self.last_rs_second = []     # codewords per packet the second pass decoded (rs=dict(erasures=True) only)
+        if isinstance(rs, dict):
+            opts = dict(rs)
+            erasures = bool(opts.pop("erasures", False))
+            if not erasures and opts:
+                raise ValueError("rs: %s need(s) erasures=True" % ", ".join(sorted(opts)))
+            if erasures:
+                if self._soft is None or self._fec is not None:
+                    raise ValueError("rs=dict(erasures=True) needs soft= and no fec=: the reliabilities are the soft "
+                                     "demapper's, and there is none behind the inner decoder yet")
+                self._rs_rel = _rs.rs_cfg(**opts)
+            self._rs = True
 
         self._ksfreq = config.make_ksfreq(self._fft_length, self._occupied_tones)  # ofdm.py:210-215
         self._rotated_const = config.rotated_constellation(self._modulation)       # ofdm.py:225-236
@@ -395,7 +413,15 @@ class ofdm_demod(object):
         that call's packets)."""
         if self._fec is not None:
             pkts = self._decode_inner(pkts, sel)
-        if self._rs:
+        if self._rs_rel is not None:
+            # (last_soft holds the delivered packets' values, in their order)
+            rel = self._engine.rs_rel_from_soft(self.last_soft) if pkts else []
+            dec = self._engine.rs_decode_rel([p for _, p in pkts], rel, self._rs_rel) if pkts else []
+            self.last_rs_second = [s for _, _, _, _, s in dec]
+            dec = [d[:4] for d in dec]
+            self.last_rs = [(bool(ok), c, f) for (ok, _), (_, _, c, f) in zip(pkts, dec)]
+            pkts = [(ok, p) for ok, p, _, _ in dec]
+        elif self._rs:
             dec = self._engine.rs_decode([p for _, p in pkts]) if pkts else []
             self.last_rs = [(bool(ok), c, f) for (ok, _), (_, _, c, f) in zip(pkts, dec)]
             pkts = [(ok, p) for ok, p, _, _ in dec]

@@ -17,13 +17,17 @@ class receive_path(object):
         ``fec``: coded link of ofdm_demod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
         ``soft``: soft-decision receive of ofdm_demod, ``True`` or ``dict(scale=32)``; None: the options' ``fec_soft``
         (--fec-soft), which turns the coded link on as well.
-        ``rs``: outer code of ofdm_demod, ``True``; None: the options' ``rs`` (--rs)."""
+        ``rs``: outer code of ofdm_demod, ``True`` or ``dict(erasures=True, max_erasures=28)``; None: the options' ``rs``
+        (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
             fec = (getattr(options, "fec", None) or True) if fec is None else fec   # (a dict where --fec-rate set one)
         if fec is None:
             fec = getattr(options, "fec", None) or None
+        if rs is None and getattr(options, "rs_erasures", None) is not None:
+            rs = dict(erasures=True, max_erasures=int(options.rs_erasures))
+            soft = True if soft is None else soft
         if rs is None:
             rs = bool(getattr(options, "rs", None))
         if iq_format is None:

@@ -5,8 +5,15 @@ the GPU (include/ofdm_hip.h, "outer code").  It sits above 
 the short bursts of wrong bytes a Viterbi decoder leaves; it also works on an uncoded link.  The code has no
 parameters.  The work is ``Engine.rs_encode`` / ``Engine.rs_decode``; ``ofdm_mod(rs=True)`` and ``ofdm_demod(rs=True)``
 put it on a link, both ends alike.
+
+Decoding with reliabilities (``Engine.rs_decode_rel``, ``ofdm_demod(rs=dict(erasures=True))``): one byte per received
+byte says how far to trust it, and a codeword that bounded-distance decoding fails is tried once more with its weakest
+symbols, ``max_erasures`` at the most, erased.  ``rs_cfg`` makes the call's configuration, ``rel_from_values`` restates
+on the host what ``Engine.rs_rel_from_soft`` computes on the GPU.
 """
 import ctypes as C
+
+import numpy as np
 
 from . import _abi
 
@@ -14,6 +21,7 @@ PARITY = _abi.OFDM_RS_PARITY
 MAX_PAYLOAD = _abi.OFDM_RS_MAX_PAYLOAD
 MAX_CODED = _abi.OFDM_RS_MAX_CODED
 MAX_PAYLOAD_UNDER_FEC = 1780          # the RS block must fit fec.MAX_PAYLOAD: W = 8, block 2040
+DEFAULT_MAX_ERASURES = 28             # leaves four parity symbols as a check on what the erasures fill in
 
 
 def coded_len(payload_len):
@@ -32,3 +40,32 @@ def payload_len(coded_len):
     if coded_len < 0 or coded_len > 0xffffffff or _abi.load().ofdm_rs_payload_len(int(coded_len), C.byref(n)) != _abi.OFDM_OK:
         return None
     return n.value
+
+
+def rs_cfg(max_erasures=DEFAULT_MAX_ERASURES):
+    """``ofdm_rs_rel_cfg`` of a decode with reliabilities: at most ``max_erasures`` (0 .. 32) symbols of a codeword are
+    erased; 0 turns the second pass off."""
+    if isinstance(max_erasures, bool) or int(max_erasures) != max_erasures or not 0 <= max_erasures <= PARITY:
+        raise ValueError("rs: max_erasures must be an integer in [0, %d]" % PARITY)
+    return _abi.ofdm_rs_rel_cfg(struct_size=C.sizeof(_abi.ofdm_rs_rel_cfg), max_erasures=int(max_erasures))
+
+
+def as_cfg(rs):
+    """None / True, a dict of rs_cfg's keywords or an ``ofdm_rs_rel_cfg`` -> ``ofdm_rs_rel_cfg``."""
+    if isinstance(rs, _abi.ofdm_rs_rel_cfg):
+        return rs
+    if rs is None or rs is True:
+        return rs_cfg()
+    if isinstance(rs, dict):
+        return rs_cfg(**rs)
+    raise ValueError("rs: expected None, True, a dict of rs_cfg's keywords or an ofdm_rs_rel_cfg")
+
+
+def rel_from_values(values):
+    """One reliability byte per byte from its eight int8 values: the smallest |v|, -128 read as 127 (0 .. 127; a byte
+    with an erased bit gets 0).  ``len(values)`` must be a multiple of 8."""
+    v = np.ascontiguousarray(values, np.int8).reshape(-1)
+    if len(v) % 8:
+        raise ValueError("rs: 8 values per byte")
+    a = np.minimum(np.abs(v.astype(np.int16)), 127).reshape(-1, 8)
+    return a.min(axis=1).astype(np.uint8)
