@@ -1197,6 +1197,52 @@ int ofdm_rx_fec_decode_soft(ofdm_handle *h, const ofdm_fec_cfg *cfg, uint8_t *pa
                             uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, int max_pkts, int *n);
 int ofdm_rx_soft_last_ms(ofdm_handle *h, double *ms);
 
+/* --- coded links, reliabilities out: a soft-output Viterbi decoder for errors-and-erasures decoding of the outer code ----
+ * A second inner decoder: ofdm_fec_decode_rel / ofdm_fec_decode_soft_rel / ofdm_rx_fec_decode_soft_rel return exactly what
+ * ofdm_fec_decode / ofdm_fec_decode_soft / ofdm_rx_fec_decode_soft return for the same input, and one reliability byte per
+ * decoded payload byte in the format ofdm_rs_decode_rel takes.  Additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_*
+ * table is unchanged, k_fec_decode, its launches and its workspace are unchanged, and without a call to these three
+ * functions nothing new launches, allocates or copies.  All arithmetic is integer: results are defined bit for bit.
+ *
+ * Definition, in the notation of "coded links": T steps, states with bit k = u[t-1-k], the deinterleaved (at a punctured
+ * rate: depunctured) mother values d, the int32 path metric = sum of (2c - 1) * v, the branch metric of a step = its two
+ * terms.
+ *   decoded bits     u^[t], payload, ok and corrected are ofdm_fec_decode's / ofdm_fec_decode_soft's, ties included: the
+ *                    same rule and the same traceback
+ *   forward metric   alpha_0(0) = 0, alpha_0(s) = -2^29 for s != 0; alpha_{t+1}(s') = the maximum over the two
+ *                    predecessors of alpha_t + branch metric (the values the decoder holds after step t)
+ *   backward metric  beta_T(0) = 0, beta_T(s) = -2^29 for s != 0; beta_t(s) = the maximum over the two successors
+ *                    s' = ((s & 31) << 1) | b of beta_{t+1}(s') + the branch metric of s -> s' at step t
+ *   alternative      for an info bit t < 8(n+4) and b in {0, 1}: A_t(b) = max over s' with (s' & 1) = b of
+ *                    alpha_{t+1}(s') + beta_{t+1}(s'), the best metric of a path from state 0 to state 0 with u[t] = b
+ *   bit reliability  M* = alpha_T(0); Delta_t = M* - A_t(1 - u^[t]).  Delta_t >= 0 (u^'s path has metric M*), even (two
+ *                    path metrics differ by 2 * sum of +-v) and finite (flipping one info bit and keeping the zero tail is
+ *                    a path).  No sum leaves int32: |metric| <= 2 * 16358 * 127, and at most two -2^29 terms meet.
+ *   byte reliability for payload byte m < n: q[m] = min(255, min over t = 8m .. 8m + 7 of Delta_t / 2).  0: a path as
+ *                    good as the decoded one disagrees in this byte; 255 is ofdm_rs_decode_rel's "never erase".  Nothing
+ *                    is produced for the CRC bytes or the tail.
+ * This is the full (Battail / max-log-MAP) soft output, not a windowed one.  A length that is no block gives ok = 0, no
+ * payload bytes and no reliability bytes.
+ *
+ * rel is a host or device pointer by the handle's mode, rel_cap its bytes; block k's n_k bytes lie at
+ * rel + payload_off[k], the offsets of the payload blob.  In device-pointer mode payloads, rel and payload_off are
+ * therefore ofdm_rs_decode_rel's coded, rel and coded_off with rel_off == NULL: the two layers chain without a host
+ * round trip.  Errors as ofdm_fec_decode (ofdm_rx_fec_decode_soft for the third); in addition a null rel is
+ * OFDM_E_INVAL, and rel_cap < payload_off[nblk] is OFDM_E_CAPACITY with the offsets set first.
+ * Workspace: next to the decision words (8 bytes per step) the forward metrics at every 64th step, 4 bytes per step and
+ * block in flight, in a buffer the handle owns, cut into the same slices.  At a punctured rate k_fec_depuncture runs
+ * first, exactly as for ofdm_fec_decode.  After these calls ofdm_fec_last_ms reports k_fec_decode_rel's slices, and
+ * ofdm_fec_punct_last_ms behaves as after ofdm_fec_decode. */
+int ofdm_fec_decode_rel(ofdm_handle *h, const ofdm_fec_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,
+                        const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap, uint64_t *payload_off,
+                        uint8_t *ok, uint32_t *corrected, uint8_t *rel, uint64_t rel_cap);
+int ofdm_fec_decode_soft_rel(ofdm_handle *h, const ofdm_fec_cfg *cfg, const int8_t *soft, const uint64_t *soft_off,
+                             const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap,
+                             uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *rel, uint64_t rel_cap);
+int ofdm_rx_fec_decode_soft_rel(ofdm_handle *h, const ofdm_fec_cfg *cfg, uint8_t *payloads, uint64_t payload_cap,
+                                uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *rel, uint64_t rel_cap,
+                                int max_pkts, int *n);
+
 /* --- outer code: Reed-Solomon over GF(2^8) on the GPU, the outer half of a concatenated link -----------------------------
  * A byte-oriented code at the payload boundary, above the coded links and independent of them (it also works on an
  * uncoded link): ofdm_rs_encode turns payloads into RS blocks that go to ofdm_fec_encode, or straight to ofdm_tx /

@@ -340,6 +340,7 @@ EXPORTS = (
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
+    "ofdm_fec_decode_rel", "ofdm_fec_decode_soft_rel", "ofdm_rx_fec_decode_soft_rel",
     "ofdm_rs_coded_len", "ofdm_rs_payload_len", "ofdm_rs_encode", "ofdm_rs_decode", "ofdm_rs_last_ms",
     "ofdm_rs_decode_rel", "ofdm_rs_rel_from_soft", "ofdm_rs_rel_last_ms",
 )
@@ -446,6 +447,9 @@ def _declare(lib):
     lib.ofdm_rx_soft.argtypes = [H, vp, C.c_uint64, u64p, C.POINTER(C.c_int)]
     lib.ofdm_rx_fec_decode_soft.argtypes = [H, FC, u8p, C.c_uint64, u64p, vp, u32p, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_rx_soft_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_fec_decode_rel.argtypes = lib.ofdm_fec_decode.argtypes + [u8p, C.c_uint64]
+    lib.ofdm_fec_decode_soft_rel.argtypes = lib.ofdm_fec_decode_rel.argtypes
+    lib.ofdm_rx_fec_decode_soft_rel.argtypes = [H, FC, u8p, C.c_uint64, u64p, vp, u32p, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_rs_coded_len.argtypes = [C.c_uint32, u32p]
     lib.ofdm_rs_payload_len.argtypes = [C.c_uint32, u32p]
     lib.ofdm_rs_encode.argtypes = [H, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]

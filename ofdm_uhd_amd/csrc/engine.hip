@@ -34,6 +34,7 @@
 #include "multipath.h"
 #include "fec.h"
 #include "fec_punct.h"
+#include "fec_rel.h"
 #include "rs.h"
 
 static std::string g_create_error;
@@ -133,6 +134,7 @@ struct ofdm_handle {
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
+  FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h / engine_fec_rel.inc)
   RsState rs;  // outer code: Reed-Solomon over the payloads, above the coded links (rs.h / engine_rs.inc)
 };
 
@@ -570,6 +572,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->multipath.release();
   h->fec.release();
   h->fec_punct.release();
+  h->fec_rel.release();
   h->rs.release();
   {
     SenseState& ss = h->sense;
@@ -1015,4 +1018,5 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_multipath.inc"
 #include "engine_fec.inc"
 #include "engine_soft.inc"
+#include "engine_fec_rel.inc"
 #include "engine_rs.inc"

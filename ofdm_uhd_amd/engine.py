@@ -909,8 +909,65 @@ class Engine(object):
         return self._fec_decode(fn, self._fec_cfg(fec), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
 
     def fec_last_ms(self):
-        """HIP-event time of k_fec_encode / k_fec_decode in the last fec call (needs prof_enable())."""
+        """HIP-event time of k_fec_encode / k_fec_decode (k_fec_decode_rel after a ``*_rel`` call) in the last fec call
+        (needs prof_enable())."""
         return self._stage_last_ms("fec")
+
+    # -- coded links, reliabilities out (the soft-output Viterbi decoder: one reliability byte per payload byte) --------
+    def _fec_decode_rel(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap, rel_ptr, rel_cap):
+        n = len(lens)
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr = np.zeros(max(n, 1), np.uint32)
+        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
+                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32)),
+                       rel_ptr, int(rel_cap)))
+        return poff, ok[:n], corr[:n]
+
+    @staticmethod
+    def _fec_rel_results(n, poff, ok, corr, out, rel):
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), rel[int(poff[i]):int(poff[i + 1])].copy())
+                for i in range(n)]
+
+    def fec_decode_rel(self, blocks, fec=None):
+        """Host mode: fec_decode() with reliabilities -> list of (ok, payload, corrected, rel): fec_decode()'s three
+        fields, and ``rel`` a uint8 array of len(payload): 0 where a path as good as the decoded one disagrees in the
+        byte, 255 "never erase" -- what rs_decode_rel() takes.  A length that is no block gives (False, b"", 0, [])."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        blob, offs, lens = pack_payloads(blocks)
+        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
+        rel = np.zeros(len(out), np.uint8)
+        poff, ok, corr = self._fec_decode_rel(self._lib.ofdm_fec_decode_rel, cfg, _ptr(blob), offs, lens, _ptr(out), len(out),
+                                              _ptr(rel), len(rel))
+        return self._fec_rel_results(len(blocks), poff, ok, corr, out, rel)
+
+    def fec_decode_soft_rel(self, values, fec=None):
+        """Host mode: fec_decode_soft() with reliabilities -> list of (ok, payload, corrected, rel) as fec_decode_rel."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
+        # (a length that is no multiple of 8 is handed on as the odd length 1: no block)
+        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
+        offs = np.zeros(max(len(vals), 1), np.uint64)
+        if len(vals) > 1:
+            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
+        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
+        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
+        rel = np.zeros(len(out), np.uint8)
+        poff, ok, corr = self._fec_decode_rel(self._lib.ofdm_fec_decode_soft_rel, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out),
+                                              len(out), _ptr(rel), len(rel))
+        return self._fec_rel_results(len(vals), poff, ok, corr, out, rel)
+
+    def fec_decode_rel_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, rel_ptr, rel_cap, fec=None, soft=False):
+        """Device mode: fec_decode_device() with the reliabilities written to the device buffer ``rel_ptr`` at the
+        payloads' offsets: (payload_ptr, rel_ptr, the returned offsets) are what rs_decode_rel_device() takes as blocks,
+        reliabilities and offsets, with ``rel_offs=None``.  Returns (payload offsets, ok, corrected) as host arrays."""
+        assert self.device_ptrs
+        fn = self._lib.ofdm_fec_decode_soft_rel if soft else self._lib.ofdm_fec_decode_rel
+        return self._fec_decode_rel(fn, self._fec_cfg(fec), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap,
+                                    C.c_void_p(rel_ptr), rel_cap)
 
     def fec_punct_last_ms(self):
         """HIP-event time of k_fec_puncture / k_fec_depuncture alone in the last fec call, which ran at a punctured
@@ -1120,6 +1177,33 @@ class Engine(object):
         assert self.device_ptrs
         n, _ = self._rx_soft_offsets()
         return self._rx_fec_decode_soft(fec, C.c_void_p(payload_ptr), payload_cap, n)
+
+    def _rx_fec_decode_soft_rel(self, fec, out_ptr, out_cap, rel_ptr, rel_cap, n):
+        poff = np.zeros(n + 1, np.uint64)
+        ok = np.zeros(max(n, 1), np.uint8)
+        corr = np.zeros(max(n, 1), np.uint32)
+        self._check(self._lib.ofdm_rx_fec_decode_soft_rel(self._h, C.byref(self._fec_cfg(fec)), out_ptr, int(out_cap),
+                                                          poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
+                                                          corr.ctypes.data_as(C.POINTER(C.c_uint32)), rel_ptr, int(rel_cap), n,
+                                                          C.byref(C.c_int(0))))
+        return poff, ok[:n], corr[:n]
+
+    def rx_fec_decode_soft_rel(self, fec=None):
+        """Host mode: rx_fec_decode_soft() with reliabilities -> list of (ok, payload, corrected, rel) as
+        fec_decode_rel."""
+        assert not self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        out = np.zeros(self._fec_payload_room(self._fec_cfg(fec), [int(off[n]) // 8]), np.uint8)
+        rel = np.zeros(len(out), np.uint8)
+        poff, ok, corr = self._rx_fec_decode_soft_rel(fec, _ptr(out), len(out), _ptr(rel), len(rel), n)
+        return self._fec_rel_results(n, poff, ok, corr, out, rel)
+
+    def rx_fec_decode_soft_rel_device(self, payload_ptr, payload_cap, rel_ptr, rel_cap, fec=None):
+        """Device mode: the same into the device buffers ``payload_ptr`` and ``rel_ptr``; returns (payload offsets
+        uint64[n + 1], ok uint8[n], corrected uint32[n]) as host arrays."""
+        assert self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._rx_fec_decode_soft_rel(fec, C.c_void_p(payload_ptr), payload_cap, C.c_void_p(rel_ptr), rel_cap, n)
 
     def rx_soft_last_ms(self):
         """HIP-event time of k_soft_demap in the last rx() / rx_device() (needs prof_enable())."""

@@ -5,6 +5,13 @@ decoder on the GPU, and its punctured rates 2/3, 3/4 and 5/6 (the 802.11 pattern
 redundancy (include/ofdm_hip.h, "coded links").  The work is ``Engine.fec_encode`` /
 ``Engine.fec_decode`` / ``Engine.fec_decode_soft``; ``ofdm_mod(fec=...)`` and ``ofdm_demod(fec=...)`` put it on a
 link, both ends with the same setting.
+
+Reliabilities out (include/ofdm_hip.h, "coded links, reliabilities out"): ``Engine.fec_decode_rel`` /
+``Engine.fec_decode_soft_rel`` / ``Engine.rx_fec_decode_soft_rel`` run a second decoder that returns the same payloads,
+verdicts and corrected counts, and one uint8 per decoded payload byte: half the metric gap between the decoded path and
+the best path that disagrees in one of the byte's bits, clamped to 255 (0: a path as good as the decoded one disagrees
+here).  That is what ``Engine.rs_decode_rel`` takes, so a concatenated link can erase the outer code's weakest symbols:
+``ofdm_demod(fec=..., rs=dict(erasures=True, source="fec"))``.
 """
 import ctypes as C
 

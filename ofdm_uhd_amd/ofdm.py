@@ -282,9 +282,13 @@ class ofdm_demod(object):
             codewords that could not be decoded; ``last_fec`` keeps its meaning; ``n_ok`` counts outer verdicts.
             ``dict(erasures=True, max_erasures=28)`` decodes with reliabilities (Engine.rs_decode_rel): a codeword that
             fails is tried once more with its weakest symbols, ``max_erasures`` at the most, erased; the reliabilities
-            come from ``last_soft`` (Engine.rs_rel_from_soft), so it needs ``soft`` and no ``fec`` -- behind the inner
-            decoder there is no source of reliabilities yet (ValueError).  ``last_rs`` keeps its three fields,
-            ``last_rs_second`` holds the codewords per packet that the second pass decoded
+            come from ``last_soft`` (Engine.rs_rel_from_soft), so without ``source`` it needs ``soft`` and no ``fec``
+            (ValueError).  ``dict(erasures=True, source="fec", max_erasures=28)`` is the same on a concatenated link:
+            it needs ``fec``, with or without ``soft``; the inner decoder is then the soft-output one
+            (Engine.rx_fec_decode_soft_rel with ``soft``, Engine.fec_decode_rel on the hard bytes without), which
+            returns the same payloads and one reliability per decoded byte, and those go to Engine.rs_decode_rel;
+            ``last_fec_rel`` holds them, one uint8 array per packet.  Any other ``source`` is a ValueError.  ``last_rs``
+            keeps its three fields, ``last_rs_second`` holds the codewords per packet that the second pass decoded
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -303,15 +307,26 @@ class ofdm_demod(object):
         self.last_rs = []            # (inner_ok, corrected, failed) of the packets the last work() / feed() returned (rs only)
         self._rs_rel = None          # ofdm_rs_rel_cfg: decode with reliabilities from last_soft
         self.last_rs_second = []     # codewords per packet the second pass decoded (rs=dict(erasures=True) only)
+        self._rs_rel_fec = False     # the reliabilities are the inner decoder's (source="fec"), not the soft demapper's
+        self.last_fec_rel = []       # uint8 reliabilities per decoded byte of the packets (source="fec" only)
         if isinstance(rs, dict):
             opts = dict(rs)
             erasures = bool(opts.pop("erasures", False))
             if not erasures and opts:
                 raise ValueError("rs: %s need(s) erasures=True" % ", ".join(sorted(opts)))
             if erasures:
-                if self._soft is None or self._fec is not None:
-                    raise ValueError("rs=dict(erasures=True) needs soft= and no fec=: the reliabilities are the soft "
-                                     "demapper's, and there is none behind the inner decoder yet")
+                source = opts.pop("source", None)
+                if source is None:
+                    if self._soft is None or self._fec is not None:
+                        raise ValueError("rs=dict(erasures=True) needs soft= and no fec=: the reliabilities are the soft "
+                                         "demapper's; behind the inner decoder ask for its own with source=\"fec\"")
+                elif source != "fec":
+                    raise ValueError("rs: source must be \"fec\" (the inner decoder's reliabilities) or left out "
+                                     "(the soft demapper's)")
+                elif self._fec is None:
+                    raise ValueError("rs=dict(erasures=True, source=\"fec\") needs fec=: the reliabilities are the "
+                                     "inner decoder's")
+                self._rs_rel_fec = source == "fec"
                 self._rs_rel = _rs.rs_cfg(**opts)
             self._rs = True
 
@@ -415,7 +430,10 @@ class ofdm_demod(object):
             pkts = self._decode_inner(pkts, sel)
         if self._rs_rel is not None:
             # (last_soft holds the delivered packets' values, in their order)
-            rel = self._engine.rs_rel_from_soft(self.last_soft) if pkts else []
+            if self._rs_rel_fec:
+                rel = self.last_fec_rel
+            else:
+                rel = self._engine.rs_rel_from_soft(self.last_soft) if pkts else []
             dec = self._engine.rs_decode_rel([p for _, p in pkts], rel, self._rs_rel) if pkts else []
             self.last_rs_second = [s for _, _, _, _, s in dec]
             dec = [d[:4] for d in dec]
@@ -428,7 +446,16 @@ class ofdm_demod(object):
         return pkts
 
     def _decode_inner(self, pkts, sel=None):
-        if self._soft is not None:
+        if self._rs_rel_fec:
+            if self._soft is not None:
+                dec = self._engine.rx_fec_decode_soft_rel(self._fec) if pkts else []
+                if sel is not None:
+                    dec = [dec[i] for i in sel]
+            else:
+                dec = self._engine.fec_decode_rel([p for _, p in pkts], self._fec) if pkts else []
+            self.last_fec_rel = [r for _, _, _, r in dec]
+            dec = [d[:3] for d in dec]
+        elif self._soft is not None:
             dec = self._engine.rx_fec_decode_soft(self._fec) if pkts else []
             if sel is not None:
                 dec = [dec[i] for i in sel]

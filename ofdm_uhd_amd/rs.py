@@ -9,7 +9,11 @@ put it on a link, both ends alike.
 Decoding with reliabilities (``Engine.rs_decode_rel``, ``ofdm_demod(rs=dict(erasures=True))``): one byte per received
 byte says how far to trust it, and a codeword that bounded-distance decoding fails is tried once more with its weakest
 symbols, ``max_erasures`` at the most, erased.  ``rs_cfg`` makes the call's configuration, ``rel_from_values`` restates
-on the host what ``Engine.rs_rel_from_soft`` computes on the GPU.
+on the host what ``Engine.rs_rel_from_soft`` computes on the GPU.  That is the source of reliabilities on an RS link
+without an inner code.  On a concatenated link the source is the inner decoder itself
+(``ofdm_demod(fec=..., rs=dict(erasures=True, source="fec"))``): the soft-output Viterbi decoder
+(``Engine.fec_decode_rel`` / ``fec_decode_soft_rel`` / ``rx_fec_decode_soft_rel``) returns one reliability per decoded
+byte, 0 .. 255, in the format ``Engine.rs_decode_rel`` takes, at the payloads' own offsets.
 """
 import ctypes as C
 
