@@ -1343,6 +1343,93 @@ int ofdm_rs_rel_from_soft(ofdm_handle *h, const int8_t *soft, const uint64_t *so
                           uint8_t *rel, uint64_t rel_cap, uint64_t *rel_off);
 int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- coded links: LDPC -- a rate-1/2 quasi-cyclic code with a layered min-sum decoder on the GPU -------------------------
+ * A second inner code next to the convolutional one, at the same boundary: ofdm_ldpc_encode turns payloads into coded
+ * blocks that go to ofdm_tx / ofdm_make_packets as payloads; ofdm_ldpc_decode takes the payloads ofdm_rx delivered
+ * (CRC-failed ones included).  Additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, no existing
+ * kernel, launch or workspace changes, and without a call to these functions nothing here launches, allocates or
+ * copies.  All arithmetic is integer: results are defined bit for bit.
+ *
+ * Code.  Circulant size Z = 64, base matrix 12 rows x 24 columns: n = 1536 bits, k = 768 info bits per codeword.
+ * Codeword bit 64 j + z is lane z of column j.  For a 64-bit column x, rot(x, s)[z] = x[(z + s) mod 64].  Check (i, z):
+ * the XOR over the entries (i, j, s) of rot(x_j, s)[z] is 0.  Info part, the shift of row i (down) and column
+ * j = 0 .. 11 (across), - for no entry:
+ *    0:  -  1  -  - 25  -  - 42  - 59  - 24
+ *    1:  -  -  - 17 48  -  -  - 37  - 21 42
+ *    2:  2  -  -  -  -  -  0  - 56  - 20 50
+ *    3:  - 52  -  -  -  5  -  - 45 19 45  -
+ *    4:  -  - 34  -  -  - 30  - 29 31  - 55
+ *    5: 17  -  -  -  -  -  5  - 53  - 21 36
+ *    6:  -  -  -  -  -  - 25 16  - 22  -  -
+ *    7:  -  - 38  -  - 54  - 48  - 56  3  -
+ *    8:  - 58  -  -  -  -  -  7 60 36  - 20
+ *    9:  -  -  - 59 35  -  -  -  - 46 38 25
+ *   10: 40  -  - 42  -  -  -  - 24 33 16  -
+ *   11:  -  - 46  -  -  1  -  - 51  - 25  5
+ * Parity part: column 12 has shift 1 in row 0, shift 0 in row 6 and shift 1 in row 11; column 13 + i (i = 0 .. 10) has
+ * shift 0 in rows i and i + 1.  58 + 25 = 83 entries; row degree 7, 6 in row 6; no 4-cycles.  The parity bits are the
+ * unique solution of all checks: with lambda_i the XOR of the info entries of row i and p_c column 12 + c,
+ *   p_0 = XOR of all lambda_i;  p_1 = lambda_0 ^ rot(p_0, 1);  p_{i+1} = lambda_i ^ p_i ^ (p_0 if i = 6), i = 1 .. 10.
+ *
+ * Block.  Info bytes of an n-byte payload (0 <= n <= OFDM_LDPC_MAX_PAYLOAD): payload | CRC-32(payload) big-endian,
+ * k = n + 4 bytes, bits MSB first; info byte m of a codeword holds codeword bits 8m .. 8m + 7.  W = ceil(k / 96)
+ * codewords, codeword w takes info bytes [96w, min(96w + 96, k)); the last codeword is shortened: its missing info bits
+ * are 0 and are not sent.  Sent, codeword after codeword: its k_w info bytes, then its 96 parity bytes.  Coded length
+ * k + 96 W, strictly increasing in n; OFDM_LDPC_MAX_PAYLOAD = 2012 gives W = 21 and OFDM_LDPC_MAX_CODED = 4032.
+ * A received length m is a block iff 100 <= m <= 4032 and ((m - 1) mod 192) >= 96; then W = ceil(m / 192) and
+ * k = m - 96 W.  Anything else is no block: ok = 0, no payload bytes, zeros in the per-block outputs, no error for the
+ * batch, and nothing of it is read.
+ *
+ * Decoder input: one signed value v per sent bit, v > 0 means 1, v = 0 is an erasure, -128 reads as -127; shortened
+ * positions read as -127; a hard byte is v = +16 / -16 per bit.
+ * Decoder: layered normalised min-sum.  P_b (int) starts as v_b, R_e = 0 for every entry e and lane z.  An iteration
+ * visits rows i = 0 .. 11 in order; for each entry e = (i, j, s) of the row and each lane z, b = 64 j + (z + s) mod 64:
+ *   1. Q_e = clamp(P_b - R_e, -127, 127)
+ *   2. beta_e = (Q_e > 0); pi = XOR of the row's beta; m_e = min of |Q_e'| over the row's other entries e' != e
+ *   3. mu_e = (3 m_e) >> 2
+ *   4. R_e = +mu_e if (pi ^ beta_e) = 1, else -mu_e
+ *   5. P_b = Q_e + R_e   (no clamp: |P| <= 222)
+ * After each full iteration x_b = (P_b > 0); a codeword stops at the first iteration after which every check holds, at
+ * the latest after max_iters iterations; at least one iteration always runs.
+ * Per block: the n payload bytes from the decoded info bits; ok = 1 when the decoded CRC matches; corrected = sent
+ * positions with v != 0 whose sign disagrees with x; iters = the largest iteration count among the block's codewords;
+ * cw_failed = codewords whose last syndrome is non-zero.
+ *
+ * Argument order, pointer modes, errors and the offsets-before-the-capacity-check rule as ofdm_fec_*: the blobs
+ * (payloads, coded, soft) are host or device pointers by the handle's mode; the offset, length, ok, corrected, iters and
+ * cw_failed arrays are host memory; coded_off / payload_off OUT have nblk + 1 entries.  cfg NULL: max_iters 20 (the
+ * encoder checks its cfg and ignores max_iters).  OFDM_E_INVAL: bad struct_size, max_iters outside 1 .. 64, a non-zero
+ * reserved word, a payload longer than OFDM_LDPC_MAX_PAYLOAD (encode), a null argument.  OFDM_E_CAPACITY: the output blob
+ * is too small.  There is no per-batch workspace and no slicing: a batch is as many one-wave codewords as it has.
+ * ofdm_rx_ldpc_decode_soft: the last ofdm_rx call's packets through ofdm_ldpc_decode_soft's decoder, the values read
+ * where they lie in the handle's buffer (ofdm_set_rx_soft), as ofdm_rx_fec_decode_soft.
+ * ofdm_ldpc_last_ms: HIP-event time of k_ldpc_encode / k_ldpc_decode in the last of these calls, which must have run
+ * with profiling on (ofdm_prof_enable) and launched; OFDM_E_INVAL otherwise.  As ofdm_fec_last_ms. */
+#define OFDM_LDPC_MAX_PAYLOAD 2012
+#define OFDM_LDPC_MAX_CODED 4032
+typedef struct ofdm_ldpc_cfg {
+  uint32_t struct_size; /* = sizeof(ofdm_ldpc_cfg) */
+  uint32_t max_iters;   /* 1 .. 64 */
+  uint32_t reserved[6]; /* 0 */
+} ofdm_ldpc_cfg;        /* 32 bytes */
+
+/* pure host functions, usable without a GPU: n + 4 + 96 W, and its inverse (OFDM_E_INVAL for a length that is no block) */
+int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t *coded_len);
+int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t *payload_len);
+int ofdm_ldpc_encode(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const uint8_t *payloads, const uint64_t *payload_off,
+                     const uint32_t *payload_len, int nblk, uint8_t *coded, uint64_t coded_cap, uint64_t *coded_off);
+int ofdm_ldpc_decode(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,
+                     const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap, uint64_t *payload_off,
+                     uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed);
+/* the same from int8 values, 8 per coded byte: block k holds 8 * coded_len[k] values from soft + soft_off[k] */
+int ofdm_ldpc_decode_soft(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const int8_t *soft, const uint64_t *soft_off,
+                          const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap,
+                          uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed);
+int ofdm_rx_ldpc_decode_soft(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, uint8_t *payloads, uint64_t payload_cap,
+                             uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed,
+                             int max_pkts, int *n);
+int ofdm_ldpc_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

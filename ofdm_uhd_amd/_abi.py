@@ -30,6 +30,8 @@ OFDM_MULTIPATH_MAX_DELAY = 1023
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
+OFDM_LDPC_MAX_PAYLOAD = 2012
+OFDM_LDPC_MAX_CODED = 4032
 OFDM_RS_PARITY = 32
 OFDM_RS_MAX_PAYLOAD = 3564
 OFDM_RS_MAX_CODED = 4080
@@ -312,6 +314,14 @@ class ofdm_rs_rel_cfg(C.Structure):
     ]
 
 
+class ofdm_ldpc_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_iters", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
 # every symbol include/ofdm_hip.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "ofdm_abi_version", "ofdm_device_count", "ofdm_create", "ofdm_destroy", "ofdm_last_error",
@@ -343,6 +353,8 @@ EXPORTS = (
     "ofdm_fec_decode_rel", "ofdm_fec_decode_soft_rel", "ofdm_rx_fec_decode_soft_rel",
     "ofdm_rs_coded_len", "ofdm_rs_payload_len", "ofdm_rs_encode", "ofdm_rs_decode", "ofdm_rs_last_ms",
     "ofdm_rs_decode_rel", "ofdm_rs_rel_from_soft", "ofdm_rs_rel_last_ms",
+    "ofdm_ldpc_coded_len", "ofdm_ldpc_payload_len", "ofdm_ldpc_encode", "ofdm_ldpc_decode", "ofdm_ldpc_decode_soft",
+    "ofdm_rx_ldpc_decode_soft", "ofdm_ldpc_last_ms",
 )
 
 _LIB = None
@@ -459,6 +471,14 @@ def _declare(lib):
                                        u32p, u32p]
     lib.ofdm_rs_rel_from_soft.argtypes = [H, vp, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
     lib.ofdm_rs_rel_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    LC = C.POINTER(ofdm_ldpc_cfg)
+    lib.ofdm_ldpc_coded_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_ldpc_payload_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_ldpc_encode.argtypes = [H, LC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
+    lib.ofdm_ldpc_decode.argtypes = [H, LC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p]
+    lib.ofdm_ldpc_decode_soft.argtypes = lib.ofdm_ldpc_decode.argtypes
+    lib.ofdm_rx_ldpc_decode_soft.argtypes = [H, LC, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_ldpc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

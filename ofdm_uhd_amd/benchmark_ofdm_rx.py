@@ -87,10 +87,17 @@ def make_parser():
     parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
                       help="coded link at this rate, as benchmark_ofdm_tx --fec-rate wrote it (implies --fec; works "
                            "with --fec-soft) [default=1/2]")
+    parser.add_option("", "--ldpc", action="store_true", default=False,
+                      help="coded link with the other inner code: the file was written by benchmark_ofdm_tx --ldpc; "
+                           "every delivered packet, the CRC-failed ones included, goes through the min-sum decoder on "
+                           "the GPU and is accounted by the CRC inside the code [default=%default]")
+    parser.add_option("", "--ldpc-soft", action="store_true", default=False,
+                      help="--ldpc with soft decisions: the decoder takes the soft demapper's value of every coded bit "
+                           "where --ldpc takes the sliced bytes [default=%default]")
     parser.add_option("", "--rs", action="store_true", default=False,
                       help="outer code: the file was written by benchmark_ofdm_tx --rs; every delivered packet goes "
                            "through the Reed-Solomon decoder on the GPU, behind the inner decoder where --fec, "
-                           "--fec-rate or --fec-soft is given, and is accounted by the CRC inside the RS block "
+                           "--fec-rate, --fec-soft, --ldpc or --ldpc-soft is given, and is accounted by the CRC inside the RS block "
                            "[default=%default]")
     parser.add_option("", "--rs-erasures", action="callback", callback=_rs_erasures, dest="rs_erasures", default=None,
                       help="--rs, decoding with reliabilities: --rs-erasures [M] erases the weakest symbols, at most M "
@@ -182,12 +189,18 @@ def main(argv=None):
         options.fec = True
     if options.fec_rate:
         options.fec = dict(rate=options.fec_rate)   # (what receive_path hands to ofdm_demod(fec=))
+    if options.ldpc_soft:
+        options.ldpc = True
+    if options.ldpc and options.fec:
+        parser.error("--ldpc / --ldpc-soft take the place of --fec / --fec-rate / --fec-soft: a link has one inner code")
+    if options.ldpc and options.rs_erasures is not None:
+        parser.error("--rs-erasures does not combine with --ldpc / --ldpc-soft: that decoder produces no byte reliabilities")
     if options.rs_erasures is not None:
         if options.fec:
             parser.error("--rs-erasures needs an RS link without an inner code: not with --fec, --fec-rate or --fec-soft")
         options.rs = True
-    if (options.fec or options.rs) and (options.resamp_freqs is not None or options.ddc_freqs is not None):
-        parser.error("--fec and --rs do not combine with --ddc-freqs or --resamp-freqs")
+    if (options.fec or options.rs or options.ldpc) and (options.resamp_freqs is not None or options.ddc_freqs is not None):
+        parser.error("--fec, --ldpc and --rs do not combine with --ddc-freqs or --resamp-freqs")
     if options.resamp_freqs is not None:
         return _main_resamp_bank(parser, options)
     if options.ddc_freqs is not None:

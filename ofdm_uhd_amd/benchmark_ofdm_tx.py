@@ -61,8 +61,12 @@ def make_parser():
     parser.add_option("", "--fec-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
                       help="coded link at this rate: the K=7 code punctured by the 802.11 patterns (implies --fec; "
                            "demodulate with the same benchmark_ofdm_rx --fec-rate) [default=1/2]")
+    parser.add_option("", "--ldpc", action="store_true", default=False,
+                      help="coded link with the other inner code, in the place of --fec: protect every payload (at "
+                           "most 2012 bytes) with the rate-1/2 QC-LDPC code, encoded on the GPU; demodulate with "
+                           "benchmark_ofdm_rx --ldpc or --ldpc-soft [default=%default]")
     parser.add_option("", "--rs", action="store_true", default=False,
-                      help="outer code: wrap every payload (at most 3564 bytes, 1780 with --fec / --fec-rate) in a "
+                      help="outer code: wrap every payload (at most 3564 bytes, 1780 with --fec / --fec-rate, 1752 with --ldpc) in a "
                            "Reed-Solomon block, 32 parity bytes per 223, encoded on the GPU ahead of the inner code; "
                            "demodulate with benchmark_ofdm_rx --rs [default=%default]")
     _options.add_tx_resamp_options(parser)
@@ -83,8 +87,8 @@ def _main_tx_resamp_bank(parser, options):
     the packets sent per link."""
     if options.duc_interp or options.duc_freq:
         parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
-    if options.fec or options.rs:
-        parser.error("--tx-resamp-freqs does not combine with --fec or --rs")
+    if options.fec or options.rs or options.ldpc:
+        parser.error("--tx-resamp-freqs does not combine with --fec, --ldpc or --rs")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -132,6 +136,8 @@ def main(argv=None):
         sys.exit(1)
     if options.fec_rate:
         options.fec = dict(rate=options.fec_rate)   # (what transmit_path hands to ofdm_mod(fec=))
+    if options.ldpc and options.fec:
+        parser.error("--ldpc takes the place of --fec / --fec-rate: a link has one inner code")
     if options.tx_resamp_freqs is not None:
         return _main_tx_resamp_bank(parser, options)
 

@@ -36,6 +36,7 @@
 #include "fec_punct.h"
 #include "fec_rel.h"
 #include "rs.h"
+#include "ldpc.h"
 
 static std::string g_create_error;
 
@@ -136,6 +137,7 @@ struct ofdm_handle {
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
   FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h / engine_fec_rel.inc)
   RsState rs;  // outer code: Reed-Solomon over the payloads, above the coded links (rs.h / engine_rs.inc)
+  LdpcState ldpc;  // coded links, the second inner code: QC-LDPC encoder and min-sum decoder (ldpc.h / engine_ldpc.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -573,6 +575,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->fec.release();
   h->fec_punct.release();
   h->fec_rel.release();
+  h->ldpc.release();
   h->rs.release();
   {
     SenseState& ss = h->sense;
@@ -1020,3 +1023,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_soft.inc"
 #include "engine_fec_rel.inc"
 #include "engine_rs.inc"
+#include "engine_ldpc.inc"

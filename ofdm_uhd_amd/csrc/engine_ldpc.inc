@@ -1,0 +1,193 @@
+// engine_ldpc.inc -- host side of the LDPC coded-link layer (ldpc.h): lengths, the codeword map of a batch, launches.
+// Included by engine.hip after engine_rs.inc.  The arithmetic that needs no GPU is ldpc_plan.h.
+
+extern "C" int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t* coded_len) { return ldpc_coded_len(payload_len, coded_len); }
+extern "C" int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t* payload_len) { return ldpc_payload_len(coded_len, payload_len); }
+
+extern "C" int ofdm_ldpc_last_ms(const ofdm_handle* h, double* ms) {
+  if (!h || !ms || !h->ldpc.timed) return OFDM_E_INVAL;
+  *ms = h->ldpc.last_ms;
+  return OFDM_OK;
+}
+
+static int ldpc_iters(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint32_t* max_iters) {
+  *max_iters = LDPC_DEFAULT_ITERS;
+  if (!cfg) return OFDM_OK;
+  if (cfg->struct_size != sizeof(ofdm_ldpc_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.struct_size does not match this library");
+  if (cfg->max_iters < 1 || cfg->max_iters > LDPC_MAX_ITERS) FAIL(h, OFDM_E_INVAL, "ldpc max_iters must be in [1, 64]");
+  for (uint32_t r : cfg->reserved)
+    if (r) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.reserved must be 0");
+  *max_iters = cfg->max_iters;
+  return OFDM_OK;
+}
+
+static int ldpc_time_begin(ofdm_handle* h, LdpcState& f, hipStream_t st, bool timing) {
+  if (!timing) return OFDM_OK;
+  if (!f.ev_a) {
+    HIPCHK(h, hipEventCreate(&f.ev_a));
+    HIPCHK(h, hipEventCreate(&f.ev_b));
+  }
+  HIPCHK(h, hipEventRecord(f.ev_a, st));
+  return OFDM_OK;
+}
+
+static int ldpc_finish(ofdm_handle* h, LdpcState& f, hipStream_t st, bool timing) {
+  HIPCHK(h, hipStreamSynchronize(st));
+  if (timing) {
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, f.ev_a, f.ev_b));
+    f.last_ms = (double)ms;
+    f.timed = true;
+  }
+  return OFDM_OK;
+}
+
+// the batch's two tables on the device: blocks, and the block of every codeword
+static int ldpc_upload_map(ofdm_handle* h, LdpcState& f, hipStream_t st, int nblk, uint64_t ncw) {
+  HIPCHK(h, f.d_blk.ensure(sizeof(LdpcBlk) * (size_t)nblk));
+  HIPCHK(h, f.d_cw.ensure(sizeof(uint32_t) * (size_t)ncw));
+  HIPCHK(h, hipMemcpyAsync(f.d_blk.p, f.blk.data(), sizeof(LdpcBlk) * (size_t)nblk, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(f.d_cw.p, f.cw.data(), sizeof(uint32_t) * (size_t)ncw, hipMemcpyHostToDevice, st));
+  return OFDM_OK;
+}
+
+/* payloads in, coded blocks out: what ofdm_tx / ofdm_make_packets then take as payloads */
+extern "C" int ofdm_ldpc_encode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* payloads, const uint64_t* payload_off,
+                                const uint32_t* payload_len, int nblk, uint8_t* coded, uint64_t coded_cap, uint64_t* coded_off) {
+  if (!h) return OFDM_E_INVAL;
+  LdpcState& f = h->ldpc;
+  if (nblk < 0 || (nblk && (!payloads || !payload_off || !payload_len)) || !coded_off) FAIL(h, OFDM_E_INVAL, "null argument");
+  uint32_t iters;
+  RCCHK(ldpc_iters(h, cfg, &iters));
+  f.blk.resize((size_t)nblk);
+  f.cw.resize((size_t)nblk * LDPC_MAX_WORDS);
+  uint64_t ncw = 0, extent = 0;
+  const uint64_t total = ldpc_plan_encode(payload_off, payload_len, (uint64_t)nblk, f.blk.data(), coded_off, f.cw.data(), &ncw, &extent);
+  if (total == ~0ull) FAIL(h, OFDM_E_INVAL, "ldpc: len(payload) must be in [0, 2012]");
+  f.timed = false;
+  if (total > coded_cap) FAIL(h, OFDM_E_CAPACITY, "coded buffer too small (see ofdm_ldpc_coded_len)");
+  if (nblk == 0) return OFDM_OK;
+  if (!coded) FAIL(h, OFDM_E_INVAL, "null argument");
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t st = h->txs;  // the transmit side: ordered with the ofdm_tx that takes the blocks
+  const uint8_t* d_in = payloads;
+  uint8_t* d_out = coded;
+  RCCHK(ldpc_upload_map(h, f, st, nblk, ncw));
+  if (!h->dev_ptrs) {
+    HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
+    if (extent) HIPCHK(h, hipMemcpyAsync(f.d_in.p, payloads, extent, hipMemcpyHostToDevice, st));
+    HIPCHK(h, f.d_out.ensure(total));
+    d_in = f.d_in.as<uint8_t>();
+    d_out = f.d_out.as<uint8_t>();
+  }
+  const bool timing = h->prof.on;
+  RCCHK(ldpc_time_begin(h, f, st, timing));
+  const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);  // every block has a codeword: ncw >= nblk >= 1
+  hipLaunchKernelGGL(k_ldpc_encode, dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw,
+                     d_out, h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>());
+  if (timing) HIPCHK(h, hipEventRecord(f.ev_b, st));
+  HIPCHK(h, hipGetLastError());
+  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(coded, d_out, total, hipMemcpyDeviceToHost, st));
+  return ldpc_finish(h, f, st, timing);  // (synchronises: the staged tables are the caller's again)
+}
+
+static void ldpc_no_blocks(int nblk, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
+  memset(ok, 0, (size_t)nblk);
+  memset(iters, 0, (size_t)nblk);
+  memset(corrected, 0, sizeof(uint32_t) * (size_t)nblk);
+  memset(cw_failed, 0, sizeof(uint32_t) * (size_t)nblk);
+}
+
+// in_on_device: the input blob is device memory whatever the handle's pointer mode (the handle's own soft values:
+// ofdm_rx_ldpc_decode_soft)
+template <bool SOFT>
+static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* in, const uint64_t* in_off, const uint32_t* coded_len,
+                            int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off, uint8_t* ok, uint32_t* corrected,
+                            uint8_t* iters, uint32_t* cw_failed, bool in_on_device = false) {
+  if (!h) return OFDM_E_INVAL;
+  LdpcState& f = h->ldpc;
+  if (nblk < 0 || (nblk && (!in || !in_off || !coded_len || !ok || !corrected || !iters || !cw_failed)) || !payload_off)
+    FAIL(h, OFDM_E_INVAL, "null argument");
+  uint32_t max_iters;
+  RCCHK(ldpc_iters(h, cfg, &max_iters));
+  f.blk.resize((size_t)nblk);
+  f.cw.resize((size_t)nblk * LDPC_MAX_WORDS);
+  uint64_t ncw = 0, extent = 0;
+  const uint64_t total = ldpc_plan_decode(in_off, coded_len, (uint64_t)nblk, SOFT ? 8u : 1u, f.blk.data(), payload_off, f.cw.data(), &ncw, &extent);
+  f.timed = false;
+  if (total > payload_cap) FAIL(h, OFDM_E_CAPACITY, "payload buffer too small (see ofdm_ldpc_payload_len)");
+  if (nblk == 0) return OFDM_OK;
+  if (total && !payloads) FAIL(h, OFDM_E_INVAL, "null argument");
+  if (ncw == 0) {  // not one block among them: nothing to launch
+    ldpc_no_blocks(nblk, ok, corrected, iters, cw_failed);
+    return OFDM_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t st = h->stream;  // the receive side: ordered behind the ofdm_rx that delivered the blocks
+  if (h->tx_pending && h->txs != h->stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev_tx_done, 0));
+  const uint8_t* d_in = in;
+  uint8_t* d_out = payloads;
+  RCCHK(ldpc_upload_map(h, f, st, nblk, ncw));
+  HIPCHK(h, f.d_res.ensure(sizeof(LdpcRes) * (size_t)nblk));
+  HIPCHK(h, hipMemsetAsync(f.d_res.p, 0, sizeof(LdpcRes) * (size_t)nblk, st));
+  if (!h->dev_ptrs) {
+    if (!in_on_device) {
+      HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
+      HIPCHK(h, hipMemcpyAsync(f.d_in.p, in, extent, hipMemcpyHostToDevice, st));
+      d_in = f.d_in.as<uint8_t>();
+    }
+    HIPCHK(h, f.d_out.ensure(std::max<uint64_t>(total, 1)));
+    d_out = f.d_out.as<uint8_t>();
+  }
+  const bool timing = h->prof.on;
+  RCCHK(ldpc_time_begin(h, f, st, timing));
+  const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(),
+                     f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, f.d_res.as<LdpcRes>(), h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(),
+                     max_iters);
+  if (timing) HIPCHK(h, hipEventRecord(f.ev_b, st));
+  HIPCHK(h, hipGetLastError());
+  f.res.resize((size_t)nblk);
+  HIPCHK(h, hipMemcpyAsync(f.res.data(), f.d_res.p, sizeof(LdpcRes) * (size_t)nblk, hipMemcpyDeviceToHost, st));
+  if (!h->dev_ptrs && total) HIPCHK(h, hipMemcpyAsync(payloads, d_out, total, hipMemcpyDeviceToHost, st));
+  RCCHK(ldpc_finish(h, f, st, timing));
+  for (int b = 0; b < nblk; b++) {  // a length that is no block had no codeword: its record is still zero
+    const LdpcRes& r = f.res[(size_t)b];
+    ok[b] = (ldpc_is_block(coded_len[b]) && r.crc == r.got) ? 1 : 0;
+    corrected[b] = r.corrected;
+    iters[b] = (uint8_t)r.iters;
+    cw_failed[b] = r.failed;
+  }
+  return OFDM_OK;
+}
+
+/* hard bytes in; payloads, ok[], corrected[], iters[] and cw_failed[] out */
+extern "C" int ofdm_ldpc_decode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* coded, const uint64_t* coded_off,
+                                const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off,
+                                uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
+  return ldpc_decode_impl<false>(h, cfg, coded, coded_off, coded_len, nblk, payloads, payload_cap, payload_off, ok, corrected, iters,
+                                 cw_failed);
+}
+
+/* the same from int8 values, 8 per coded byte */
+extern "C" int ofdm_ldpc_decode_soft(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const int8_t* soft, const uint64_t* soft_off,
+                                     const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap,
+                                     uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
+  return ldpc_decode_impl<true>(h, cfg, reinterpret_cast<const uint8_t*>(soft), soft_off, coded_len, nblk, payloads, payload_cap,
+                                payload_off, ok, corrected, iters, cw_failed);
+}
+
+/* the last ofdm_rx call's packets, decoded from the handle's own soft values */
+extern "C" int ofdm_rx_ldpc_decode_soft(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint8_t* payloads, uint64_t payload_cap,
+                                        uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed,
+                                        int max_pkts, int* n) {
+  if (!h) return OFDM_E_INVAL;
+  if (!n || max_pkts < 0) FAIL(h, OFDM_E_INVAL, "null argument");
+  RxState& rx = h->rx;
+  if (!rx.soft_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without soft values (ofdm_set_rx_soft)");
+  const size_t np = rx.soft_len.size();
+  *n = (int)np;
+  if ((size_t)max_pkts < np) FAIL(h, OFDM_E_CAPACITY, "ok / corrected / iters / cw_failed / payload_off arrays too small");
+  return ldpc_decode_impl<true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), (int)np, payloads, payload_cap,
+                                payload_off, ok, corrected, iters, cw_failed, true);
+}

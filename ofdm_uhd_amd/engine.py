@@ -1209,6 +1209,127 @@ class Engine(object):
         """HIP-event time of k_soft_demap in the last rx() / rx_device() (needs prof_enable())."""
         return self._stage_last_ms("rx_soft")
 
+    # -- coded links, the second inner code (QC-LDPC encoder and layered min-sum decoder over the payloads) -----------
+    def _ldpc_cfg(self, ldpc):
+        from . import ldpc as _ldpc
+        cfg = _ldpc.as_cfg(True if ldpc is None else ldpc)
+        if cfg is None:
+            raise ValueError("ldpc=False names no code")
+        return cfg
+
+    def ldpc_encode(self, payloads, ldpc=None):
+        """Host mode: list of payloads (0 .. 2012 bytes each) -> list of coded blocks (ldpc.coded_len(n) bytes each),
+        the payloads tx() then takes.  ``ldpc``: None / True, max_iters, a dict of ldpc.ldpc_cfg's keywords or an
+        ``ofdm_ldpc_cfg`` (the encoder only checks it)."""
+        assert not self.device_ptrs
+        cfg = self._ldpc_cfg(ldpc)
+        blob, offs, lens = pack_payloads(payloads)
+        # n + 4 + 96 ceil((n + 4) / 96) <= 2 n + 104
+        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 104 * len(payloads), 1), np.uint8)
+        coff = np.zeros(len(payloads) + 1, np.uint64)
+        self._check(self._lib.ofdm_ldpc_encode(self._h, C.byref(cfg), _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
+                                               coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+
+    def ldpc_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap, ldpc=None):
+        """Device mode: payload bytes and coded blocks are device pointers; offs / lens are NumPy host arrays.
+        Returns the nblk + 1 block offsets (uint64)."""
+        assert self.device_ptrs
+        cfg = self._ldpc_cfg(ldpc)
+        coff = np.zeros(len(lens) + 1, np.uint64)
+        self._check(self._lib.ofdm_ldpc_encode(self._h, C.byref(cfg), C.c_void_p(payload_ptr),
+                                               offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
+                                               int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return coff
+
+    @staticmethod
+    def _ldpc_outputs(n):
+        return (np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32),
+                np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32))
+
+    def _ldpc_decode(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap):
+        n = len(lens)
+        poff, ok, corr, iters, failed = self._ldpc_outputs(n)
+        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
+                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32)),
+                       _ptr(iters), failed.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return poff, ok[:n], corr[:n], iters[:n], failed[:n]
+
+    @staticmethod
+    def _ldpc_results(n, poff, ok, corr, iters, failed, out):
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(iters[i]), int(failed[i]))
+                for i in range(n)]
+
+    def ldpc_decode(self, blocks, ldpc=None):
+        """Host mode: list of received blocks (hard bytes of any length, e.g. the payloads rx() delivered whatever
+        their CRC said) -> list of (ok, payload, corrected, iters, cw_failed): the decoded payload, whether its inner
+        CRC matches, the sent bits the decoder changed, the most iterations one of the block's codewords took and
+        the codewords that never met all checks.  A length that is no block gives (False, b"", 0, 0, 0)."""
+        assert not self.device_ptrs
+        cfg = self._ldpc_cfg(ldpc)
+        blob, offs, lens = pack_payloads(blocks)
+        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        res = self._ldpc_decode(self._lib.ofdm_ldpc_decode, cfg, _ptr(blob), offs, lens, _ptr(out), len(out))
+        return self._ldpc_results(len(blocks), *res, out)
+
+    def ldpc_decode_soft(self, values, ldpc=None):
+        """Host mode: list of int8 arrays, one value per sent bit (v > 0 means 1, 0 is an erasure, -128 reads as
+        -127), 8 per coded byte -> list of (ok, payload, corrected, iters, cw_failed) as ldpc_decode.  An array whose
+        length is no multiple of 8, or no block's, gives (False, b"", 0, 0, 0)."""
+        assert not self.device_ptrs
+        cfg = self._ldpc_cfg(ldpc)
+        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
+        # (a length that is no multiple of 8 is handed on as the length 1: no block)
+        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
+        offs = np.zeros(max(len(vals), 1), np.uint64)
+        if len(vals) > 1:
+            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
+        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
+        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        res = self._ldpc_decode(self._lib.ofdm_ldpc_decode_soft, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out), len(out))
+        return self._ldpc_results(len(vals), *res, out)
+
+    def ldpc_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, ldpc=None, soft=False):
+        """Device mode: the blocks (hard bytes, or int8 values with ``soft``: 8 per coded byte, offsets in values) and
+        the payloads are device pointers; offs / lens (coded bytes) are NumPy host arrays.  Returns (payload offsets
+        uint64[nblk + 1], ok uint8[nblk], corrected uint32[nblk], iters uint8[nblk], cw_failed uint32[nblk]) as host
+        arrays."""
+        assert self.device_ptrs
+        fn = self._lib.ofdm_ldpc_decode_soft if soft else self._lib.ofdm_ldpc_decode
+        return self._ldpc_decode(fn, self._ldpc_cfg(ldpc), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+
+    def _rx_ldpc_decode_soft(self, ldpc, out_ptr, out_cap, n):
+        poff, ok, corr, iters, failed = self._ldpc_outputs(n)
+        self._check(self._lib.ofdm_rx_ldpc_decode_soft(self._h, C.byref(self._ldpc_cfg(ldpc)), out_ptr, int(out_cap),
+                                                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
+                                                       corr.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(iters),
+                                                       failed.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(C.c_int(0))))
+        return poff, ok[:n], corr[:n], iters[:n], failed[:n]
+
+    def rx_ldpc_decode_soft(self, ldpc=None):
+        """Host mode: the packets the last rx() returned, decoded from the handle's own soft values (they never visit
+        the host) -> list of (ok, payload, corrected, iters, cw_failed) as ldpc_decode_soft.  Needs set_rx_soft()
+        before that rx()."""
+        assert not self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        out = np.zeros(max(int(off[n]) // 16, 1), np.uint8)
+        res = self._rx_ldpc_decode_soft(ldpc, _ptr(out), len(out), n)
+        return self._ldpc_results(n, *res, out)
+
+    def rx_ldpc_decode_soft_device(self, payload_ptr, payload_cap, ldpc=None):
+        """Device mode: the same into the device buffer ``payload_ptr``; returns the host arrays of
+        ldpc_decode_device."""
+        assert self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._rx_ldpc_decode_soft(ldpc, C.c_void_p(payload_ptr), payload_cap, n)
+
+    def ldpc_last_ms(self):
+        """HIP-event time of k_ldpc_encode / k_ldpc_decode in the last ldpc call (needs prof_enable())."""
+        return self._stage_last_ms("ldpc")
+
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""
         n = C.c_int(0)

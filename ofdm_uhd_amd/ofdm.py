@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -27,7 +27,7 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None):
+                 resample=None, fec=None, rs=None, ldpc=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param msgq_limit: maximum number of messages in message queue (kept for API
@@ -54,9 +54,13 @@ class ofdm_mod(object):
                the same setting.  None: the payloads go out as they are and nothing new runs
         @param rs: outer code: ``True`` wraps every payload in a Reed-Solomon block (rs.py, Engine.rs_encode: payload |
                CRC-32, 32 parity bytes per 223, byte-interleaved) before the inner code, if any, and the modulator:
-               flush() encodes outer, then inner, then modulates.  send_pkt then takes up to 3564 bytes, or 1780 with
-               ``fec`` (the RS block must fit the inner code); the receiving end is ofdm_demod(rs=True).  None /
-               False: nothing new runs
+               flush() encodes outer, then inner, then modulates.  send_pkt then takes up to 3564 bytes, 1780 with
+               ``fec`` or 1752 with ``ldpc`` (the RS block must fit the inner code); the receiving end is
+               ofdm_demod(rs=True).  None / False: nothing new runs
+        @param ldpc: coded link with the other inner code, in the place of ``fec`` (both: ValueError): ``True``,
+               ``dict(max_iters=20)`` or an int (ldpc.py).  send_pkt then takes up to 2012 bytes and flush() encodes the
+               batch on the GPU (Engine.ldpc_encode: payload | CRC-32 in rate-1/2 QC-LDPC codewords of 96 info and 96
+               parity bytes, ldpc.coded_len(n) bytes); the receiving end is ofdm_demod(ldpc=).  None: nothing new runs
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
@@ -94,6 +98,9 @@ class ofdm_mod(object):
         elif iqio.check_format(iq_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
         self._fec = _fec.as_cfg(fec)
+        self._ldpc = _ldpc.as_cfg(ldpc)
+        if self._fec is not None and self._ldpc is not None:
+            raise ValueError("fec= and ldpc= are two inner codes: a link has one of them")
         self._rs = bool(rs)
         self._pending = []
         self._sink = None
@@ -138,11 +145,21 @@ class ofdm_mod(object):
         # the offending packet only: the padded, whitened body must fit the mask too (whiten(), :84-87)
         if self._rs:
             limit = _rs.MAX_PAYLOAD if self._fec is None else _rs.MAX_PAYLOAD_UNDER_FEC
+            if self._ldpc is not None:
+                limit = _rs.MAX_PAYLOAD_UNDER_LDPC
             if len(payload) > limit:
                 raise ValueError("len(payload) must be in [0, %d]" % (limit,))
             block = _rs.coded_len(len(payload))
             # what gets framed: the RS block, or the inner code's block around it
+            if self._ldpc is not None:
+                block = _ldpc.coded_len(block)
             self._engine.framed_len(block if self._fec is None else _fec.coded_len(block, self._fec))
+            self._pending.append(payload)
+            return
+        if self._ldpc is not None:
+            if len(payload) > _ldpc.MAX_PAYLOAD:
+                raise ValueError("len(payload) must be in [0, %d]" % (_ldpc.MAX_PAYLOAD,))
+            self._engine.framed_len(_ldpc.coded_len(len(payload)))   # the coded block is what gets framed
             self._pending.append(payload)
             return
         if self._fec is not None:
@@ -177,6 +194,8 @@ class ofdm_mod(object):
                 pending = self._engine.rs_encode(pending)
             if self._fec is not None:
                 pending = self._engine.fec_encode(pending, self._fec)
+            if self._ldpc is not None:
+                pending = self._engine.ldpc_encode(pending, self._ldpc)
             iq = self._engine.tx(pending)
             self.symbols_sent += self._engine.last_stats.get("symbols", 0)
             self.packets_sent += len(pending)
@@ -245,7 +264,7 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None, rs=None):
+                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
         @param callback:  function of two args: ok, payload
@@ -289,6 +308,12 @@ class ofdm_demod(object):
             returns the same payloads and one reliability per decoded byte, and those go to Engine.rs_decode_rel;
             ``last_fec_rel`` holds them, one uint8 array per packet.  Any other ``source`` is a ValueError.  ``last_rs``
             keeps its three fields, ``last_rs_second`` holds the codewords per packet that the second pass decoded
+        @param ldpc: coded link with the other inner code, as for ofdm_mod, in the place of ``fec`` (both: ValueError):
+            every delivered packet goes through the min-sum decoder in one batch (Engine.ldpc_decode on the hard bytes;
+            with ``soft`` Engine.rx_ldpc_decode_soft on the values, on the GPU).  ``last_fec`` keeps its shape,
+            (outer_ok, corrected) per packet; ``last_ldpc`` holds (iters, cw_failed) per packet.  ``rs=True`` works above
+            it as above ``fec``; ``rs=dict(erasures=True, ...)`` with ``ldpc`` is a ValueError: this decoder produces no
+            byte reliabilities yet
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -300,7 +325,14 @@ class ofdm_demod(object):
         self._callback = callback
         self._quality_callback = quality_callback
         self._fec = _fec.as_cfg(fec)
-        self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec only)
+        self._ldpc = _ldpc.as_cfg(ldpc)
+        if self._fec is not None and self._ldpc is not None:
+            raise ValueError("fec= and ldpc= are two inner codes: a link has one of them")
+        if self._ldpc is not None and isinstance(rs, dict) and rs.get("erasures"):
+            raise ValueError("rs=dict(erasures=True) does not combine with ldpc=: this decoder produces no byte "
+                             "reliabilities yet")
+        self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec / ldpc)
+        self.last_ldpc = []          # (iters, cw_failed) of the packets the last work() / feed() returned (ldpc only)
         self._soft = None if (soft is None or soft is False) else soft
         self.last_soft = []          # int8 values of the packets the last work() / feed() returned (soft only)
         self._rs = bool(rs)
@@ -428,6 +460,8 @@ class ofdm_demod(object):
         that call's packets)."""
         if self._fec is not None:
             pkts = self._decode_inner(pkts, sel)
+        elif self._ldpc is not None:
+            pkts = self._decode_ldpc(pkts, sel)
         if self._rs_rel is not None:
             # (last_soft holds the delivered packets' values, in their order)
             if self._rs_rel_fec:
@@ -463,6 +497,17 @@ class ofdm_demod(object):
             dec = self._engine.fec_decode([p for _, p in pkts], self._fec) if pkts else []
         self.last_fec = [(bool(ok), c) for (ok, _), (_, _, c) in zip(pkts, dec)]
         return [(ok, p) for ok, p, _ in dec]
+
+    def _decode_ldpc(self, pkts, sel=None):
+        if self._soft is not None:
+            dec = self._engine.rx_ldpc_decode_soft(self._ldpc) if pkts else []
+            if sel is not None:
+                dec = [dec[i] for i in sel]
+        else:
+            dec = self._engine.ldpc_decode([p for _, p in pkts], self._ldpc) if pkts else []
+        self.last_fec = [(bool(ok), d[2]) for (ok, _), d in zip(pkts, dec)]
+        self.last_ldpc = [(d[3], d[4]) for d in dec]
+        return [(d[0], d[1]) for d in dec]
 
     def _deliver(self, pkts):
         for i, (ok, payload) in enumerate(pkts):

@@ -6,7 +6,7 @@ from . import ofdm, options as _options
 
 class receive_path(object):
     def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
-                 ddc=None, resample=None, fec=None, soft=None, rs=None):
+                 ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
@@ -18,13 +18,20 @@ class receive_path(object):
         ``soft``: soft-decision receive of ofdm_demod, ``True`` or ``dict(scale=32)``; None: the options' ``fec_soft``
         (--fec-soft), which turns the coded link on as well.
         ``rs``: outer code of ofdm_demod, ``True`` or ``dict(erasures=True, max_erasures=28)``; None: the options' ``rs``
-        (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well."""
+        (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well.
+        ``ldpc``: the other inner code of ofdm_demod, ``True`` or ``dict(max_iters=20)``; None: the options' ``ldpc``
+        (--ldpc), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
             fec = (getattr(options, "fec", None) or True) if fec is None else fec   # (a dict where --fec-rate set one)
         if fec is None:
             fec = getattr(options, "fec", None) or None
+        if soft is None and getattr(options, "ldpc_soft", None):
+            soft = True
+            ldpc = True if ldpc is None else ldpc
+        if ldpc is None:
+            ldpc = getattr(options, "ldpc", None) or None
         if rs is None and getattr(options, "rs_erasures", None) is not None:
             rs = dict(erasures=True, max_erasures=int(options.rs_erasures))
             soft = True if soft is None else soft
@@ -47,7 +54,7 @@ class receive_path(object):
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
                                        quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
-                                       ddc=ddc, resample=resample, fec=fec, soft=soft, rs=rs)
+                                       ddc=ddc, resample=resample, fec=fec, soft=soft, rs=rs, ldpc=ldpc)
 
         if self._verbose:
             self._print_verbage()

@@ -25,6 +25,7 @@ PARITY = _abi.OFDM_RS_PARITY
 MAX_PAYLOAD = _abi.OFDM_RS_MAX_PAYLOAD
 MAX_CODED = _abi.OFDM_RS_MAX_CODED
 MAX_PAYLOAD_UNDER_FEC = 1780          # the RS block must fit fec.MAX_PAYLOAD: W = 8, block 2040
+MAX_PAYLOAD_UNDER_LDPC = 1752         # the RS block must fit ldpc.MAX_PAYLOAD: W = 8, block 2012
 DEFAULT_MAX_ERASURES = 28             # leaves four parity symbols as a check on what the erasures fill in
 
 

@@ -1,0 +1,151 @@
+"""The LDPC kernels (k_ldpc_encode, k_ldpc_decode) on one MI355X, next to k_fec_encode / k_fec_decode at rate 1/2 from
+the same run:
+python tools/bench_ldpc.py
+
+Device pointers; bench_fec.py's payload set (65 536 blocks of 1 026 payload bytes, the C2 packet, PCG64 seed 0x0FEC), the
+K = 7 code with 16 interleaver columns, the LDPC decoder at max_iters 20.  Inputs: the clean coded blocks as hard bytes
+and as +-16 / +-1 values (every LDPC codeword stops after one iteration), and input near the LDPC decoder's threshold:
+hard bytes with 5 % of the bits flipped, and BPSK / AWGN values rint(4 LLR) at --ebn0 dB (2.0), both made on the device
+from a seed.  After two warm-ups per variant: ROUNDS alternations of CALLS calls of every variant; the kernels' HIP-event
+times from ofdm_ldpc_last_ms / ofdm_fec_last_ms (the Viterbi decoder's covers all its slices).  Prints one JSON line:
+median / min / max ms per variant, ns per payload byte, the LDPC decoder's block verdicts and mean iteration counts, and
+every LDPC time as a ratio to k_fec_decode / k_fec_encode on the same kind of input."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from ofdm_uhd_amd import config, engine, fec, ldpc, options  # noqa: E402
+
+
+def _stats(v):
+    return [round(float(np.median(v)), 4), round(float(np.min(v)), 4), round(float(np.max(v)), 4)]
+
+
+def _bits(d_coded, lo, hi):
+    """Bits of coded bytes [lo, hi), MSB first, as a float tensor of +-1."""
+    sh = torch.arange(7, -1, -1, dtype=torch.uint8, device=d_coded.device)
+    b = (d_coded[lo:hi].unsqueeze(1) >> sh) & 1
+    return b.reshape(-1).to(torch.float32) * 2.0 - 1.0
+
+
+def hard_values(d_coded, amp, chunk=1 << 24):
+    out = torch.empty(d_coded.numel() * 8, dtype=torch.int8, device=d_coded.device)
+    for lo in range(0, d_coded.numel(), chunk):
+        hi = min(lo + chunk, d_coded.numel())
+        out[8 * lo:8 * hi] = (_bits(d_coded, lo, hi) * amp).to(torch.int8)
+    return out
+
+
+def awgn_values(d_coded, ebn0_db, gen, chunk=1 << 24):
+    """BPSK over AWGN at Eb/N0 for a rate-1/2 code: int8 values rint(4 LLR) clamped to +-127."""
+    sigma2 = 1.0 / (2.0 * 0.5 * 10.0 ** (ebn0_db / 10.0))
+    out = torch.empty(d_coded.numel() * 8, dtype=torch.int8, device=d_coded.device)
+    for lo in range(0, d_coded.numel(), chunk):
+        hi = min(lo + chunk, d_coded.numel())
+        y = _bits(d_coded, lo, hi)
+        y += torch.randn(y.numel(), generator=gen, device=y.device) * sigma2 ** 0.5
+        out[8 * lo:8 * hi] = torch.clamp(torch.round(y * (8.0 / sigma2)), -127, 127).to(torch.int8)
+    return out
+
+
+def flipped(d_coded, rate, gen, chunk=1 << 24):
+    out = d_coded.clone()
+    w = (1 << torch.arange(8, device=d_coded.device)).to(torch.int32)
+    for lo in range(0, d_coded.numel(), chunk):
+        hi = min(lo + chunk, d_coded.numel())
+        m = (torch.rand((hi - lo, 8), generator=gen, device=d_coded.device) < rate).to(torch.int32)
+        out[lo:hi] ^= (m * w).sum(dim=1).to(torch.uint8)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=65536)
+    ap.add_argument("--size", type=int, default=1026)
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--ebn0", type=float, default=2.0)
+    ap.add_argument("--flip-rate", type=float, default=0.05)
+    ap.add_argument("--max-iters", type=int, default=20)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    P, size = a.blocks, a.size
+    fsize, lsize = fec.coded_len(size), ldpc.coded_len(size)
+    opt = options.default_options(modulation="qpsk", fft_length=512, occupied_tones=200, cp_length=128, tx_amplitude=0.25)
+    e = engine.Engine(cfg=config.make_cfg(opt, device_ptrs=True))
+    e.prof_enable(True)
+    rng = np.random.Generator(np.random.PCG64(0x0FEC))
+    d_pay = torch.from_numpy(rng.integers(0, 256, P * size, dtype=np.uint8)).to(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0x1D9C)
+    offs = np.arange(P, dtype=np.uint64) * np.uint64(size)
+    lens = np.full(P, size, np.uint32)
+    d_dec = torch.empty(P * size, dtype=torch.uint8, device=dev)
+    code = {}
+    for name, csize, enc in (("fec", fsize, e.fec_encode_device), ("ldpc", lsize, e.ldpc_encode_device)):
+        d_coded = torch.empty(P * csize, dtype=torch.uint8, device=dev)
+        enc(d_pay.data_ptr(), offs, lens, d_coded.data_ptr(), d_coded.numel())
+        code[name] = dict(csize=csize, coffs=np.arange(P, dtype=np.uint64) * np.uint64(csize), clens=np.full(P, csize, np.uint32),
+                          clean=d_coded, clean_soft=hard_values(d_coded, 16 if name == "ldpc" else 1),
+                          noisy=flipped(d_coded, a.flip_rate, gen), noisy_soft=awgn_values(d_coded, a.ebn0, gen))
+    state = {}
+    lcfg = ldpc.ldpc_cfg(a.max_iters)
+
+    def encode(name):
+        c = code[name]
+        fn = e.fec_encode_device if name == "fec" else e.ldpc_encode_device
+        fn(d_pay.data_ptr(), offs, lens, c["clean"].data_ptr(), c["clean"].numel())
+        return e.fec_last_ms() if name == "fec" else e.ldpc_last_ms()
+
+    def decode(name, what, soft):
+        c = code[name]
+        buf = c[what + ("_soft" if soft else "")]
+        o = c["coffs"] * np.uint64(8) if soft else c["coffs"]
+        if name == "fec":
+            _, ok, corr = e.fec_decode_device(buf.data_ptr(), o, c["clens"], d_dec.data_ptr(), d_dec.numel(), soft=soft)
+            state[(name, what, soft)] = dict(ok=int(ok.sum()), right=int((d_dec == d_pay).reshape(P, size).all(dim=1).sum()))
+            return e.fec_last_ms()
+        _, ok, corr, it, failed = e.ldpc_decode_device(buf.data_ptr(), o, c["clens"], d_dec.data_ptr(), d_dec.numel(), lcfg, soft=soft)
+        state[(name, what, soft)] = dict(ok=int(ok.sum()), right=int((d_dec == d_pay).reshape(P, size).all(dim=1).sum()),
+                                         mean_block_iters=round(float(it.mean()), 2), cw_failed=int(failed.sum()))
+        return e.ldpc_last_ms()
+
+    variants = [("k_%s_encode" % n, (lambda n=n: encode(n))) for n in ("fec", "ldpc")]
+    for what in ("clean", "noisy"):
+        for soft in (False, True):
+            for n in ("fec", "ldpc"):
+                variants.append(("k_%s_decode %s %s" % (n, what, "soft" if soft else "hard"),
+                                 (lambda n=n, what=what, soft=soft: decode(n, what, soft))))
+    for _, f in variants:
+        for _ in range(2):
+            f()
+    for soft in (False, True):
+        for n in ("fec", "ldpc"):
+            assert state[(n, "clean", soft)]["right"] == P and state[(n, "clean", soft)]["ok"] == P
+    assert state[("ldpc", "clean", True)]["mean_block_iters"] == 1.0
+    ms = {v: [] for v, _ in variants}
+    for _ in range(a.rounds):
+        for v, f in variants:
+            ms[v] += [f() for _ in range(a.calls)]
+    med = {v: float(np.median(t)) for v, t in ms.items()}
+    out = {"blocks": P, "payload_bytes": size, "fec_coded_bytes": fsize, "ldpc_coded_bytes": lsize,
+           "ldpc_codewords": P * ((size + 4 + 95) // 96), "max_iters": a.max_iters, "ebn0_db": a.ebn0, "flip_rate": a.flip_rate,
+           "calls": a.calls * a.rounds, "ms_median_min_max": {v: _stats(t) for v, t in ms.items()},
+           "ns_per_payload_byte": {v: round(med[v] * 1e6 / (P * size), 4) for v in med},
+           "verdicts": {"%s %s %s" % (n, w, "soft" if s else "hard"): st for (n, w, s), st in state.items()},
+           "ldpc_over_fec": {"encode": round(med["k_ldpc_encode"] / med["k_fec_encode"], 4)}}
+    for what in ("clean", "noisy"):
+        for soft in ("hard", "soft"):
+            out["ldpc_over_fec"]["decode %s %s" % (what, soft)] = round(
+                med["k_ldpc_decode %s %s" % (what, soft)] / med["k_fec_decode %s %s" % (what, soft)], 4)
+    print(json.dumps(out), flush=True)
+    e.close()
+
+
+if __name__ == "__main__":
+    main()
