@@ -308,20 +308,24 @@ def test_device_pointers():
 
 def test_feed_equals_work():
     """A capture cut in two through feed() / flush() gives the last_soft of one work(), concatenated; with fec as well,
-    the same decoded packets."""
+    the same decoded packets.  The capture is longer than two spans (the seven payloads four times over, 8000 silent
+    samples between the bursts), so that either cut has feed() deliver packets before flush(): a shorter one leaves
+    everything to flush(), which is one call on the whole capture (tests/test_gpu_coded_stream.py has the long form)."""
     opt = options.default_options(modulation="qam16")
     orc = _orc()
     cfg = make_cfg("qam16")
     rng = np.random.default_rng(77)
     pay = [_body(n, rng) for n in (210, 64, 0, 333, 100, 12, 250)]
-    x = orc.tx(cfg, pay, lead=1500, tail=3000)
-    orc.channel(x, sigma=float(np.sqrt(np.mean(np.abs(x[1500:-3000]) ** 2) / 10 ** 1.8)), seed=5)
+    burst = orc.tx(cfg, pay)
+    x = np.concatenate([np.zeros(1500, np.complex64)] + 4 * [burst, np.zeros(8000, np.complex64)])
+    orc.channel(x, sigma=float(np.sqrt(np.mean(np.abs(burst) ** 2) / 10 ** 1.8)), seed=5)
     one = ofdm.ofdm_demod(opt, fec=True, soft=True)
     two = ofdm.ofdm_demod(opt, fec=True, soft=dict(scale=32))
     bare = ofdm.ofdm_demod(opt, soft=True)
     try:
         want_pk = one.work(x)
         want = [v.copy() for v in one.last_soft]
+        assert len(x) >= 2 * one._stream_geometry()[1]
         assert len(want) == len(want_pk) >= 6 and one.last_fec and len(one.last_fec) == len(want_pk)
         raw = bare.work(x)                                       # soft without fec only fills last_soft
         _equal(bare.last_soft, want)
@@ -333,6 +337,7 @@ def test_feed_equals_work():
                 got_pk += two.feed(piece)
                 got += [v.copy() for v in two.last_soft]
                 assert len(got) == len(got_pk)
+            assert len(got_pk) >= 1                              # delivered by feed(), before flush()
             got_pk += two.flush()
             got += [v.copy() for v in two.last_soft]
             assert got_pk == want_pk
