@@ -135,7 +135,7 @@ struct ofdm_handle {
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
-  FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h / engine_fec_rel.inc)
+  FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h)
   RsState rs;  // outer code: Reed-Solomon over the payloads, above the coded links (rs.h / engine_rs.inc)
   LdpcState ldpc;  // coded links, the second inner code: QC-LDPC encoder and min-sum decoder (ldpc.h / engine_ldpc.inc)
 };
@@ -1019,8 +1019,8 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_duc_bank.inc"
 #include "engine_tx_resamp_bank.inc"
 #include "engine_multipath.inc"
+#include "engine_codec.inc"
 #include "engine_fec.inc"
 #include "engine_soft.inc"
-#include "engine_fec_rel.inc"
 #include "engine_rs.inc"
 #include "engine_ldpc.inc"

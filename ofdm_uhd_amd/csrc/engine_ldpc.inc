@@ -1,14 +1,11 @@
-// engine_ldpc.inc -- host side of the LDPC coded-link layer (ldpc.h): lengths, the codeword map of a batch, launches.
-// Included by engine.hip after engine_rs.inc.  The arithmetic that needs no GPU is ldpc_plan.h.
+// engine_ldpc.inc -- host side of the LDPC coded-link layer (ldpc.h): lengths, the codeword map of a batch, launches,
+// over the steps of engine_codec.inc.  Included by engine.hip after engine_rs.inc.  The arithmetic that needs no GPU is
+// ldpc_plan.h.
 
 extern "C" int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t* coded_len) { return ldpc_coded_len(payload_len, coded_len); }
 extern "C" int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t* payload_len) { return ldpc_payload_len(coded_len, payload_len); }
 
-extern "C" int ofdm_ldpc_last_ms(const ofdm_handle* h, double* ms) {
-  if (!h || !ms || !h->ldpc.timed) return OFDM_E_INVAL;
-  *ms = h->ldpc.last_ms;
-  return OFDM_OK;
-}
+extern "C" int ofdm_ldpc_last_ms(const ofdm_handle* h, double* ms) { return h ? codec_last_ms(h->ldpc, ms) : OFDM_E_INVAL; }
 
 static int ldpc_iters(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint32_t* max_iters) {
   *max_iters = LDPC_DEFAULT_ITERS;
@@ -18,36 +15,6 @@ static int ldpc_iters(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint32_t* max_it
   for (uint32_t r : cfg->reserved)
     if (r) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.reserved must be 0");
   *max_iters = cfg->max_iters;
-  return OFDM_OK;
-}
-
-static int ldpc_time_begin(ofdm_handle* h, LdpcState& f, hipStream_t st, bool timing) {
-  if (!timing) return OFDM_OK;
-  if (!f.ev_a) {
-    HIPCHK(h, hipEventCreate(&f.ev_a));
-    HIPCHK(h, hipEventCreate(&f.ev_b));
-  }
-  HIPCHK(h, hipEventRecord(f.ev_a, st));
-  return OFDM_OK;
-}
-
-static int ldpc_finish(ofdm_handle* h, LdpcState& f, hipStream_t st, bool timing) {
-  HIPCHK(h, hipStreamSynchronize(st));
-  if (timing) {
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, f.ev_a, f.ev_b));
-    f.last_ms = (double)ms;
-    f.timed = true;
-  }
-  return OFDM_OK;
-}
-
-// the batch's two tables on the device: blocks, and the block of every codeword
-static int ldpc_upload_map(ofdm_handle* h, LdpcState& f, hipStream_t st, int nblk, uint64_t ncw) {
-  HIPCHK(h, f.d_blk.ensure(sizeof(LdpcBlk) * (size_t)nblk));
-  HIPCHK(h, f.d_cw.ensure(sizeof(uint32_t) * (size_t)ncw));
-  HIPCHK(h, hipMemcpyAsync(f.d_blk.p, f.blk.data(), sizeof(LdpcBlk) * (size_t)nblk, hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(f.d_cw.p, f.cw.data(), sizeof(uint32_t) * (size_t)ncw, hipMemcpyHostToDevice, st));
   return OFDM_OK;
 }
 
@@ -68,27 +35,22 @@ extern "C" int ofdm_ldpc_encode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const 
   if (total > coded_cap) FAIL(h, OFDM_E_CAPACITY, "coded buffer too small (see ofdm_ldpc_coded_len)");
   if (nblk == 0) return OFDM_OK;
   if (!coded) FAIL(h, OFDM_E_INVAL, "null argument");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  hipStream_t st = h->txs;  // the transmit side: ordered with the ofdm_tx that takes the blocks
-  const uint8_t* d_in = payloads;
-  uint8_t* d_out = coded;
-  RCCHK(ldpc_upload_map(h, f, st, nblk, ncw));
-  if (!h->dev_ptrs) {
-    HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
-    if (extent) HIPCHK(h, hipMemcpyAsync(f.d_in.p, payloads, extent, hipMemcpyHostToDevice, st));
-    HIPCHK(h, f.d_out.ensure(total));
-    d_in = f.d_in.as<uint8_t>();
-    d_out = f.d_out.as<uint8_t>();
-  }
+  hipStream_t st;
+  RCCHK(codec_begin_encode(h, &st));
+  const uint8_t* d_in;
+  uint8_t* d_out;
+  RCCHK(codec_upload(h, st, f.d_blk, f.blk, (size_t)nblk));  // the batch's two tables: blocks, and the block of every codeword
+  RCCHK(codec_upload(h, st, f.d_cw, f.cw, (size_t)ncw));
+  RCCHK(codec_stage_in(h, st, f.d_in, payloads, extent, false, &d_in));
+  RCCHK(codec_stage_out(h, f.d_out, coded, total, &d_out));
   const bool timing = h->prof.on;
-  RCCHK(ldpc_time_begin(h, f, st, timing));
+  RCCHK(codec_time_begin(h, f, st, timing));
   const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);  // every block has a codeword: ncw >= nblk >= 1
   hipLaunchKernelGGL(k_ldpc_encode, dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw,
                      d_out, h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>());
-  if (timing) HIPCHK(h, hipEventRecord(f.ev_b, st));
-  HIPCHK(h, hipGetLastError());
-  if (!h->dev_ptrs) HIPCHK(h, hipMemcpyAsync(coded, d_out, total, hipMemcpyDeviceToHost, st));
-  return ldpc_finish(h, f, st, timing);  // (synchronises: the staged tables are the caller's again)
+  RCCHK(codec_launched(h, f, st, timing));
+  RCCHK(codec_read_out(h, st, coded, d_out, total));
+  return codec_finish(h, f, st, timing);
 }
 
 static void ldpc_no_blocks(int nblk, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
@@ -122,35 +84,27 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
     ldpc_no_blocks(nblk, ok, corrected, iters, cw_failed);
     return OFDM_OK;
   }
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  hipStream_t st = h->stream;  // the receive side: ordered behind the ofdm_rx that delivered the blocks
-  if (h->tx_pending && h->txs != h->stream) HIPCHK(h, hipStreamWaitEvent(st, h->ev_tx_done, 0));
-  const uint8_t* d_in = in;
-  uint8_t* d_out = payloads;
-  RCCHK(ldpc_upload_map(h, f, st, nblk, ncw));
+  hipStream_t st;
+  RCCHK(codec_begin_decode(h, &st));
+  const uint8_t* d_in;
+  uint8_t* d_out;
+  RCCHK(codec_upload(h, st, f.d_blk, f.blk, (size_t)nblk));
+  RCCHK(codec_upload(h, st, f.d_cw, f.cw, (size_t)ncw));
   HIPCHK(h, f.d_res.ensure(sizeof(LdpcRes) * (size_t)nblk));
   HIPCHK(h, hipMemsetAsync(f.d_res.p, 0, sizeof(LdpcRes) * (size_t)nblk, st));
-  if (!h->dev_ptrs) {
-    if (!in_on_device) {
-      HIPCHK(h, f.d_in.ensure(std::max<uint64_t>(extent, 1)));
-      HIPCHK(h, hipMemcpyAsync(f.d_in.p, in, extent, hipMemcpyHostToDevice, st));
-      d_in = f.d_in.as<uint8_t>();
-    }
-    HIPCHK(h, f.d_out.ensure(std::max<uint64_t>(total, 1)));
-    d_out = f.d_out.as<uint8_t>();
-  }
+  RCCHK(codec_stage_in(h, st, f.d_in, in, extent, in_on_device, &d_in));
+  RCCHK(codec_stage_out(h, f.d_out, payloads, total, &d_out));
   const bool timing = h->prof.on;
-  RCCHK(ldpc_time_begin(h, f, st, timing));
+  RCCHK(codec_time_begin(h, f, st, timing));
   const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(),
                      f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, f.d_res.as<LdpcRes>(), h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(),
                      max_iters);
-  if (timing) HIPCHK(h, hipEventRecord(f.ev_b, st));
-  HIPCHK(h, hipGetLastError());
+  RCCHK(codec_launched(h, f, st, timing));
   f.res.resize((size_t)nblk);
-  HIPCHK(h, hipMemcpyAsync(f.res.data(), f.d_res.p, sizeof(LdpcRes) * (size_t)nblk, hipMemcpyDeviceToHost, st));
-  if (!h->dev_ptrs && total) HIPCHK(h, hipMemcpyAsync(payloads, d_out, total, hipMemcpyDeviceToHost, st));
-  RCCHK(ldpc_finish(h, f, st, timing));
+  RCCHK(codec_read(h, st, f.res.data(), f.d_res, nblk));
+  RCCHK(codec_read_out(h, st, payloads, d_out, total));
+  RCCHK(codec_finish(h, f, st, timing));
   for (int b = 0; b < nblk; b++) {  // a length that is no block had no codeword: its record is still zero
     const LdpcRes& r = f.res[(size_t)b];
     ok[b] = (ldpc_is_block(coded_len[b]) && r.crc == r.got) ? 1 : 0;
@@ -182,12 +136,8 @@ extern "C" int ofdm_rx_ldpc_decode_soft(ofdm_handle* h, const ofdm_ldpc_cfg* cfg
                                         uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed,
                                         int max_pkts, int* n) {
   if (!h) return OFDM_E_INVAL;
-  if (!n || max_pkts < 0) FAIL(h, OFDM_E_INVAL, "null argument");
-  RxState& rx = h->rx;
-  if (!rx.soft_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without soft values (ofdm_set_rx_soft)");
-  const size_t np = rx.soft_len.size();
-  *n = (int)np;
-  if ((size_t)max_pkts < np) FAIL(h, OFDM_E_CAPACITY, "ok / corrected / iters / cw_failed / payload_off arrays too small");
-  return ldpc_decode_impl<true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), (int)np, payloads, payload_cap,
+  RCCHK(codec_rx_soft_batch(h, max_pkts, n, "ok / corrected / iters / cw_failed / payload_off arrays too small"));
+  const RxState& rx = h->rx;
+  return ldpc_decode_impl<true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), *n, payloads, payload_cap,
                                 payload_off, ok, corrected, iters, cw_failed, true);
 }

@@ -1,6 +1,7 @@
-// engine_soft.inc -- host side of the soft-decision receive option (rx_soft.h): the setting, the accessors of the last
-// call's values and the decoder call that reads them where they lie.  Included by engine.hip after engine_fec.inc; the
-// stage itself (rx_soft_values) runs inside ofdm_rx: engine_rx.inc.  The arithmetic that needs no GPU is soft_plan.h.
+// engine_soft.inc -- host side of the soft-decision receive option (rx_soft.h): the setting and the accessors of the
+// last call's values.  The decoder calls that read them where they lie (ofdm_rx_*_decode_soft*) are with their codecs,
+// behind codec_rx_soft_batch (engine_codec.inc).  Included by engine.hip after engine_fec.inc; the stage itself
+// (rx_soft_values) runs inside ofdm_rx: engine_rx.inc.  The arithmetic that needs no GPU is soft_plan.h.
 
 extern "C" int ofdm_set_rx_soft(ofdm_handle* h, const ofdm_soft_cfg* cfg) {
   if (!h) return OFDM_E_INVAL;
@@ -52,19 +53,6 @@ extern "C" int ofdm_rx_soft(ofdm_handle* h, int8_t* out, uint64_t cap, uint64_t*
   HIPCHK(h, hipMemcpyAsync(out, rx.soft_vals.p, total, h->dev_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return OFDM_OK;
-}
-
-extern "C" int ofdm_rx_fec_decode_soft(ofdm_handle* h, const ofdm_fec_cfg* cfg, uint8_t* payloads, uint64_t payload_cap,
-                                       uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, int max_pkts, int* n) {
-  if (!h) return OFDM_E_INVAL;
-  if (!n || max_pkts < 0) FAIL(h, OFDM_E_INVAL, "null argument");
-  RxState& rx = h->rx;
-  if (!rx.soft_valid) FAIL(h, OFDM_E_INVAL, "the last ofdm_rx ran without soft values (ofdm_set_rx_soft)");
-  const size_t np = rx.soft_len.size();
-  *n = (int)np;
-  if ((size_t)max_pkts < np) FAIL(h, OFDM_E_CAPACITY, "ok / corrected / payload_off arrays too small");
-  return fec_decode_impl<true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), (int)np, payloads, payload_cap,
-                               payload_off, ok, corrected, true);
 }
 
 extern "C" int ofdm_rx_soft_last_ms(ofdm_handle* h, double* ms) {

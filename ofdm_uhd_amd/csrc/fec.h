@@ -22,18 +22,18 @@
 // start metric of the 63 states the trellis cannot start in: below every reachable path (|metric| <= 2 * 16358 * 127)
 #define FEC_UNREACHABLE (-(1 << 29))
 
-struct FecState {
-  DevBuf d_in, d_out, d_blk, d_ok, d_corr, d_ws;
+// host side (engine_fec.inc): CodecStage (host_util.h) and the code's own
+struct FecState : CodecStage {
+  DevBuf d_ok, d_corr, d_ws;
   std::vector<FecBlk> blk;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;  // last_ms is of the last fec call
+  std::vector<hipEvent_t> ev;  // three per slice of a timed decode: depuncture | decoder
   void release() {
-    DevBuf* bufs[] = {&d_in, &d_out, &d_blk, &d_ok, &d_corr, &d_ws};
-    for (DevBuf* b : bufs) b->release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    d_ok.release();
+    d_corr.release();
+    d_ws.release();
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    ev.clear();
+    CodecStage::release();
   }
 };
 

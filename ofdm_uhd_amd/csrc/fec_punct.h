@@ -15,14 +15,11 @@
 struct FecPunctState {
   DevBuf d_pblk, d_mother;        // k_fec_depuncture's block table; the mother values of one slice
   std::vector<FecBlk> pblk;
-  std::vector<hipEvent_t> ev;     // three per slice of a timed decode
   double last_ms = 0.0;
   bool timed = false;             // last_ms is of the last fec call
   void release() {
     d_pblk.release();
     d_mother.release();
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    ev.clear();
   }
 };
 

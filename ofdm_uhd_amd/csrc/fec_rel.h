@@ -14,12 +14,9 @@
 // what the soft-output decoder keeps on a handle next to FecState: nothing of it exists until a call to it
 struct FecRelState {
   DevBuf d_ckpt, d_rel;          // the forward metrics at every chunk start (4 bytes per step and block in flight); rel staging
-  std::vector<hipEvent_t> ev;    // three per slice of a timed decode
   void release() {
     d_ckpt.release();
     d_rel.release();
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    ev.clear();
   }
 };
 

@@ -84,6 +84,31 @@ struct StreamStage {
   }
 };
 
+// What the coded-link calls (the K = 7 code with its punctured rates and soft output, the Reed-Solomon outer code, LDPC)
+// share on the host: the host-mode staging buffers, the batch's block table on the device, and the HIP-event pair and
+// time of the last call (CodecClock: the outer code keeps a second one for ofdm_rs_rel_from_soft).  Each codec's state
+// derives from it and adds its own per-block outputs, tables and workspaces; the code that works on these fields is
+// engine_codec.inc.
+struct CodecClock {
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  double last_ms = 0.0;
+  bool timed = false;  // last_ms is of the codec's last call
+  void release() {
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+    ev_a = ev_b = nullptr;
+  }
+};
+struct CodecStage : CodecClock {
+  DevBuf d_in, d_out, d_blk;
+  void release() {
+    d_in.release();
+    d_out.release();
+    d_blk.release();
+    CodecClock::release();
+  }
+};
+
 struct ProfSpan {
   int kernel;
   hipEvent_t a, b;

@@ -22,20 +22,16 @@
 #define LDPC_N (LDPC_COLS * LDPC_Z)
 #define LDPC_HARD 16  // a hard bit as a decoder value
 
-struct LdpcState {
-  DevBuf d_in, d_out, d_blk, d_cw, d_res;
+// host side (engine_ldpc.inc): CodecStage (host_util.h) and the code's own
+struct LdpcState : CodecStage {
+  DevBuf d_cw, d_res;
   std::vector<LdpcBlk> blk;
   std::vector<uint32_t> cw;  // codeword -> block
   std::vector<LdpcRes> res;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;  // last_ms is of the last ldpc call
   void release() {
-    DevBuf* bufs[] = {&d_in, &d_out, &d_blk, &d_cw, &d_res};
-    for (DevBuf* b : bufs) b->release();
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    ev_a = ev_b = nullptr;
+    d_cw.release();
+    d_res.release();
+    CodecStage::release();
   }
 };
 

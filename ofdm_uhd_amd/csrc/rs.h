@@ -21,26 +21,19 @@
 #define RS_HALVES (RS_THREADS / 32)
 #define RS_LDS_BLOCK (OFDM_RS_MAX_CODED + 16)  // the block behind the up to 15 bytes that align it with its source
 
-struct RsState {
-  DevBuf d_in, d_out, d_blk, d_ok, d_corr, d_fail;
+// host side (engine_rs.inc): CodecStage (host_util.h) and the code's own
+struct RsState : CodecStage {
+  DevBuf d_ok, d_corr, d_fail;
   std::vector<RsBlk> blk;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  double last_ms = 0.0;
-  bool timed = false;  // last_ms is of the last rs call
   // decoding with reliabilities (ofdm_rs_decode_rel, ofdm_rs_rel_from_soft): nothing of it exists before their first call
   DevBuf d_rel, d_reloff, d_sec, d_soft;
   std::vector<uint64_t> reloff;
-  hipEvent_t ev_ra = nullptr, ev_rb = nullptr;
-  double rel_last_ms = 0.0;
-  bool rel_timed = false;  // rel_last_ms is of the last ofdm_rs_rel_from_soft
+  CodecClock rel_clock;  // of the last ofdm_rs_rel_from_soft
   void release() {
-    DevBuf* bufs[] = {&d_in, &d_out, &d_blk, &d_ok, &d_corr, &d_fail, &d_rel, &d_reloff, &d_sec, &d_soft};
+    DevBuf* bufs[] = {&d_ok, &d_corr, &d_fail, &d_rel, &d_reloff, &d_sec, &d_soft};
     for (DevBuf* b : bufs) b->release();
-    hipEvent_t* evs[] = {&ev_a, &ev_b, &ev_ra, &ev_rb};
-    for (hipEvent_t* e : evs) {
-      if (*e) (void)hipEventDestroy(*e);
-      *e = nullptr;
-    }
+    rel_clock.release();
+    CodecStage::release();
   }
 };
 

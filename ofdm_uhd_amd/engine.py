@@ -44,6 +44,14 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _u32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _u64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
 def pack_payloads(payloads):
     """list of bytes -> (blob uint8, offsets uint64, lengths uint32)"""
     lens = np.array([len(p) for p in payloads], np.uint32)
@@ -54,6 +62,21 @@ def pack_payloads(payloads):
     if blob.size == 0:
         blob = np.zeros(1, np.uint8)
     return np.ascontiguousarray(blob), offs[:len(payloads)] if len(payloads) else offs[:0], lens
+
+
+def _pack_values(values, strict=False):
+    """list of int8 arrays, 8 values per coded byte -> (blob int8, offsets uint64 in values, lengths uint32 in bytes): what
+    the ``*_soft`` calls take.  The blob ends in 8 zero values of padding, so that no offset points past it.  A length
+    that is no multiple of 8 is handed on as the length 1, which is no block to any decoder; with ``strict`` (the outer
+    code's reliabilities, which have no such answer) it raises ValueError."""
+    vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
+    if strict and any(len(v) % 8 for v in vals):
+        raise ValueError("rs: 8 values per byte")
+    lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
+    offs = np.zeros(max(len(vals), 1), np.uint64)
+    if len(vals) > 1:
+        offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
+    return np.concatenate(vals + [np.zeros(8, np.int8)]), offs[:len(vals)], lens
 
 
 class Engine(object):
@@ -820,6 +843,47 @@ class Engine(object):
         """HIP-event time of k_multipath in the last multipath() / multipath_device() (needs prof_enable())."""
         return self._stage_last_ms("multipath")
 
+    # -- coded links: the two call shapes every codec shares (the counterpart of csrc/engine_codec.inc) ----------------
+    # ``head`` is what a call takes ahead of its batch: () or (C.byref(cfg),).
+    def _codec_encode(self, fn, head, in_ptr, offs, lens, out_ptr, out_cap):
+        """fn(handle, *head, in, offs, lens, nblk, out, cap, block offsets) -> the nblk + 1 block offsets (uint64)."""
+        coff = np.zeros(len(lens) + 1, np.uint64)
+        self._check(fn(self._h, *head, in_ptr, _u64(offs), _u32(lens), len(lens), out_ptr, int(out_cap), _u64(coff)))
+        return coff
+
+    def _codec_encode_host(self, fn, head, payloads, room):
+        """Host mode of an encode call: list of payloads -> list of blocks, in ``room(lens)`` bytes at the most."""
+        assert not self.device_ptrs
+        blob, offs, lens = pack_payloads(payloads)
+        out = np.zeros(max(int(room(lens.astype(np.int64))), 1), np.uint8)
+        coff = self._codec_encode(fn, head, _ptr(blob), offs, lens, _ptr(out), len(out))
+        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+
+    def _codec_decode(self, fn, head, n, out_ptr, out_cap, extra=(), tail=()):
+        """fn(handle, *head, out, cap, payload offsets, ok, corrected, *extra, *tail) over n blocks: ``head`` ends with
+        the batch (_batch()) where the call takes one, ``extra`` names the dtypes of the per-block outputs after
+        ``corrected``, ``tail`` is what follows them.  Returns (payload offsets uint64[n + 1], ok uint8[n],
+        corrected uint32[n], one array[n] per ``extra``) as host arrays."""
+        poff = np.zeros(n + 1, np.uint64)
+        cols = [np.zeros(max(n, 1), dt) for dt in (np.uint8, np.uint32) + tuple(extra)]
+        self._check(fn(self._h, *head, out_ptr, int(out_cap), _u64(poff), *[_u32(c) if c.dtype == np.uint32 else _ptr(c) for c in cols],
+                       *tail))
+        return (poff,) + tuple(c[:n] for c in cols)
+
+    @staticmethod
+    def _batch(in_ptr, offs, lens, *more):
+        """The batch of a decode call as it follows ``head``: (in, offs, lens, nblk) and what a codec puts behind them."""
+        return (in_ptr, _u64(offs), _u32(lens), len(lens)) + more
+
+    def _rx_batch(self, n):
+        """What an rx_*_decode_soft call takes in a batch's place, behind its outputs: (max_pkts, &n)."""
+        return (n, C.byref(C.c_int(0)))
+
+    @staticmethod
+    def _codec_results(out, poff, ok, *cols):
+        """(ok, payload, one int per column) per block, out of what _codec_decode returned."""
+        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes()) + tuple(int(c[i]) for c in cols) for i in range(len(ok))]
+
     # -- coded links (convolutional encoder and Viterbi decoder over the payloads) ---------------------------------
     def _fec_cfg(self, fec):
         from . import fec as _fec
@@ -839,66 +903,39 @@ class Engine(object):
         """Host mode: list of payloads (0 .. 2040 bytes each) -> list of coded blocks (2 n + 10 bytes each), the
         payloads tx() then takes.  ``fec``: None / True (16 interleaver columns), a column count, a dict of
         fec.fec_cfg's keywords or an ``ofdm_fec_cfg``."""
-        assert not self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        blob, offs, lens = pack_payloads(payloads)
-        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 10 * len(payloads), 1), np.uint8)   # (covers every rate)
-        coff = np.zeros(len(payloads) + 1, np.uint64)
-        self._check(self._lib.ofdm_fec_encode(self._h, C.byref(cfg), _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                              lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
-                                              coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+        return self._codec_encode_host(self._lib.ofdm_fec_encode, (C.byref(self._fec_cfg(fec)),), payloads,
+                                       lambda lens: 2 * lens.sum() + 10 * len(lens))   # (covers every rate)
 
     def fec_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap, fec=None):
         """Device mode: payload bytes and coded blocks are device pointers; offs / lens are NumPy host arrays.
         Returns the nblk + 1 block offsets (uint64)."""
         assert self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        coff = np.zeros(len(lens) + 1, np.uint64)
-        self._check(self._lib.ofdm_fec_encode(self._h, C.byref(cfg), C.c_void_p(payload_ptr),
-                                              offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                              lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
-                                              int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return coff
+        return self._codec_encode(self._lib.ofdm_fec_encode, (C.byref(self._fec_cfg(fec)),), C.c_void_p(payload_ptr), offs, lens,
+                                  C.c_void_p(coded_ptr), coded_cap)
 
-    def _fec_decode(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap):
-        n = len(lens)
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr = np.zeros(max(n, 1), np.uint32)
-        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
-                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return poff, ok[:n], corr[:n]
+    def _fec_decode_host(self, fn, fec, packed, rel):
+        """Host mode of the four fec decode calls: ``packed`` is pack_payloads' or _pack_values' (blob, offs, lens)."""
+        assert not self.device_ptrs
+        cfg = self._fec_cfg(fec)
+        blob, offs, lens = packed
+        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
+        head = (C.byref(cfg),) + self._batch(_ptr(blob), offs, lens)
+        if not rel:
+            return self._codec_results(out, *self._codec_decode(fn, head, len(lens), _ptr(out), len(out)))
+        q = np.zeros(len(out), np.uint8)
+        return self._fec_rel_results(out, q, *self._codec_decode(fn, head, len(lens), _ptr(out), len(out), tail=(_ptr(q), len(q))))
 
     def fec_decode(self, blocks, fec=None):
         """Host mode: list of received blocks (hard bytes of any length, e.g. the payloads rx() delivered whatever
         their CRC said) -> list of (ok, payload, corrected): the decoded payload, whether its inner CRC matches, and
         the number of coded bits the decoder changed.  A length that is no block gives (False, b"", 0)."""
-        assert not self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        blob, offs, lens = pack_payloads(blocks)
-        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
-        poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode, cfg, _ptr(blob), offs, lens, _ptr(out), len(out))
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(blocks))]
+        return self._fec_decode_host(self._lib.ofdm_fec_decode, fec, pack_payloads(blocks), False)
 
     def fec_decode_soft(self, values, fec=None):
         """Host mode: list of int8 arrays, one value per transmitted bit (v > 0 means 1, 0 is an erasure, -128 reads
         as -127), 8 per coded byte -> list of (ok, payload, corrected) as fec_decode.  An array whose length is no
         multiple of 8, or no block's, gives (False, b"", 0)."""
-        assert not self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
-        # (a length that is no multiple of 8 is handed on as the odd length 1: no block)
-        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
-        offs = np.zeros(max(len(vals), 1), np.uint64)
-        if len(vals) > 1:
-            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
-        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
-        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
-        poff, ok, corr = self._fec_decode(self._lib.ofdm_fec_decode_soft, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out),
-                                          len(out))
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(len(vals))]
+        return self._fec_decode_host(self._lib.ofdm_fec_decode_soft, fec, _pack_values(values), False)
 
     def fec_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, fec=None, soft=False):
         """Device mode: the blocks (hard bytes, or int8 values with ``soft``: 8 per coded byte, offsets in values) and
@@ -906,7 +943,8 @@ class Engine(object):
         uint64[nblk + 1], ok uint8[nblk], corrected uint32[nblk]) as host arrays."""
         assert self.device_ptrs
         fn = self._lib.ofdm_fec_decode_soft if soft else self._lib.ofdm_fec_decode
-        return self._fec_decode(fn, self._fec_cfg(fec), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+        head = (C.byref(self._fec_cfg(fec)),) + self._batch(C.c_void_p(in_ptr), offs, lens)
+        return self._codec_decode(fn, head, len(lens), C.c_void_p(payload_ptr), payload_cap)
 
     def fec_last_ms(self):
         """HIP-event time of k_fec_encode / k_fec_decode (k_fec_decode_rel after a ``*_rel`` call) in the last fec call
@@ -914,51 +952,19 @@ class Engine(object):
         return self._stage_last_ms("fec")
 
     # -- coded links, reliabilities out (the soft-output Viterbi decoder: one reliability byte per payload byte) --------
-    def _fec_decode_rel(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap, rel_ptr, rel_cap):
-        n = len(lens)
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr = np.zeros(max(n, 1), np.uint32)
-        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
-                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       rel_ptr, int(rel_cap)))
-        return poff, ok[:n], corr[:n]
-
     @staticmethod
-    def _fec_rel_results(n, poff, ok, corr, out, rel):
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), rel[int(poff[i]):int(poff[i + 1])].copy())
-                for i in range(n)]
+    def _fec_rel_results(out, rel, poff, ok, corr):
+        return [r + (rel[int(poff[i]):int(poff[i + 1])].copy(),) for i, r in enumerate(Engine._codec_results(out, poff, ok, corr))]
 
     def fec_decode_rel(self, blocks, fec=None):
         """Host mode: fec_decode() with reliabilities -> list of (ok, payload, corrected, rel): fec_decode()'s three
         fields, and ``rel`` a uint8 array of len(payload): 0 where a path as good as the decoded one disagrees in the
         byte, 255 "never erase" -- what rs_decode_rel() takes.  A length that is no block gives (False, b"", 0, [])."""
-        assert not self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        blob, offs, lens = pack_payloads(blocks)
-        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
-        rel = np.zeros(len(out), np.uint8)
-        poff, ok, corr = self._fec_decode_rel(self._lib.ofdm_fec_decode_rel, cfg, _ptr(blob), offs, lens, _ptr(out), len(out),
-                                              _ptr(rel), len(rel))
-        return self._fec_rel_results(len(blocks), poff, ok, corr, out, rel)
+        return self._fec_decode_host(self._lib.ofdm_fec_decode_rel, fec, pack_payloads(blocks), True)
 
     def fec_decode_soft_rel(self, values, fec=None):
         """Host mode: fec_decode_soft() with reliabilities -> list of (ok, payload, corrected, rel) as fec_decode_rel."""
-        assert not self.device_ptrs
-        cfg = self._fec_cfg(fec)
-        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
-        # (a length that is no multiple of 8 is handed on as the odd length 1: no block)
-        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
-        offs = np.zeros(max(len(vals), 1), np.uint64)
-        if len(vals) > 1:
-            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
-        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
-        out = np.zeros(self._fec_payload_room(cfg, lens), np.uint8)
-        rel = np.zeros(len(out), np.uint8)
-        poff, ok, corr = self._fec_decode_rel(self._lib.ofdm_fec_decode_soft_rel, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out),
-                                              len(out), _ptr(rel), len(rel))
-        return self._fec_rel_results(len(vals), poff, ok, corr, out, rel)
+        return self._fec_decode_host(self._lib.ofdm_fec_decode_soft_rel, fec, _pack_values(values), True)
 
     def fec_decode_rel_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, rel_ptr, rel_cap, fec=None, soft=False):
         """Device mode: fec_decode_device() with the reliabilities written to the device buffer ``rel_ptr`` at the
@@ -966,8 +972,8 @@ class Engine(object):
         reliabilities and offsets, with ``rel_offs=None``.  Returns (payload offsets, ok, corrected) as host arrays."""
         assert self.device_ptrs
         fn = self._lib.ofdm_fec_decode_soft_rel if soft else self._lib.ofdm_fec_decode_rel
-        return self._fec_decode_rel(fn, self._fec_cfg(fec), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap,
-                                    C.c_void_p(rel_ptr), rel_cap)
+        head = (C.byref(self._fec_cfg(fec)),) + self._batch(C.c_void_p(in_ptr), offs, lens)
+        return self._codec_decode(fn, head, len(lens), C.c_void_p(payload_ptr), payload_cap, tail=(C.c_void_p(rel_ptr), int(rel_cap)))
 
     def fec_punct_last_ms(self):
         """HIP-event time of k_fec_puncture / k_fec_depuncture alone in the last fec call, which ran at a punctured
@@ -978,37 +984,14 @@ class Engine(object):
     def rs_encode(self, payloads):
         """Host mode: list of payloads (0 .. 3564 bytes each) -> list of RS blocks (rs.coded_len(n) bytes each), the
         payloads fec_encode() or tx() then takes."""
-        assert not self.device_ptrs
-        blob, offs, lens = pack_payloads(payloads)
-        k = lens.astype(np.int64) + 4
-        out = np.zeros(max(int((k + 32 * ((k + 222) // 223)).sum()), 1), np.uint8)
-        coff = np.zeros(len(payloads) + 1, np.uint64)
-        self._check(self._lib.ofdm_rs_encode(self._h, _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
-                                             coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+        return self._codec_encode_host(self._lib.ofdm_rs_encode, (), payloads,
+                                       lambda lens: (lens + 4 + 32 * ((lens + 4 + 222) // 223)).sum())
 
     def rs_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap):
         """Device mode: payload bytes and RS blocks are device pointers; offs / lens are NumPy host arrays.  Returns
         the nblk + 1 block offsets (uint64), which fec_encode_device() takes as its payload offsets."""
         assert self.device_ptrs
-        coff = np.zeros(len(lens) + 1, np.uint64)
-        self._check(self._lib.ofdm_rs_encode(self._h, C.c_void_p(payload_ptr), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
-                                             int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return coff
-
-    def _rs_decode(self, in_ptr, offs, lens, out_ptr, out_cap):
-        n = len(lens)
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr = np.zeros(max(n, 1), np.uint32)
-        fail = np.zeros(max(n, 1), np.uint32)
-        u32p = C.POINTER(C.c_uint32)
-        self._check(self._lib.ofdm_rs_decode(self._h, in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(u32p),
-                                             n, out_ptr, int(out_cap), poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
-                                             corr.ctypes.data_as(u32p), fail.ctypes.data_as(u32p)))
-        return poff, ok[:n], corr[:n], fail[:n]
+        return self._codec_encode(self._lib.ofdm_rs_encode, (), C.c_void_p(payload_ptr), offs, lens, C.c_void_p(coded_ptr), coded_cap)
 
     def rs_decode(self, blocks):
         """Host mode: list of received RS blocks (bytes of any length, e.g. what fec_decode() returned whatever its
@@ -1018,62 +1001,41 @@ class Engine(object):
         assert not self.device_ptrs
         blob, offs, lens = pack_payloads(blocks)
         out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
-        poff, ok, corr, fail = self._rs_decode(_ptr(blob), offs, lens, _ptr(out), len(out))
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(fail[i])) for i in range(len(blocks))]
+        return self._codec_results(out, *self._codec_decode(self._lib.ofdm_rs_decode, self._batch(_ptr(blob), offs, lens), len(lens),
+                                                            _ptr(out), len(out), extra=(np.uint32,)))
 
     def rs_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap):
         """Device mode: the blocks and the payloads are device pointers (the blocks can be what fec_decode_device()
         wrote, with its payload offsets); offs / lens are NumPy host arrays.  Returns (payload offsets uint64[nblk + 1],
         ok uint8[nblk], corrected uint32[nblk], failed uint32[nblk]) as host arrays."""
         assert self.device_ptrs
-        return self._rs_decode(C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+        return self._codec_decode(self._lib.ofdm_rs_decode, self._batch(C.c_void_p(in_ptr), offs, lens), len(lens),
+                                  C.c_void_p(payload_ptr), payload_cap, extra=(np.uint32,))
 
     def rs_last_ms(self):
         """HIP-event time of k_rs_encode / k_rs_decode in the last rs call (needs prof_enable())."""
         return self._stage_last_ms("rs")
 
     # -- outer code, decoding with reliabilities (errors-and-erasures, the erased symbols chosen per codeword) ---------
-    def _rs_rel_from_soft(self, soft_ptr, offs, lens, rel_ptr, rel_cap):
-        roff = np.zeros(len(lens) + 1, np.uint64)
-        self._check(self._lib.ofdm_rs_rel_from_soft(self._h, soft_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                    lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), rel_ptr, int(rel_cap),
-                                                    roff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return roff
-
     def rs_rel_from_soft(self, values):
         """Host mode: list of int8 arrays, 8 values per byte (what rx_soft() returns for the packets of an RS link
         without an inner code) -> list of uint8 arrays, one reliability per byte (rs.rel_from_values on the GPU)."""
         assert not self.device_ptrs
-        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
-        if any(len(v) % 8 for v in vals):
-            raise ValueError("rs: 8 values per byte")
-        lens = np.array([len(v) // 8 for v in vals], np.uint32)
-        offs = np.zeros(max(len(vals), 1), np.uint64)
-        if len(vals) > 1:
-            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
-        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
+        blob, offs, lens = _pack_values(values, strict=True)
         out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
-        roff = self._rs_rel_from_soft(_ptr(blob), offs[:len(vals)], lens, _ptr(out), len(out))
-        return [out[int(roff[i]):int(roff[i + 1])].copy() for i in range(len(vals))]
+        roff = self._codec_encode(self._lib.ofdm_rs_rel_from_soft, (), _ptr(blob), offs, lens, _ptr(out), len(out))
+        return [out[int(roff[i]):int(roff[i + 1])].copy() for i in range(len(lens))]
 
     def rs_rel_from_soft_device(self, soft_ptr, offs, lens, rel_ptr, rel_cap):
         """Device mode: the values (e.g. what rx_soft_device() wrote, with its offsets; lens in bytes = values / 8) and
         the reliabilities are device pointers; offs / lens are NumPy host arrays.  Returns the nblk + 1 reliability
         offsets (uint64), which rs_decode_rel_device() takes as ``rel_offs``."""
         assert self.device_ptrs
-        return self._rs_rel_from_soft(C.c_void_p(soft_ptr), offs, lens, C.c_void_p(rel_ptr), rel_cap)
+        return self._codec_encode(self._lib.ofdm_rs_rel_from_soft, (), C.c_void_p(soft_ptr), offs, lens, C.c_void_p(rel_ptr), rel_cap)
 
     def _rs_decode_rel(self, cfg, in_ptr, offs, lens, rel_ptr, rel_offs, out_ptr, out_cap):
-        n = len(lens)
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr, fail, sec = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
-        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-        self._check(self._lib.ofdm_rs_decode_rel(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(u64p), lens.ctypes.data_as(u32p), n,
-                                                 rel_ptr, None if rel_offs is None else rel_offs.ctypes.data_as(u64p), out_ptr,
-                                                 int(out_cap), poff.ctypes.data_as(u64p), _ptr(ok), corr.ctypes.data_as(u32p),
-                                                 fail.ctypes.data_as(u32p), sec.ctypes.data_as(u32p)))
-        return poff, ok[:n], corr[:n], fail[:n], sec[:n]
+        head = (C.byref(cfg),) + self._batch(in_ptr, offs, lens, rel_ptr, None if rel_offs is None else _u64(rel_offs))
+        return self._codec_decode(self._lib.ofdm_rs_decode_rel, head, len(lens), out_ptr, out_cap, extra=(np.uint32, np.uint32))
 
     def rs_decode_rel(self, blocks, rel, rs=None):
         """Host mode: rs_decode() with reliabilities: ``rel`` holds one uint8 array (or bytes) per block, one value per
@@ -1092,10 +1054,8 @@ class Engine(object):
                 raise ValueError("rs: one reliability per byte of every block")
             rblob = np.concatenate(rel + [np.zeros(1, np.uint8)])     # laid out like the blocks: rel_off = coded_off
         out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)
-        poff, ok, corr, fail, sec = self._rs_decode_rel(cfg, _ptr(blob), offs, lens, None if rblob is None else _ptr(rblob), None,
-                                                        _ptr(out), len(out))
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(fail[i]), int(sec[i]))
-                for i in range(len(blocks))]
+        return self._codec_results(out, *self._rs_decode_rel(cfg, _ptr(blob), offs, lens, None if rblob is None else _ptr(rblob), None,
+                                                             _ptr(out), len(out)))
 
     def rs_decode_rel_device(self, in_ptr, offs, lens, rel_ptr, rel_offs, payload_ptr, payload_cap, rs=None):
         """Device mode: blocks, reliabilities (``rel_ptr`` 0 / None: none; ``rel_offs`` None: at the blocks' offsets)
@@ -1131,7 +1091,7 @@ class Engine(object):
         n = C.c_int(0)
         self._check(self._lib.ofdm_rx_soft(self._h, None, 0, None, C.byref(n)))
         off = np.zeros(n.value + 1, np.uint64)
-        self._check(self._lib.ofdm_rx_soft(self._h, None, 0, off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        self._check(self._lib.ofdm_rx_soft(self._h, None, 0, _u64(off), C.byref(n)))
         return n.value, off
 
     def rx_soft(self):
@@ -1153,63 +1113,50 @@ class Engine(object):
         self._check(self._lib.ofdm_rx_soft(self._h, C.c_void_p(out_ptr), int(cap), None, C.byref(C.c_int(0))))
         return off
 
-    def _rx_fec_decode_soft(self, fec, out_ptr, out_cap, n):
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr = np.zeros(max(n, 1), np.uint32)
-        self._check(self._lib.ofdm_rx_fec_decode_soft(self._h, C.byref(self._fec_cfg(fec)), out_ptr, int(out_cap),
-                                                      poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
-                                                      corr.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(C.c_int(0))))
-        return poff, ok[:n], corr[:n]
-
     def rx_fec_decode_soft(self, fec=None):
         """Host mode: the packets the last rx() returned, decoded from the handle's own soft values (they never visit
         the host) -> list of (ok, payload, corrected) as fec_decode_soft.  Needs set_rx_soft() before that rx()."""
         assert not self.device_ptrs
         n, off = self._rx_soft_offsets()
-        out = np.zeros(self._fec_payload_room(self._fec_cfg(fec), [int(off[n]) // 8]), np.uint8)
-        poff, ok, corr = self._rx_fec_decode_soft(fec, _ptr(out), len(out), n)
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i])) for i in range(n)]
+        cfg = self._fec_cfg(fec)
+        out = np.zeros(self._fec_payload_room(cfg, [int(off[n]) // 8]), np.uint8)
+        return self._codec_results(out, *self._codec_decode(self._lib.ofdm_rx_fec_decode_soft, (C.byref(cfg),), n, _ptr(out), len(out),
+                                                            tail=self._rx_batch(n)))
 
     def rx_fec_decode_soft_device(self, payload_ptr, payload_cap, fec=None):
         """Device mode: the same into the device buffer ``payload_ptr``; returns (payload offsets uint64[n + 1],
         ok uint8[n], corrected uint32[n]) as host arrays."""
         assert self.device_ptrs
         n, _ = self._rx_soft_offsets()
-        return self._rx_fec_decode_soft(fec, C.c_void_p(payload_ptr), payload_cap, n)
-
-    def _rx_fec_decode_soft_rel(self, fec, out_ptr, out_cap, rel_ptr, rel_cap, n):
-        poff = np.zeros(n + 1, np.uint64)
-        ok = np.zeros(max(n, 1), np.uint8)
-        corr = np.zeros(max(n, 1), np.uint32)
-        self._check(self._lib.ofdm_rx_fec_decode_soft_rel(self._h, C.byref(self._fec_cfg(fec)), out_ptr, int(out_cap),
-                                                          poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
-                                                          corr.ctypes.data_as(C.POINTER(C.c_uint32)), rel_ptr, int(rel_cap), n,
-                                                          C.byref(C.c_int(0))))
-        return poff, ok[:n], corr[:n]
+        return self._codec_decode(self._lib.ofdm_rx_fec_decode_soft, (C.byref(self._fec_cfg(fec)),), n, C.c_void_p(payload_ptr),
+                                  payload_cap, tail=self._rx_batch(n))
 
     def rx_fec_decode_soft_rel(self, fec=None):
         """Host mode: rx_fec_decode_soft() with reliabilities -> list of (ok, payload, corrected, rel) as
         fec_decode_rel."""
         assert not self.device_ptrs
         n, off = self._rx_soft_offsets()
-        out = np.zeros(self._fec_payload_room(self._fec_cfg(fec), [int(off[n]) // 8]), np.uint8)
+        cfg = self._fec_cfg(fec)
+        out = np.zeros(self._fec_payload_room(cfg, [int(off[n]) // 8]), np.uint8)
         rel = np.zeros(len(out), np.uint8)
-        poff, ok, corr = self._rx_fec_decode_soft_rel(fec, _ptr(out), len(out), _ptr(rel), len(rel), n)
-        return self._fec_rel_results(n, poff, ok, corr, out, rel)
+        return self._fec_rel_results(out, rel, *self._codec_decode(self._lib.ofdm_rx_fec_decode_soft_rel, (C.byref(cfg),), n, _ptr(out),
+                                                                   len(out), tail=(_ptr(rel), len(rel)) + self._rx_batch(n)))
 
     def rx_fec_decode_soft_rel_device(self, payload_ptr, payload_cap, rel_ptr, rel_cap, fec=None):
         """Device mode: the same into the device buffers ``payload_ptr`` and ``rel_ptr``; returns (payload offsets
         uint64[n + 1], ok uint8[n], corrected uint32[n]) as host arrays."""
         assert self.device_ptrs
         n, _ = self._rx_soft_offsets()
-        return self._rx_fec_decode_soft_rel(fec, C.c_void_p(payload_ptr), payload_cap, C.c_void_p(rel_ptr), rel_cap, n)
+        return self._codec_decode(self._lib.ofdm_rx_fec_decode_soft_rel, (C.byref(self._fec_cfg(fec)),), n, C.c_void_p(payload_ptr),
+                                  payload_cap, tail=(C.c_void_p(rel_ptr), int(rel_cap)) + self._rx_batch(n))
 
     def rx_soft_last_ms(self):
         """HIP-event time of k_soft_demap in the last rx() / rx_device() (needs prof_enable())."""
         return self._stage_last_ms("rx_soft")
 
     # -- coded links, the second inner code (QC-LDPC encoder and layered min-sum decoder over the payloads) -----------
+    _LDPC_EXTRA = (np.uint8, np.uint32)   # iters, cw_failed
+
     def _ldpc_cfg(self, ldpc):
         from . import ldpc as _ldpc
         cfg = _ldpc.as_cfg(True if ldpc is None else ldpc)
@@ -1221,76 +1168,39 @@ class Engine(object):
         """Host mode: list of payloads (0 .. 2012 bytes each) -> list of coded blocks (ldpc.coded_len(n) bytes each),
         the payloads tx() then takes.  ``ldpc``: None / True, max_iters, a dict of ldpc.ldpc_cfg's keywords or an
         ``ofdm_ldpc_cfg`` (the encoder only checks it)."""
-        assert not self.device_ptrs
-        cfg = self._ldpc_cfg(ldpc)
-        blob, offs, lens = pack_payloads(payloads)
         # n + 4 + 96 ceil((n + 4) / 96) <= 2 n + 104
-        out = np.zeros(max(int(2 * lens.astype(np.int64).sum()) + 104 * len(payloads), 1), np.uint8)
-        coff = np.zeros(len(payloads) + 1, np.uint64)
-        self._check(self._lib.ofdm_ldpc_encode(self._h, C.byref(cfg), _ptr(blob), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                               lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(payloads), _ptr(out), len(out),
-                                               coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return [out[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(payloads))]
+        return self._codec_encode_host(self._lib.ofdm_ldpc_encode, (C.byref(self._ldpc_cfg(ldpc)),), payloads,
+                                       lambda lens: 2 * lens.sum() + 104 * len(lens))
 
     def ldpc_encode_device(self, payload_ptr, offs, lens, coded_ptr, coded_cap, ldpc=None):
         """Device mode: payload bytes and coded blocks are device pointers; offs / lens are NumPy host arrays.
         Returns the nblk + 1 block offsets (uint64)."""
         assert self.device_ptrs
-        cfg = self._ldpc_cfg(ldpc)
-        coff = np.zeros(len(lens) + 1, np.uint64)
-        self._check(self._lib.ofdm_ldpc_encode(self._h, C.byref(cfg), C.c_void_p(payload_ptr),
-                                               offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                               lens.ctypes.data_as(C.POINTER(C.c_uint32)), len(lens), C.c_void_p(coded_ptr),
-                                               int(coded_cap), coff.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return coff
+        return self._codec_encode(self._lib.ofdm_ldpc_encode, (C.byref(self._ldpc_cfg(ldpc)),), C.c_void_p(payload_ptr), offs, lens,
+                                  C.c_void_p(coded_ptr), coded_cap)
 
-    @staticmethod
-    def _ldpc_outputs(n):
-        return (np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32),
-                np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32))
+    def _ldpc_decode(self, fn, ldpc, in_ptr, offs, lens, out_ptr, out_cap):
+        head = (C.byref(self._ldpc_cfg(ldpc)),) + self._batch(in_ptr, offs, lens)
+        return self._codec_decode(fn, head, len(lens), out_ptr, out_cap, extra=self._LDPC_EXTRA)
 
-    def _ldpc_decode(self, fn, cfg, in_ptr, offs, lens, out_ptr, out_cap):
-        n = len(lens)
-        poff, ok, corr, iters, failed = self._ldpc_outputs(n)
-        self._check(fn(self._h, C.byref(cfg), in_ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                       lens.ctypes.data_as(C.POINTER(C.c_uint32)), n, out_ptr, int(out_cap),
-                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok), corr.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       _ptr(iters), failed.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return poff, ok[:n], corr[:n], iters[:n], failed[:n]
-
-    @staticmethod
-    def _ldpc_results(n, poff, ok, corr, iters, failed, out):
-        return [(bool(ok[i]), out[int(poff[i]):int(poff[i + 1])].tobytes(), int(corr[i]), int(iters[i]), int(failed[i]))
-                for i in range(n)]
+    def _ldpc_decode_host(self, fn, ldpc, packed):
+        assert not self.device_ptrs
+        blob, offs, lens = packed
+        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        return self._codec_results(out, *self._ldpc_decode(fn, ldpc, _ptr(blob), offs, lens, _ptr(out), len(out)))
 
     def ldpc_decode(self, blocks, ldpc=None):
         """Host mode: list of received blocks (hard bytes of any length, e.g. the payloads rx() delivered whatever
         their CRC said) -> list of (ok, payload, corrected, iters, cw_failed): the decoded payload, whether its inner
         CRC matches, the sent bits the decoder changed, the most iterations one of the block's codewords took and
         the codewords that never met all checks.  A length that is no block gives (False, b"", 0, 0, 0)."""
-        assert not self.device_ptrs
-        cfg = self._ldpc_cfg(ldpc)
-        blob, offs, lens = pack_payloads(blocks)
-        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
-        res = self._ldpc_decode(self._lib.ofdm_ldpc_decode, cfg, _ptr(blob), offs, lens, _ptr(out), len(out))
-        return self._ldpc_results(len(blocks), *res, out)
+        return self._ldpc_decode_host(self._lib.ofdm_ldpc_decode, ldpc, pack_payloads(blocks))
 
     def ldpc_decode_soft(self, values, ldpc=None):
         """Host mode: list of int8 arrays, one value per sent bit (v > 0 means 1, 0 is an erasure, -128 reads as
         -127), 8 per coded byte -> list of (ok, payload, corrected, iters, cw_failed) as ldpc_decode.  An array whose
         length is no multiple of 8, or no block's, gives (False, b"", 0, 0, 0)."""
-        assert not self.device_ptrs
-        cfg = self._ldpc_cfg(ldpc)
-        vals = [np.ascontiguousarray(v, np.int8).reshape(-1) for v in values]
-        # (a length that is no multiple of 8 is handed on as the length 1: no block)
-        lens = np.array([len(v) // 8 if len(v) % 8 == 0 else 1 for v in vals], np.uint32)
-        offs = np.zeros(max(len(vals), 1), np.uint64)
-        if len(vals) > 1:
-            offs[1:] = np.cumsum([len(v) for v in vals[:-1]], dtype=np.uint64)
-        blob = np.concatenate(vals + [np.zeros(8, np.int8)])
-        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
-        res = self._ldpc_decode(self._lib.ofdm_ldpc_decode_soft, cfg, _ptr(blob), offs[:len(vals)], lens, _ptr(out), len(out))
-        return self._ldpc_results(len(vals), *res, out)
+        return self._ldpc_decode_host(self._lib.ofdm_ldpc_decode_soft, ldpc, _pack_values(values))
 
     def ldpc_decode_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, ldpc=None, soft=False):
         """Device mode: the blocks (hard bytes, or int8 values with ``soft``: 8 per coded byte, offsets in values) and
@@ -1299,15 +1209,11 @@ class Engine(object):
         arrays."""
         assert self.device_ptrs
         fn = self._lib.ofdm_ldpc_decode_soft if soft else self._lib.ofdm_ldpc_decode
-        return self._ldpc_decode(fn, self._ldpc_cfg(ldpc), C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
+        return self._ldpc_decode(fn, ldpc, C.c_void_p(in_ptr), offs, lens, C.c_void_p(payload_ptr), payload_cap)
 
     def _rx_ldpc_decode_soft(self, ldpc, out_ptr, out_cap, n):
-        poff, ok, corr, iters, failed = self._ldpc_outputs(n)
-        self._check(self._lib.ofdm_rx_ldpc_decode_soft(self._h, C.byref(self._ldpc_cfg(ldpc)), out_ptr, int(out_cap),
-                                                       poff.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(ok),
-                                                       corr.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(iters),
-                                                       failed.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(C.c_int(0))))
-        return poff, ok[:n], corr[:n], iters[:n], failed[:n]
+        return self._codec_decode(self._lib.ofdm_rx_ldpc_decode_soft, (C.byref(self._ldpc_cfg(ldpc)),), n, out_ptr, out_cap,
+                                  extra=self._LDPC_EXTRA, tail=self._rx_batch(n))
 
     def rx_ldpc_decode_soft(self, ldpc=None):
         """Host mode: the packets the last rx() returned, decoded from the handle's own soft values (they never visit
@@ -1316,8 +1222,7 @@ class Engine(object):
         assert not self.device_ptrs
         n, off = self._rx_soft_offsets()
         out = np.zeros(max(int(off[n]) // 16, 1), np.uint8)
-        res = self._rx_ldpc_decode_soft(ldpc, _ptr(out), len(out), n)
-        return self._ldpc_results(n, *res, out)
+        return self._codec_results(out, *self._rx_ldpc_decode_soft(ldpc, _ptr(out), len(out), n))
 
     def rx_ldpc_decode_soft_device(self, payload_ptr, payload_cap, ldpc=None):
         """Device mode: the same into the device buffer ``payload_ptr``; returns the host arrays of
