@@ -1343,7 +1343,7 @@ int ofdm_rs_rel_from_soft(ofdm_handle *h, const int8_t *soft, const uint64_t *so
                           uint8_t *rel, uint64_t rel_cap, uint64_t *rel_off);
 int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
 
-/* --- coded links: LDPC -- a rate-1/2 quasi-cyclic code with a layered min-sum decoder on the GPU -------------------------
+/* --- coded links: LDPC -- quasi-cyclic codes of rate 1/2, 2/3, 3/4 and 5/6 with a layered min-sum decoder on the GPU -------
  * A second inner code next to the convolutional one, at the same boundary: ofdm_ldpc_encode turns payloads into coded
  * blocks that go to ofdm_tx / ofdm_make_packets as payloads; ofdm_ldpc_decode takes the payloads ofdm_rx delivered
  * (CRC-failed ones included).  Additions only: OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, no existing
@@ -1371,6 +1371,36 @@ int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
  * unique solution of all checks: with lambda_i the XOR of the info entries of row i and p_c column 12 + c,
  *   p_0 = XOR of all lambda_i;  p_1 = lambda_0 ^ rot(p_0, 1);  p_{i+1} = lambda_i ^ p_i ^ (p_0 if i = 6), i = 1 .. 10.
  *
+ * Rates.  The above is OFDM_LDPC_RATE_1_2, the rate of a NULL or zeroed cfg.  The other rates are other base matrices of
+ * the same shape: Z = 64 and 24 columns (n = 1536 at every rate), mb rows and kb = 24 - mb info columns, KI = 8 kb info
+ * bytes and PB = 8 mb parity bytes per codeword (96 / 96, 128 / 64, 144 / 48, 160 / 32).  Parity part, with
+ * mid = mb / 2: column kb has shift 1 in row 0, shift 0 in row mid and shift 1 in row mb - 1; column kb + 1 + i
+ * (i = 0 .. mb - 2) has shift 0 in rows i and i + 1.  With p_c column kb + c:
+ *   p_0 = XOR of all lambda_i;  p_1 = lambda_0 ^ rot(p_0, 1);  p_{i+1} = lambda_i ^ p_i ^ (p_0 if i = mid), i = 1 .. mb - 2
+ * (at mb = 12 the recursion above).  No table has a 4-cycle.  Info parts, laid out as above:
+ * OFDM_LDPC_RATE_2_3: mb = 8, kb = 16, mid = 4; 54 + 17 = 71 entries, row degrees 8, 9, 9, 9, 9, 9, 9, 9.
+ *  2/3 0:  -  1 61  - 10  -  - 43  -  - 15  -  - 28  -  -
+ *  2/3 1:  7 21  - 32  - 25  -  -  -  - 60  - 56  - 16  -
+ *  2/3 2: 30  - 37  -  4  - 12  - 58  -  - 14  -  -  2  -
+ *  2/3 3: 34  -  -  9  -  4 47  -  9  -  -  - 10  - 23  -
+ *  2/3 4:  -  -  - 14  - 28  - 47  - 58  -  -  5  -  - 42
+ *  2/3 5:  - 13 43  -  - 11 13  -  -  - 63 36  - 16  -  -
+ *  2/3 6:  - 12  - 61 57  -  -  -  0 19  -  -  - 35  - 50
+ *  2/3 7:  0  - 29  - 16  -  - 21  - 12  - 43  -  -  - 41
+ * OFDM_LDPC_RATE_3_4: mb = 6, kb = 18, mid = 3; 60 + 13 = 73 entries, row degrees 12, 12, 12, 12, 13, 12.
+ *  3/4 0: 40 21  5  -  -  7 42  - 18  -  - 24  0  -  5  -  - 40
+ *  3/4 1:  0  - 58  - 60  1 28  -  - 27 10  - 27  - 40  - 61  -
+ *  3/4 2:  -  1 39 26  - 25  - 23 43  - 29  -  - 35  - 52  - 34
+ *  3/4 3:  - 40  - 13  7  - 52  -  - 21  - 51 34  -  -  2 42  -
+ *  3/4 4:  8  - 21 37 47  6  - 30  -  5  -  -  - 15  6  -  3 36
+ *  3/4 5: 43 17  - 10 32  -  - 44  5  - 12 50  -  5  - 58  -  -
+ * OFDM_LDPC_RATE_5_6: mb = 4, kb = 20, mid = 2; 64 + 9 = 73 entries, row degrees 18, 18, 19, 18.
+ *  5/6 0: 38 18 31 40 46 13  -  1 40 47 43  - 16  0 29  - 33 15 49  -
+ *  5/6 1: 14 30 51 26 63  0 14  0  - 51  -  5 59 39  -  2 27  - 23 55
+ *  5/6 2: 57 40 19 23  -  9 34  - 41 52 25 62  -  - 41  7 22  0 40 27
+ *  5/6 3: 48 42  8 33 34  - 33 62 15  - 17 30 48 59  0 61  - 44  - 14
+ * Both ends of a link are set to the same rate; no field on the air names it.
+ *
  * Block.  Info bytes of an n-byte payload (0 <= n <= OFDM_LDPC_MAX_PAYLOAD): payload | CRC-32(payload) big-endian,
  * k = n + 4 bytes, bits MSB first; info byte m of a codeword holds codeword bits 8m .. 8m + 7.  W = ceil(k / 96)
  * codewords, codeword w takes info bytes [96w, min(96w + 96, k)); the last codeword is shortened: its missing info bits
@@ -1379,11 +1409,16 @@ int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
  * A received length m is a block iff 100 <= m <= 4032 and ((m - 1) mod 192) >= 96; then W = ceil(m / 192) and
  * k = m - 96 W.  Anything else is no block: ok = 0, no payload bytes, zeros in the per-block outputs, no error for the
  * batch, and nothing of it is read.
+ * At the other rates the same with KI and PB in the place of 96: W = ceil(k / KI), codeword w takes info bytes
+ * [KI w, min(KI w + KI, k)) and is sent as its info bytes and then its PB parity bytes; coded length k + PB W; a full
+ * codeword is 192 bytes at every rate.  OFDM_LDPC_MAX_CODED stays 4032 (W <= 21), so the largest payload is 21 KI - 4:
+ * 2012, 2684, 3020, 3356.  A received length m is a block at a rate iff PB + 4 <= m <= 4032 and
+ * ((m - 1) mod 192) >= PB; then W = ceil(m / 192) and k = m - PB W.
  *
  * Decoder input: one signed value v per sent bit, v > 0 means 1, v = 0 is an erasure, -128 reads as -127; shortened
  * positions read as -127; a hard byte is v = +16 / -16 per bit.
  * Decoder: layered normalised min-sum.  P_b (int) starts as v_b, R_e = 0 for every entry e and lane z.  An iteration
- * visits rows i = 0 .. 11 in order; for each entry e = (i, j, s) of the row and each lane z, b = 64 j + (z + s) mod 64:
+ * visits rows i = 0 .. mb - 1 in order; for each entry e = (i, j, s) of the row and each lane z, b = 64 j + (z + s) mod 64:
  *   1. Q_e = clamp(P_b - R_e, -127, 127)
  *   2. beta_e = (Q_e > 0); pi = XOR of the row's beta; m_e = min of |Q_e'| over the row's other entries e' != e
  *   3. mu_e = (3 m_e) >> 2
@@ -1397,25 +1432,36 @@ int ofdm_rs_rel_last_ms(const ofdm_handle *h, double *ms);
  *
  * Argument order, pointer modes, errors and the offsets-before-the-capacity-check rule as ofdm_fec_*: the blobs
  * (payloads, coded, soft) are host or device pointers by the handle's mode; the offset, length, ok, corrected, iters and
- * cw_failed arrays are host memory; coded_off / payload_off OUT have nblk + 1 entries.  cfg NULL: max_iters 20 (the
- * encoder checks its cfg and ignores max_iters).  OFDM_E_INVAL: bad struct_size, max_iters outside 1 .. 64, a non-zero
- * reserved word, a payload longer than OFDM_LDPC_MAX_PAYLOAD (encode), a null argument.  OFDM_E_CAPACITY: the output blob
- * is too small.  There is no per-batch workspace and no slicing: a batch is as many one-wave codewords as it has.
+ * cw_failed arrays are host memory; coded_off / payload_off OUT have nblk + 1 entries.  cfg NULL: max_iters 20 at rate
+ * 1/2 (the encoder checks its cfg and ignores max_iters).  OFDM_E_INVAL: bad struct_size, max_iters outside 1 .. 64, a
+ * rate above OFDM_LDPC_RATE_5_6, a non-zero reserved word behind it, a payload longer than the rate's largest (encode),
+ * a null argument.  OFDM_E_CAPACITY: the output blob is too small.  There is no per-batch workspace and no slicing: a
+ * batch is as many one-wave codewords as it has.
  * ofdm_rx_ldpc_decode_soft: the last ofdm_rx call's packets through ofdm_ldpc_decode_soft's decoder, the values read
  * where they lie in the handle's buffer (ofdm_set_rx_soft), as ofdm_rx_fec_decode_soft.
  * ofdm_ldpc_last_ms: HIP-event time of k_ldpc_encode / k_ldpc_decode in the last of these calls, which must have run
  * with profiling on (ofdm_prof_enable) and launched; OFDM_E_INVAL otherwise.  As ofdm_fec_last_ms. */
-#define OFDM_LDPC_MAX_PAYLOAD 2012
+#define OFDM_LDPC_MAX_PAYLOAD 2012 /* at rate 1/2; 2684, 3020 and 3356 at the other rates */
 #define OFDM_LDPC_MAX_CODED 4032
+#define OFDM_LDPC_RATE_1_2 0
+#define OFDM_LDPC_RATE_2_3 1
+#define OFDM_LDPC_RATE_3_4 2
+#define OFDM_LDPC_RATE_5_6 3
 typedef struct ofdm_ldpc_cfg {
   uint32_t struct_size; /* = sizeof(ofdm_ldpc_cfg) */
   uint32_t max_iters;   /* 1 .. 64 */
-  uint32_t reserved[6]; /* 0 */
-} ofdm_ldpc_cfg;        /* 32 bytes */
+  union {
+    uint32_t reserved[6]; /* 0 behind the first word */
+    uint32_t rate;        /* OFDM_LDPC_RATE_*: the word that is reserved[0]; 0 is rate 1/2 */
+  };
+} ofdm_ldpc_cfg; /* 32 bytes */
 
-/* pure host functions, usable without a GPU: n + 4 + 96 W, and its inverse (OFDM_E_INVAL for a length that is no block) */
+/* pure host functions, usable without a GPU: n + 4 + 96 W, and its inverse (OFDM_E_INVAL for a length that is no block);
+ * the _rate forms take OFDM_LDPC_RATE_* first (n + 4 + PB W), the other two mean rate 1/2 */
 int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t *coded_len);
 int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t *payload_len);
+int ofdm_ldpc_coded_len_rate(uint32_t rate, uint32_t payload_len, uint32_t *coded_len);
+int ofdm_ldpc_payload_len_rate(uint32_t rate, uint32_t coded_len, uint32_t *payload_len);
 int ofdm_ldpc_encode(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const uint8_t *payloads, const uint64_t *payload_off,
                      const uint32_t *payload_len, int nblk, uint8_t *coded, uint64_t coded_cap, uint64_t *coded_off);
 int ofdm_ldpc_decode(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,

@@ -32,6 +32,7 @@ OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
 OFDM_LDPC_MAX_PAYLOAD = 2012
 OFDM_LDPC_MAX_CODED = 4032
+OFDM_LDPC_RATE_1_2, OFDM_LDPC_RATE_2_3, OFDM_LDPC_RATE_3_4, OFDM_LDPC_RATE_5_6 = 0, 1, 2, 3
 OFDM_RS_PARITY = 32
 OFDM_RS_MAX_PAYLOAD = 3564
 OFDM_RS_MAX_CODED = 4080
@@ -314,11 +315,19 @@ class ofdm_rs_rel_cfg(C.Structure):
     ]
 
 
+class _ofdm_ldpc_cfg_tail(C.Union):       # the header's anonymous union: the rate is the word that is reserved[0]
+    _fields_ = [
+        ("reserved", C.c_uint32 * 6),
+        ("rate", C.c_uint32),
+    ]
+
+
 class ofdm_ldpc_cfg(C.Structure):
+    _anonymous_ = ("_tail",)
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("max_iters", C.c_uint32),
-        ("reserved", C.c_uint32 * 6),
+        ("_tail", _ofdm_ldpc_cfg_tail),
     ]
 
 
@@ -354,7 +363,7 @@ EXPORTS = (
     "ofdm_rs_coded_len", "ofdm_rs_payload_len", "ofdm_rs_encode", "ofdm_rs_decode", "ofdm_rs_last_ms",
     "ofdm_rs_decode_rel", "ofdm_rs_rel_from_soft", "ofdm_rs_rel_last_ms",
     "ofdm_ldpc_coded_len", "ofdm_ldpc_payload_len", "ofdm_ldpc_encode", "ofdm_ldpc_decode", "ofdm_ldpc_decode_soft",
-    "ofdm_rx_ldpc_decode_soft", "ofdm_ldpc_last_ms",
+    "ofdm_rx_ldpc_decode_soft", "ofdm_ldpc_last_ms", "ofdm_ldpc_coded_len_rate", "ofdm_ldpc_payload_len_rate",
 )
 
 _LIB = None
@@ -474,6 +483,8 @@ def _declare(lib):
     LC = C.POINTER(ofdm_ldpc_cfg)
     lib.ofdm_ldpc_coded_len.argtypes = [C.c_uint32, u32p]
     lib.ofdm_ldpc_payload_len.argtypes = [C.c_uint32, u32p]
+    lib.ofdm_ldpc_coded_len_rate.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    lib.ofdm_ldpc_payload_len_rate.argtypes = [C.c_uint32, C.c_uint32, u32p]
     lib.ofdm_ldpc_encode.argtypes = [H, LC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
     lib.ofdm_ldpc_decode.argtypes = [H, LC, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p]
     lib.ofdm_ldpc_decode_soft.argtypes = lib.ofdm_ldpc_decode.argtypes

@@ -94,6 +94,9 @@ def make_parser():
     parser.add_option("", "--ldpc-soft", action="store_true", default=False,
                       help="--ldpc with soft decisions: the decoder takes the soft demapper's value of every coded bit "
                            "where --ldpc takes the sliced bytes [default=%default]")
+    parser.add_option("", "--ldpc-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
+                      help="the QC-LDPC code of this rate, as benchmark_ofdm_tx --ldpc-rate wrote it (implies --ldpc; works "
+                           "with --ldpc-soft) [default=1/2]")
     parser.add_option("", "--rs", action="store_true", default=False,
                       help="outer code: the file was written by benchmark_ofdm_tx --rs; every delivered packet goes "
                            "through the Reed-Solomon decoder on the GPU, behind the inner decoder where --fec, "
@@ -191,6 +194,8 @@ def main(argv=None):
         options.fec = dict(rate=options.fec_rate)   # (what receive_path hands to ofdm_demod(fec=))
     if options.ldpc_soft:
         options.ldpc = True
+    if options.ldpc_rate:
+        options.ldpc = dict(rate=options.ldpc_rate)   # (what receive_path hands to ofdm_demod(ldpc=))
     if options.ldpc and options.fec:
         parser.error("--ldpc / --ldpc-soft take the place of --fec / --fec-rate / --fec-soft: a link has one inner code")
     if options.ldpc and options.rs_erasures is not None:

@@ -65,8 +65,12 @@ def make_parser():
                       help="coded link with the other inner code, in the place of --fec: protect every payload (at "
                            "most 2012 bytes) with the rate-1/2 QC-LDPC code, encoded on the GPU; demodulate with "
                            "benchmark_ofdm_rx --ldpc or --ldpc-soft [default=%default]")
+    parser.add_option("", "--ldpc-rate", type="choice", choices=("1/2", "2/3", "3/4", "5/6"), default=None,
+                      help="--ldpc with the QC-LDPC code of this rate (payloads of at most 2012, 2684, 3020 or 3356 bytes; "
+                           "demodulate with the same benchmark_ofdm_rx --ldpc-rate) [default=1/2]")
     parser.add_option("", "--rs", action="store_true", default=False,
-                      help="outer code: wrap every payload (at most 3564 bytes, 1780 with --fec / --fec-rate, 1752 with --ldpc) in a "
+                      help="outer code: wrap every payload (at most 3564 bytes, 1780 with --fec / --fec-rate, 1752 with --ldpc, "
+                           "2328 / 2632 / 2904 with --ldpc-rate 2/3 / 3/4 / 5/6) in a "
                            "Reed-Solomon block, 32 parity bytes per 223, encoded on the GPU ahead of the inner code; "
                            "demodulate with benchmark_ofdm_rx --rs [default=%default]")
     _options.add_tx_resamp_options(parser)
@@ -136,8 +140,10 @@ def main(argv=None):
         sys.exit(1)
     if options.fec_rate:
         options.fec = dict(rate=options.fec_rate)   # (what transmit_path hands to ofdm_mod(fec=))
+    if options.ldpc_rate:
+        options.ldpc = dict(rate=options.ldpc_rate)   # (what transmit_path hands to ofdm_mod(ldpc=))
     if options.ldpc and options.fec:
-        parser.error("--ldpc takes the place of --fec / --fec-rate: a link has one inner code")
+        parser.error("--ldpc / --ldpc-rate take the place of --fec / --fec-rate: a link has one inner code")
     if options.tx_resamp_freqs is not None:
         return _main_tx_resamp_bank(parser, options)
 

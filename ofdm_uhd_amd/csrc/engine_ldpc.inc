@@ -4,18 +4,58 @@
 
 extern "C" int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t* coded_len) { return ldpc_coded_len(payload_len, coded_len); }
 extern "C" int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t* payload_len) { return ldpc_payload_len(coded_len, payload_len); }
+extern "C" int ofdm_ldpc_coded_len_rate(uint32_t rate, uint32_t payload_len, uint32_t* coded_len) {
+  return ldpc_coded_len_rate(rate, payload_len, coded_len);
+}
+extern "C" int ofdm_ldpc_payload_len_rate(uint32_t rate, uint32_t coded_len, uint32_t* payload_len) {
+  return ldpc_payload_len_rate(rate, coded_len, payload_len);
+}
 
 extern "C" int ofdm_ldpc_last_ms(const ofdm_handle* h, double* ms) { return h ? codec_last_ms(h->ldpc, ms) : OFDM_E_INVAL; }
 
-static int ldpc_iters(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint32_t* max_iters) {
+// the call's max_iters and rate: 20 and rate 1/2 without a cfg
+static int ldpc_cfg_check(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint32_t* max_iters, uint32_t* rate) {
   *max_iters = LDPC_DEFAULT_ITERS;
+  *rate = OFDM_LDPC_RATE_1_2;
   if (!cfg) return OFDM_OK;
   if (cfg->struct_size != sizeof(ofdm_ldpc_cfg)) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.struct_size does not match this library");
   if (cfg->max_iters < 1 || cfg->max_iters > LDPC_MAX_ITERS) FAIL(h, OFDM_E_INVAL, "ldpc max_iters must be in [1, 64]");
-  for (uint32_t r : cfg->reserved)
-    if (r) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.reserved must be 0");
+  if (cfg->rate >= LDPC_RATES) FAIL(h, OFDM_E_INVAL, "ldpc rate must be one of OFDM_LDPC_RATE_*");
+  for (int i = 1; i < 6; i++)  // (reserved[0] is the rate)
+    if (cfg->reserved[i]) FAIL(h, OFDM_E_INVAL, "ofdm_ldpc_cfg.reserved must be 0");
   *max_iters = cfg->max_iters;
+  *rate = cfg->rate;
   return OFDM_OK;
+}
+
+// one instantiation per rate (ldpc_cfg_check has refused any other value)
+static void ldpc_launch_encode(uint32_t rate, unsigned grid, hipStream_t st, const uint8_t* d_in, const LdpcBlk* blk, const uint32_t* cw,
+                               uint32_t ncw, uint8_t* d_out, const uint32_t* crc, const uint32_t* xp8) {
+#define LDPC_ENC(R) \
+  case R: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_encode<R>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, blk, cw, ncw, d_out, crc, xp8); break
+  switch (rate) {
+    LDPC_ENC(OFDM_LDPC_RATE_1_2);
+    LDPC_ENC(OFDM_LDPC_RATE_2_3);
+    LDPC_ENC(OFDM_LDPC_RATE_3_4);
+    LDPC_ENC(OFDM_LDPC_RATE_5_6);
+  }
+#undef LDPC_ENC
+}
+template <bool SOFT>
+static void ldpc_launch_decode(uint32_t rate, unsigned grid, hipStream_t st, const uint8_t* d_in, const LdpcBlk* blk, const uint32_t* cw,
+                               uint32_t ncw, uint8_t* d_out, LdpcRes* res, const uint32_t* crc, const uint32_t* xp8, uint32_t max_iters) {
+#define LDPC_DEC(R)                                                                                                                         \
+  case R:                                                                                                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT, R>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, blk, cw, ncw, d_out, res, crc, \
+                       xp8, max_iters);                                                                                                     \
+    break
+  switch (rate) {
+    LDPC_DEC(OFDM_LDPC_RATE_1_2);
+    LDPC_DEC(OFDM_LDPC_RATE_2_3);
+    LDPC_DEC(OFDM_LDPC_RATE_3_4);
+    LDPC_DEC(OFDM_LDPC_RATE_5_6);
+  }
+#undef LDPC_DEC
 }
 
 /* payloads in, coded blocks out: what ofdm_tx / ofdm_make_packets then take as payloads */
@@ -24,13 +64,14 @@ extern "C" int ofdm_ldpc_encode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const 
   if (!h) return OFDM_E_INVAL;
   LdpcState& f = h->ldpc;
   if (nblk < 0 || (nblk && (!payloads || !payload_off || !payload_len)) || !coded_off) FAIL(h, OFDM_E_INVAL, "null argument");
-  uint32_t iters;
-  RCCHK(ldpc_iters(h, cfg, &iters));
+  uint32_t iters, rate;
+  RCCHK(ldpc_cfg_check(h, cfg, &iters, &rate));
   f.blk.resize((size_t)nblk);
   f.cw.resize((size_t)nblk * LDPC_MAX_WORDS);
   uint64_t ncw = 0, extent = 0;
-  const uint64_t total = ldpc_plan_encode(payload_off, payload_len, (uint64_t)nblk, f.blk.data(), coded_off, f.cw.data(), &ncw, &extent);
-  if (total == ~0ull) FAIL(h, OFDM_E_INVAL, "ldpc: len(payload) must be in [0, 2012]");
+  const uint64_t total =
+      ldpc_plan_encode_rate(rate, payload_off, payload_len, (uint64_t)nblk, f.blk.data(), coded_off, f.cw.data(), &ncw, &extent);
+  if (total == ~0ull) FAIL(h, OFDM_E_INVAL, "ldpc: len(payload) must be in [0, 2012] (2684, 3020, 3356 at rates 2/3, 3/4, 5/6)");
   f.timed = false;
   if (total > coded_cap) FAIL(h, OFDM_E_CAPACITY, "coded buffer too small (see ofdm_ldpc_coded_len)");
   if (nblk == 0) return OFDM_OK;
@@ -46,8 +87,8 @@ extern "C" int ofdm_ldpc_encode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const 
   const bool timing = h->prof.on;
   RCCHK(codec_time_begin(h, f, st, timing));
   const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);  // every block has a codeword: ncw >= nblk >= 1
-  hipLaunchKernelGGL(k_ldpc_encode, dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw,
-                     d_out, h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>());
+  ldpc_launch_encode(rate, grid, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, h->d_crc.as<uint32_t>(),
+                     h->d_xp8.as<uint32_t>());
   RCCHK(codec_launched(h, f, st, timing));
   RCCHK(codec_read_out(h, st, coded, d_out, total));
   return codec_finish(h, f, st, timing);
@@ -70,12 +111,13 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
   LdpcState& f = h->ldpc;
   if (nblk < 0 || (nblk && (!in || !in_off || !coded_len || !ok || !corrected || !iters || !cw_failed)) || !payload_off)
     FAIL(h, OFDM_E_INVAL, "null argument");
-  uint32_t max_iters;
-  RCCHK(ldpc_iters(h, cfg, &max_iters));
+  uint32_t max_iters, rate;
+  RCCHK(ldpc_cfg_check(h, cfg, &max_iters, &rate));
   f.blk.resize((size_t)nblk);
   f.cw.resize((size_t)nblk * LDPC_MAX_WORDS);
   uint64_t ncw = 0, extent = 0;
-  const uint64_t total = ldpc_plan_decode(in_off, coded_len, (uint64_t)nblk, SOFT ? 8u : 1u, f.blk.data(), payload_off, f.cw.data(), &ncw, &extent);
+  const uint64_t total =
+      ldpc_plan_decode_rate(rate, in_off, coded_len, (uint64_t)nblk, SOFT ? 8u : 1u, f.blk.data(), payload_off, f.cw.data(), &ncw, &extent);
   f.timed = false;
   if (total > payload_cap) FAIL(h, OFDM_E_CAPACITY, "payload buffer too small (see ofdm_ldpc_payload_len)");
   if (nblk == 0) return OFDM_OK;
@@ -97,9 +139,8 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
   const bool timing = h->prof.on;
   RCCHK(codec_time_begin(h, f, st, timing));
   const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, f.d_blk.as<LdpcBlk>(),
-                     f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, f.d_res.as<LdpcRes>(), h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(),
-                     max_iters);
+  ldpc_launch_decode<SOFT>(rate, grid, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, f.d_res.as<LdpcRes>(),
+                           h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(), max_iters);
   RCCHK(codec_launched(h, f, st, timing));
   f.res.resize((size_t)nblk);
   RCCHK(codec_read(h, st, f.res.data(), f.d_res, nblk));
@@ -107,7 +148,7 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
   RCCHK(codec_finish(h, f, st, timing));
   for (int b = 0; b < nblk; b++) {  // a length that is no block had no codeword: its record is still zero
     const LdpcRes& r = f.res[(size_t)b];
-    ok[b] = (ldpc_is_block(coded_len[b]) && r.crc == r.got) ? 1 : 0;
+    ok[b] = (ldpc_is_block_rate(rate, coded_len[b]) && r.crc == r.got) ? 1 : 0;
     corrected[b] = r.corrected;
     iters[b] = (uint8_t)r.iters;
     cw_failed[b] = r.failed;

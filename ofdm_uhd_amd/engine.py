@@ -1165,10 +1165,10 @@ class Engine(object):
         return cfg
 
     def ldpc_encode(self, payloads, ldpc=None):
-        """Host mode: list of payloads (0 .. 2012 bytes each) -> list of coded blocks (ldpc.coded_len(n) bytes each),
-        the payloads tx() then takes.  ``ldpc``: None / True, max_iters, a dict of ldpc.ldpc_cfg's keywords or an
-        ``ofdm_ldpc_cfg`` (the encoder only checks it)."""
-        # n + 4 + 96 ceil((n + 4) / 96) <= 2 n + 104
+        """Host mode: list of payloads (0 .. ldpc.max_payload(rate) bytes each) -> list of coded blocks
+        (ldpc.coded_len(n, rate) bytes each), the payloads tx() then takes.  ``ldpc``: None / True, max_iters, a dict of
+        ldpc.ldpc_cfg's keywords or an ``ofdm_ldpc_cfg`` (the encoder takes its rate and only checks the rest)."""
+        # n + 4 + PB ceil((n + 4) / KI) <= 2 n + 104 at every rate (PB <= KI, PB <= 96)
         return self._codec_encode_host(self._lib.ofdm_ldpc_encode, (C.byref(self._ldpc_cfg(ldpc)),), payloads,
                                        lambda lens: 2 * lens.sum() + 104 * len(lens))
 
@@ -1186,7 +1186,7 @@ class Engine(object):
     def _ldpc_decode_host(self, fn, ldpc, packed):
         assert not self.device_ptrs
         blob, offs, lens = packed
-        out = np.zeros(max(int(lens.astype(np.int64).sum()) // 2, 1), np.uint8)
+        out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)      # a payload is shorter than its block
         return self._codec_results(out, *self._ldpc_decode(fn, ldpc, _ptr(blob), offs, lens, _ptr(out), len(out)))
 
     def ldpc_decode(self, blocks, ldpc=None):
@@ -1221,7 +1221,7 @@ class Engine(object):
         before that rx()."""
         assert not self.device_ptrs
         n, off = self._rx_soft_offsets()
-        out = np.zeros(max(int(off[n]) // 16, 1), np.uint8)
+        out = np.zeros(max(int(off[n]) // 8, 1), np.uint8)                      # 8 values per coded byte
         return self._codec_results(out, *self._rx_ldpc_decode_soft(ldpc, _ptr(out), len(out), n))
 
     def rx_ldpc_decode_soft_device(self, payload_ptr, payload_cap, ldpc=None):

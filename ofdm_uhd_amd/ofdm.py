@@ -55,12 +55,16 @@ class ofdm_mod(object):
         @param rs: outer code: ``True`` wraps every payload in a Reed-Solomon block (rs.py, Engine.rs_encode: payload |
                CRC-32, 32 parity bytes per 223, byte-interleaved) before the inner code, if any, and the modulator:
                flush() encodes outer, then inner, then modulates.  send_pkt then takes up to 3564 bytes, 1780 with
-               ``fec`` or 1752 with ``ldpc`` (the RS block must fit the inner code); the receiving end is
+               ``fec`` or 1752 with ``ldpc`` (2328, 2632, 2904 at its rates 2/3, 3/4, 5/6: the RS block must fit the inner
+               code); the receiving end is
                ofdm_demod(rs=True).  None / False: nothing new runs
         @param ldpc: coded link with the other inner code, in the place of ``fec`` (both: ValueError): ``True``,
-               ``dict(max_iters=20)`` or an int (ldpc.py).  send_pkt then takes up to 2012 bytes and flush() encodes the
-               batch on the GPU (Engine.ldpc_encode: payload | CRC-32 in rate-1/2 QC-LDPC codewords of 96 info and 96
-               parity bytes, ldpc.coded_len(n) bytes); the receiving end is ofdm_demod(ldpc=).  None: nothing new runs
+               ``dict(max_iters=20, rate="1/2")`` or an int (ldpc.py).  send_pkt then takes up to 2012 bytes and flush()
+               encodes the batch on the GPU (Engine.ldpc_encode: payload | CRC-32 in rate-1/2 QC-LDPC codewords of 96 info
+               and 96 parity bytes, ldpc.coded_len(n) bytes; ``rate`` "2/3", "3/4" or "5/6" takes the code of that rate,
+               codewords of 128 / 64, 144 / 48 or 160 / 32 bytes, payloads up to 2684, 3020 or 3356 bytes,
+               ldpc.coded_len(n, rate) bytes); the receiving end is ofdm_demod(ldpc=) with the same setting.  None:
+               nothing new runs
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
@@ -146,20 +150,20 @@ class ofdm_mod(object):
         if self._rs:
             limit = _rs.MAX_PAYLOAD if self._fec is None else _rs.MAX_PAYLOAD_UNDER_FEC
             if self._ldpc is not None:
-                limit = _rs.MAX_PAYLOAD_UNDER_LDPC
+                limit = _rs.max_payload_under(_ldpc.max_payload(self._ldpc))   # the RS block must fit the inner code at its rate
             if len(payload) > limit:
                 raise ValueError("len(payload) must be in [0, %d]" % (limit,))
             block = _rs.coded_len(len(payload))
             # what gets framed: the RS block, or the inner code's block around it
             if self._ldpc is not None:
-                block = _ldpc.coded_len(block)
+                block = _ldpc.coded_len(block, self._ldpc)
             self._engine.framed_len(block if self._fec is None else _fec.coded_len(block, self._fec))
             self._pending.append(payload)
             return
         if self._ldpc is not None:
-            if len(payload) > _ldpc.MAX_PAYLOAD:
-                raise ValueError("len(payload) must be in [0, %d]" % (_ldpc.MAX_PAYLOAD,))
-            self._engine.framed_len(_ldpc.coded_len(len(payload)))   # the coded block is what gets framed
+            if len(payload) > _ldpc.max_payload(self._ldpc):
+                raise ValueError("len(payload) must be in [0, %d]" % (_ldpc.max_payload(self._ldpc),))
+            self._engine.framed_len(_ldpc.coded_len(len(payload), self._ldpc))   # the coded block (at the link's rate) is what gets framed
             self._pending.append(payload)
             return
         if self._fec is not None:
@@ -308,7 +312,8 @@ class ofdm_demod(object):
             returns the same payloads and one reliability per decoded byte, and those go to Engine.rs_decode_rel;
             ``last_fec_rel`` holds them, one uint8 array per packet.  Any other ``source`` is a ValueError.  ``last_rs``
             keeps its three fields, ``last_rs_second`` holds the codewords per packet that the second pass decoded
-        @param ldpc: coded link with the other inner code, as for ofdm_mod, in the place of ``fec`` (both: ValueError):
+        @param ldpc: coded link with the other inner code, as for ofdm_mod and at the same rate (no field on the air names
+            it), in the place of ``fec`` (both: ValueError):
             every delivered packet goes through the min-sum decoder in one batch (Engine.ldpc_decode on the hard bytes;
             with ``soft`` Engine.rx_ldpc_decode_soft on the values, on the GPU).  ``last_fec`` keeps its shape,
             (outer_ok, corrected) per packet; ``last_ldpc`` holds (iters, cw_failed) per packet.  ``rs=True`` works above

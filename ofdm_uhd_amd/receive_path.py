@@ -19,8 +19,8 @@ class receive_path(object):
         (--fec-soft), which turns the coded link on as well.
         ``rs``: outer code of ofdm_demod, ``True`` or ``dict(erasures=True, max_erasures=28)``; None: the options' ``rs``
         (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well.
-        ``ldpc``: the other inner code of ofdm_demod, ``True`` or ``dict(max_iters=20)``; None: the options' ``ldpc``
-        (--ldpc), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well."""
+        ``ldpc``: the other inner code of ofdm_demod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
+        (--ldpc, --ldpc-rate), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well."""
         options = copy.copy(options)    # make a copy so we can destructively modify
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
@@ -29,7 +29,7 @@ class receive_path(object):
             fec = getattr(options, "fec", None) or None
         if soft is None and getattr(options, "ldpc_soft", None):
             soft = True
-            ldpc = True if ldpc is None else ldpc
+            ldpc = (getattr(options, "ldpc", None) or True) if ldpc is None else ldpc   # (a dict where --ldpc-rate set one)
         if ldpc is None:
             ldpc = getattr(options, "ldpc", None) or None
         if rs is None and getattr(options, "rs_erasures", None) is not None:

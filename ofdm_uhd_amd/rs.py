@@ -38,6 +38,19 @@ def coded_len(payload_len):
     return n.value
 
 
+def max_payload_under(limit):
+    """The largest payload whose RS block fits an inner code that takes ``limit`` bytes (1752 under 2012, 2328, 2632 and
+    2904 under the LDPC code's 2684, 3020 and 3356)."""
+    def block(n):
+        return n + 4 + PARITY * ((n + 4 + 222) // 223)
+    n = min(int(limit), MAX_PAYLOAD)
+    while n >= 0 and block(n) > limit:
+        n -= 1
+    if n < 0:
+        raise ValueError("rs: no block fits %d bytes" % limit)
+    return n
+
+
 def payload_len(coded_len):
     """Payload bytes of an RS block of ``coded_len`` bytes, None for a length that is no block (one the block length
     never reaches, under 36, over MAX_CODED)."""

@@ -31,7 +31,8 @@ class transmit_path(object):
         (--tx-resamp-*).
         ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
         ``rs``: outer code of ofdm_mod, ``True``; None: the options' ``rs`` (--rs).
-        ``ldpc``: the other inner code of ofdm_mod, ``True`` or ``dict(max_iters=20)``; None: the options' ``ldpc`` (--ldpc)."""
+        ``ldpc``: the other inner code of ofdm_mod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
+        (--ldpc, --ldpc-rate)."""
         opts = copy.copy(options)
         if rs is None:
             rs = bool(getattr(opts, "rs", None))
