@@ -1476,6 +1476,42 @@ int ofdm_rx_ldpc_decode_soft(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, uint8_t *
                              int max_pkts, int *n);
 int ofdm_ldpc_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- coded links: LDPC, reliabilities out: one byte per payload byte for errors-and-erasures decoding of the outer code ---
+ * ofdm_ldpc_decode_rel / ofdm_ldpc_decode_soft_rel / ofdm_rx_ldpc_decode_soft_rel return exactly what ofdm_ldpc_decode /
+ * ofdm_ldpc_decode_soft / ofdm_rx_ldpc_decode_soft return for the same input (payloads, ok, corrected, iters, cw_failed),
+ * and one reliability byte per decoded payload byte in the format ofdm_rs_decode_rel takes.  Additions only:
+ * OFDM_ABI_VERSION stays 6, the OFDM_K_* table is unchanged, k_ldpc_decode and its launches are unchanged, and without a
+ * call to these three functions nothing new launches, allocates or copies.  All arithmetic is integer: results are
+ * defined bit for bit.
+ *
+ * Definition.  The decoder is the one above, unchanged: same schedule, same normalisation, same stop rule, same
+ * max_iters.  For one codeword of a block:
+ *   P[b]   the value the decoder holds for bit b when the codeword stops (after its last iteration)
+ *   conv   1 if the codeword's syndrome is zero at that point, else 0: the term that otherwise adds to cw_failed
+ *   q[g]   for payload byte g < n of the block, info byte m of its codeword (bits 8m .. 8m + 7):
+ *            q[g] = min(127, min over i = 0 .. 7 of |P[8m + i]|) + 128 * conv
+ * q lies in 0 .. 255; every byte of a codeword that failed ranks below every byte of one that converged; 255 needs a
+ * converged codeword with all eight |P| >= 127 and is ofdm_rs_decode_rel's "never erase".  Nothing is produced for the
+ * block's CRC bytes, the shortened positions or the parity.  Hard input (+-16) uses the same rule.  A length that is no
+ * block gives ok = 0, no payload bytes and no reliability bytes: nothing of it is read or written.
+ *
+ * rel is a host or device pointer by the handle's mode, rel_cap its bytes; block k's n_k bytes lie at
+ * rel + payload_off[k], the offsets of the payload blob.  In device-pointer mode payloads, rel and payload_off are
+ * therefore ofdm_rs_decode_rel's coded, rel and coded_off with rel_off == NULL: the two layers chain without a host
+ * round trip.  Errors as ofdm_ldpc_decode (ofdm_rx_ldpc_decode_soft for the third); in addition a null rel is
+ * OFDM_E_INVAL, and rel_cap < payload_off[nblk] is OFDM_E_CAPACITY with the offsets set first.  After these calls
+ * ofdm_ldpc_last_ms reports k_ldpc_decode_rel. */
+int ofdm_ldpc_decode_rel(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const uint8_t *coded, const uint64_t *coded_off,
+                         const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap, uint64_t *payload_off,
+                         uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed, uint8_t *rel, uint64_t rel_cap);
+int ofdm_ldpc_decode_soft_rel(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, const int8_t *soft, const uint64_t *soft_off,
+                              const uint32_t *coded_len, int nblk, uint8_t *payloads, uint64_t payload_cap,
+                              uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed,
+                              uint8_t *rel, uint64_t rel_cap);
+int ofdm_rx_ldpc_decode_soft_rel(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, uint8_t *payloads, uint64_t payload_cap,
+                                 uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed,
+                                 uint8_t *rel, uint64_t rel_cap, int max_pkts, int *n);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

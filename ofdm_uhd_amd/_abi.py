@@ -364,6 +364,7 @@ EXPORTS = (
     "ofdm_rs_decode_rel", "ofdm_rs_rel_from_soft", "ofdm_rs_rel_last_ms",
     "ofdm_ldpc_coded_len", "ofdm_ldpc_payload_len", "ofdm_ldpc_encode", "ofdm_ldpc_decode", "ofdm_ldpc_decode_soft",
     "ofdm_rx_ldpc_decode_soft", "ofdm_ldpc_last_ms", "ofdm_ldpc_coded_len_rate", "ofdm_ldpc_payload_len_rate",
+    "ofdm_ldpc_decode_rel", "ofdm_ldpc_decode_soft_rel", "ofdm_rx_ldpc_decode_soft_rel",
 )
 
 _LIB = None
@@ -490,6 +491,10 @@ def _declare(lib):
     lib.ofdm_ldpc_decode_soft.argtypes = lib.ofdm_ldpc_decode.argtypes
     lib.ofdm_rx_ldpc_decode_soft.argtypes = [H, LC, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p, C.c_int, C.POINTER(C.c_int)]
     lib.ofdm_ldpc_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_ldpc_decode_rel.argtypes = lib.ofdm_ldpc_decode.argtypes + [u8p, C.c_uint64]
+    lib.ofdm_ldpc_decode_soft_rel.argtypes = lib.ofdm_ldpc_decode_rel.argtypes
+    lib.ofdm_rx_ldpc_decode_soft_rel.argtypes = [H, LC, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p, u8p, C.c_uint64, C.c_int,
+                                                 C.POINTER(C.c_int)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

@@ -105,7 +105,9 @@ def make_parser():
     parser.add_option("", "--rs-erasures", action="callback", callback=_rs_erasures, dest="rs_erasures", default=None,
                       help="--rs, decoding with reliabilities: --rs-erasures [M] erases the weakest symbols, at most M "
                            "(0 .. 32, 28 if not given), of every codeword that fails, chosen by the soft demapper's "
-                           "values; for an RS link without an inner code (not with --fec, --fec-rate or --fec-soft) "
+                           "values; for an RS link without an inner code (not with --fec, --fec-rate or --fec-soft); "
+                           "with --ldpc, --ldpc-rate or --ldpc-soft the symbols are chosen by the min-sum decoder's own "
+                           "byte reliabilities "
                            "[default=off]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
@@ -198,11 +200,9 @@ def main(argv=None):
         options.ldpc = dict(rate=options.ldpc_rate)   # (what receive_path hands to ofdm_demod(ldpc=))
     if options.ldpc and options.fec:
         parser.error("--ldpc / --ldpc-soft take the place of --fec / --fec-rate / --fec-soft: a link has one inner code")
-    if options.ldpc and options.rs_erasures is not None:
-        parser.error("--rs-erasures does not combine with --ldpc / --ldpc-soft: that decoder produces no byte reliabilities")
     if options.rs_erasures is not None:
         if options.fec:
-            parser.error("--rs-erasures needs an RS link without an inner code: not with --fec, --fec-rate or --fec-soft")
+            parser.error("--rs-erasures needs an RS link without an inner code, or --ldpc: not with --fec, --fec-rate or --fec-soft")
         options.rs = True
     if (options.fec or options.rs or options.ldpc) and (options.resamp_freqs is not None or options.ddc_freqs is not None):
         parser.error("--fec, --ldpc and --rs do not combine with --ddc-freqs or --resamp-freqs")

@@ -1,6 +1,7 @@
 // engine_ldpc.inc -- host side of the LDPC coded-link layer (ldpc.h): lengths, the codeword map of a batch, launches,
-// over the steps of engine_codec.inc.  Included by engine.hip after engine_rs.inc.  The arithmetic that needs no GPU is
-// ldpc_plan.h.
+// over the steps of engine_codec.inc.  The three *_rel calls are the decode calls with k_ldpc_decode_rel in
+// k_ldpc_decode's place and one reliability byte per payload byte next to the payloads, at the payloads' offsets.
+// Included by engine.hip after engine_rs.inc.  The arithmetic that needs no GPU is ldpc_plan.h.
 
 extern "C" int ofdm_ldpc_coded_len(uint32_t payload_len, uint32_t* coded_len) { return ldpc_coded_len(payload_len, coded_len); }
 extern "C" int ofdm_ldpc_payload_len(uint32_t coded_len, uint32_t* payload_len) { return ldpc_payload_len(coded_len, payload_len); }
@@ -41,13 +42,19 @@ static void ldpc_launch_encode(uint32_t rate, unsigned grid, hipStream_t st, con
   }
 #undef LDPC_ENC
 }
-template <bool SOFT>
+// k_ldpc_decode, or with REL k_ldpc_decode_rel and the reliabilities to d_rel
+template <bool SOFT, bool REL>
 static void ldpc_launch_decode(uint32_t rate, unsigned grid, hipStream_t st, const uint8_t* d_in, const LdpcBlk* blk, const uint32_t* cw,
-                               uint32_t ncw, uint8_t* d_out, LdpcRes* res, const uint32_t* crc, const uint32_t* xp8, uint32_t max_iters) {
-#define LDPC_DEC(R)                                                                                                                         \
-  case R:                                                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT, R>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, blk, cw, ncw, d_out, res, crc, \
-                       xp8, max_iters);                                                                                                     \
+                               uint32_t ncw, uint8_t* d_out, uint8_t* d_rel, LdpcRes* res, const uint32_t* crc, const uint32_t* xp8,
+                               uint32_t max_iters) {
+#define LDPC_DEC(R)                                                                                                                      \
+  case R:                                                                                                                                \
+    if constexpr (REL)                                                                                                                   \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode_rel<SOFT, R>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, blk, cw, ncw, d_out,  \
+                         d_rel, res, crc, xp8, max_iters);                                                                               \
+    else                                                                                                                                 \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ldpc_decode<SOFT, R>), dim3(grid), dim3(LDPC_THREADS), 0, st, d_in, blk, cw, ncw, d_out, res, \
+                         crc, xp8, max_iters);                                                                                           \
     break
   switch (rate) {
     LDPC_DEC(OFDM_LDPC_RATE_1_2);
@@ -101,15 +108,16 @@ static void ldpc_no_blocks(int nblk, uint8_t* ok, uint32_t* corrected, uint8_t* 
   memset(cw_failed, 0, sizeof(uint32_t) * (size_t)nblk);
 }
 
-// in_on_device: the input blob is device memory whatever the handle's pointer mode (the handle's own soft values:
-// ofdm_rx_ldpc_decode_soft)
-template <bool SOFT>
+// REL: k_ldpc_decode_rel in k_ldpc_decode's place, one reliability byte per payload byte to `rel` at the payloads' offsets
+// (NULL, 0 without).  in_on_device: the input blob is device memory whatever the handle's pointer mode (the handle's own
+// soft values: ofdm_rx_ldpc_decode_soft)
+template <bool SOFT, bool REL>
 static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* in, const uint64_t* in_off, const uint32_t* coded_len,
                             int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off, uint8_t* ok, uint32_t* corrected,
-                            uint8_t* iters, uint32_t* cw_failed, bool in_on_device = false) {
+                            uint8_t* iters, uint32_t* cw_failed, uint8_t* rel, uint64_t rel_cap, bool in_on_device = false) {
   if (!h) return OFDM_E_INVAL;
   LdpcState& f = h->ldpc;
-  if (nblk < 0 || (nblk && (!in || !in_off || !coded_len || !ok || !corrected || !iters || !cw_failed)) || !payload_off)
+  if (nblk < 0 || (nblk && (!in || !in_off || !coded_len || !ok || !corrected || !iters || !cw_failed)) || !payload_off || (REL && !rel))
     FAIL(h, OFDM_E_INVAL, "null argument");
   uint32_t max_iters, rate;
   RCCHK(ldpc_cfg_check(h, cfg, &max_iters, &rate));
@@ -120,6 +128,7 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
       ldpc_plan_decode_rate(rate, in_off, coded_len, (uint64_t)nblk, SOFT ? 8u : 1u, f.blk.data(), payload_off, f.cw.data(), &ncw, &extent);
   f.timed = false;
   if (total > payload_cap) FAIL(h, OFDM_E_CAPACITY, "payload buffer too small (see ofdm_ldpc_payload_len)");
+  if (REL && total > rel_cap) FAIL(h, OFDM_E_CAPACITY, "reliability buffer too small (one byte per payload byte)");
   if (nblk == 0) return OFDM_OK;
   if (total && !payloads) FAIL(h, OFDM_E_INVAL, "null argument");
   if (ncw == 0) {  // not one block among them: nothing to launch
@@ -129,22 +138,24 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
   hipStream_t st;
   RCCHK(codec_begin_decode(h, &st));
   const uint8_t* d_in;
-  uint8_t* d_out;
+  uint8_t *d_out, *d_rel = nullptr;
   RCCHK(codec_upload(h, st, f.d_blk, f.blk, (size_t)nblk));
   RCCHK(codec_upload(h, st, f.d_cw, f.cw, (size_t)ncw));
   HIPCHK(h, f.d_res.ensure(sizeof(LdpcRes) * (size_t)nblk));
   HIPCHK(h, hipMemsetAsync(f.d_res.p, 0, sizeof(LdpcRes) * (size_t)nblk, st));
   RCCHK(codec_stage_in(h, st, f.d_in, in, extent, in_on_device, &d_in));
   RCCHK(codec_stage_out(h, f.d_out, payloads, total, &d_out));
+  if (REL) RCCHK(codec_stage_out(h, f.d_rel, rel, total, &d_rel));
   const bool timing = h->prof.on;
   RCCHK(codec_time_begin(h, f, st, timing));
   const unsigned grid = (unsigned)((ncw + LDPC_WAVES - 1) / LDPC_WAVES);
-  ldpc_launch_decode<SOFT>(rate, grid, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, f.d_res.as<LdpcRes>(),
-                           h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(), max_iters);
+  ldpc_launch_decode<SOFT, REL>(rate, grid, st, d_in, f.d_blk.as<LdpcBlk>(), f.d_cw.as<uint32_t>(), (uint32_t)ncw, d_out, d_rel,
+                                f.d_res.as<LdpcRes>(), h->d_crc.as<uint32_t>(), h->d_xp8.as<uint32_t>(), max_iters);
   RCCHK(codec_launched(h, f, st, timing));
   f.res.resize((size_t)nblk);
   RCCHK(codec_read(h, st, f.res.data(), f.d_res, nblk));
   RCCHK(codec_read_out(h, st, payloads, d_out, total));
+  if (REL) RCCHK(codec_read_out(h, st, rel, d_rel, total));
   RCCHK(codec_finish(h, f, st, timing));
   for (int b = 0; b < nblk; b++) {  // a length that is no block had no codeword: its record is still zero
     const LdpcRes& r = f.res[(size_t)b];
@@ -160,16 +171,16 @@ static int ldpc_decode_impl(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint
 extern "C" int ofdm_ldpc_decode(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* coded, const uint64_t* coded_off,
                                 const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off,
                                 uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
-  return ldpc_decode_impl<false>(h, cfg, coded, coded_off, coded_len, nblk, payloads, payload_cap, payload_off, ok, corrected, iters,
-                                 cw_failed);
+  return ldpc_decode_impl<false, false>(h, cfg, coded, coded_off, coded_len, nblk, payloads, payload_cap, payload_off, ok, corrected,
+                                        iters, cw_failed, nullptr, 0);
 }
 
 /* the same from int8 values, 8 per coded byte */
 extern "C" int ofdm_ldpc_decode_soft(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const int8_t* soft, const uint64_t* soft_off,
                                      const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap,
                                      uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed) {
-  return ldpc_decode_impl<true>(h, cfg, reinterpret_cast<const uint8_t*>(soft), soft_off, coded_len, nblk, payloads, payload_cap,
-                                payload_off, ok, corrected, iters, cw_failed);
+  return ldpc_decode_impl<true, false>(h, cfg, reinterpret_cast<const uint8_t*>(soft), soft_off, coded_len, nblk, payloads, payload_cap,
+                                       payload_off, ok, corrected, iters, cw_failed, nullptr, 0);
 }
 
 /* the last ofdm_rx call's packets, decoded from the handle's own soft values */
@@ -179,6 +190,34 @@ extern "C" int ofdm_rx_ldpc_decode_soft(ofdm_handle* h, const ofdm_ldpc_cfg* cfg
   if (!h) return OFDM_E_INVAL;
   RCCHK(codec_rx_soft_batch(h, max_pkts, n, "ok / corrected / iters / cw_failed / payload_off arrays too small"));
   const RxState& rx = h->rx;
-  return ldpc_decode_impl<true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), *n, payloads, payload_cap,
-                                payload_off, ok, corrected, iters, cw_failed, true);
+  return ldpc_decode_impl<true, false>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), *n, payloads,
+                                       payload_cap, payload_off, ok, corrected, iters, cw_failed, nullptr, 0, true);
+}
+
+/* ofdm_ldpc_decode with one reliability byte per payload byte */
+extern "C" int ofdm_ldpc_decode_rel(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const uint8_t* coded, const uint64_t* coded_off,
+                                    const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap, uint64_t* payload_off,
+                                    uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed, uint8_t* rel, uint64_t rel_cap) {
+  return ldpc_decode_impl<false, true>(h, cfg, coded, coded_off, coded_len, nblk, payloads, payload_cap, payload_off, ok, corrected,
+                                       iters, cw_failed, rel, rel_cap);
+}
+
+/* ofdm_ldpc_decode_soft with one reliability byte per payload byte */
+extern "C" int ofdm_ldpc_decode_soft_rel(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, const int8_t* soft, const uint64_t* soft_off,
+                                         const uint32_t* coded_len, int nblk, uint8_t* payloads, uint64_t payload_cap,
+                                         uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed,
+                                         uint8_t* rel, uint64_t rel_cap) {
+  return ldpc_decode_impl<true, true>(h, cfg, reinterpret_cast<const uint8_t*>(soft), soft_off, coded_len, nblk, payloads, payload_cap,
+                                      payload_off, ok, corrected, iters, cw_failed, rel, rel_cap);
+}
+
+/* ofdm_rx_ldpc_decode_soft with one reliability byte per payload byte */
+extern "C" int ofdm_rx_ldpc_decode_soft_rel(ofdm_handle* h, const ofdm_ldpc_cfg* cfg, uint8_t* payloads, uint64_t payload_cap,
+                                            uint64_t* payload_off, uint8_t* ok, uint32_t* corrected, uint8_t* iters, uint32_t* cw_failed,
+                                            uint8_t* rel, uint64_t rel_cap, int max_pkts, int* n) {
+  if (!h) return OFDM_E_INVAL;
+  RCCHK(codec_rx_soft_batch(h, max_pkts, n, "ok / corrected / iters / cw_failed / payload_off arrays too small"));
+  const RxState& rx = h->rx;
+  return ldpc_decode_impl<true, true>(h, cfg, rx.soft_vals.as<uint8_t>(), rx.soft_off.data(), rx.soft_len.data(), *n, payloads,
+                                      payload_cap, payload_off, ok, corrected, iters, cw_failed, rel, rel_cap, true);
 }

@@ -26,13 +26,14 @@
 
 // host side (engine_ldpc.inc): CodecStage (host_util.h) and the code's own
 struct LdpcState : CodecStage {
-  DevBuf d_cw, d_res;
+  DevBuf d_cw, d_res, d_rel;  // d_rel: host mode of the _rel calls only
   std::vector<LdpcBlk> blk;
   std::vector<uint32_t> cw;  // codeword -> block
   std::vector<LdpcRes> res;
   void release() {
     d_cw.release();
     d_res.release();
+    d_rel.release();
     CodecStage::release();
   }
 };
@@ -175,6 +176,8 @@ __global__ void __launch_bounds__(LDPC_THREADS) k_ldpc_encode(const uint8_t* __r
 //            take 64: magnitudes and a 5-bit position in the low half, the signs in the high half.
 //   stop     24 ballots of P > 0 make the hard decisions wave-uniform 64-bit columns; the syndrome is one scalar
 //            rotate-XOR per entry (83 at rate 1/2) and the exit branch is uniform.
+//   rel      (k_ldpc_decode_rel) in the epilogue the lane that forms info byte m from the eight int16 at P + 8 m also
+//            takes the smallest of their magnitudes: the byte's reliability is min(127, that) + 128 where syn == 0.
 // The rows of one iteration run in order 0 .. mb - 1; a row's entries lie in distinct columns, so its reads and writes of P
 // never meet inside the row, and ldpc_wave_sync() stands between rows.
 // ---------------------------------------------------------------------------------
@@ -274,88 +277,25 @@ __device__ __forceinline__ uint64_t ldpc_syndrome(const uint64_t (&X)[LDPC_COLS]
 
 typedef int ldpc_i32x4 __attribute__((ext_vector_type(4), may_alias));
 
+// The decoder's two entry points over one body (ldpc_decode_body.inc): k_ldpc_decode, and k_ldpc_decode_rel with one
+// reliability byte per payload byte (include/ofdm_hip.h, "coded links: LDPC, reliabilities out").
 template <bool SOFT, uint32_t RATE>
 __global__ void __launch_bounds__(LDPC_THREADS) k_ldpc_decode(const uint8_t* __restrict__ in_all, const LdpcBlk* __restrict__ blk,
                                                               const uint32_t* __restrict__ cw_blk, uint32_t ncw, uint8_t* __restrict__ payloads,
                                                               LdpcRes* __restrict__ res, const uint32_t* __restrict__ crc_table,
                                                               const uint32_t* __restrict__ xp8, uint32_t max_iters) {
-  constexpr int MB = LDPC_TABLE_R<RATE>.mb;
-  constexpr uint32_t KI = ldpc_rate_info(RATE);
-  __shared__ __attribute__((aligned(16))) int16_t s_P[LDPC_WAVES][LDPC_N];
-  LdpcCw c;
-  if (!ldpc_my_codeword(blk, cw_blk, ncw, c)) return;
-  const int lane = lane_id();
-  const uint32_t k = ldpc_block_info_of<RATE>(c.b.len), n = k - 4u;  // (only blocks have codewords)
-  const uint32_t g0 = KI * c.w, kw = ldpc_cw_info_of<RATE>(k, c.w);
-  const uint8_t* in = in_all + c.b.in_off + (uint64_t)(SOFT ? 8u : 1u) * LDPC_CW_SENT * c.w;
-  int16_t* P = s_P[wave_id()];
+#define LDPC_DECODE_REL 0
+#include "ldpc_decode_body.inc"
+#undef LDPC_DECODE_REL
+}
 
-#pragma unroll
-  for (int j = 0; j < LDPC_COLS; j++) {
-    bool sent;
-    P[LDPC_Z * j + lane] = (int16_t)ldpc_value<SOFT, RATE>(in, kw, (uint32_t)(LDPC_Z * j + lane), sent);
-  }
-  ldpc_wave_sync();
-
-  typename LdpcRw<RATE>::type rw[MB];
-#pragma unroll
-  for (int i = 0; i < MB; i++) rw[i] = 0;  // R = 0
-  uint32_t it = 0;
-  uint64_t syn;
-#pragma unroll 1
-  do {
-    it++;
-    ldpc_iteration<RATE>(P, rw, lane, std::make_integer_sequence<int, MB>{});
-    uint64_t X[LDPC_COLS];
-#pragma unroll
-    for (int j = 0; j < LDPC_COLS; j++) X[j] = __ballot(P[LDPC_Z * j + lane] > 0);
-    syn = ldpc_syndrome<RATE>(X, std::make_integer_sequence<int, MB>{});
-  } while (syn != 0ull && it < max_iters);
-
-  // ---- the codeword's info bytes: payload out, its share of the block's CRC, the received CRC bytes ---------------
-  uint8_t* out = payloads + c.b.out_off;
-  uint32_t acc = 0, got = 0;
-#pragma unroll
-  for (uint32_t m = (uint32_t)lane; m < KI; m += WAVE) {
-    if (m >= kw) continue;
-    const ldpc_i32x4 pk = *reinterpret_cast<const ldpc_i32x4*>(P + 8u * m);  // eight int16
-    const uint32_t wd[4] = {(uint32_t)pk.x, (uint32_t)pk.y, (uint32_t)pk.z, (uint32_t)pk.w};
-    uint32_t by = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      by = (by << 1) | ((int16_t)(wd[q] & 0xFFFFu) > 0 ? 1u : 0u);
-      by = (by << 1) | ((int16_t)(wd[q] >> 16) > 0 ? 1u : 0u);
-    }
-    const uint32_t g = g0 + m;
-    if (g < n) {
-      out[g] = (uint8_t)by;
-      // CRC-32 of the one byte, moved to its place: crc(A || B) = crc(A) x^(8 |B|) + crc(B)
-      acc ^= crc_multmodp(xp8[n - (g + 1u)], crc_table[by ^ 0xFFu] ^ 0xFF000000u);
-    } else {
-      got |= by << (8u * (3u - (g - n)));
-    }
-  }
-  // ---- corrected: sent positions that are no erasure and whose sign disagrees with the decision -------------------
-  uint32_t bad = 0;
-#pragma unroll
-  for (int j = 0; j < LDPC_COLS; j++) {
-    bool sent;
-    const int v = ldpc_value<SOFT, RATE>(in, kw, (uint32_t)(LDPC_Z * j + lane), sent);
-    const bool x = P[LDPC_Z * j + lane] > 0;
-    bad += (sent && v != 0 && (v > 0) != x) ? 1u : 0u;
-  }
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) {
-    acc ^= __shfl_xor(acc, d, WAVE);
-    got |= __shfl_xor(got, d, WAVE);
-  }
-  bad = wave_sum(bad);
-  if (lane == 0) {  // the block's record starts at zero (the host clears it); its codewords meet in it
-    LdpcRes* r = res + c.bi;
-    atomicXor(&r->crc, acc);
-    atomicOr(&r->got, got);
-    atomicAdd(&r->corrected, bad);
-    atomicMax(&r->iters, it);
-    atomicAdd(&r->failed, syn != 0ull ? 1u : 0u);
-  }
+template <bool SOFT, uint32_t RATE>
+__global__ void __launch_bounds__(LDPC_THREADS) k_ldpc_decode_rel(const uint8_t* __restrict__ in_all, const LdpcBlk* __restrict__ blk,
+                                                                  const uint32_t* __restrict__ cw_blk, uint32_t ncw,
+                                                                  uint8_t* __restrict__ payloads, uint8_t* __restrict__ rel,
+                                                                  LdpcRes* __restrict__ res, const uint32_t* __restrict__ crc_table,
+                                                                  const uint32_t* __restrict__ xp8, uint32_t max_iters) {
+#define LDPC_DECODE_REL 1
+#include "ldpc_decode_body.inc"
+#undef LDPC_DECODE_REL
 }

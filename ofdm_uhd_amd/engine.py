@@ -1232,8 +1232,65 @@ class Engine(object):
         return self._rx_ldpc_decode_soft(ldpc, C.c_void_p(payload_ptr), payload_cap, n)
 
     def ldpc_last_ms(self):
-        """HIP-event time of k_ldpc_encode / k_ldpc_decode in the last ldpc call (needs prof_enable())."""
+        """HIP-event time of k_ldpc_encode / k_ldpc_decode (k_ldpc_decode_rel after a ``*_rel`` call) in the last ldpc
+        call (needs prof_enable())."""
         return self._stage_last_ms("ldpc")
+
+    # -- LDPC coded links, reliabilities out (one byte per payload byte from the min-sum decoder's final values) --------
+    @staticmethod
+    def _ldpc_rel_results(out, rel, poff, ok, *cols):
+        return [r + (rel[int(poff[i]):int(poff[i + 1])].copy(),) for i, r in enumerate(Engine._codec_results(out, poff, ok, *cols))]
+
+    def _ldpc_decode_rel_host(self, fn, ldpc, packed):
+        assert not self.device_ptrs
+        blob, offs, lens = packed
+        out = np.zeros(max(int(lens.astype(np.int64).sum()), 1), np.uint8)      # a payload is shorter than its block
+        rel = np.zeros(len(out), np.uint8)
+        head = (C.byref(self._ldpc_cfg(ldpc)),) + self._batch(_ptr(blob), offs, lens)
+        return self._ldpc_rel_results(out, rel, *self._codec_decode(fn, head, len(lens), _ptr(out), len(out), extra=self._LDPC_EXTRA,
+                                                                    tail=(_ptr(rel), len(rel))))
+
+    def ldpc_decode_rel(self, blocks, ldpc=None):
+        """Host mode: ldpc_decode() with reliabilities -> list of (ok, payload, corrected, iters, cw_failed, rel):
+        ldpc_decode()'s five fields, and ``rel`` a uint8 array of len(payload): min(127, the smallest final |P| of the
+        byte's eight bits), plus 128 where the byte's codeword met all checks; 255 is "never erase" -- what
+        rs_decode_rel() takes.  A length that is no block gives (False, b"", 0, 0, 0, [])."""
+        return self._ldpc_decode_rel_host(self._lib.ofdm_ldpc_decode_rel, ldpc, pack_payloads(blocks))
+
+    def ldpc_decode_soft_rel(self, values, ldpc=None):
+        """Host mode: ldpc_decode_soft() with reliabilities -> list of (ok, payload, corrected, iters, cw_failed, rel) as
+        ldpc_decode_rel."""
+        return self._ldpc_decode_rel_host(self._lib.ofdm_ldpc_decode_soft_rel, ldpc, _pack_values(values))
+
+    def ldpc_decode_rel_device(self, in_ptr, offs, lens, payload_ptr, payload_cap, rel_ptr, rel_cap, ldpc=None, soft=False):
+        """Device mode: ldpc_decode_device() with the reliabilities written to the device buffer ``rel_ptr`` at the
+        payloads' offsets: (payload_ptr, rel_ptr, the returned offsets) are what rs_decode_rel_device() takes as blocks,
+        reliabilities and offsets, with ``rel_offs=None``.  Returns the host arrays of ldpc_decode_device."""
+        assert self.device_ptrs
+        fn = self._lib.ofdm_ldpc_decode_soft_rel if soft else self._lib.ofdm_ldpc_decode_rel
+        head = (C.byref(self._ldpc_cfg(ldpc)),) + self._batch(C.c_void_p(in_ptr), offs, lens)
+        return self._codec_decode(fn, head, len(lens), C.c_void_p(payload_ptr), payload_cap, extra=self._LDPC_EXTRA,
+                                  tail=(C.c_void_p(rel_ptr), int(rel_cap)))
+
+    def _rx_ldpc_decode_soft_rel(self, ldpc, out_ptr, out_cap, rel_ptr, rel_cap, n):
+        return self._codec_decode(self._lib.ofdm_rx_ldpc_decode_soft_rel, (C.byref(self._ldpc_cfg(ldpc)),), n, out_ptr, out_cap,
+                                  extra=self._LDPC_EXTRA, tail=(rel_ptr, int(rel_cap)) + self._rx_batch(n))
+
+    def rx_ldpc_decode_soft_rel(self, ldpc=None):
+        """Host mode: rx_ldpc_decode_soft() with reliabilities -> list of (ok, payload, corrected, iters, cw_failed, rel)
+        as ldpc_decode_rel."""
+        assert not self.device_ptrs
+        n, off = self._rx_soft_offsets()
+        out = np.zeros(max(int(off[n]) // 8, 1), np.uint8)                      # 8 values per coded byte
+        rel = np.zeros(len(out), np.uint8)
+        return self._ldpc_rel_results(out, rel, *self._rx_ldpc_decode_soft_rel(ldpc, _ptr(out), len(out), _ptr(rel), len(rel), n))
+
+    def rx_ldpc_decode_soft_rel_device(self, payload_ptr, payload_cap, rel_ptr, rel_cap, ldpc=None):
+        """Device mode: the same into the device buffers ``payload_ptr`` and ``rel_ptr``; returns the host arrays of
+        ldpc_decode_device."""
+        assert self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._rx_ldpc_decode_soft_rel(ldpc, C.c_void_p(payload_ptr), payload_cap, C.c_void_p(rel_ptr), rel_cap, n)
 
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""

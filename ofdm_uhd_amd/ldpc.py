@@ -5,6 +5,11 @@ matrix, 1536-bit codewords at every rate) decoded by a layered normalised min-su
 codeword (include/ofdm_hip.h, "coded links: LDPC").  The work is ``Engine.ldpc_encode`` /
 ``Engine.ldpc_decode`` / ``Engine.ldpc_decode_soft``; ``ofdm_mod(ldpc=...)`` and ``ofdm_demod(ldpc=...)`` put it on a
 link in the place of ``fec=``, both ends at the same rate.
+
+Reliabilities out (``Engine.ldpc_decode_rel`` / ``ldpc_decode_soft_rel`` / ``rx_ldpc_decode_soft_rel``,
+``ofdm_demod(ldpc=..., rs=dict(erasures=True, source="ldpc"))``): the same decoder also returns one byte per payload byte
+for ``Engine.rs_decode_rel`` -- min(127, the smallest final |P| of the byte's eight bits), plus 128 where the byte's
+codeword met all checks (include/ofdm_hip.h, "coded links: LDPC, reliabilities out").
 """
 import ctypes as C
 

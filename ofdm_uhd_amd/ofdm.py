@@ -310,15 +310,21 @@ class ofdm_demod(object):
             it needs ``fec``, with or without ``soft``; the inner decoder is then the soft-output one
             (Engine.rx_fec_decode_soft_rel with ``soft``, Engine.fec_decode_rel on the hard bytes without), which
             returns the same payloads and one reliability per decoded byte, and those go to Engine.rs_decode_rel;
-            ``last_fec_rel`` holds them, one uint8 array per packet.  Any other ``source`` is a ValueError.  ``last_rs``
+            ``last_fec_rel`` holds them, one uint8 array per packet.  ``source="ldpc"`` is the same above ``ldpc`` (below); any other ``source`` is a
+            ValueError.  ``last_rs``
             keeps its three fields, ``last_rs_second`` holds the codewords per packet that the second pass decoded
         @param ldpc: coded link with the other inner code, as for ofdm_mod and at the same rate (no field on the air names
             it), in the place of ``fec`` (both: ValueError):
             every delivered packet goes through the min-sum decoder in one batch (Engine.ldpc_decode on the hard bytes;
             with ``soft`` Engine.rx_ldpc_decode_soft on the values, on the GPU).  ``last_fec`` keeps its shape,
             (outer_ok, corrected) per packet; ``last_ldpc`` holds (iters, cw_failed) per packet.  ``rs=True`` works above
-            it as above ``fec``; ``rs=dict(erasures=True, ...)`` with ``ldpc`` is a ValueError: this decoder produces no
-            byte reliabilities yet
+            it as above ``fec``.  ``rs=dict(erasures=True, source="ldpc", max_erasures=28)`` is the concatenated link with
+            reliabilities: it needs ``ldpc`` and no ``fec``; the decoder is then k_ldpc_decode_rel
+            (Engine.rx_ldpc_decode_soft_rel with ``soft``, Engine.ldpc_decode_rel on the hard bytes without), which returns
+            the same payloads and one reliability per decoded byte (min(127, the byte's smallest final |P|), plus 128
+            where its codeword met all checks), and those go to Engine.rs_decode_rel as they are; ``last_ldpc_rel``
+            holds them, one uint8 array per packet.  ``rs=dict(erasures=True, ...)`` with ``ldpc`` and any other
+            ``source``, or none, is a ValueError
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
@@ -333,7 +339,7 @@ class ofdm_demod(object):
         self._ldpc = _ldpc.as_cfg(ldpc)
         if self._fec is not None and self._ldpc is not None:
             raise ValueError("fec= and ldpc= are two inner codes: a link has one of them")
-        if self._ldpc is not None and isinstance(rs, dict) and rs.get("erasures"):
+        if self._ldpc is not None and isinstance(rs, dict) and rs.get("erasures") and rs.get("source") != "ldpc":
             raise ValueError("rs=dict(erasures=True) does not combine with ldpc=: this decoder produces no byte "
                              "reliabilities yet")
         self.last_fec = []           # (outer_ok, corrected) of the packets the last work() / feed() returned (fec / ldpc)
@@ -346,6 +352,8 @@ class ofdm_demod(object):
         self.last_rs_second = []     # codewords per packet the second pass decoded (rs=dict(erasures=True) only)
         self._rs_rel_fec = False     # the reliabilities are the inner decoder's (source="fec"), not the soft demapper's
         self.last_fec_rel = []       # uint8 reliabilities per decoded byte of the packets (source="fec" only)
+        self._rs_rel_ldpc = False    # the reliabilities are the min-sum decoder's (source="ldpc")
+        self.last_ldpc_rel = []      # uint8 reliabilities per decoded byte of the packets (source="ldpc" only)
         if isinstance(rs, dict):
             opts = dict(rs)
             erasures = bool(opts.pop("erasures", False))
@@ -357,6 +365,13 @@ class ofdm_demod(object):
                     if self._soft is None or self._fec is not None:
                         raise ValueError("rs=dict(erasures=True) needs soft= and no fec=: the reliabilities are the soft "
                                          "demapper's; behind the inner decoder ask for its own with source=\"fec\"")
+                elif source == "ldpc":
+                    if self._fec is not None:
+                        raise ValueError("rs=dict(erasures=True, source=\"ldpc\") does not combine with fec=: that decoder's "
+                                         "reliabilities are source=\"fec\"")
+                    if self._ldpc is None:
+                        raise ValueError("rs=dict(erasures=True, source=\"ldpc\") needs ldpc=: the reliabilities are the "
+                                         "min-sum decoder's")
                 elif source != "fec":
                     raise ValueError("rs: source must be \"fec\" (the inner decoder's reliabilities) or left out "
                                      "(the soft demapper's)")
@@ -364,6 +379,7 @@ class ofdm_demod(object):
                     raise ValueError("rs=dict(erasures=True, source=\"fec\") needs fec=: the reliabilities are the "
                                      "inner decoder's")
                 self._rs_rel_fec = source == "fec"
+                self._rs_rel_ldpc = source == "ldpc"
                 self._rs_rel = _rs.rs_cfg(**opts)
             self._rs = True
 
@@ -471,6 +487,8 @@ class ofdm_demod(object):
             # (last_soft holds the delivered packets' values, in their order)
             if self._rs_rel_fec:
                 rel = self.last_fec_rel
+            elif self._rs_rel_ldpc:
+                rel = self.last_ldpc_rel
             else:
                 rel = self._engine.rs_rel_from_soft(self.last_soft) if pkts else []
             dec = self._engine.rs_decode_rel([p for _, p in pkts], rel, self._rs_rel) if pkts else []
@@ -504,12 +522,15 @@ class ofdm_demod(object):
         return [(ok, p) for ok, p, _ in dec]
 
     def _decode_ldpc(self, pkts, sel=None):
+        eng = self._engine
         if self._soft is not None:
-            dec = self._engine.rx_ldpc_decode_soft(self._ldpc) if pkts else []
+            dec = (eng.rx_ldpc_decode_soft_rel if self._rs_rel_ldpc else eng.rx_ldpc_decode_soft)(self._ldpc) if pkts else []
             if sel is not None:
                 dec = [dec[i] for i in sel]
         else:
-            dec = self._engine.ldpc_decode([p for _, p in pkts], self._ldpc) if pkts else []
+            dec = (eng.ldpc_decode_rel if self._rs_rel_ldpc else eng.ldpc_decode)([p for _, p in pkts], self._ldpc) if pkts else []
+        if self._rs_rel_ldpc:
+            self.last_ldpc_rel = [d[5] for d in dec]
         self.last_fec = [(bool(ok), d[2]) for (ok, _), d in zip(pkts, dec)]
         self.last_ldpc = [(d[3], d[4]) for d in dec]
         return [(d[0], d[1]) for d in dec]

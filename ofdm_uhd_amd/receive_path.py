@@ -18,7 +18,8 @@ class receive_path(object):
         ``soft``: soft-decision receive of ofdm_demod, ``True`` or ``dict(scale=32)``; None: the options' ``fec_soft``
         (--fec-soft), which turns the coded link on as well.
         ``rs``: outer code of ofdm_demod, ``True`` or ``dict(erasures=True, max_erasures=28)``; None: the options' ``rs``
-        (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well.
+        (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well; on an ``ldpc`` link
+        it selects ``source="ldpc"`` instead and leaves ``soft`` as it is.
         ``ldpc``: the other inner code of ofdm_demod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
         (--ldpc, --ldpc-rate), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well."""
         options = copy.copy(options)    # make a copy so we can destructively modify
@@ -34,7 +35,10 @@ class receive_path(object):
             ldpc = getattr(options, "ldpc", None) or None
         if rs is None and getattr(options, "rs_erasures", None) is not None:
             rs = dict(erasures=True, max_erasures=int(options.rs_erasures))
-            soft = True if soft is None else soft
+            if ldpc:
+                rs["source"] = "ldpc"           # the min-sum decoder's own reliabilities, hard bytes (--ldpc) or values (--ldpc-soft)
+            else:
+                soft = True if soft is None else soft
         if rs is None:
             rs = bool(getattr(options, "rs", None))
         if iq_format is None:

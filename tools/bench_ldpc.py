@@ -16,7 +16,12 @@ as many LDPC codewords as the rate-1/2 ones (11, the last one filled to the same
 bytes), the noisy inputs at --rate-ebn0 dB (2.5 / 3.0 / 3.75, at the nominal rate R) and --rate-flip-rate (3 / 2 / 1 %).
 The K = 7 times at R are the decode call's k_fec_decode time (the depuncture kernel's, ofdm_fec_punct_last_ms, is listed
 next to it).  "rate_over_half" holds every rate-R LDPC time as a ratio to the rate-1/2 LDPC kernel on the same kind of
-input in this job, "ldpc_over_fec_at_rate" as a ratio to the K = 7 code at R."""
+input in this job, "ldpc_over_fec_at_rate" as a ratio to the K = 7 code at R.
+
+--rel: k_ldpc_decode_rel next to k_ldpc_decode of the same build instead, nothing of the K = 7 code: for each of the four
+rates the batch above at that rate (clean and near the threshold, hard and soft), both kernels on the same buffers in
+alternation, the two calls' payloads and per-block arrays compared once.  Prints one JSON line per rate: median / min /
+max ms of either kernel per kind of input and "rel_over_plain", the ratio of the medians."""
 import argparse
 import json
 import os
@@ -70,6 +75,89 @@ def flipped(d_coded, rate, gen, chunk=1 << 24):
     return out
 
 
+RATE_NOMINAL = {"1/2": 0.5, "2/3": 2.0 / 3.0, "3/4": 0.75, "5/6": 5.0 / 6.0}
+RATE_EBN0 = {"2/3": 2.5, "3/4": 3.0, "5/6": 3.75}
+RATE_FLIP = {"2/3": 0.03, "3/4": 0.02, "5/6": 0.01}
+
+
+def rate_size(size, R):
+    """Payload bytes of a rate-R block of as many codewords as the rate-1/2 block of ``size``, the last one as full."""
+    KI = ldpc.cw_info(R)
+    W = (size + 4 + 95) // 96
+    return (W - 1) * KI + ((size + 4 - 96 * (W - 1)) * KI) // 96 - 4
+
+
+def main_rel(a):
+    dev = torch.device("cuda", 0)
+    P = a.blocks
+    opt = options.default_options(modulation="qpsk", fft_length=512, occupied_tones=200, cp_length=128, tx_amplitude=0.25)
+    e = engine.Engine(cfg=config.make_cfg(opt, device_ptrs=True))
+    e.prof_enable(True)
+    rng = np.random.Generator(np.random.PCG64(0x0FEC))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0x1D9C)
+    for R in ("1/2", "2/3", "3/4", "5/6"):
+        size = a.size if R == "1/2" else rate_size(a.size, R)
+        ebn0 = a.ebn0 if R == "1/2" else (RATE_EBN0[R] if a.rate_ebn0 is None else a.rate_ebn0)
+        flip = a.flip_rate if R == "1/2" else (RATE_FLIP[R] if a.rate_flip_rate is None else a.rate_flip_rate)
+        cfg = ldpc.ldpc_cfg(a.max_iters, R)
+        csize = ldpc.coded_len(size, R)
+        d_pay = torch.from_numpy(rng.integers(0, 256, P * size, dtype=np.uint8)).to(dev)
+        offs, lens = np.arange(P, dtype=np.uint64) * np.uint64(size), np.full(P, size, np.uint32)
+        coffs, clens = np.arange(P, dtype=np.uint64) * np.uint64(csize), np.full(P, csize, np.uint32)
+        d_coded = torch.empty(P * csize, dtype=torch.uint8, device=dev)
+        e.ldpc_encode_device(d_pay.data_ptr(), offs, lens, d_coded.data_ptr(), d_coded.numel(), cfg)
+        bufs = {("clean", False): d_coded, ("clean", True): hard_values(d_coded, 16), ("noisy", False): flipped(d_coded, flip, gen),
+                ("noisy", True): awgn_values(d_coded, ebn0, gen, rate=RATE_NOMINAL[R])}
+        d_dec = torch.empty(P * size, dtype=torch.uint8, device=dev)
+        d_dec_rel = torch.empty(P * size, dtype=torch.uint8, device=dev)
+        d_rel = torch.empty(P * size, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        state = {}
+
+        def run(what, soft, rel):
+            buf = bufs[(what, soft)]
+            o = coffs * np.uint64(8) if soft else coffs
+            if rel:
+                res = e.ldpc_decode_rel_device(buf.data_ptr(), o, clens, d_dec_rel.data_ptr(), d_dec_rel.numel(), d_rel.data_ptr(),
+                                               d_rel.numel(), cfg, soft=soft)
+            else:
+                res = e.ldpc_decode_device(buf.data_ptr(), o, clens, d_dec.data_ptr(), d_dec.numel(), cfg, soft=soft)
+            state[(what, soft, rel)] = res
+            return e.ldpc_last_ms()
+
+        kinds = [(w, s) for w in ("clean", "noisy") for s in (False, True)]
+        name = lambda w, s, rel: "k_ldpc_decode%s %s %s" % ("_rel" if rel else "", w, "soft" if s else "hard")
+        verdicts = {}
+        for w, s in kinds:
+            for rel in (False, True):
+                for _ in range(2):
+                    run(w, s, rel)
+            plain, withrel = state[(w, s, False)], state[(w, s, True)]
+            assert all(np.array_equal(x, y) for x, y in zip(plain, withrel)) and bool((d_dec == d_dec_rel).all())
+            failed = withrel[4] > 0
+            q = d_rel.reshape(P, size)
+            verdicts["%s %s" % (w, "soft" if s else "hard")] = dict(
+                ok=int(withrel[1].sum()), cw_failed=int(withrel[4].sum()), mean_block_iters=round(float(withrel[3].mean()), 2),
+                rel_min=int(q.min()), rel_max=int(q.max()),
+                rel_below_128_in_ok_blocks=int((q[torch.from_numpy(~failed).to(dev)] < 128).sum()))
+        ms = {name(w, s, rel): [] for w, s in kinds for rel in (False, True)}
+        for _ in range(a.rounds):
+            for w, s in kinds:
+                for rel in (False, True):
+                    ms[name(w, s, rel)] += [run(w, s, rel) for _ in range(a.calls)]
+        med = {v: float(np.median(t)) for v, t in ms.items()}
+        print(json.dumps({"rate": R, "blocks": P, "payload_bytes": size, "ldpc_coded_bytes": csize,
+                          "ldpc_codewords": P * ((size + 4 + ldpc.cw_info(R) - 1) // ldpc.cw_info(R)), "max_iters": a.max_iters,
+                          "ebn0_db": ebn0, "flip_rate": flip, "calls": a.calls * a.rounds,
+                          "ms_median_min_max": {v: _stats(t) for v, t in ms.items()}, "verdicts": verdicts,
+                          "rel_over_plain": {"%s %s" % (w, "soft" if s else "hard"): round(med[name(w, s, True)] / med[name(w, s, False)], 4)
+                                             for w, s in kinds}}), flush=True)
+        del bufs, d_coded, d_pay, d_dec, d_dec_rel, d_rel
+        torch.cuda.empty_cache()
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=65536)
@@ -82,15 +170,17 @@ def main():
     ap.add_argument("--rate", choices=("1/2", "2/3", "3/4", "5/6"), default="1/2")
     ap.add_argument("--rate-ebn0", type=float, default=None)
     ap.add_argument("--rate-flip-rate", type=float, default=None)
+    ap.add_argument("--rel", action="store_true", help="k_ldpc_decode_rel next to k_ldpc_decode, every rate (see above)")
     a = ap.parse_args()
+    if a.rel:
+        return main_rel(a)
     R = a.rate if a.rate != "1/2" else None
     if R:
-        nominal = {"2/3": 2.0 / 3.0, "3/4": 0.75, "5/6": 5.0 / 6.0}[R]
-        r_ebn0 = {"2/3": 2.5, "3/4": 3.0, "5/6": 3.75}[R] if a.rate_ebn0 is None else a.rate_ebn0
-        r_flip = {"2/3": 0.03, "3/4": 0.02, "5/6": 0.01}[R] if a.rate_flip_rate is None else a.rate_flip_rate
+        nominal = RATE_NOMINAL[R]
+        r_ebn0 = RATE_EBN0[R] if a.rate_ebn0 is None else a.rate_ebn0
+        r_flip = RATE_FLIP[R] if a.rate_flip_rate is None else a.rate_flip_rate
         KI = ldpc.cw_info(R)
-        W = (a.size + 4 + 95) // 96
-        rsize = (W - 1) * KI + ((a.size + 4 - 96 * (W - 1)) * KI) // 96 - 4      # as many codewords, the last as full
+        rsize = rate_size(a.size, R)                                             # as many codewords, the last as full
     dev = torch.device("cuda", 0)
     P, size = a.blocks, a.size
     fsize, lsize = fec.coded_len(size), ldpc.coded_len(size)
