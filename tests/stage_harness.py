@@ -904,6 +904,31 @@ def check_tx_model(y, x, taps, st, shape, fc, first, fmt, what, add=None):
     return worst
 
 
+def check_tx_bank_model(y, x, taps, st, shape, sel, first, fmt, what):
+    """check_tx_model for a transmit bank: the band of the rows ``x`` on the frequencies or channels ``sel`` against the
+    bank's float64 model within its derived bound (<stage>_cases.bound); 16-bit output as check_tx_model has it."""
+    bc = st.cases
+    if st.phase_free:
+        y64, s = bc.model(x, taps, *shape, sel)
+        bound = bc.bound(len(taps), shape[0], s)
+    else:
+        y64, s = bc.model(x, taps, *shape, sel, first)
+        bound = bc.bound(len(sel), len(taps), shape[0], s)
+    assert len(y) == len(y64) == st.count(first, np.asarray(x).shape[-1], *shape), what
+    d = as_complex(y, fmt) - y64
+    if fmt == "sc16":
+        free = (np.abs(y64.real) * SCALE < 32767 - 1) & (np.abs(y64.imag) * SCALE < 32767 - 1)
+        assert np.count_nonzero(free) > 0.9 * len(y), what
+        err = np.maximum(np.abs(d.real), np.abs(d.imag))[free]
+        bound = (0.5 / SCALE + bound)[free]
+    else:
+        err = np.abs(d)
+    worst = float(np.max(err / np.maximum(bound, 1e-300))) if len(err) else 0.0
+    print("%s: %d outputs, worst error / bound = %.3g" % (what, len(y), worst))
+    assert np.all(err <= bound), "%s: worst error / bound = %.3g" % (what, worst)
+    return worst
+
+
 def check_unit_stage_returns_its_input(eng, st, shape):
     x = tx_stream(np.random.default_rng(1), 5000)
     try:
