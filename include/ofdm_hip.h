@@ -1512,6 +1512,60 @@ int ofdm_rx_ldpc_decode_soft_rel(ofdm_handle *h, const ofdm_ldpc_cfg *cfg, uint8
                                  uint64_t *payload_off, uint8_t *ok, uint32_t *corrected, uint8_t *iters, uint32_t *cw_failed,
                                  uint8_t *rel, uint64_t rel_cap, int max_pkts, int *n);
 
+/* --- coded links: the signal field ---------------------------------------------------------------------------------
+ * A 12-byte field in front of a coded block that names the block's coding, so that a receiver needs no setting of its
+ * own and a batch can hold packets of different codings.  The field lies inside the packet's payload: header, whitening
+ * and packet CRC treat it like any payload byte.  A block is field | body, OFDM_SIG_FIELD_BYTES + len(body) bytes.
+ *
+ * The coding word, 12 bits, MSB first:
+ *   bits 11..10  codec      OFDM_SIG_CODEC_NONE, _FEC (the convolutional code), _LDPC; 3 is reserved
+ *   bits  9..8   rate id    OFDM_FEC_RATE_* / OFDM_LDPC_RATE_* (0 .. 3); 0 with OFDM_SIG_CODEC_NONE
+ *   bit   7      the Reed-Solomon outer code is present
+ *   bits  6..4   log2 of the convolutional interleaver's column count, 0 .. 4; 0 for the other codecs
+ *   bits  3..0   reserved, zero
+ * 2 + 40 + 8 = 50 words are valid.
+ *
+ * The codeword of a word w, extended Golay (24,12,8): the 12 word bits MSB first, then the 11 bits of the remainder of
+ * w(x) x^11 modulo g(x) = x^11 + x^10 + x^6 + x^5 + x^4 + x^2 + 1 (0xC75), then one bit that makes the weight even.
+ * The field is four copies of the codeword: field bit t (0 .. 95, MSB first within a byte) is codeword bit t mod 24.
+ *
+ * Decoding is exhaustive maximum likelihood in integers.  v_t is the value of field bit t (soft: the int8 value, v > 0
+ * means 1, 0 is an erasure, -128 reads as -127; hard: +1 / -1 from the bit), c_j = v_j + v_(j+24) + v_(j+48) + v_(j+72),
+ * m(w) = sum over j of c_j * (+1 where bit j of w's codeword is 1, else -1).  `word` is the w with the largest m, the
+ * smallest such w on a tie, whether valid or not (ofdm_sig_word_valid tells); `margin` is m(word) minus the largest m
+ * of any other w, 0 .. 24384.  A packet shorter than 12 bytes gives word OFDM_SIG_NO_WORD and margin 0.
+ *
+ * ofdm_sig_word packs a word (interleave_cols: 1, 2, 4, 8 or 16 with OFDM_SIG_CODEC_FEC, 0 or 1 otherwise),
+ * ofdm_sig_word_fields unpacks one (interleave_cols 0 where the codec has none), ofdm_sig_word_valid returns 1 or 0;
+ * the first two return OFDM_E_INVAL for what is no valid word.  None of the three needs a handle or a GPU.
+ *
+ * ofdm_sig_encode: block k of `out`, at out_off[k], is the field of words[k] followed by the body_len[k] bytes at
+ * bodies + body_off[k]; out_off has nblk + 1 entries and is set before the capacity is checked.  `bodies` and `out` are
+ * host or device pointers by the handle's mode; words, offsets and lengths are host arrays.  An invalid word is
+ * OFDM_E_INVAL, out_cap < out_off[nblk] OFDM_E_CAPACITY.  Ordered with ofdm_tx like the other encode calls.
+ *
+ * ofdm_sig_decode (hard bytes) / ofdm_sig_decode_soft (int8 values, 8 per byte, soft_off in values, len in bytes):
+ * word[k] and margin[k] (host arrays) of the packet of len[k] bytes at off[k]; only the field is read.
+ * ofdm_rx_sig_decode_soft does the same for the packets of the last ofdm_rx from the handle's own soft values
+ * (ofdm_set_rx_soft), *n of them; max_pkts < *n is OFDM_E_CAPACITY with *n set.  ofdm_sig_last_ms: the HIP-event time
+ * of k_sig_encode / k_sig_decode in the last of these calls (ofdm_prof_enable), OFDM_E_INVAL if it was not timed. */
+#define OFDM_SIG_FIELD_BYTES 12
+#define OFDM_SIG_CODEC_NONE 0
+#define OFDM_SIG_CODEC_FEC 1
+#define OFDM_SIG_CODEC_LDPC 2
+#define OFDM_SIG_NO_WORD 0xFFFF
+int ofdm_sig_word(uint32_t codec, uint32_t rate, uint32_t rs, uint32_t interleave_cols, uint16_t *word);
+int ofdm_sig_word_fields(uint32_t word, uint32_t *codec, uint32_t *rate, uint32_t *rs, uint32_t *interleave_cols);
+int ofdm_sig_word_valid(uint32_t word);
+int ofdm_sig_encode(ofdm_handle *h, const uint16_t *words, const uint8_t *bodies, const uint64_t *body_off,
+                    const uint32_t *body_len, int nblk, uint8_t *out, uint64_t out_cap, uint64_t *out_off);
+int ofdm_sig_decode(ofdm_handle *h, const uint8_t *in, const uint64_t *off, const uint32_t *len, int nblk, uint16_t *word,
+                    uint16_t *margin);
+int ofdm_sig_decode_soft(ofdm_handle *h, const int8_t *soft, const uint64_t *soft_off, const uint32_t *len, int nblk,
+                         uint16_t *word, uint16_t *margin);
+int ofdm_rx_sig_decode_soft(ofdm_handle *h, uint16_t *word, uint16_t *margin, int max_pkts, int *n);
+int ofdm_sig_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- chunked streams -------------------------------------------------------------
  * ofdm_rx treats each call as one stream that starts at its first sample (filter and
  * correlator history zero, detector average 0, NCO phase 0), as the reference's flow graph

@@ -33,6 +33,9 @@ OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 
 OFDM_LDPC_MAX_PAYLOAD = 2012
 OFDM_LDPC_MAX_CODED = 4032
 OFDM_LDPC_RATE_1_2, OFDM_LDPC_RATE_2_3, OFDM_LDPC_RATE_3_4, OFDM_LDPC_RATE_5_6 = 0, 1, 2, 3
+OFDM_SIG_FIELD_BYTES = 12
+OFDM_SIG_CODEC_NONE, OFDM_SIG_CODEC_FEC, OFDM_SIG_CODEC_LDPC = 0, 1, 2
+OFDM_SIG_NO_WORD = 0xFFFF
 OFDM_RS_PARITY = 32
 OFDM_RS_MAX_PAYLOAD = 3564
 OFDM_RS_MAX_CODED = 4080
@@ -365,6 +368,8 @@ EXPORTS = (
     "ofdm_ldpc_coded_len", "ofdm_ldpc_payload_len", "ofdm_ldpc_encode", "ofdm_ldpc_decode", "ofdm_ldpc_decode_soft",
     "ofdm_rx_ldpc_decode_soft", "ofdm_ldpc_last_ms", "ofdm_ldpc_coded_len_rate", "ofdm_ldpc_payload_len_rate",
     "ofdm_ldpc_decode_rel", "ofdm_ldpc_decode_soft_rel", "ofdm_rx_ldpc_decode_soft_rel",
+    "ofdm_sig_word", "ofdm_sig_word_fields", "ofdm_sig_word_valid", "ofdm_sig_encode", "ofdm_sig_decode",
+    "ofdm_sig_decode_soft", "ofdm_rx_sig_decode_soft", "ofdm_sig_last_ms",
 )
 
 _LIB = None
@@ -495,6 +500,15 @@ def _declare(lib):
     lib.ofdm_ldpc_decode_soft_rel.argtypes = lib.ofdm_ldpc_decode_rel.argtypes
     lib.ofdm_rx_ldpc_decode_soft_rel.argtypes = [H, LC, u8p, C.c_uint64, u64p, vp, u32p, vp, u32p, u8p, C.c_uint64, C.c_int,
                                                  C.POINTER(C.c_int)]
+    u16p = C.POINTER(C.c_uint16)
+    lib.ofdm_sig_word.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u16p]
+    lib.ofdm_sig_word_fields.argtypes = [C.c_uint32, u32p, u32p, u32p, u32p]
+    lib.ofdm_sig_word_valid.argtypes = [C.c_uint32]
+    lib.ofdm_sig_encode.argtypes = [H, u16p, u8p, u64p, u32p, C.c_int, u8p, C.c_uint64, u64p]
+    lib.ofdm_sig_decode.argtypes = [H, u8p, u64p, u32p, C.c_int, u16p, u16p]
+    lib.ofdm_sig_decode_soft.argtypes = lib.ofdm_sig_decode.argtypes
+    lib.ofdm_rx_sig_decode_soft.argtypes = [H, u16p, u16p, C.c_int, C.POINTER(C.c_int)]
+    lib.ofdm_sig_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_taps.argtypes = [H, C.c_uint32]
     lib.ofdm_tap.argtypes = [H, C.c_int, vp, C.c_uint64, u64p]
     lib.ofdm_prof_enable.argtypes = [H, C.c_int]

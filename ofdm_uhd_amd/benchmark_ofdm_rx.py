@@ -109,6 +109,14 @@ def make_parser():
                            "with --ldpc, --ldpc-rate or --ldpc-soft the symbols are chosen by the min-sum decoder's own "
                            "byte reliabilities "
                            "[default=off]")
+    parser.add_option("", "--sig", action="store_true", default=False,
+                      help="self-describing coded link: the file was written by benchmark_ofdm_tx --sig; the signal "
+                           "field in front of every block names its coding, its fields are decoded on the GPU and every "
+                           "packet goes through the decoders its field names -- no coding flag goes with it "
+                           "[default=%default]")
+    parser.add_option("", "--sig-soft", action="store_true", default=False,
+                      help="--sig with soft decisions: field and bodies are decoded from the soft demapper's values "
+                           "[default=%default]")
     _options.add_resamp_options(parser)
     parser.add_option("", "--resamp-freqs", default=None,
                       help="with --resamp-interp / --resamp-decim, instead of --resamp-freq: comma-separated centres of "
@@ -190,6 +198,13 @@ def main(argv=None):
     if len(args) != 0:
         parser.print_help(sys.stderr)
         sys.exit(1)
+    if options.sig_soft:
+        options.sig = True
+    if options.sig and (options.fec or options.fec_soft or options.fec_rate or options.ldpc or options.ldpc_soft or options.ldpc_rate
+                        or options.rs or options.rs_erasures is not None):
+        parser.error("--sig / --sig-soft take no coding flags: the signal field names every packet's coding")
+    if options.sig and (options.resamp_freqs is not None or options.ddc_freqs is not None):
+        parser.error("--sig does not combine with --ddc-freqs or --resamp-freqs")
     if options.fec_soft:
         options.fec = True
     if options.fec_rate:

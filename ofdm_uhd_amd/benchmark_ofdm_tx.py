@@ -73,6 +73,11 @@ def make_parser():
                            "2328 / 2632 / 2904 with --ldpc-rate 2/3 / 3/4 / 5/6) in a "
                            "Reed-Solomon block, 32 parity bytes per 223, encoded on the GPU ahead of the inner code; "
                            "demodulate with benchmark_ofdm_rx --rs [default=%default]")
+    parser.add_option("", "--sig", action="store_true", default=False,
+                      help="self-describing coded link: every block goes out behind a 12-byte signal field that names "
+                           "its coding -- the one --fec / --fec-rate / --ldpc / --ldpc-rate / --rs choose, none of them: "
+                           "uncoded -- so benchmark_ofdm_rx --sig needs no coding flags; the largest payloads shrink by "
+                           "up to 12 bytes [default=%default]")
     _options.add_tx_resamp_options(parser)
     parser.add_option("", "--tx-resamp-freqs", default=None,
                       help="with --tx-resamp-interp / --tx-resamp-decim, instead of --tx-resamp-freq: comma-separated "
@@ -91,8 +96,8 @@ def _main_tx_resamp_bank(parser, options):
     the packets sent per link."""
     if options.duc_interp or options.duc_freq:
         parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
-    if options.fec or options.rs or options.ldpc:
-        parser.error("--tx-resamp-freqs does not combine with --fec, --ldpc or --rs")
+    if options.fec or options.rs or options.ldpc or options.sig:
+        parser.error("--tx-resamp-freqs does not combine with --fec, --ldpc, --rs or --sig")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:

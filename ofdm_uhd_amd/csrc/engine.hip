@@ -37,6 +37,7 @@
 #include "fec_rel.h"
 #include "rs.h"
 #include "ldpc.h"
+#include "sig.h"
 
 static std::string g_create_error;
 
@@ -138,6 +139,7 @@ struct ofdm_handle {
   FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h)
   RsState rs;  // outer code: Reed-Solomon over the payloads, above the coded links (rs.h / engine_rs.inc)
   LdpcState ldpc;  // coded links, the second inner code: QC-LDPC encoder and min-sum decoder (ldpc.h / engine_ldpc.inc)
+  SigState sig;  // coded links: the signal field that names a block's coding (sig.h / engine_sig.inc)
 };
 
 // bytes per sample of the caller's receive / transmit buffers
@@ -576,6 +578,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->fec_punct.release();
   h->fec_rel.release();
   h->ldpc.release();
+  h->sig.release();
   h->rs.release();
   {
     SenseState& ss = h->sense;
@@ -1024,3 +1027,4 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_soft.inc"
 #include "engine_rs.inc"
 #include "engine_ldpc.inc"
+#include "engine_sig.inc"

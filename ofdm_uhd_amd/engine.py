@@ -1292,6 +1292,86 @@ class Engine(object):
         n, _ = self._rx_soft_offsets()
         return self._rx_ldpc_decode_soft_rel(ldpc, C.c_void_p(payload_ptr), payload_cap, C.c_void_p(rel_ptr), rel_cap, n)
 
+    # -- coded links: the signal field (12 bytes in front of a block that name its coding; sig.py) ----------------------
+    @staticmethod
+    def _sig_words(words):
+        from . import sig as _sig
+        return np.ascontiguousarray([w.word if isinstance(w, _sig.Coding) else int(w) for w in words], np.uint16)
+
+    def sig_encode(self, words, bodies):
+        """Host mode: one coding word (or sig.Coding) and one body (bytes, e.g. what fec_encode() returned) per block
+        -> list of blocks, the 12-byte field in front of each body: the payloads tx() then takes.  ValueError for a
+        word that is not valid."""
+        assert not self.device_ptrs
+        words = self._sig_words(words)
+        if len(words) != len(bodies):
+            raise ValueError("sig: one word per body")
+        return self._codec_encode_host(self._lib.ofdm_sig_encode, (words.ctypes.data_as(C.POINTER(C.c_uint16)),), bodies,
+                                       lambda lens: lens.sum() + 12 * len(lens))
+
+    def sig_encode_device(self, words, body_ptr, offs, lens, out_ptr, out_cap):
+        """Device mode: bodies and blocks are device pointers; words / offs / lens are host arrays.  Returns the
+        nblk + 1 block offsets (uint64)."""
+        assert self.device_ptrs
+        words = self._sig_words(words)
+        if len(words) != len(lens):
+            raise ValueError("sig: one word per body")
+        return self._codec_encode(self._lib.ofdm_sig_encode, (words.ctypes.data_as(C.POINTER(C.c_uint16)),), C.c_void_p(body_ptr), offs,
+                                  lens, C.c_void_p(out_ptr), out_cap)
+
+    def _sig_decode(self, fn, head, n, tail=()):
+        """fn(handle, *head, word, margin, *tail) over n packets -> (word uint16[n], margin uint16[n])."""
+        word, margin = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.uint16)
+        u16p = C.POINTER(C.c_uint16)
+        self._check(fn(self._h, *head, word.ctypes.data_as(u16p), margin.ctypes.data_as(u16p), *tail))
+        return word[:n], margin[:n]
+
+    @staticmethod
+    def _sig_results(word, margin):
+        return [(int(w), int(m)) for w, m in zip(word, margin)]
+
+    def sig_decode(self, blocks):
+        """Host mode: list of received blocks (hard bytes of any length, e.g. the payloads rx() delivered whatever
+        their CRC said) -> list of (word, margin): the most likely coding word of each block's field -- valid or not,
+        sig.word_valid() tells -- and how far its metric lies above the next word's (0 .. 24384; 0: a tie).  A block
+        under 12 bytes gives (0xFFFF, 0)."""
+        assert not self.device_ptrs
+        blob, offs, lens = pack_payloads(blocks)
+        return self._sig_results(*self._sig_decode(self._lib.ofdm_sig_decode, self._batch(_ptr(blob), offs, lens), len(lens)))
+
+    def sig_decode_soft(self, values):
+        """Host mode: list of int8 arrays, one value per bit (v > 0 means 1, 0 is an erasure, -128 reads as -127), 8 per
+        byte of the block -> list of (word, margin) as sig_decode.  An array under 96 values, or whose length is no
+        multiple of 8, gives (0xFFFF, 0)."""
+        assert not self.device_ptrs
+        blob, offs, lens = _pack_values(values)
+        return self._sig_results(*self._sig_decode(self._lib.ofdm_sig_decode_soft, self._batch(_ptr(blob), offs, lens), len(lens)))
+
+    def sig_decode_device(self, in_ptr, offs, lens, soft=False):
+        """Device mode: the blocks (hard bytes, or int8 values with ``soft``: 8 per byte, offsets in values) are a
+        device pointer; offs / lens (bytes) are NumPy host arrays.  Returns (word uint16[nblk], margin uint16[nblk])
+        as host arrays."""
+        assert self.device_ptrs
+        fn = self._lib.ofdm_sig_decode_soft if soft else self._lib.ofdm_sig_decode
+        return self._sig_decode(fn, self._batch(C.c_void_p(in_ptr), offs, lens), len(lens))
+
+    def rx_sig_decode_soft(self):
+        """Host mode: the fields of the packets the last rx() returned, decoded from the handle's own soft values (they
+        never visit the host) -> list of (word, margin) as sig_decode_soft.  Needs set_rx_soft() before that rx()."""
+        assert not self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._sig_results(*self._sig_decode(self._lib.ofdm_rx_sig_decode_soft, (), n, tail=self._rx_batch(n)))
+
+    def rx_sig_decode_soft_device(self):
+        """Device mode: the same; returns the host arrays of sig_decode_device."""
+        assert self.device_ptrs
+        n, _ = self._rx_soft_offsets()
+        return self._sig_decode(self._lib.ofdm_rx_sig_decode_soft, (), n, tail=self._rx_batch(n))
+
+    def sig_last_ms(self):
+        """HIP-event time of k_sig_encode / k_sig_decode in the last sig call (needs prof_enable())."""
+        return self._stage_last_ms("sig")
+
     def rx_packet_pos(self):
         """Flag sample (relative to the last rx() call's IQ) of every packet it delivered."""
         n = C.c_int(0)

@@ -9,12 +9,13 @@ GPU call and writes the samples to the connected sink; ``ofdm_demod.work(iq)``
 demodulates one contiguous IQ stream and fires ``callback(ok, payload)`` once per
 recovered packet, in stream order, on the caller's thread.
 """
+import collections
 import math
 import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -27,9 +28,16 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=False):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
+        @param sig: self-describing coded link (sig.py): every block goes out behind a 12-byte signal field that names
+               its coding, so the receiving end, ofdm_demod(sig=True), needs no coding setting.  ``fec`` / ``ldpc`` /
+               ``rs`` then only choose the default coding; ``send_pkt(payload, coding=...)`` overrides it per packet, and
+               one batch may mix codings: flush() groups the queued packets by coding, encodes each group with the calls
+               below, puts the fields in front with one Engine.sig_encode over the whole batch, in the packets' order,
+               and modulates once.  The largest payloads shrink by up to 12 bytes (sig.max_payload).  False: no field,
+               nothing new runs
         @param msgq_limit: maximum number of messages in message queue (kept for API
                compatibility: the reference blocks send_pkt at this depth, ofdm.py:148;
                here packets are batched until flush)
@@ -68,6 +76,8 @@ class ofdm_mod(object):
         """
         if duc is not None and resample is not None:
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
+        if sig:
+            _sig.coding(fec=fec, ldpc=ldpc, rs=bool(rs))    # (ValueError for what is no coding, before anything is built)
         self._pad_for_usrp = pad_for_usrp
         self._msgq_limit = msgq_limit
         self._modulation = options.modulation
@@ -106,6 +116,9 @@ class ofdm_mod(object):
         if self._fec is not None and self._ldpc is not None:
             raise ValueError("fec= and ldpc= are two inner codes: a link has one of them")
         self._rs = bool(rs)
+        # the coding a packet gets without one of its own (sig only), and the codings of the queued packets
+        self._sig = _sig.coding(fec=self._fec, ldpc=self._ldpc, rs=self._rs) if sig else None
+        self._pending_coding = []
         self._pending = []
         self._sink = None
         self.symbols_sent = 0
@@ -132,12 +145,15 @@ class ofdm_mod(object):
         return self._engine
 
     # -- packets ------------------------------------------------------------------
-    def send_pkt(self, payload='', eof=False):
+    def send_pkt(self, payload='', eof=False, coding=None):
         """
         Send the payload.
 
         @param payload: data to send
         @type payload: bytes (str is encoded latin-1)
+        @param coding: this packet's coding on a link with a signal field (ofdm_mod(sig=True); ValueError without):
+               a sig.Coding, a coding word, or a dict of sig.coding's keywords (``fec``, ``ldpc``, ``rs``).  None: the
+               link's default
         """
         if eof:
             self.flush(end=True)  # gr.message(1): no more packets (ofdm.py:142)
@@ -145,6 +161,17 @@ class ofdm_mod(object):
         if isinstance(payload, str):
             payload = payload.encode("latin-1")
         payload = bytes(payload)
+        if coding is not None and self._sig is None:
+            raise ValueError("send_pkt(coding=) needs ofdm_mod(sig=True): without a signal field the link has one coding")
+        if self._sig is not None:
+            cod = self._sig if coding is None else (_sig.coding(**coding) if isinstance(coding, dict) else _sig.coding(coding))
+            try:
+                self._engine.framed_len(_sig.coded_len(len(payload), cod))   # the block, field included, is what gets framed
+            except ValueError:
+                raise ValueError("len(payload) must be in [0, %d]" % (_sig.max_payload(cod),))
+            self._pending.append(payload)
+            self._pending_coding.append(cod)
+            return
         # same limit and exception as make_packet (ofdm_packet_utils.py:123-126) -- and, like it, raised HERE for
         # the offending packet only: the padded, whitened body must fit the mask too (whiten(), :84-87)
         if self._rs:
@@ -194,12 +221,16 @@ class ofdm_mod(object):
         iq = None
         if self._pending:
             pending, self._pending = self._pending, []   # a failing batch never poisons the queue
-            if self._rs:
-                pending = self._engine.rs_encode(pending)
-            if self._fec is not None:
-                pending = self._engine.fec_encode(pending, self._fec)
-            if self._ldpc is not None:
-                pending = self._engine.ldpc_encode(pending, self._ldpc)
+            codings, self._pending_coding = self._pending_coding, []
+            if self._sig is not None:
+                pending = self._encode_sig(pending, codings)
+            else:
+                if self._rs:
+                    pending = self._engine.rs_encode(pending)
+                if self._fec is not None:
+                    pending = self._engine.fec_encode(pending, self._fec)
+                if self._ldpc is not None:
+                    pending = self._engine.ldpc_encode(pending, self._ldpc)
             iq = self._engine.tx(pending)
             self.symbols_sent += self._engine.last_stats.get("symbols", 0)
             self.packets_sent += len(pending)
@@ -219,6 +250,26 @@ class ofdm_mod(object):
         if self._sink is not None:
             self._sink.write(iq)
         return iq
+
+    def _encode_sig(self, payloads, codings):
+        """The blocks of a batch on a link with a signal field: the packets grouped by coding, each group through its
+        coding's encoders, the fields put in front of all bodies in one call, in the packets' order."""
+        eng = self._engine
+        groups = {}
+        for i, cod in enumerate(codings):
+            groups.setdefault(cod, []).append(i)
+        bodies = [None] * len(payloads)
+        for cod, idx in groups.items():
+            part = [payloads[i] for i in idx]
+            if cod.rs:
+                part = eng.rs_encode(part)
+            if cod.codec == _sig.CODEC_FEC:
+                part = eng.fec_encode(part, cod.fec)
+            elif cod.codec == _sig.CODEC_LDPC:
+                part = eng.ldpc_encode(part, cod.ldpc())
+            for i, body in zip(idx, part):
+                bodies[i] = body
+        return eng.sig_encode(codings, bodies)
 
     def _write_logs(self, iq):
         # the reference's --log probe points (ofdm.py:123-131)
@@ -268,9 +319,21 @@ class ofdm_demod(object):
     """
 
     def __init__(self, options, callback=None, device_id=0, quality_callback=None, csi=False, iq_format="fc32",
-                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None):
+                 iq_scale=None, ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None, sig=False):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
+        @param sig: self-describing coded link, the receiving end of ofdm_mod(sig=True): the first 12 bytes of every
+            delivered packet are a signal field that names the coding of the body behind it (sig.py).  The fields of
+            all delivered packets are decoded in one call (Engine.rx_sig_decode_soft with ``soft``, on the GPU where
+            the values lie; Engine.sig_decode on the bytes without), the packets grouped by the word found, and each
+            group's bodies go through that coding's decoders (Engine.fec_decode[_soft] / ldpc_decode[_soft], then
+            rs_decode; with ``soft`` on the ``last_soft`` values behind the field).  ``callback(ok, payload)`` and the
+            returned list carry the decoded payloads and the last stage's verdict, in packet order; a packet whose word
+            is not valid comes back as (False, the body as received).  ``last_sig`` holds (word, margin, sig.Coding or
+            None) per packet; ``last_fec``, ``last_ldpc`` and ``last_rs`` keep their shapes, with (stage below's
+            verdict, 0) / (0, 0) / (stage below's verdict, 0, 0) for a packet whose coding lacks that stage.  The
+            field says the coding, so ``fec=`` and ``rs=True`` are a ValueError, ``ldpc=`` may carry ``max_iters``
+            only, and ``rs=dict(erasures=...)`` is a ValueError (not on these links yet)
         @param callback:  function of two args: ok, payload
         @type callback: ok: bool; payload: bytes
         @param quality_callback: optional function of three args: ok, payload, quality -- turns on the per-packet
@@ -313,7 +376,7 @@ class ofdm_demod(object):
             ``last_fec_rel`` holds them, one uint8 array per packet.  ``source="ldpc"`` is the same above ``ldpc`` (below); any other ``source`` is a
             ValueError.  ``last_rs``
             keeps its three fields, ``last_rs_second`` holds the codewords per packet that the second pass decoded
-        @param ldpc: coded link with the other inner code, as for ofdm_mod and at the same rate (no field on the air names
+        @param ldpc: coded link with the other inner code, as for ofdm_mod and at the same rate (without ``sig`` no field on the air names
             it), in the place of ``fec`` (both: ValueError):
             every delivered packet goes through the min-sum decoder in one batch (Engine.ldpc_decode on the hard bytes;
             with ``soft`` Engine.rx_ldpc_decode_soft on the values, on the GPU).  ``last_fec`` keeps its shape,
@@ -328,6 +391,27 @@ class ofdm_demod(object):
         """
         if ddc is not None and resample is not None:
             raise ValueError("ofdm_demod takes ddc= or resample=, not both")
+        self._sig = bool(sig)
+        self._sig_iters = None       # the LDPC decoder's max_iters on a link with a signal field (None: the default)
+        self.last_sig = []           # (word, margin, Coding or None) of the packets the last work() / feed() returned (sig only)
+        if self._sig:
+            if fec is not None and fec is not False:
+                raise ValueError("ofdm_demod(sig=True) takes no fec=: the signal field names the coding")
+            if isinstance(rs, dict) and rs.get("erasures"):
+                raise ValueError("ofdm_demod(sig=True) does not decode with erasures yet: rs=dict(erasures=...) needs a "
+                                 "link whose coding both ends set")
+            if rs:
+                raise ValueError("ofdm_demod(sig=True) takes no rs=: the signal field says whether the outer code is there")
+            if ldpc is not None and ldpc is not False and ldpc is not True:
+                if isinstance(ldpc, dict):
+                    if set(ldpc) - {"max_iters"}:
+                        raise ValueError("ofdm_demod(sig=True): ldpc= may carry max_iters only, the signal field names the rate")
+                    ldpc = ldpc.get("max_iters")
+                elif isinstance(ldpc, bool) or not isinstance(ldpc, int):
+                    raise ValueError("ofdm_demod(sig=True): ldpc= may carry max_iters only, the signal field names the rate")
+                if ldpc is not None:
+                    self._sig_iters = _ldpc.ldpc_cfg(max_iters=ldpc).max_iters
+            fec = rs = ldpc = None
         self._modulation = options.modulation
         self._fft_length = options.fft_length
         self._occupied_tones = options.occupied_tones
@@ -408,6 +492,7 @@ class ofdm_demod(object):
             self._engine.set_rx_quality(True)
         # link-quality records of the packets the last work() / feed() returned (quality_callback only)
         self.last_quality = np.zeros(0, engine.QUALITY_DTYPE)
+        self.reset_coding_history()  # preamble SNR of the packets delivered with ok set (suggest_coding)
         # channel-state rows of the packets the last work() / feed() returned (csi only), and their running sums
         self._csi = bool(csi)
         if self._csi:
@@ -479,6 +564,8 @@ class ofdm_demod(object):
         """The coded link's receiving end: the delivered packets' bytes, whatever their CRC said, through the decoder
         (``soft``: their soft values, on the GPU where the last rx() left them; ``sel`` picks the delivered ones among
         that call's packets)."""
+        if self._sig:
+            return self._decode_sig(pkts, sel)
         if self._fec is not None:
             pkts = self._decode_inner(pkts, sel)
         elif self._ldpc is not None:
@@ -535,11 +622,71 @@ class ofdm_demod(object):
         self.last_ldpc = [(d[3], d[4]) for d in dec]
         return [(d[0], d[1]) for d in dec]
 
+    def _decode_sig(self, pkts, sel=None):
+        """The receiving end of a link with a signal field: every packet's field in one call, the packets grouped by
+        the word found, each group through its coding's decoders, the results back in packet order."""
+        eng = self._engine
+        soft = self._soft is not None
+        if soft:
+            found = eng.rx_sig_decode_soft() if pkts else []
+            if sel is not None:
+                found = [found[i] for i in sel]
+        else:
+            found = eng.sig_decode([p for _, p in pkts]) if pkts else []
+        self.last_sig = [(w, m, _sig.coding(w) if _sig.word_valid(w) else None) for w, m in found]
+        FB = _sig.FIELD_BYTES
+        out = [(False, p[FB:]) for _, p in pkts]                   # what a packet without a valid word comes back as
+        self.last_fec = [(bool(ok), 0) for ok, _ in pkts]
+        self.last_ldpc = [(0, 0)] * len(pkts)
+        self.last_rs = [(bool(ok), 0, 0) for ok, _ in pkts]
+        groups = {}
+        for i, (_, _, cod) in enumerate(self.last_sig):
+            if cod is not None:
+                groups.setdefault(cod, []).append(i)
+        for cod, idx in groups.items():
+            cur = [(bool(pkts[i][0]), pkts[i][1][FB:]) for i in idx]      # (verdict of the stage below, bytes)
+            if cod.codec != _sig.CODEC_NONE:
+                # (last_soft holds the delivered packets' values, in their order: 8 per byte, the field's first)
+                args = ([self.last_soft[i][8 * FB:] for i in idx],) if soft else ([p for _, p in cur],)
+                if cod.codec == _sig.CODEC_FEC:
+                    dec = (eng.fec_decode_soft if soft else eng.fec_decode)(*args, cod.fec)
+                else:
+                    dec = (eng.ldpc_decode_soft if soft else eng.ldpc_decode)(*args, cod.ldpc(self._sig_iters))
+                    for i, d in zip(idx, dec):
+                        self.last_ldpc[i] = (d[3], d[4])
+                for i, (below, _), d in zip(idx, cur, dec):
+                    self.last_fec[i] = (below, d[2])
+                cur = [(d[0], d[1]) for d in dec]
+            if cod.rs:
+                dec = eng.rs_decode([p for _, p in cur])
+                for i, (below, _), d in zip(idx, cur, dec):
+                    self.last_rs[i] = (bool(below), d[2], d[3])
+                cur = [(d[0], d[1]) for d in dec]
+            for i, r in zip(idx, cur):
+                out[i] = r
+        return out
+
+    def suggest_coding(self, table=None, margin_db=1.0):
+        """The coding the link could carry now (sig.suggest_coding): the least redundant coding of ``table`` -- an
+        ordered list of (min_snr_db, coding), None: sig.default_table() -- whose threshold plus ``margin_db`` the
+        median preamble SNR of the packets delivered with ok set since construction or reset_coding_history() clears;
+        None while there is no such packet.  For the transmitter's ``send_pkt(coding=)``.  Needs link quality
+        (``quality_callback``): ValueError without."""
+        if self._quality_callback is None:
+            raise ValueError("suggest_coding() needs link quality: ofdm_demod(..., quality_callback=)")
+        return _sig.suggest_coding(self._snr_history, table, margin_db)
+
+    def reset_coding_history(self):
+        """Starts the SNR history behind suggest_coding() afresh (it holds the last 65536 packets at the most)."""
+        self._snr_history = collections.deque(maxlen=65536)
+
     def _deliver(self, pkts):
         for i, (ok, payload) in enumerate(pkts):
             self.n_packets += 1
             if ok:
                 self.n_ok += 1
+                if self._quality_callback is not None:
+                    self._snr_history.append(float(self.last_quality[i]["snr_preamble_db"]))
             if self._callback:
                 self._callback(ok, payload)  # _queue_watcher_thread.run (ofdm.py:300-305)
             if self._quality_callback is not None:

@@ -6,7 +6,7 @@ from . import ofdm, options as _options
 
 class receive_path(object):
     def __init__(self, rx_callback, options, device_id=0, quality_callback=None, csi=False, iq_format=None, iq_scale=None,
-                 ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None):
+                 ddc=None, resample=None, fec=None, soft=None, rs=None, ldpc=None, sig=None):
         """``iq_format`` / ``iq_scale``: sample format of the stream (ofdm_demod); None: the options' ``iq_format`` /
         ``iq_scale`` (--iq-format / --iq-scale), "fc32" where they have none.
         ``ddc``: wideband front end of ofdm_demod, ``dict(decimation=, center_freq=, taps=None)``; None: the options'
@@ -21,8 +21,14 @@ class receive_path(object):
         (--rs), or their ``rs_erasures`` (--rs-erasures [M]), which turns the soft values on as well; on an ``ldpc`` link
         it selects ``source="ldpc"`` instead and leaves ``soft`` as it is.
         ``ldpc``: the other inner code of ofdm_demod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
-        (--ldpc, --ldpc-rate), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well."""
+        (--ldpc, --ldpc-rate), or their ``ldpc_soft`` (--ldpc-soft), which turns the soft values on as well.
+        ``sig``: the signal field of ofdm_demod, ``True``; None: the options' ``sig`` (--sig), or their ``sig_soft``
+        (--sig-soft), which turns the soft values on as well.  The field names the coding: no coding setting goes with it."""
         options = copy.copy(options)    # make a copy so we can destructively modify
+        if sig is None:
+            sig = bool(getattr(options, "sig", None) or getattr(options, "sig_soft", None))
+        if sig and soft is None and getattr(options, "sig_soft", None):
+            soft = True
         if soft is None and getattr(options, "fec_soft", None):
             soft = True
             fec = (getattr(options, "fec", None) or True) if fec is None else fec   # (a dict where --fec-rate set one)
@@ -58,7 +64,7 @@ class receive_path(object):
 
         self.ofdm_rx = ofdm.ofdm_demod(options, callback=self._rx_callback, device_id=device_id,
                                        quality_callback=quality_callback, csi=csi, iq_format=iq_format, iq_scale=iq_scale,
-                                       ddc=ddc, resample=resample, fec=fec, soft=soft, rs=rs, ldpc=ldpc)
+                                       ddc=ddc, resample=resample, fec=fec, soft=soft, rs=rs, ldpc=ldpc, sig=sig)
 
         if self._verbose:
             self._print_verbage()

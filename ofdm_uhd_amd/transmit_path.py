@@ -18,7 +18,7 @@ _FLAGS = (
 
 class transmit_path(object):
     def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
@@ -32,7 +32,9 @@ class transmit_path(object):
         ``fec``: coded link of ofdm_mod, ``True`` or ``dict(interleave=16, rate="1/2")``; None: the options' ``fec`` (--fec).
         ``rs``: outer code of ofdm_mod, ``True``; None: the options' ``rs`` (--rs).
         ``ldpc``: the other inner code of ofdm_mod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
-        (--ldpc, --ldpc-rate)."""
+        (--ldpc, --ldpc-rate).
+        ``sig``: the signal field of ofdm_mod, ``True``; None: the options' ``sig`` (--sig).  ``fec`` / ``ldpc`` / ``rs``
+        then choose the coding that every packet announces."""
         opts = copy.copy(options)
         if rs is None:
             rs = bool(getattr(opts, "rs", None))
@@ -40,6 +42,8 @@ class transmit_path(object):
             fec = getattr(opts, "fec", None) or None
         if ldpc is None:
             ldpc = getattr(opts, "ldpc", None) or None
+        if sig is None:
+            sig = bool(getattr(opts, "sig", None))
         if iq_format is None:
             iq_format = getattr(opts, "iq_format", None) or "fc32"
         if iq_scale is None:
@@ -53,7 +57,7 @@ class transmit_path(object):
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
-                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc)
+                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc, sig=sig)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
