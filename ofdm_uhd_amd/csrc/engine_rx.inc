@@ -37,31 +37,22 @@ static int launch_demod_v(ofdm_handle* h, const DemodParams& q, size_t shmem) {
   return instr ? launch_demod_t<N, TWL, true>(h, q, shmem) : launch_demod_t<N, TWL, false>(h, q, shmem);
 }
 
-// LDS extras of the demodulator (twiddle table for long transforms, the sink's carrier map): taken when they do not
-// reduce the workgroups a CU holds -- what its register budget admits (12 waves at 168 registers, 16 at 128 for the
-// frames of four waves and more) and what the LDS admits without them.
+// LDS extras of the demodulator (twiddle table for long transforms, the sink's carrier map): demod_launch_choice
+// (rx_demod.h) decides from the geometry, the tuning knob afterwards.
 template <int N>
 static int launch_demod(ofdm_handle* h, const DemodParams& q0) {
   DemodParams q = q0;
-  constexpr int T = N / 8, WAVES = demod_fpw(N) * ((T + WAVE - 1) / WAVE);
   const bool grid = q.grid != nullptr;
   const bool csi = q.csi_eq != nullptr;
-  auto bytes = [&](bool twl, bool sm) {
-    return (size_t)demod_lds_bytes(N, twl, sm, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid, csi);
-  };
-  constexpr int CU_WAVES = 4 * demod_waves_per_simd(N);  // waves a CU holds at the kernel's register budget
-  auto wgs = [&](size_t b) { return std::max<size_t>(1, std::min<size_t>(std::max(1, CU_WAVES / WAVES), CU_LDS_BYTES / b)); };
-  constexpr bool base_twl = !fft_onebuf(N);
-  const size_t w0 = wgs(bytes(base_twl, false));
-  bool twl = base_twl;
-  if constexpr (fft_onebuf(N)) twl = wgs(bytes(true, false)) == w0 && bytes(true, false) <= CU_LDS_BYTES;
-  q.smap_lds = (wgs(bytes(twl, true)) == w0 && bytes(twl, true) <= CU_LDS_BYTES) ? 1 : 0;
+  const DemodLaunch dl = demod_launch_choice(N, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid, csi);
+  bool twl = dl.twl;
+  q.smap_lds = dl.smap_lds ? 1 : 0;
   if (const char* e = getenv("OFDM_DEMOD_LDS")) {  // tuning knob: bit 0 twiddles (N >= 2048), bit 1 carrier map
     const int v = atoi(e);
     if constexpr (fft_onebuf(N)) twl = (v & 1) != 0;
     q.smap_lds = (v >> 1) & 1;
   }
-  const size_t shmem = bytes(twl, q.smap_lds != 0);
+  const size_t shmem = (size_t)demod_lds_bytes(N, twl, q.smap_lds != 0, q.occ, q.arity, q.nmap, q.nbits, q.shift, grid, csi);
   if (shmem > CU_LDS_BYTES) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_rx_demod");
   if constexpr (fft_onebuf(N)) {
     return twl ? launch_demod_v<N, true>(h, q, shmem) : launch_demod_v<N, false>(h, q, shmem);
@@ -94,9 +85,7 @@ static int sync_params(ofdm_handle* h, uint64_t nsamples, bool cap_full, SyncPar
   RxState& rx = h->rx;
   const int N = h->N, CP = h->CP, T = SYNC_TILE;
   const uint64_t ntiles = (nsamples + T - 1) / T;
-  // a segment = the tiles one k_sync workgroup walks (behind a prologue of 2D samples and one warm-up tile; any
-  // segmentation gives the same bits).  Longer symbols get longer segments: the prologue grows with N.
-  const int tiles_per_seg = 32 * ((N + CP + T - 1) / T);
+  const int tiles_per_seg = sync_tiles_per_seg(N, CP);  // (the tiles one k_sync workgroup walks: rx_sync.h)
   // (k_sync_exact's workgroups take candidate / piece storage in chunks: one chunk of slack per workgroup)
   const uint64_t egrid = std::min<uint64_t>(ntiles, 256ull * 8ull), egrid_small = std::min<uint64_t>(ntiles, 256ull * 16ull);
   // candidate storage: 1/16 of the samples plus one allocation chunk per workgroup; full-size buffers serve as the
@@ -132,7 +121,7 @@ static int sync_params(ofdm_handle* h, uint64_t nsamples, bool cap_full, SyncPar
   sp.N = N;
   sp.D = N / 2;
   sp.CP = CP;
-  sp.HY = (N + 7) / 8 * 8;  // 2*D: the correlator's two lags (the fixed-point re-evaluation reads y from global memory)
+  sp.HY = sync_hist_y(N);  // 2*D: the correlator's two lags (the fixed-point re-evaluation reads y from global memory)
   sp.HM = CP;
   sp.R = sync_ring_samples(sp.HY);
   sp.tiles_per_seg = tiles_per_seg;
@@ -209,30 +198,25 @@ static bool front_fused(const ofdm_handle* h) {
   if (h->cfg.sync_mode != OFDM_SYNC_PN) return false;
   const char* e = getenv("OFDM_FRONT");
   if (!e || atoi(e) == 0) return false;
-  const int F = h->filtF, B = F - (int)h->cfg.ntaps + 1;
-  if (F > 512) return false;
-  const int HY = (h->N + 7) / 8 * 8, C = (B + 7) / 8 * 8;
-  if (HY + C > SYNC_TILE || h->CP > SYNC_TILE) return false;
-  return front_lds_layout(sync_ring_samples(HY), h->CP, B, F).total <= CU_LDS_BYTES / 3;
+  return front_eligible(h->N, h->CP, (int)h->cfg.ntaps);
 }
 
 // k_sync over the whole filtered stream (the float32 pre-selection; the counters are cleared first)
 static int launch_sync(ofdm_handle* h, SyncParams& sp) {
   RxState& rx = h->rx;
-  const int T = SYNC_TILE;
   const uint64_t nseg = sync_nseg(sp);
   HIPCHK(h, hipMemsetAsync(rx.counters.p, 0, CT_COUNT * sizeof(uint64_t), h->stream));
 #ifdef SYNC_STAMPS
   if (int rs = stamps_prepare(h, sp, nseg)) return rs;
 #endif
-  const size_t sync_shmem = sync_lds_layout(sp.R, sp.HM).total;
+  const SyncLaunch sl = sync_launch_choice(sp.N, sp.CP);
+  const size_t sync_shmem = sl.lds;
   if (sync_shmem > CU_LDS_BYTES) FAIL(h, OFDM_E_INVAL, "configuration needs more than 160 KiB of LDS in k_sync");
   {
     ProfScope span(h->prof, OFDM_K_SYNC, h->stream);
-    // register budget for as many workgroups per CU as the LDS footprint admits (5 at C2, fewer for long symbols)
-    int wg = (int)std::min<size_t>(SYNC_MAX_WG, CU_LDS_BYTES / sync_shmem);
+    int wg = sl.wg;
     if (const char* w = getenv("OFDM_SYNC_W")) wg = std::min(wg, atoi(w));  // tuning knob: a larger register budget
-    bool fixed_layout = sp.R - (int)T <= (int)T;  // history no longer than a tile: [history | tile] at fixed LDS places
+    bool fixed_layout = sl.fixed_layout;
     // tuning knob: the ring where the fixed layout would do.  Not where the tile's M values overlay its samples
     // (sync_mt_overlay: N <= 512) -- only the fixed layout has the tile at one place, the ring would read M for y.
     if (const char* e = getenv("OFDM_SYNC_STATIC")) fixed_layout = fixed_layout && (atoi(e) != 0 || sync_mt_overlay(sp.R));
@@ -486,7 +470,7 @@ static int rx_sync_exact(RxCall& c, SyncParams& sp, bool cap_full) {
     ProfScope span(h->prof, OFDM_K_EXACT, h->stream);
     const size_t esh = exact_lds_layout(sp.CP, SYNC_TILE).total, esh_small = exact_lds_layout(sp.CP, sp.exact_small).total;
     // (deltas kept in registers between the two passes: pays for long symbols only)
-    const void* fbig = sp.D >= 2048 ? reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, true>)
+    const void* fbig = sync_exact_keep(sp.N) ? reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, true>)
                                     : reinterpret_cast<const void*>(&k_sync_exact<SYNC_THREADS, false>);
     if (esh > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(fbig, hipFuncAttributeMaxDynamicSharedMemorySize, (int)esh));
     if (sp.exact_small > 0)

@@ -423,6 +423,32 @@ __device__ unsigned long long g_demod_stamps[16];
 #define DEMOD_WAVES_BIG 4
 #endif
 __host__ __device__ constexpr int demod_waves_per_simd(int n) { return (n / 8 >= 256) ? DEMOD_WAVES_BIG : DEMOD_WAVES; }
+// LDS extras of the demodulator (twiddle table for long transforms, the sink's carrier map) as a function of the
+// geometry alone (host only: launch_demod in engine_rx.inc applies the OFDM_DEMOD_LDS knob afterwards).  They are taken
+// when they do not reduce the workgroups a CU holds -- what its register budget admits (12 waves at 168 registers, 16 at
+// 128 for the frames of four waves and more) and what the LDS admits without them.
+struct DemodLaunch {
+  bool twl, smap_lds;
+  size_t lds;  // dynamic LDS of the launch (beyond CU_LDS_BYTES the call is refused)
+};
+inline DemodLaunch demod_launch_choice(int n, int occ, int arity, int nmap, int nbits, int shift, bool grid, bool csi) {
+  const int T = n / 8, WAVES = demod_fpw(n) * ((T + WAVE - 1) / WAVE);
+  auto bytes = [&](bool twl, bool sm) { return (size_t)demod_lds_bytes(n, twl, sm, occ, arity, nmap, nbits, shift, grid, csi); };
+  const int CU_WAVES = 4 * demod_waves_per_simd(n);  // waves a CU holds at the kernel's register budget
+  auto wgs = [&](size_t b) {
+    const size_t by_waves = (size_t)(CU_WAVES / WAVES > 1 ? CU_WAVES / WAVES : 1), by_lds = (size_t)CU_LDS_BYTES / b;
+    const size_t m = by_waves < by_lds ? by_waves : by_lds;
+    return m > 1 ? m : (size_t)1;
+  };
+  const bool base_twl = !fft_onebuf(n);
+  const size_t w0 = wgs(bytes(base_twl, false));
+  DemodLaunch l;
+  l.twl = base_twl;
+  if (fft_onebuf(n)) l.twl = wgs(bytes(true, false)) == w0 && bytes(true, false) <= (size_t)CU_LDS_BYTES;
+  l.smap_lds = wgs(bytes(l.twl, true)) == w0 && bytes(l.twl, true) <= (size_t)CU_LDS_BYTES;
+  l.lds = bytes(l.twl, l.smap_lds);
+  return l;
+}
 // synchronisation of one frame's threads: a workgroup barrier -- or, where the frame is one wave sharing its workgroup
 // with other frames, wave-level fences (DS instructions of a wave execute in order)
 template <int FPW>

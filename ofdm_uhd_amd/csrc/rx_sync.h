@@ -1240,6 +1240,42 @@ __host__ __device__ inline int sync_exact_small(int CP, int D) {
   const int r = 2 * CP + 768;
   return r > SYNC_TILE ? SYNC_TILE : r;
 }
+
+// ---------------------------------------------------------------------------------
+// Launch decisions of the synchronisation pass, as functions of the geometry alone (host only: engine_rx.inc calls them
+// and applies the OFDM_* tuning knobs afterwards; tools/core_geom_check.cpp walks them over every accepted geometry).
+// ---------------------------------------------------------------------------------
+inline int sync_hist_y(int N) { return (N + 7) / 8 * 8; }  // 2*D: the correlator's two lags
+// a segment = the tiles one k_sync workgroup walks (behind a prologue of 2D samples and one warm-up tile; any
+// segmentation gives the same bits).  Longer symbols get longer segments: the prologue grows with N.
+inline int sync_tiles_per_seg(int N, int CP) { return 32 * ((N + CP + SYNC_TILE - 1) / SYNC_TILE); }
+struct SyncLaunch {
+  int wg;             // workgroups per CU the register budget is chosen for: k_sync<wg, fixed_layout>
+  bool fixed_layout;  // history no longer than a tile: [history | tile] at fixed LDS places
+  size_t lds;         // dynamic LDS of the launch (beyond CU_LDS_BYTES the call is refused)
+};
+inline SyncLaunch sync_launch_choice(int N, int CP) {
+  const int R = sync_ring_samples(sync_hist_y(N));
+  SyncLaunch l;
+  l.lds = sync_lds_layout(R, CP).total;
+  // register budget for as many workgroups per CU as the LDS footprint admits (5 at C2, fewer for long symbols)
+  const size_t fit = (size_t)CU_LDS_BYTES / l.lds;
+  l.wg = (int)(fit < (size_t)SYNC_MAX_WG ? fit : (size_t)SYNC_MAX_WG);
+  l.fixed_layout = R - SYNC_TILE <= SYNC_TILE;
+  return l;
+}
+// k_sync_exact's 256-thread variant keeps the deltas in registers between its two passes: pays for long symbols only
+inline bool sync_exact_keep(int N) { return N / 2 >= 2048; }
+// The fused front end (k_sync<3, true, F>) needs wave-sized transforms (F <= 512) and the fixed LDS layout with
+// history + carry no longer than a tile, at three workgroups per CU.
+inline bool front_eligible(int N, int CP, int ntaps) {
+  const int F = sync_filter_F(ntaps), B = F - ntaps + 1;
+  if (F > 512) return false;
+  const int HY = sync_hist_y(N), C = (B + 7) / 8 * 8;
+  if (HY + C > SYNC_TILE || CP > SYNC_TILE) return false;
+  return front_lds_layout(sync_ring_samples(HY), CP, B, F).total <= (size_t)CU_LDS_BYTES / 3;
+}
+
 template <int NT, bool KEEP>
 __global__ void __launch_bounds__(NT) k_sync_exact(SyncParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
