@@ -1,6 +1,6 @@
 // fec_punct.h -- the punctured rates 2/3, 3/4 and 5/6 of the coded-link layer (fec.h): the layer that leaves coded bits
-// out on the way to the air and puts erasures back in front of the decoder.  k_fec_encode and k_fec_decode are not
-// touched: the encoder here forms only the kept parities, the decoder reads the expanded block as any other soft block.
+// out on the way to the air and puts erasures back in front of the decoder.  The encoder here forms only the kept
+// parities, the decoder (k_fec_decode, unchanged) reads the expanded block as any other soft block.
 // Definition: include/ofdm_hip.h ("punctured rates"), arithmetic: punct_plan.h, DESIGN.md section 7.
 //
 //   kept bit q   = mother bit punct_unrank(q), q < K; zero for K <= q < 8P
@@ -24,10 +24,9 @@ struct FecPunctState {
 };
 
 // ---------------------------------------------------------------------------------
-// Punctured encoder: one workgroup per block, as k_fec_encode and with its helpers -- the payload goes to LDS once, the
-// CRC is summed there, then every thread composes whole output bytes.  A sent bit is found through the C' interleaver
-// and the pattern's unrank, and is one parity over seven info bits: the mother block is never formed, a dropped bit
-// costs nothing.  No atomics: each output byte has one writer.  blk: {payload offset, block offset, payload bytes}.
+// Punctured encoder: k_fec_encode's two passes (fec.h: fec_stage_info, fec_compose) with another bit source.  A sent bit
+// is found through the C' interleaver and the pattern's unrank, and is one parity over seven info bits: the mother
+// block is never formed, a dropped bit costs nothing.  blk: {payload offset, block offset, payload bytes}.
 // ---------------------------------------------------------------------------------
 template <uint32_t RATE>
 __global__ void __launch_bounds__(FEC_ENC_THREADS) k_fec_puncture(const uint8_t* __restrict__ payloads, const FecBlk* __restrict__ blk,
@@ -37,50 +36,11 @@ __global__ void __launch_bounds__(FEC_ENC_THREADS) k_fec_puncture(const uint8_t*
   __shared__ uint32_t red[FEC_ENC_THREADS / WAVE];
   const FecBlk b = blk[blockIdx.x];
   const uint32_t n = b.len;  // <= OFDM_FEC_MAX_PAYLOAD (the host refuses longer ones)
-  const uint8_t* src = payloads + b.in_off;
-  uint8_t* out = coded + b.out_off;
   const int tid = threadIdx.x;
-  for (int i = tid; i < FEC_INFO_LDS; i += FEC_ENC_THREADS) {
-    const int k = i - 8;
-    info[i] = (k >= 0 && (uint32_t)k < n) ? src[k] : (uint8_t)0;
-  }
-  __syncthreads();
-  uint32_t acc = fec_crc_part<8>(info, n, tid, crc_table, xp8);
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) acc ^= __shfl_xor(acc, d, WAVE);
-  if (lane_id() == 0) red[wave_id()] = acc;
-  __syncthreads();
-  if (tid < 4) {
-    uint32_t crc32 = 0;
-#pragma unroll
-    for (int w = 0; w < FEC_ENC_THREADS / WAVE; w++) crc32 ^= red[w];
-    info[8u + n + (uint32_t)tid] = (uint8_t)(crc32 >> (8 * (3 - tid)));  // struct.pack(">I", crc)
-  }
-  __syncthreads();
-
+  fec_stage_info(info, red, payloads + b.in_off, n, tid, crc_table, xp8);
   const uint32_t K = punct_kept_bits<RATE>(n);
   const uint32_t nout = (K + 7u) >> 3;
-  const uint32_t lgc = punct_log2_cols(lgC, nout);
-  const uint32_t R = (8u * nout) >> lgc;
-  for (uint32_t ob = (uint32_t)tid; ob < nout; ob += FEC_ENC_THREADS) {
-    uint32_t col = (8u * ob) / R, row = 8u * ob - col * R;
-    uint32_t by = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const uint32_t q = (row << lgc) + col;
-      uint32_t bit = 0;
-      if (q < K) {
-        const uint32_t i = punct_unrank<RATE>(q);
-        bit = (uint32_t)__popc(fec_register(info, i >> 1) & ((i & 1u) ? FEC_MASK_B : FEC_MASK_A)) & 1u;
-      }
-      by = (by << 1) | bit;
-      if (++row == R) {
-        row = 0;
-        col++;
-      }
-    }
-    out[ob] = (uint8_t)by;
-  }
+  fec_compose(coded + b.out_off, info, nout, punct_log2_cols(lgC, nout), K, tid, [](uint32_t q) { return punct_unrank<RATE>(q); });
 }
 
 // ---------------------------------------------------------------------------------

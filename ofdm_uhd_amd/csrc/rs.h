@@ -224,6 +224,43 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_encode(const uint8_t* __restr
   rs_stage_out(coded + b.out_off, info, k + OFDM_RS_PARITY * W, tid);
 }
 
+// ---- what both decoders begin and end with.  SEC: with the `second` count and its per-codeword column s_sec, which
+// only the decoder with reliabilities has (nullptr in the other) ----
+// a length that is no block: every count 0, nothing else written
+template <bool SEC>
+__device__ __forceinline__ void rs_no_block(int tid, uint8_t* __restrict__ ok, uint32_t* __restrict__ corrected, uint32_t* __restrict__ failed,
+                                            uint32_t* __restrict__ second) {
+  if (tid == 0) {
+    ok[blockIdx.x] = 0;
+    corrected[blockIdx.x] = 0;
+    failed[blockIdx.x] = 0;
+    if (SEC) second[blockIdx.x] = 0;
+  }
+}
+// the n payload bytes of the decoded block to dst, the CRC-32 of them held against the corrected CRC bytes, and the sums
+// over the block's W codewords.  Follows the barrier behind the codeword loop.
+template <bool SEC>
+__device__ __forceinline__ void rs_finish(uint8_t* __restrict__ dst, const uint8_t* blkb, uint32_t n, uint32_t W, int tid, uint32_t* red,
+                                          const uint32_t* s_corr, const uint32_t* s_fail, const uint32_t* s_sec, uint8_t* __restrict__ ok,
+                                          uint32_t* __restrict__ corrected, uint32_t* __restrict__ failed, uint32_t* __restrict__ second,
+                                          const uint32_t* __restrict__ crc_table, const uint32_t* __restrict__ xp8) {
+  rs_stage_out(dst, blkb, n, tid);
+  const uint32_t crc32 = rs_crc(blkb, n, tid, red, crc_table, xp8);
+  if (tid == 0) {
+    const uint32_t got = ((uint32_t)blkb[n] << 24) | ((uint32_t)blkb[n + 1u] << 16) | ((uint32_t)blkb[n + 2u] << 8) | (uint32_t)blkb[n + 3u];
+    uint32_t c = 0, f = 0, s2 = 0;
+    for (uint32_t w = 0; w < W; w++) {
+      c += s_corr[w];
+      f += s_fail[w];
+      if (SEC) s2 += s_sec[w];
+    }
+    ok[blockIdx.x] = crc32 == got ? 1 : 0;
+    corrected[blockIdx.x] = c;
+    failed[blockIdx.x] = f;
+    if (SEC) second[blockIdx.x] = s2;
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Decoder, per codeword (half of a wave):
 //   syndromes  lane i runs Horner by its constant alpha^i over the codeword's k_w + 32 symbols, read from the staged
@@ -236,7 +273,8 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_encode(const uint8_t* __restr
 //              shortened region is never found, so such a locator has fewer roots than its degree and fails.
 //   Forney     e = Omega(z) / (z O(z^2)), Omega = S Lambda mod x^32 (first root alpha^0: X z cancels).
 //   verdict    degree L <= 16 with L roots found: the L symbols are changed in LDS; else the codeword failed and stays.
-// Then the n payload bytes leave, and the CRC-32 of them is held against the corrected CRC bytes.
+// Then the n payload bytes leave, and the CRC-32 of them is held against the corrected CRC bytes (rs_finish).
+// The steps from the locator to the verdict are rs_errors_only.inc, one text for this kernel and k_rs_decode_rel.
 // ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(RS_THREADS) k_rs_decode(const uint8_t* __restrict__ coded, const RsBlk* __restrict__ blk,
                                                           uint8_t* __restrict__ payloads, uint8_t* __restrict__ ok,
@@ -248,14 +286,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode(const uint8_t* __restr
   const RsBlk b = blk[blockIdx.x];
   const int tid = threadIdx.x;
   uint32_t k;
-  if (!rs_info_len(b.len, &k)) {  // (uniform over the workgroup)
-    if (tid == 0) {
-      ok[blockIdx.x] = 0;
-      corrected[blockIdx.x] = 0;
-      failed[blockIdx.x] = 0;
-    }
-    return;
-  }
+  if (!rs_info_len(b.len, &k)) return rs_no_block<false>(tid, ok, corrected, failed, nullptr);  // (uniform over the workgroup)
   const uint32_t n = k - 4u, W = rs_words(k);
   const uint32_t a = rs_stage_in(lds, coded + b.in_off, b.len, tid);
   uint8_t* blkb = lds + a;
@@ -290,77 +321,10 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode(const uint8_t* __restr
       continue;
     }
     const bool dirty = rs_half_sum(S != 0 ? 1u : 0u) != 0;
-
-    // ---- Berlekamp-Massey, inversion-free ----
-    uint32_t lam = i == 0 ? 1u : 0u, B = lam, L = 0, gam = 1;
-    for (uint32_t r = 0; r < OFDM_RS_PARITY; r++) {
-      uint32_t sv = (uint32_t)__shfl((int)S, (int)((r - i) & 31u), 32);
-      sv = i <= r ? sv : 0u;
-      const uint32_t d = rs_half_xor(rs_mul(lam, sv));
-      uint32_t Bs = (uint32_t)__shfl_up((int)B, 1, 32);
-      if (i == 0) Bs = 0;
-      const uint32_t T = rs_mul(gam, lam) ^ rs_mul(d, Bs);
-      const bool upd = d != 0 && 2u * L <= r;
-      B = upd ? lam : Bs;
-      gam = upd ? d : gam;
-      L = upd ? r + 1u - L : L;
-      lam = T;
-    }
-    // every lane gets Lambda_0 .. Lambda_16 and Omega_0 .. Omega_15 of its half
-    uint32_t lm[17], om[16];
-#pragma unroll
-    for (int j = 0; j < 17; j++) lm[j] = (uint32_t)__shfl((int)lam, j, 32);
+    uint32_t L;  // locator, roots, Forney, verdict
+    bool good;
     {
-      uint32_t acc = 0;  // Omega_i = sum_{j <= i} Lambda_j S_(i - j), in lane i < 16
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        const uint32_t sv = (uint32_t)__shfl((int)S, (int)((i - (uint32_t)j) & 31u), 32);
-        acc ^= (uint32_t)j <= i ? rs_mul(lm[j], sv) : 0u;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; j++) om[j] = (uint32_t)__shfl((int)acc, j, 32);
-    }
-
-    // ---- roots over the real positions, Forney ----
-    const bool tryit = L >= 1u && L <= 16u;
-    uint32_t err[8], nroot = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      err[q] = 0;
-      const uint32_t p = i + 32u * (uint32_t)q;
-      if (tryit && p < len) {
-        const uint32_t deg = len - 1u - p;                    // the symbol's power of x: X = alpha^deg
-        const uint32_t z = rs_tab.exp[deg ? 255u - deg : 0u];  // X^-1
-        const RsCols cz = rs_cols(z);
-        const RsCols cy = rs_cols(rs_mulc(cz, z));
-        uint32_t E = lm[16], O = lm[15];
-#pragma unroll
-        for (int j = 6; j >= 0; j--) {
-          E = rs_mulc(cy, E) ^ lm[2 * j + 2];
-          O = rs_mulc(cy, O) ^ lm[2 * j + 1];
-        }
-        E = rs_mulc(cy, E) ^ lm[0];
-        const uint32_t zO = rs_mulc(cz, O);
-        if ((E ^ zO) == 0u) {
-          nroot++;
-          uint32_t v = om[15];
-#pragma unroll
-          for (int j = 14; j >= 0; j--) v = rs_mulc(cz, v) ^ om[j];
-          err[q] = rs_mul(v, rs_inv(zO));
-        }
-      }
-    }
-    nroot = rs_half_sum(nroot);
-    const bool good = tryit && nroot == L;
-    if (good) {
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        const uint32_t p = i + 32u * (uint32_t)q;
-        if (err[q]) {  // (only where p < len) one writer per byte: position p of codeword w is this lane's alone
-          const uint32_t at = p < kw ? p * W + w : k + (p - kw) * W + w;
-          blkb[at] = (uint8_t)((uint32_t)blkb[at] ^ err[q]);
-        }
-      }
+#include "rs_errors_only.inc"
     }
     if (active && i == 0) {
       s_corr[w] = good ? L : 0u;
@@ -369,24 +333,12 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode(const uint8_t* __restr
   }
   __syncthreads();
 
-  rs_stage_out(payloads + b.out_off, blkb, n, tid);
-  const uint32_t crc32 = rs_crc(blkb, n, tid, red, crc_table, xp8);
-  if (tid == 0) {
-    const uint32_t got = ((uint32_t)blkb[n] << 24) | ((uint32_t)blkb[n + 1u] << 16) | ((uint32_t)blkb[n + 2u] << 8) | (uint32_t)blkb[n + 3u];
-    uint32_t c = 0, f = 0;
-    for (uint32_t w = 0; w < W; w++) {
-      c += s_corr[w];
-      f += s_fail[w];
-    }
-    ok[blockIdx.x] = crc32 == got ? 1 : 0;
-    corrected[blockIdx.x] = c;
-    failed[blockIdx.x] = f;
-  }
+  rs_finish<false>(payloads + b.out_off, blkb, n, W, tid, red, s_corr, s_fail, nullptr, ok, corrected, failed, nullptr, crc_table, xp8);
 }
 
 // ---------------------------------------------------------------------------------
 // Decoder with reliabilities (include/ofdm_hip.h, "decoding with reliabilities").  k_rs_decode's layout and, as the first
-// pass, k_rs_decode's steps, restated here so that k_rs_decode's own text stays what it is; the block's reliability
+// pass, k_rs_decode's steps: syndromes by the same Horner loop, then the same rs_errors_only.inc; the block's reliability
 // bytes are staged next to it.  Two wave-uniform exits: clean input, and no half of the wave failing the first pass.
 // A half whose codeword failed goes on:
 //   threshold  tau* by an 8-step search upwards bit by bit; each step counts over the lane's <= 8 positions and sums over
@@ -415,15 +367,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode_rel(const uint8_t* __r
   const RsBlk b = blk[blockIdx.x];
   const int tid = threadIdx.x;
   uint32_t k;
-  if (!rs_info_len(b.len, &k)) {  // (uniform over the workgroup)
-    if (tid == 0) {
-      ok[blockIdx.x] = 0;
-      corrected[blockIdx.x] = 0;
-      failed[blockIdx.x] = 0;
-      second[blockIdx.x] = 0;
-    }
-    return;
-  }
+  if (!rs_info_len(b.len, &k)) return rs_no_block<true>(tid, ok, corrected, failed, second);  // (uniform over the workgroup)
   const uint32_t n = k - 4u, W = rs_words(k);
   const uint32_t a = rs_stage_in(lds, coded + b.in_off, b.len, tid);
   const uint32_t ar = rs_stage_in(lds_rel, rel + rel_off[blockIdx.x], b.len, tid);
@@ -438,7 +382,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode_rel(const uint8_t* __r
     const bool active = w < W;
     const uint32_t kw = active ? rs_cw_info(k, W, w) : 0u;  // (a half without a codeword sees the empty word: clean)
     const uint32_t len = active ? kw + OFDM_RS_PARITY : 0u;
-    // ---- first pass: k_rs_decode's steps ----
+    // ---- first pass: syndromes, then the errors-only pass ----
     uint32_t S = 0;
     for (uint32_t s = 0; s < kw; s++) S = rs_mulc(ai, S) ^ (uint32_t)blkb[s * W + w];
     for (uint32_t s = kw; s < len; s++) S = rs_mulc(ai, S) ^ (uint32_t)blkb[k + (s - kw) * W + w];
@@ -451,73 +395,10 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode_rel(const uint8_t* __r
       continue;
     }
     const bool dirty = rs_half_sum(S != 0 ? 1u : 0u) != 0;
-    uint32_t lam = i == 0 ? 1u : 0u, B = lam, L = 0, gam = 1;
-    for (uint32_t r = 0; r < OFDM_RS_PARITY; r++) {
-      uint32_t sv = (uint32_t)__shfl((int)S, (int)((r - i) & 31u), 32);
-      sv = i <= r ? sv : 0u;
-      const uint32_t d = rs_half_xor(rs_mul(lam, sv));
-      uint32_t Bs = (uint32_t)__shfl_up((int)B, 1, 32);
-      if (i == 0) Bs = 0;
-      const uint32_t T = rs_mul(gam, lam) ^ rs_mul(d, Bs);
-      const bool upd = d != 0 && 2u * L <= r;
-      B = upd ? lam : Bs;
-      gam = upd ? d : gam;
-      L = upd ? r + 1u - L : L;
-      lam = T;
-    }
+    uint32_t L;
     bool good;
     {
-      uint32_t lm[17], om[16];
-#pragma unroll
-      for (int j = 0; j < 17; j++) lm[j] = (uint32_t)__shfl((int)lam, j, 32);
-      uint32_t acc = 0;
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        const uint32_t sv = (uint32_t)__shfl((int)S, (int)((i - (uint32_t)j) & 31u), 32);
-        acc ^= (uint32_t)j <= i ? rs_mul(lm[j], sv) : 0u;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; j++) om[j] = (uint32_t)__shfl((int)acc, j, 32);
-      const bool tryit = L >= 1u && L <= 16u;
-      uint32_t err[8], nroot = 0;
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        err[q] = 0;
-        const uint32_t p = i + 32u * (uint32_t)q;
-        if (tryit && p < len) {
-          const uint32_t deg = len - 1u - p;
-          const uint32_t z = rs_tab.exp[deg ? 255u - deg : 0u];
-          const RsCols cz = rs_cols(z);
-          const RsCols cy = rs_cols(rs_mulc(cz, z));
-          uint32_t E = lm[16], O = lm[15];
-#pragma unroll
-          for (int j = 6; j >= 0; j--) {
-            E = rs_mulc(cy, E) ^ lm[2 * j + 2];
-            O = rs_mulc(cy, O) ^ lm[2 * j + 1];
-          }
-          E = rs_mulc(cy, E) ^ lm[0];
-          const uint32_t zO = rs_mulc(cz, O);
-          if ((E ^ zO) == 0u) {
-            nroot++;
-            uint32_t v = om[15];
-#pragma unroll
-            for (int j = 14; j >= 0; j--) v = rs_mulc(cz, v) ^ om[j];
-            err[q] = rs_mul(v, rs_inv(zO));
-          }
-        }
-      }
-      nroot = rs_half_sum(nroot);
-      good = tryit && nroot == L;
-      if (good) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-          const uint32_t p = i + 32u * (uint32_t)q;
-          if (err[q]) {
-            const uint32_t at = p < kw ? p * W + w : k + (p - kw) * W + w;
-            blkb[at] = (uint8_t)((uint32_t)blkb[at] ^ err[q]);
-          }
-        }
-      }
+#include "rs_errors_only.inc"
     }
     const bool fail1 = dirty && !good;
     if (__ballot(fail1) == 0ull) {  // the first pass decoded every codeword of the wave: wave-uniform
@@ -662,21 +543,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_decode_rel(const uint8_t* __r
   }
   __syncthreads();
 
-  rs_stage_out(payloads + b.out_off, blkb, n, tid);
-  const uint32_t crc32 = rs_crc(blkb, n, tid, red, crc_table, xp8);
-  if (tid == 0) {
-    const uint32_t got = ((uint32_t)blkb[n] << 24) | ((uint32_t)blkb[n + 1u] << 16) | ((uint32_t)blkb[n + 2u] << 8) | (uint32_t)blkb[n + 3u];
-    uint32_t c = 0, f = 0, s2 = 0;
-    for (uint32_t w = 0; w < W; w++) {
-      c += s_corr[w];
-      f += s_fail[w];
-      s2 += s_sec[w];
-    }
-    ok[blockIdx.x] = crc32 == got ? 1 : 0;
-    corrected[blockIdx.x] = c;
-    failed[blockIdx.x] = f;
-    second[blockIdx.x] = s2;
-  }
+  rs_finish<true>(payloads + b.out_off, blkb, n, W, tid, red, s_corr, s_fail, s_sec, ok, corrected, failed, second, crc_table, xp8);
 }
 
 // ---------------------------------------------------------------------------------
