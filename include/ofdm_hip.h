@@ -1061,6 +1061,72 @@ int ofdm_multipath(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, const of
  * and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is unchanged. */
 int ofdm_multipath_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- transmit crest-factor reduction: peak windowing in front of a converter -----------------------------------------
+ * The modem's output has a peak-to-average power ratio of 10 to 11 dB; the clamp of the ofdm_sc16 store is a hard clip
+ * per I and Q part.  This stage is the last one of a transmit chain, behind ofdm_tx and ofdm_duc / ofdm_tx_resamp:
+ * every peak above a threshold is pulled down to it by a smooth dip of the gain, of the shape of a window the caller
+ * supplies, and the stage counts what it did.  It has the call shape of ofdm_multipath without `add`: nin samples in,
+ * nin samples out, stateful across calls.
+ * Definition.  A = threshold, H = (ntaps - 1) / 2, w[k] = taps[k]; n is the stream index, x[n] indexed from the last
+ * reset (ofdm_set_cfr, ofdm_cfr_reset) and zero before it.  All arithmetic is float32, every operation rounded once:
+ *   m[n]   = sqrtf(x[n].re * x[n].re + x[n].im * x[n].im)     two products, one addition, one square root
+ *   c[n]   = m[n] > A ? 1.0f - A / m[n] : 0.0f                 (a NaN magnitude gives 0; c[n] = 0 for n before the reset)
+ *   s[n]   = sum over k in [0, 2H] of w[k] * c[n - k]          product, then addition, in ascending k, begun at +0
+ *   b[n]   = fmaxf(0.0f, 1.0f - s[n])
+ *   y[n]   = (b[n] * x[n - H].re, b[n] * x[n - H].im)
+ *   out[n] = store(y[n])                                       complex64, or ofdm_sc16 by the transmit rule of ofdm_duc
+ * The output is the input delayed by H samples.  H = 0 is the polar clip.  Because w[H] = 1, s[n] >= c[n - H] and
+ * |y[n]| <= A up to rounding: max |y| <= A (1 + 2^-22) + 2^-24 max |x|.  Every term is a function of the stream alone: a
+ * stream fed in any segmentation gives bit-identical outputs; calls of 0 inputs and calls shorter than 2H are included.
+ *   state     the last 2H inputs.  A call with nin inputs produces exactly nin outputs; the last H samples of a
+ *             stream come out when H more samples (zeros) are pushed behind it.
+ * Statistics accumulate from ofdm_set_cfr / ofdm_cfr_reset on, over the inputs (n, n_over, peak_in, sum_in) and the
+ * outputs (the others) of the calls since.  m^2 and |y|^2 are the float32 re * re + im * im; a term of sum_err is the
+ * float32 (y.re - x.re)^2 + (y.im - x.im)^2 with x = x[n - H]: two differences, two squares, one addition.  Counts and
+ * maxima (fmaxf, from 0: a NaN is not counted) do not depend on how the stream was cut; the float64 sums are added per
+ * workgroup and then per call in a fixed order, so equal calls give equal sums, and two segmentations differ by the
+ * rounding of float64 additions alone.
+ * Pointers are host or device as the handle was created.  iq_in is complex64 and must not overlap iq_out: a workgroup
+ * reads the inputs of its neighbours' outputs.  Like ofdm_duc, the call orders itself behind an ofdm_tx_async still in
+ * flight and returns after the stream drained.  The kernel takes no id in the OFDM_K_* table (ofdm_cfr_last_ms).
+ * OFDM_E_INVAL: bad struct_size; a threshold not finite or <= 0; ntaps even, 0 or above OFDM_CFR_MAX_TAPS;
+ * taps[H] != 1; a tap outside [0, 1] or NaN; bad out_format or out_scale (entries beyond ntaps are not looked at);
+ * ofdm_cfr / ofdm_cfr_reset / ofdm_cfr_stats without a configuration; a float32 pointer not 8-byte (ofdm_sc16:
+ * 4-byte) aligned; iq_in overlapping iq_out; a call too long for one grid (2^34 samples: split it).  A refused
+ * configuration leaves the one in force (or none), stream state and statistics included, as it was.
+ * OFDM_E_CAPACITY: out_cap < nin (*nout is set); the stream state is then unchanged. */
+#define OFDM_CFR_MAX_TAPS 1023
+typedef struct ofdm_cfr_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_cfr_cfg) */
+  float threshold;        /* A: finite, > 0 */
+  uint32_t ntaps;         /* 2H + 1: odd, 1..OFDM_CFR_MAX_TAPS */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  float taps[OFDM_CFR_MAX_TAPS]; /* the window: every value in [0, 1], taps[H] == 1 */
+} ofdm_cfr_cfg;
+struct ofdm_cfr_stats {   /* (a tag only: ofdm_cfr_stats is the function below) */
+  uint64_t n;             /* samples */
+  uint64_t n_over;        /* inputs with m > A */
+  uint64_t n_touched;     /* outputs with b < 1 */
+  float peak_in;          /* max m^2 */
+  float peak_out;         /* max |y|^2 */
+  double sum_in;          /* sum of m^2 */
+  double sum_out;         /* sum of |y|^2 */
+  double sum_err;         /* sum of |y[n] - x[n - H]|^2 */
+};
+/* NULL: none (touches no device memory).  Resets the stream state (history zero) and the statistics. */
+int ofdm_set_cfr(ofdm_handle *h, const ofdm_cfr_cfg *cfg);
+/* a new stream: history zero, statistics zero */
+int ofdm_cfr_reset(ofdm_handle *h);
+/* the next nin samples of the stream in, nin samples out */
+int ofdm_cfr(ofdm_handle *h, const ofdm_c32 *iq_in, uint64_t nin, void *iq_out, uint64_t out_cap, uint64_t *nout);
+/* the statistics since ofdm_set_cfr / ofdm_cfr_reset */
+int ofdm_cfr_stats(ofdm_handle *h, struct ofdm_cfr_stats *out);
+/* HIP-event time of k_cfr and the reduction of its partials in the last ofdm_cfr, which must have run with profiling
+ * on (ofdm_prof_enable) and produced output; OFDM_E_INVAL otherwise.  As ofdm_ddc_last_ms: the OFDM_K_* table is
+ * unchanged. */
+int ofdm_cfr_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- coded links: rate-1/2, K = 7 convolutional code over the payload, Viterbi decoder on the GPU --------------------
  * A forward-error-correcting layer at the payload boundary: ofdm_fec_encode turns payloads into coded blocks that go
  * to ofdm_tx / ofdm_make_packets as payloads; ofdm_fec_decode takes the payloads ofdm_rx delivered (CRC-failed ones

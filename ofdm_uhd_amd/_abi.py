@@ -27,6 +27,7 @@ OFDM_PFB_MAX_TAPS = 1024
 OFDM_MULTIPATH_MAX_PATHS = 16
 OFDM_MULTIPATH_MAX_TONES = 4
 OFDM_MULTIPATH_MAX_DELAY = 1023
+OFDM_CFR_MAX_TAPS = 1023
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
@@ -294,6 +295,33 @@ class ofdm_multipath_cfg(C.Structure):
     ]
 
 
+class ofdm_cfr_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("threshold", C.c_float),
+        ("ntaps", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("out_scale", C.c_float),
+        ("taps", C.c_float * OFDM_CFR_MAX_TAPS),
+    ]
+
+
+class ofdm_cfr_stats(C.Structure):        # the header's ``struct ofdm_cfr_stats`` (a tag: the name is the function's)
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_over", C.c_uint64),
+        ("n_touched", C.c_uint64),
+        ("peak_in", C.c_float),
+        ("peak_out", C.c_float),
+        ("sum_in", C.c_double),
+        ("sum_out", C.c_double),
+        ("sum_err", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ofdm_fec_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -359,6 +387,7 @@ EXPORTS = (
     "ofdm_set_tx_resamp_bank", "ofdm_tx_resamp_bank_reset", "ofdm_tx_resamp_bank_count", "ofdm_tx_resamp_bank",
     "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
+    "ofdm_set_cfr", "ofdm_cfr_reset", "ofdm_cfr", "ofdm_cfr_stats", "ofdm_cfr_last_ms",
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
@@ -460,6 +489,11 @@ def _declare(lib):
     lib.ofdm_multipath_reset.argtypes = [H, C.c_uint64]
     lib.ofdm_multipath.argtypes = [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
     lib.ofdm_multipath_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_cfr.argtypes = [H, C.POINTER(ofdm_cfr_cfg)]
+    lib.ofdm_cfr_reset.argtypes = [H]
+    lib.ofdm_cfr.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
+    lib.ofdm_cfr_stats.argtypes = [H, C.POINTER(ofdm_cfr_stats)]
+    lib.ofdm_cfr_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     FC = C.POINTER(ofdm_fec_cfg)
     lib.ofdm_fec_coded_len.argtypes = [C.c_uint32, u32p]
     lib.ofdm_fec_payload_len.argtypes = [C.c_uint32, u32p]

@@ -54,6 +54,13 @@ def make_parser():
     parser.add_option("", "--duc-freq", type="eng_float", default=0.0,
                       help="with --duc-interp: centre of the link in the wideband file, cycles per sample in "
                            "[-0.5, 0.5] (the radio's set_center_freq over the file's rate) [default=%default]")
+    parser.add_option("", "--cfr-papr", type="eng_float", default=None,
+                      help="crest-factor reduction as the last stage, on the GPU: pull every peak down to this many dB "
+                           "above the level of the data symbols by a smooth dip of the gain; the figures (PAPR in and "
+                           "out, EVM) are printed at the end [default=off]")
+    parser.add_option("", "--cfr-half-width", type="intx", default=16,
+                      help="with --cfr-papr: half-width of the gain dip in samples, 0 to 511 (0: polar clip); the "
+                           "stream comes out this many samples late [default=%default]")
     parser.add_option("", "--fec", action="store_true", default=False,
                       help="coded link: protect every payload (at most 2040 bytes) with the rate-1/2 K=7 convolutional "
                            "code and interleaver, encoded on the GPU; demodulate with benchmark_ofdm_rx --fec "
@@ -98,6 +105,8 @@ def _main_tx_resamp_bank(parser, options):
         parser.error("--tx-resamp-freqs does not combine with --duc-interp or --duc-freq")
     if options.fec or options.rs or options.ldpc or options.sig:
         parser.error("--tx-resamp-freqs does not combine with --fec, --ldpc, --rs or --sig")
+    if options.cfr_papr is not None:
+        parser.error("--tx-resamp-freqs does not combine with --cfr-papr")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -156,7 +165,12 @@ def main(argv=None):
     if src is not None:
         print(os.path.getsize(options.from_file))
 
-    txpath = transmit_path.transmit_path(options)
+    try:
+        txpath = transmit_path.transmit_path(options)
+    except ValueError as e:
+        if options.cfr_papr is None:
+            raise
+        parser.error("--cfr-papr / --cfr-half-width: %s" % e)
     sink = iqio.file_sink(options.to_file, fmt=options.iq_format)   # (transmit_path takes the format, --fec, --rs and --duc-interp / --duc-freq, --tx-resamp-* from the options)
     txpath.connect(sink)
     npk = 0
@@ -167,6 +181,10 @@ def main(argv=None):
     txpath.send_pkt(eof=True)
     sink.close()
     sys.stderr.write("\n%d packets, %d symbols -> %s\n" % (npk, txpath.ofdm_tx.symbols_sent, options.to_file))
+    r = txpath.ofdm_tx.last_cfr
+    if r is not None:
+        sys.stderr.write("cfr: PAPR %.2f -> %.2f dB, EVM %.1f dB, %.3g of the samples over the threshold, %.3g touched\n" % (
+            r["papr_in_db"], r["papr_out_db"], r["evm_db"], r["share_over"], r["share_touched"]))
     return npk
 
 

@@ -10,7 +10,8 @@
 // copy in their place.  Included by engine.hip ahead of engine_{ddc,ddc_bank,duc,resamp,resamp_bank,tx_resamp,pfb,
 // pfb_synth,duc_bank,tx_resamp_bank}.inc (in that order: a bank uses its single stage's index limit), which keep what
 // is a stage's own: its configuration checks and messages, its index limits, its output count, its Params and its
-// template dispatch.  engine_multipath.inc, the propagation channel stage, follows them with the transmit single shape.
+// template dispatch.  engine_multipath.inc, the propagation channel stage, and engine_cfr.inc, the crest-factor reduction
+// stage, follow them with the transmit single shape.
 
 #define RCCHK(expr)         \
   do {                      \

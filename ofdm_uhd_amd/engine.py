@@ -112,6 +112,7 @@ class Engine(object):
         self.duc_bank_cfg = None  # the DUC bank's configuration in force (set_duc_bank), None without one
         self.tx_resamp_bank_cfg = None  # the transmit resampler bank's configuration in force (set_tx_resamp_bank), None without one
         self.multipath_cfg = None  # the propagation channel's configuration in force (set_multipath), None without one
+        self.cfr_cfg = None  # the crest-factor reduction stage's configuration in force (set_cfr), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -842,6 +843,47 @@ class Engine(object):
     def multipath_last_ms(self):
         """HIP-event time of k_multipath in the last multipath() / multipath_device() (needs prof_enable())."""
         return self._stage_last_ms("multipath")
+
+    # -- transmit crest-factor reduction (peak windowing, the last stage in front of a converter) -------------------
+    def set_cfr(self, cfg=None, **kw):
+        """Configure the crest-factor reduction stage: an ``ofdm_cfr_cfg`` (cfr.cfr_cfg) or its keywords (threshold=,
+        window=, out_format=, out_scale=).  ``set_cfr(None)`` with no keywords removes it.  Resets the stream state
+        and the statistics."""
+        self._stage_set("cfr", "cfr.cfr_cfg", cfg, kw)
+
+    def cfr_reset(self):
+        """Start a new stream: the history and the statistics are zero."""
+        self._check(self._lib.ofdm_cfr_reset(self._h))
+
+    def cfr(self, iq):
+        """Host mode: the next complex64 samples of the stream -> as many samples (complex64, or int16 of shape (n, 2)
+        with out_format "sc16"), delayed by the window's half-width, every peak above the threshold pulled down to it.
+        Stateful: any segmentation of a stream gives the same bits."""
+        assert not self.device_ptrs
+        if self.cfr_cfg is None:
+            raise ValueError("cfr() without set_cfr()")
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("cfr() takes complex64 samples (its 16-bit side is the output)")
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        n = len(iq)
+        sc16 = self.cfr_cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(n, 1), 2), np.int16) if sc16 else np.zeros(max(n, 1), np.complex64)
+        return out[:self._stage_call("cfr", _ptr(iq) if n else None, n, _ptr(out), len(out))]
+
+    def cfr_device(self, iq_ptr, nin, out_ptr, out_cap):
+        """Device mode: both buffers are device pointers and must not overlap.  Returns the number of outputs written."""
+        return self._stage_device("cfr", C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap))
+
+    def cfr_stats(self):
+        """The statistics since set_cfr() / cfr_reset() as a dict: n, n_over, n_touched, peak_in, peak_out, sum_in,
+        sum_out, sum_err (ofdm_cfr_stats; cfr.report turns them into PAPR and EVM figures)."""
+        st = _abi.ofdm_cfr_stats()
+        self._check(self._lib.ofdm_cfr_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def cfr_last_ms(self):
+        """HIP-event time of k_cfr and its reduction in the last cfr() / cfr_device() (needs prof_enable())."""
+        return self._stage_last_ms("cfr")
 
     # -- coded links: the two call shapes every codec shares (the counterpart of csrc/engine_codec.inc) ----------------
     # ``head`` is what a call takes ahead of its batch: () or (C.byref(cfg),).

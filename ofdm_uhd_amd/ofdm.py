@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from . import config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import cfr as _cfr, config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -28,9 +28,18 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=False):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=False, cfr=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
+        @param cfr: crest-factor reduction, ``dict(papr_db=7.0, half_width=16[, threshold=][, kind="hann"])``: the
+               engine's peak-windowing stage (cfr.py, Engine.cfr) runs last, behind ``duc`` / ``resample`` where there is
+               one; those stages then emit complex64 and this one does the ``iq_format`` store.  Peaks are pulled down to
+               ``threshold``, by default ``papr_db`` above cfr.modem_rms(options) times the pass-band gain of the
+               wideband stage in front (the level of the data symbols in the stream that enters the stage).  The stream
+               comes out ``half_width`` samples late and continues across flush() calls; flush(end=True) /
+               send_pkt(eof=True) pushes ``half_width`` zeros so that the tail comes out, and starts the stage afresh.
+               ``last_cfr`` holds the figures (cfr.report, against that level) of the stream that ended last, or of
+               the running one.  None: nothing new runs
         @param sig: self-describing coded link (sig.py): every block goes out behind a 12-byte signal field that names
                its coding, so the receiving end, ofdm_demod(sig=True), needs no coding setting.  ``fec`` / ``ldpc`` /
                ``rs`` then only choose the default coding; ``send_pkt(payload, coding=...)`` overrides it per packet, and
@@ -96,21 +105,41 @@ class ofdm_mod(object):
         self._duc = None             # the wideband stage in force: "duc" or "tx_resamp" (Engine.<stage>, <stage>_reset, <stage>_cfg)
         self._duc_live = False       # the wideband stream holds samples whose filter tail is still to come
         occ = self._occupied_tones / float(self._fft_length)
+        self._cfr = None if cfr is None else dict(cfr)   # with it, the stage in front stores complex64
+        stage_format, stage_scale = (iq_format, iq_scale) if cfr is None else ("fc32", None)
         if duc is not None:
             # the 16-bit format, if any, is the wideband side's: the modulator's output (the stage's input) is complex64
             d = dict(duc)
             self._engine.set_duc(_duc.duc_cfg(d.pop("interpolation"), d.pop("center_freq"), taps=d.pop("taps", None),
                                               occupied_fraction=occ,
-                                              out_format=iqio.check_format(iq_format), out_scale=iq_scale, **d))
+                                              out_format=iqio.check_format(stage_format), out_scale=stage_scale, **d))
             self._duc = "duc"
         elif resample is not None:
             d = dict(resample)
             self._engine.set_tx_resamp(_tx_resample.tx_resamp_cfg(
                 d.pop("interpolation"), d.pop("decimation"), d.pop("center_freq", 0.0), taps=d.pop("taps", None),
-                occupied_fraction=occ, out_format=iqio.check_format(iq_format), out_scale=iq_scale, **d))
+                occupied_fraction=occ, out_format=iqio.check_format(stage_format), out_scale=stage_scale, **d))
             self._duc = "tx_resamp"
-        elif iqio.check_format(iq_format) != "fc32":
+        elif iqio.check_format(stage_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
+        self._cfr_live = False       # the stage holds samples that are still to come out
+        self._cfr_rms = None         # the level its threshold was set against
+        self._last_cfr = None
+        if self._cfr is not None:
+            d = self._cfr
+            gain = 1.0
+            if self._duc is not None:
+                # pass-band gain of the stage in front: its prototype low-pass at zero frequency, over L
+                wide = getattr(self._engine, self._duc + "_cfg")
+                gain = abs(float(np.sum(np.array(wide.taps[:wide.ntaps], np.float64)))) / float(wide.interpolation)
+            thr = d.pop("threshold", None)
+            papr = d.pop("papr_db", 7.0)
+            window = _cfr.design(d.pop("half_width", 16), d.pop("kind", "hann"))
+            if d:
+                raise ValueError("cfr= takes papr_db, half_width, threshold and kind, not %s" % ", ".join(sorted(d)))
+            self._cfr = dict(threshold=thr, papr_db=papr, window=window, level=_cfr.modem_rms(cfg_opts) * gain,
+                             out_format=iqio.check_format(iq_format), out_scale=iq_scale)
+            self.set_cfr_amplitude(1.0)
         self._fec = _fec.as_cfg(fec)
         self._ldpc = _ldpc.as_cfg(ldpc)
         if self._fec is not None and self._ldpc is not None:
@@ -143,6 +172,25 @@ class ofdm_mod(object):
 
     def engine(self):
         return self._engine
+
+    def set_cfr_amplitude(self, ampl):
+        """Tell the crest-factor reduction stage (cfr=) the transmit amplitude of the engine (transmit_path does, with
+        every set_tx_amplitude): the level its threshold is ``papr_db`` above follows it.  Starts the stage afresh."""
+        if self._cfr is None:
+            return
+        c = self._cfr
+        self._cfr_rms = c["level"] * float(ampl)
+        thr = c["threshold"] if c["threshold"] is not None else _cfr.threshold_for(c["papr_db"], self._cfr_rms)
+        self._engine.set_cfr(_cfr.cfr_cfg(thr, c["window"], out_format=c["out_format"], out_scale=c["out_scale"]))
+        self._cfr_live = False
+
+    @property
+    def last_cfr(self):
+        """cfr.report of the crest-factor reduction stage (cfr=), against the level its threshold was set against: of
+        the stream flush(end=True) ended last, or of the running one.  None without the stage or before any sample."""
+        if self._cfr is not None and self._cfr_live:
+            return _cfr.report(self._engine.cfr_stats(), self._cfr_rms)
+        return self._last_cfr
 
     # -- packets ------------------------------------------------------------------
     def send_pkt(self, payload='', eof=False, coding=None):
@@ -214,8 +262,10 @@ class ofdm_mod(object):
     def flush(self, end=False):
         """Modulate everything queued so far; returns the samples (also written to the sink).  With a wideband stage
         (duc= / resample=) they are the wideband stream's next samples (with resample= possibly none yet); ``end=True`` then appends the filter's tail (Q zero
-        narrowband samples pushed through) and starts the stage afresh."""
-        end = end and self._duc is not None and (self._duc_live or bool(self._pending))
+        narrowband samples pushed through) and starts the stage afresh.  With cfr= the samples went through the
+        crest-factor reduction stage last and come out half_width samples late; ``end=True`` pushes that many zeros."""
+        end = end and (self._duc is not None or self._cfr is not None) and (
+            self._duc_live or self._cfr_live or bool(self._pending))
         if not self._pending and not end:
             return None
         iq = None
@@ -246,6 +296,16 @@ class ofdm_mod(object):
                 parts.append(run(np.zeros((cfg.ntaps - 1) // cfg.interpolation, np.complex64)))
                 getattr(eng, self._duc + "_reset")(0)
                 self._duc_live = False
+            iq = np.concatenate(parts) if len(parts) > 1 else parts[0]
+        if self._cfr is not None:
+            eng = self._engine
+            parts = [eng.cfr(iq)] if iq is not None else []
+            self._cfr_live = True
+            if end:
+                parts.append(eng.cfr(np.zeros(_cfr.half_width(eng.cfr_cfg), np.complex64)))
+                self._last_cfr = _cfr.report(eng.cfr_stats(), self._cfr_rms)
+                eng.cfr_reset()
+                self._cfr_live = False
             iq = np.concatenate(parts) if len(parts) > 1 else parts[0]
         if self._sink is not None:
             self._sink.write(iq)

@@ -18,7 +18,7 @@ _FLAGS = (
 
 class transmit_path(object):
     def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=None, cfr=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
@@ -34,7 +34,10 @@ class transmit_path(object):
         ``ldpc``: the other inner code of ofdm_mod, ``True`` or ``dict(max_iters=20, rate="1/2")``; None: the options' ``ldpc``
         (--ldpc, --ldpc-rate).
         ``sig``: the signal field of ofdm_mod, ``True``; None: the options' ``sig`` (--sig).  ``fec`` / ``ldpc`` / ``rs``
-        then choose the coding that every packet announces."""
+        then choose the coding that every packet announces.
+        ``cfr``: crest-factor reduction of ofdm_mod, ``dict(papr_db=7.0, half_width=16[, threshold=])``, the last stage;
+        None: the options' ``cfr_papr`` / ``cfr_half_width`` (--cfr-papr / --cfr-half-width), no stage where cfr_papr
+        is unset.  The threshold follows the transmit amplitude."""
         opts = copy.copy(options)
         if rs is None:
             rs = bool(getattr(opts, "rs", None))
@@ -52,12 +55,17 @@ class transmit_path(object):
             duc = dict(interpolation=int(opts.duc_interp), center_freq=float(getattr(opts, "duc_freq", 0.0) or 0.0))
         if resample is None:
             resample = _options.tx_resamp_from_options(opts)
+        if cfr is None and getattr(opts, "cfr_papr", None) is not None:
+            hw = getattr(opts, "cfr_half_width", None)
+            cfr = dict(papr_db=float(opts.cfr_papr), half_width=16 if hw is None else int(hw))
         self._apply_carrier_map = bool(apply_carrier_map)
+        self._cfr = cfr is not None
         self._verbose = bool(getattr(opts, "verbose", False))
         self._samples_per_symbol = getattr(opts, "samples_per_symbol", 2)
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
-                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc, sig=sig)
+                                     iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc, sig=sig,
+                                     cfr=cfr)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
@@ -73,6 +81,8 @@ class transmit_path(object):
         """Output gain, clamped to [0, 1] as transmit_path.py:56-62 does."""
         self._tx_amplitude = min(max(ampl, 0.0), 1)
         self.ofdm_tx.engine().set_tx_amplitude(self._tx_amplitude)
+        if self._cfr:
+            self.ofdm_tx.set_cfr_amplitude(self._tx_amplitude)   # the threshold follows the amplitude
 
     def send_pkt(self, payload='', eof=False, carrier_map_new="FE7F"):
         """Queue one packet (or end the burst with eof=True).  A changed carrier map is only recorded,
