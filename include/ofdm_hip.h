@@ -1127,6 +1127,77 @@ int ofdm_cfr_stats(ofdm_handle *h, struct ofdm_cfr_stats *out);
  * unchanged. */
 int ofdm_cfr_last_ms(const ofdm_handle *h, double *ms);
 
+/* --- transmit linearisation: a memory polynomial as predistorter and as power-amplifier model -------------------------
+ * Peaks are limited (ofdm_cfr) because a power amplifier follows the converter.  This stage is a memory polynomial over
+ * the stream: with one coefficient table it is the usual behavioural model of such an amplifier, with another it is
+ * that amplifier's digital predistorter (the table comes from a least-squares fit on the host: dpd.py).  A handle
+ * holds two instances, each with its own configuration, history, statistics and timer: slot OFDM_MEMPOLY_DPD, the
+ * transmit side (behind ofdm_cfr, in front of the converter), and slot OFDM_MEMPOLY_PA, the air side (in front of
+ * ofdm_multipath).  It has the call shape of ofdm_cfr: nin samples in, nin samples out, stateful across calls, no delay.
+ * Definition.  M = memory, K = orders (the odd orders 1, 3, .., 2K - 1), a[m][k] = coef[m * OFDM_MEMPOLY_MAX_ORDERS + k];
+ * n is the stream index, x[n] indexed from the last reset (ofdm_set_mempoly, ofdm_mempoly_reset) and zero before it.
+ * All arithmetic is float32, every operation rounded once, nothing contracted:
+ *   p[j]   = x[j].re * x[j].re + x[j].im * x[j].im           two products, one addition
+ *   h_m[j] = Horner in p[j], from the top: h = a[m][K-1]; for k = K-2 .. 0:
+ *            h = (h.re * p[j] + a[m][k].re, h.im * p[j] + a[m][k].im)       product, then addition: never an fmaf
+ *   t_m[n] = h_m[n-m] (x) x[n-m] = (hr * xr - hi * xi, hr * xi + hi * xr)   the gr_complex product of the other stages
+ *   y[n]   = t_0[n] + t_1[n] + .. + t_{M-1}[n]               float32 additions per part, ascending m, begun at t_0 (not +0)
+ *   out[n] = store(y[n])                                     complex64, or ofdm_sc16 by the transmit rule of ofdm_duc
+ * Every term is a function of the stream alone: a stream fed in any segmentation gives bit-identical outputs; calls of
+ * 0 inputs and calls shorter than M - 1 are included.  The stage is causal: state is the last M - 1 inputs.
+ * Statistics accumulate from ofdm_set_mempoly / ofdm_mempoly_reset on, as ofdm_cfr's do: n; peak_in and sum_in over
+ * p[n]; peak_out and sum_out over |y|^2 = y.re * y.re + y.im * y.im (float32); n_over the outputs with |y|^2 above the
+ * float32 product limit * limit.  `limit` is the converter's full scale: the stage counts and clamps nothing (a
+ * predistorter expands peaks); +inf counts none.  Counts and maxima (fmaxf, from 0) do not depend on how the stream was
+ * cut; the float64 sums are added per workgroup and then per call in a fixed order.
+ * Pointers are host or device as the handle was created.  iq_in is complex64 and must not overlap iq_out: a workgroup
+ * reads the inputs of its neighbour's outputs.  Like ofdm_cfr, the call orders itself behind an ofdm_tx_async still in
+ * flight and returns after the stream drained.  The kernel takes no id in the OFDM_K_* table (ofdm_mempoly_last_ms).
+ * Additions only: OFDM_ABI_VERSION stays 6, and with no slot configured nothing here launches, allocates or copies.
+ * OFDM_E_INVAL: a slot that is neither OFDM_MEMPOLY_DPD nor OFDM_MEMPOLY_PA; bad struct_size; memory outside
+ * [1, OFDM_MEMPOLY_MAX_MEMORY]; orders outside [1, OFDM_MEMPOLY_MAX_ORDERS]; a coefficient a[m][k] with m < memory and
+ * k < orders that is not finite (the other entries are not looked at); a limit that is NaN or <= 0; bad out_format or
+ * out_scale; ofdm_mempoly / ofdm_mempoly_reset / ofdm_mempoly_stats on a slot without a configuration; a float32
+ * pointer not 8-byte (ofdm_sc16: 4-byte) aligned; iq_in overlapping iq_out; a call too long for two levels of the
+ * statistics' reduction (2^34 samples: split it).  A refused configuration leaves the one in force (or none), stream
+ * state and statistics included, as it was; a refused call moves nothing.
+ * OFDM_E_CAPACITY: out_cap < nin (*nout is set); the stream state is then unchanged. */
+#define OFDM_MEMPOLY_MAX_MEMORY 8
+#define OFDM_MEMPOLY_MAX_ORDERS 5
+#define OFDM_MEMPOLY_DPD 0u   /* slot: the predistorter, transmit side */
+#define OFDM_MEMPOLY_PA 1u    /* slot: the amplifier model, air side */
+#define OFDM_MEMPOLY_SLOTS 2
+typedef struct ofdm_mempoly_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_mempoly_cfg) */
+  uint32_t memory;        /* M: 1..OFDM_MEMPOLY_MAX_MEMORY */
+  uint32_t orders;        /* K: 1..OFDM_MEMPOLY_MAX_ORDERS (polynomial orders 1, 3, .., 2K - 1) */
+  uint32_t out_format;    /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float out_scale;        /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^15 */
+  float limit;            /* > 0; +inf: n_over stays 0 */
+  ofdm_c32 coef[OFDM_MEMPOLY_MAX_MEMORY * OFDM_MEMPOLY_MAX_ORDERS]; /* a[m][k] at [m * OFDM_MEMPOLY_MAX_ORDERS + k] */
+} ofdm_mempoly_cfg;
+struct ofdm_mempoly_stats {  /* (a tag only: ofdm_mempoly_stats is the function below) */
+  uint64_t n;             /* samples */
+  uint64_t n_over;        /* outputs with |y|^2 > limit * limit */
+  float peak_in;          /* max p */
+  float peak_out;         /* max |y|^2 */
+  double sum_in;          /* sum of p */
+  double sum_out;         /* sum of |y|^2 */
+};
+/* NULL: none (touches no device memory).  Resets the slot's stream state (history zero) and statistics. */
+int ofdm_set_mempoly(ofdm_handle *h, uint32_t slot, const ofdm_mempoly_cfg *cfg);
+/* a new stream on the slot: history zero, statistics zero */
+int ofdm_mempoly_reset(ofdm_handle *h, uint32_t slot);
+/* the next nin samples of the slot's stream in, nin samples out */
+int ofdm_mempoly(ofdm_handle *h, uint32_t slot, const ofdm_c32 *iq_in, uint64_t nin, void *iq_out, uint64_t out_cap,
+                 uint64_t *nout);
+/* the slot's statistics since ofdm_set_mempoly / ofdm_mempoly_reset */
+int ofdm_mempoly_stats(ofdm_handle *h, uint32_t slot, struct ofdm_mempoly_stats *out);
+/* HIP-event time of k_mempoly and the reduction of its partials in the slot's last ofdm_mempoly, which must have run
+ * with profiling on (ofdm_prof_enable) and produced output; OFDM_E_INVAL otherwise.  As ofdm_cfr_last_ms: the OFDM_K_*
+ * table is unchanged. */
+int ofdm_mempoly_last_ms(const ofdm_handle *h, uint32_t slot, double *ms);
+
 /* --- coded links: rate-1/2, K = 7 convolutional code over the payload, Viterbi decoder on the GPU --------------------
  * A forward-error-correcting layer at the payload boundary: ofdm_fec_encode turns payloads into coded blocks that go
  * to ofdm_tx / ofdm_make_packets as payloads; ofdm_fec_decode takes the payloads ofdm_rx delivered (CRC-failed ones

@@ -28,6 +28,10 @@ OFDM_MULTIPATH_MAX_PATHS = 16
 OFDM_MULTIPATH_MAX_TONES = 4
 OFDM_MULTIPATH_MAX_DELAY = 1023
 OFDM_CFR_MAX_TAPS = 1023
+OFDM_MEMPOLY_MAX_MEMORY = 8
+OFDM_MEMPOLY_MAX_ORDERS = 5
+OFDM_MEMPOLY_DPD, OFDM_MEMPOLY_PA = 0, 1     # the two slots of ofdm_set_mempoly
+OFDM_MEMPOLY_SLOTS = 2
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
@@ -322,6 +326,32 @@ class ofdm_cfr_stats(C.Structure):        # the header's ``struct ofdm_cfr_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ofdm_mempoly_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("memory", C.c_uint32),
+        ("orders", C.c_uint32),
+        ("out_format", C.c_uint32),
+        ("out_scale", C.c_float),
+        ("limit", C.c_float),
+        ("coef", ofdm_c32 * (OFDM_MEMPOLY_MAX_MEMORY * OFDM_MEMPOLY_MAX_ORDERS)),
+    ]
+
+
+class ofdm_mempoly_stats(C.Structure):    # the header's ``struct ofdm_mempoly_stats`` (a tag: the name is the function's)
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_over", C.c_uint64),
+        ("peak_in", C.c_float),
+        ("peak_out", C.c_float),
+        ("sum_in", C.c_double),
+        ("sum_out", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class ofdm_fec_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -388,6 +418,7 @@ EXPORTS = (
     "ofdm_tx_resamp_bank_taps", "ofdm_tx_resamp_bank_last_ms",
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
     "ofdm_set_cfr", "ofdm_cfr_reset", "ofdm_cfr", "ofdm_cfr_stats", "ofdm_cfr_last_ms",
+    "ofdm_set_mempoly", "ofdm_mempoly_reset", "ofdm_mempoly", "ofdm_mempoly_stats", "ofdm_mempoly_last_ms",
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
@@ -494,6 +525,11 @@ def _declare(lib):
     lib.ofdm_cfr.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
     lib.ofdm_cfr_stats.argtypes = [H, C.POINTER(ofdm_cfr_stats)]
     lib.ofdm_cfr_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_mempoly.argtypes = [H, C.c_uint32, C.POINTER(ofdm_mempoly_cfg)]
+    lib.ofdm_mempoly_reset.argtypes = [H, C.c_uint32]
+    lib.ofdm_mempoly.argtypes = [H, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p]
+    lib.ofdm_mempoly_stats.argtypes = [H, C.c_uint32, C.POINTER(ofdm_mempoly_stats)]
+    lib.ofdm_mempoly_last_ms.argtypes = [H, C.c_uint32, C.POINTER(C.c_double)]
     FC = C.POINTER(ofdm_fec_cfg)
     lib.ofdm_fec_coded_len.argtypes = [C.c_uint32, u32p]
     lib.ofdm_fec_payload_len.argtypes = [C.c_uint32, u32p]

@@ -11,7 +11,7 @@ import struct
 import sys
 from optparse import OptionParser
 
-from . import iqio, ofdm, options as _options, transmit_path
+from . import dpd, iqio, ofdm, options as _options, transmit_path
 
 
 def build_payloads(options, data_source=None):
@@ -61,6 +61,11 @@ def make_parser():
     parser.add_option("", "--cfr-half-width", type="intx", default=16,
                       help="with --cfr-papr: half-width of the gain dip in samples, 0 to 511 (0: polar clip); the "
                            "stream comes out this many samples late [default=%default]")
+    parser.add_option("", "--dpd", default=None, metavar="FILE.npy",
+                      help="digital predistortion as the last stage, behind --cfr-papr, on the GPU: the memory-polynomial "
+                           "table of shape (memory, orders) in this .npy file (dpd.train / dpd.fit), which holds for the "
+                           "--tx-amplitude and --cfr-papr it was trained at; gain, peak expansion and the share of "
+                           "samples above full scale are printed at the end [default=off]")
     parser.add_option("", "--fec", action="store_true", default=False,
                       help="coded link: protect every payload (at most 2040 bytes) with the rate-1/2 K=7 convolutional "
                            "code and interleaver, encoded on the GPU; demodulate with benchmark_ofdm_rx --fec "
@@ -107,6 +112,8 @@ def _main_tx_resamp_bank(parser, options):
         parser.error("--tx-resamp-freqs does not combine with --fec, --ldpc, --rs or --sig")
     if options.cfr_papr is not None:
         parser.error("--tx-resamp-freqs does not combine with --cfr-papr")
+    if options.dpd is not None:
+        parser.error("--tx-resamp-freqs does not combine with --dpd")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -165,8 +172,16 @@ def main(argv=None):
     if src is not None:
         print(os.path.getsize(options.from_file))
 
+    dpd_stage = None
+    if options.dpd is not None:
+        try:
+            # the converter's full scale in the stream's units: 1, or what --iq-scale maps onto 2^15
+            full = 32768.0 / options.iq_scale if options.iq_format == "sc16" and options.iq_scale else 1.0
+            dpd_stage = dict(coef=dpd.load_coef(options.dpd), limit=full)
+        except (OSError, ValueError) as e:
+            parser.error("--dpd: %s" % e)
     try:
-        txpath = transmit_path.transmit_path(options)
+        txpath = transmit_path.transmit_path(options, dpd=dpd_stage)
     except ValueError as e:
         if options.cfr_papr is None:
             raise
@@ -185,6 +200,10 @@ def main(argv=None):
     if r is not None:
         sys.stderr.write("cfr: PAPR %.2f -> %.2f dB, EVM %.1f dB, %.3g of the samples over the threshold, %.3g touched\n" % (
             r["papr_in_db"], r["papr_out_db"], r["evm_db"], r["share_over"], r["share_touched"]))
+    r = txpath.ofdm_tx.last_dpd
+    if r is not None:
+        sys.stderr.write("dpd: gain %.2f dB, peak expansion %.2f dB, %.3g of the samples above full scale\n" % (
+            r["gain_db"], r["peak_expansion_db"], r["share_over"]))
     return npk
 
 

@@ -12,7 +12,7 @@ from optparse import OptionParser
 
 import numpy as np
 
-from . import iqio, multipath, options as _options
+from . import dpd, iqio, multipath, options as _options
 
 
 def make_parser():
@@ -22,6 +22,10 @@ def make_parser():
     parser.add_option("", "--paths", default="0:1",
                       help="paths as delay:gain[@doppler] separated by ';' -- delay in samples (0..1023), gain a complex "
                            "number, doppler in cycles per sample -- e.g. \"0:1;4:0.35+0.35j;9:0.1@1e-4\" [default=%default]")
+    parser.add_option("", "--pa", default=None, metavar="example|FILE.npy",
+                      help="a power amplifier in front of the paths, on the GPU: the memory-polynomial model whose table of "
+                           "shape (memory, orders) this .npy file holds, or the built-in example (dpd.example_pa); its "
+                           "gain and peak expansion are printed at the end [default=off]")
     parser.add_option("", "--tones", default="",
                       help="continuous tones as amp:freq[@phase] separated by ';' -- freq in cycles per sample "
                            "[-0.5, 0.5], phase in cycles -- e.g. \"0.01:0.15625\" [default=none]")
@@ -80,6 +84,12 @@ def main(argv=None):
         multipath.multipath_cfg(paths=paths, tones=tones, cfo=cfo)           # refused before a file is touched
     except ValueError as e:
         parser.error("--paths / --tones / --cfo-bins / --iq-scale: %s" % e)
+    pa = None
+    if options.pa is not None:
+        try:
+            pa = dpd.mempoly_cfg(dpd.example_pa() if options.pa == "example" else dpd.load_coef(options.pa))
+        except (OSError, ValueError) as e:
+            parser.error("--pa: %s" % e)
     source = iqio.file_source(options.from_file, fmt=options.iq_format)
     sigma = 0.0
     if options.snr is not None:
@@ -91,16 +101,22 @@ def main(argv=None):
     nout = 0
     try:
         ch = multipath.channel(cfg)
+        amplify = (lambda x: x) if pa is None else ch.engine().pa
+        if pa is not None:
+            ch.engine().set_pa(pa)
         if chunk:
             for piece in source.read_chunks(chunk):
-                y = ch.feed(_complex(piece, options.iq_format, scale))
+                y = ch.feed(amplify(_complex(piece, options.iq_format, scale)))
                 sink.write(y)
                 nout += len(y)
             y = ch.flush()
         else:
-            y = ch.work(_complex(source.read_all(), options.iq_format, scale))
+            y = ch.work(amplify(_complex(source.read_all(), options.iq_format, scale)))
         sink.write(y)
         nout += len(y)
+        if pa is not None and ch.engine().pa_stats()["n"]:
+            r = dpd.report(ch.engine().pa_stats())
+            print("channel_sim: amplifier gain %.2f dB, peak expansion %.2f dB" % (r["gain_db"], r["peak_expansion_db"]))
     finally:
         if ch is not None:
             ch.close()

@@ -22,100 +22,37 @@
 //               comes from global memory at a uniform index (scalar loads).
 // Both paths give the definition's bits: the fast path is the slow one with every term +0.
 //
-// Statistics (ofdm_cfr_stats): counts, the two maxima and three float64 sums.  A thread adds its own terms in
-// ascending order, a wave reduces by an xor butterfly, thread 0 adds the four waves' results in ascending order and
-// writes the tile's partial; k_cfr_reduce adds the partials of a call in a fixed order, in one or two levels, onto the
-// running totals.  No float atomics: a call's sums depend on nothing but its samples and its length.
+// Statistics (ofdm_cfr_stats): counts, the two maxima and three float64 sums, per thread, wave and tile and then per
+// call in a fixed order (stream_stats.h, shared with mempoly.h): no float atomics.
 #pragma once
 #include "common.h"
 #include "host_util.h"
+#include "stream_stats.h"
 
-constexpr int CFR_THREADS = 256;
+constexpr int CFR_THREADS = STAT_THREADS;
 constexpr int CFR_OPT = 4;  // outputs per thread: T = 1024
 constexpr int CFR_TILE = CFR_THREADS * CFR_OPT;
 constexpr int CFR_MAX_H = (OFDM_CFR_MAX_TAPS - 1) / 2;
 constexpr int CFR_STAGED = CFR_TILE + 2 * CFR_MAX_H;  // 2046 words: 32 groups of 64
-constexpr int CFR_REDUCE_SPAN = 4096;                  // partials one workgroup of k_cfr_reduce adds
 static_assert(CFR_STAGED <= 32 * 64, "one mask bit per 64 staged words");
-
-struct CfrPartial {  // of one tile, or of CFR_REDUCE_SPAN tiles
-  double sum_in, sum_out, sum_err;
-  float peak_in, peak_out;
-  uint32_t n_over, n_touched;
-};
-struct CfrTotals {  // since ofdm_set_cfr / ofdm_cfr_reset
-  double sum_in, sum_out, sum_err;
-  float peak_in, peak_out;
-  uint64_t n_over, n_touched;
-};
 
 struct CfrParams {
   const c32* x;     // this call's samples; x[0] is the stream's next sample
   const c32* hist;  // the 2H samples before x[0] (zeros before the stream start)
   void* out;
-  CfrPartial* part;  // one per tile
+  StatPartial* part;  // one per tile
   uint64_t nin;
   float A;
   int H;
   float scale;  // sc16 output: full scale
 };
 
-// the float64 / float32 / uint32 reductions of one wave: every lane ends with the same value, in a fixed order
-__device__ __forceinline__ double cfr_wave_sum(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-__device__ __forceinline__ float cfr_wave_max(float v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
-  return v;
-}
-__device__ __forceinline__ uint32_t cfr_wave_count(uint32_t v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
-struct CfrAcc {  // a thread's statistics
-  double sum_in = 0.0, sum_out = 0.0, sum_err = 0.0;
-  float peak_in = 0.f, peak_out = 0.f;
-  uint32_t n_over = 0, n_touched = 0;
-};
-
-// the workgroup's accumulators into one partial (thread 0 holds it on return); sh: one CfrPartial per wave
-template <int NW>
-__device__ __forceinline__ CfrPartial cfr_block_reduce(const CfrAcc& a, CfrPartial* sh, int tid) {
-  CfrPartial p;
-  p.sum_in = cfr_wave_sum(a.sum_in);
-  p.sum_out = cfr_wave_sum(a.sum_out);
-  p.sum_err = cfr_wave_sum(a.sum_err);
-  p.peak_in = cfr_wave_max(a.peak_in);
-  p.peak_out = cfr_wave_max(a.peak_out);
-  p.n_over = cfr_wave_count(a.n_over);
-  p.n_touched = cfr_wave_count(a.n_touched);
-  if ((tid & 63) == 0) sh[tid >> 6] = p;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < NW; i++) {
-      p.sum_in += sh[i].sum_in;
-      p.sum_out += sh[i].sum_out;
-      p.sum_err += sh[i].sum_err;
-      p.peak_in = fmaxf(p.peak_in, sh[i].peak_in);
-      p.peak_out = fmaxf(p.peak_out, sh[i].peak_out);
-      p.n_over += sh[i].n_over;
-      p.n_touched += sh[i].n_touched;
-    }
-  }
-  return p;
-}
-
 template <typename OUT>
 __global__ void __launch_bounds__(CFR_THREADS) k_cfr(CfrParams q, const float* __restrict__ w) {  // w: 2H + 1 window values
   constexpr int NT = CFR_THREADS, T = CFR_TILE;
   __shared__ float cs[CFR_STAGED];
   __shared__ uint32_t wmask[NT / 64];
-  __shared__ CfrPartial wpart[NT / 64];
+  __shared__ StatPartial wpart[NT / 64];
   const int tid = threadIdx.x;
   const int H = q.H, H2 = 2 * q.H;
   const float A = q.A;
@@ -124,7 +61,7 @@ __global__ void __launch_bounds__(CFR_THREADS) k_cfr(CfrParams q, const float* _
   const int total = T + H2;
   const int64_t nin = (int64_t)q.nin;
   const bool interior = g0 >= 0 && g0 + total <= nin;
-  CfrAcc acc;
+  StatAcc acc;
 
   // c[] of the tile's inputs into LDS.  In step j a wave stages the 64 words of group 4 j + wave: `mine` gathers the
   // bits of this wave's groups with a non-zero word.  The tile's own inputs (u >= 2H, inside the call) are counted.
@@ -190,43 +127,8 @@ __global__ void __launch_bounds__(CFR_THREADS) k_cfr(CfrParams q, const float* _
     iq_store(out, o, y, q.scale);
   }
 
-  const CfrPartial p = cfr_block_reduce<NT / 64>(acc, wpart, tid);
+  const StatPartial p = stat_block_reduce<NT / 64>(acc, wpart, tid);
   if (tid == 0) q.part[blockIdx.x] = p;
-}
-
-// The partials of a call into the totals, in a fixed order.  LAST = false: workgroup g adds in[g * SPAN .. ) (SPAN of
-// them, fewer in the last) into out[g].  LAST = true: one workgroup adds all n (at most SPAN) onto *tot.
-template <bool LAST>
-__global__ void __launch_bounds__(CFR_THREADS) k_cfr_reduce(const CfrPartial* __restrict__ in, uint32_t n, CfrPartial* __restrict__ out,
-                                                            CfrTotals* __restrict__ tot) {
-  __shared__ CfrPartial wpart[CFR_THREADS / 64];
-  const int tid = threadIdx.x;
-  const uint32_t lo = blockIdx.x * (uint32_t)CFR_REDUCE_SPAN;
-  const uint32_t hi = min(n, lo + (uint32_t)CFR_REDUCE_SPAN);
-  CfrAcc a;
-  for (uint32_t i = lo + tid; i < hi; i += CFR_THREADS) {
-    const CfrPartial p = in[i];
-    a.sum_in += p.sum_in;
-    a.sum_out += p.sum_out;
-    a.sum_err += p.sum_err;
-    a.peak_in = fmaxf(a.peak_in, p.peak_in);
-    a.peak_out = fmaxf(a.peak_out, p.peak_out);
-    a.n_over += p.n_over;
-    a.n_touched += p.n_touched;
-  }
-  const CfrPartial p = cfr_block_reduce<CFR_THREADS / 64>(a, wpart, tid);
-  if (tid != 0) return;
-  if constexpr (LAST) {
-    tot->sum_in += p.sum_in;
-    tot->sum_out += p.sum_out;
-    tot->sum_err += p.sum_err;
-    tot->peak_in = fmaxf(tot->peak_in, p.peak_in);
-    tot->peak_out = fmaxf(tot->peak_out, p.peak_out);
-    tot->n_over += p.n_over;
-    tot->n_touched += p.n_touched;
-  } else {
-    out[blockIdx.x] = p;
-  }
 }
 
 // (the history kernel is k_stream_hist<c32>, stream_hist.h, with H = 2H: the last 2H inputs after a call)
@@ -237,13 +139,11 @@ struct CfrState : StreamStage {
   float A = 0.f;
   int out_fmt = OFDM_IQ_FC32;
   float out_scale = 32768.0f;
-  uint64_t n = 0;          // samples since ofdm_set_cfr / ofdm_cfr_reset
-  DevBuf d_w, d_part, d_part2, d_tot;
+  DevBuf d_w;
+  StatState st;  // since ofdm_set_cfr / ofdm_cfr_reset
   void release() {
     d_w.release();
-    d_part.release();
-    d_part2.release();
-    d_tot.release();
+    st.release();
     StreamStage::release();
   }
 };

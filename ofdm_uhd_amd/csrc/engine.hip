@@ -33,6 +33,7 @@
 #include "pfb_synth.h"
 #include "multipath.h"
 #include "cfr.h"
+#include "mempoly.h"
 #include "fec.h"
 #include "fec_punct.h"
 #include "fec_rel.h"
@@ -136,6 +137,7 @@ struct ofdm_handle {
   TxResampBankState tx_resamp_bank;  // the same at a rational rate (tx_resamp_bank.h / engine_tx_resamp_bank.inc)
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   CfrState cfr;              // transmit crest-factor reduction, the last stage before a converter (cfr.h / engine_cfr.inc)
+  MempolyState mempoly[OFDM_MEMPOLY_SLOTS];  // memory polynomials: the predistorter and the amplifier model (mempoly.h / engine_mempoly.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
   FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h)
@@ -577,6 +579,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->tx_resamp_bank.release();
   h->multipath.release();
   h->cfr.release();
+  for (MempolyState& m : h->mempoly) m.release();
   h->fec.release();
   h->fec_punct.release();
   h->fec_rel.release();
@@ -1026,6 +1029,7 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_tx_resamp_bank.inc"
 #include "engine_multipath.inc"
 #include "engine_cfr.inc"
+#include "engine_mempoly.inc"
 #include "engine_codec.inc"
 #include "engine_fec.inc"
 #include "engine_soft.inc"

@@ -2,12 +2,6 @@
 // Included by engine.hip after engine_multipath.inc; like it, the stage uses the stream skeleton of engine_stage.inc
 // with the transmit single shape (no `add`).
 
-static int cfr_zero_stats(ofdm_handle* h, CfrState& d) {
-  HIPCHK(h, hipMemsetAsync(d.d_tot.p, 0, sizeof(CfrTotals), h->stream));
-  d.n = 0;
-  return OFDM_OK;
-}
-
 extern "C" int ofdm_set_cfr(ofdm_handle* h, const ofdm_cfr_cfg* cfg) {
   if (!h) return OFDM_E_INVAL;
   CfrState& d = h->cfr;
@@ -27,9 +21,8 @@ extern "C" int ofdm_set_cfr(ofdm_handle* h, const ofdm_cfr_cfg* cfg) {
   d.out_fmt = (int)cfg->out_format;
   d.out_scale = scale;
   HIPCHK(h, d.d_w.ensure(sizeof(float) * cfg->ntaps));
-  HIPCHK(h, d.d_tot.ensure(sizeof(CfrTotals)));
   HIPCHK(h, hipMemcpyAsync(d.d_w.p, cfg->taps, sizeof(float) * cfg->ntaps, hipMemcpyHostToDevice, h->stream));
-  RCCHK(cfr_zero_stats(h, d));
+  RCCHK(stage_stats_zero(h, d.st));
   return stage_arm(h, d, 2 * H);
 }
 
@@ -38,7 +31,7 @@ extern "C" int ofdm_cfr_reset(ofdm_handle* h) {
   CfrState& d = h->cfr;
   if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_cfr_reset without ofdm_set_cfr");
   HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  RCCHK(cfr_zero_stats(h, d));
+  RCCHK(stage_stats_zero(h, d.st));
   return stage_reset(h, d, 0);
 }
 
@@ -52,11 +45,9 @@ extern "C" int ofdm_cfr_stats(ofdm_handle* h, struct ofdm_cfr_stats* out) {
   CfrState& d = h->cfr;
   if (!out) FAIL(h, OFDM_E_INVAL, "null argument");
   if (!d.on) FAIL(h, OFDM_E_INVAL, "ofdm_cfr_stats without ofdm_set_cfr");
-  HIPCHK(h, hipSetDevice(h->cfg.device_id));
-  CfrTotals t;
-  HIPCHK(h, hipMemcpyAsync(&t, d.d_tot.p, sizeof(t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  out->n = d.n;
+  StatTotals t;
+  RCCHK(stage_stats_read(h, d.st, &t));
+  out->n = d.st.n;
   out->n_over = t.n_over;
   out->n_touched = t.n_touched;
   out->peak_in = t.peak_in;
@@ -87,8 +78,7 @@ extern "C" int ofdm_cfr(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, voi
   d.timed = false;
   if (nin == 0) return OFDM_OK;
   const uint64_t grid = (nin + (uint64_t)CFR_TILE - 1) / (uint64_t)CFR_TILE;
-  // (two levels of k_cfr_reduce add at most CFR_REDUCE_SPAN^2 partials)
-  if (grid > (uint64_t)CFR_REDUCE_SPAN * CFR_REDUCE_SPAN) FAIL(h, OFDM_E_INVAL, "ofdm_cfr: call too long (split it)");
+  if (!stage_stats_fits(grid)) FAIL(h, OFDM_E_INVAL, "ofdm_cfr: call too long (split it)");
   RCCHK(stage_enter(h));
 
   const c32* d_in = reinterpret_cast<const c32*>(iq_in);
@@ -96,16 +86,14 @@ extern "C" int ofdm_cfr(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, voi
   void* d_out = iq_out;
   RCCHK(stage_tx_rows_in(h, d, iq_in, 0, 1, nin, &d_in, nullptr));
   RCCHK(stage_tx_out(h, d, nullptr, nin, oss, &d_add, &d_out));
-  const uint32_t groups = (uint32_t)((grid + CFR_REDUCE_SPAN - 1) / CFR_REDUCE_SPAN);
-  HIPCHK(h, d.d_part.ensure(sizeof(CfrPartial) * grid));
-  if (groups > 1) HIPCHK(h, d.d_part2.ensure(sizeof(CfrPartial) * groups));
+  RCCHK(stage_stats_room(h, d.st, grid));
   const bool timing = h->prof.on;
   CfrParams p;
   memset(&p, 0, sizeof(p));
   p.x = d_in;
   p.hist = d.d_hist[d.cur].as<c32>();
   p.out = d_out;
-  p.part = d.d_part.as<CfrPartial>();
+  p.part = d.st.d_part.as<StatPartial>();
   p.nin = nin;
   p.A = d.A;
   p.H = d.H;
@@ -114,20 +102,11 @@ extern "C" int ofdm_cfr(ofdm_handle* h, const ofdm_c32* iq_in, uint64_t nin, voi
   RCCHK(stage_time_begin(h, d, timing));
   if (s16) hipLaunchKernelGGL(k_cfr<sc16>, dim3((unsigned)grid), dim3(CFR_THREADS), 0, h->stream, p, w);
   else hipLaunchKernelGGL(k_cfr<c32>, dim3((unsigned)grid), dim3(CFR_THREADS), 0, h->stream, p, w);
-  const CfrPartial* parts = p.part;
-  uint32_t nparts = (uint32_t)grid;
-  if (groups > 1) {
-    hipLaunchKernelGGL(k_cfr_reduce<false>, dim3(groups), dim3(CFR_THREADS), 0, h->stream, parts, nparts, d.d_part2.as<CfrPartial>(),
-                       (CfrTotals*)nullptr);
-    parts = d.d_part2.as<CfrPartial>();
-    nparts = groups;
-  }
-  hipLaunchKernelGGL(k_cfr_reduce<true>, dim3(1), dim3(CFR_THREADS), 0, h->stream, parts, nparts, (CfrPartial*)nullptr,
-                     d.d_tot.as<CfrTotals>());
+  stage_stats_reduce(h, d.st, grid);
   RCCHK(stage_time_end(h, d, timing));
   RCCHK(stage_roll_history(h, d, d_in, nin, 0.f));
   RCCHK(stage_tx_readback(h, iq_out, d_out, nin, oss));
   RCCHK(stage_finish(h, d, nin, timing));
-  d.n += nin;
+  d.st.n += nin;
   return OFDM_OK;
 }

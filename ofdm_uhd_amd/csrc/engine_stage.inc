@@ -10,8 +10,9 @@
 // copy in their place.  Included by engine.hip ahead of engine_{ddc,ddc_bank,duc,resamp,resamp_bank,tx_resamp,pfb,
 // pfb_synth,duc_bank,tx_resamp_bank}.inc (in that order: a bank uses its single stage's index limit), which keep what
 // is a stage's own: its configuration checks and messages, its index limits, its output count, its Params and its
-// template dispatch.  engine_multipath.inc, the propagation channel stage, and engine_cfr.inc, the crest-factor reduction
-// stage, follow them with the transmit single shape.
+// template dispatch.  engine_multipath.inc, the propagation channel stage, engine_cfr.inc, the crest-factor reduction
+// stage, and engine_mempoly.inc, the memory-polynomial stage, follow them with the transmit single shape; the last two
+// keep statistics (stream_stats.h) through the stage_stats_* steps below.
 
 #define RCCHK(expr)         \
   do {                      \
@@ -296,6 +297,42 @@ static int stage_roll_rows_history(ofdm_handle* h, StreamStage& d, const c32* x,
   hipLaunchKernelGGL(k_stream_hist_rows, dim3((unsigned)((Q + 255) / 256), (unsigned)rows), dim3(256), 0, h->stream, x, stride, nin,
                      d.d_hist[d.cur].as<c32>(), d.d_hist[d.cur ^ 1].as<c32>(), Q);
   HIPCHK(h, hipGetLastError());
+  return OFDM_OK;
+}
+
+// the statistics of the stages that keep some (stream_stats.h): zero the totals; room for a call's `grid` partials (two
+// levels of k_stat_reduce add at most STAT_REDUCE_SPAN^2 of them: stage_stats_fits, asked before anything moves); the
+// reduction behind the compute kernel; the totals on the host
+static int stage_stats_zero(ofdm_handle* h, StatState& st) {
+  HIPCHK(h, st.d_tot.ensure(sizeof(StatTotals)));
+  HIPCHK(h, hipMemsetAsync(st.d_tot.p, 0, sizeof(StatTotals), h->stream));
+  st.n = 0;
+  return OFDM_OK;
+}
+static bool stage_stats_fits(uint64_t grid) { return grid <= (uint64_t)STAT_REDUCE_SPAN * STAT_REDUCE_SPAN; }
+static int stage_stats_room(ofdm_handle* h, StatState& st, uint64_t grid) {
+  HIPCHK(h, st.d_part.ensure(sizeof(StatPartial) * grid));
+  if (grid > (uint64_t)STAT_REDUCE_SPAN)
+    HIPCHK(h, st.d_part2.ensure(sizeof(StatPartial) * ((grid + STAT_REDUCE_SPAN - 1) / STAT_REDUCE_SPAN)));
+  return OFDM_OK;
+}
+static void stage_stats_reduce(ofdm_handle* h, StatState& st, uint64_t grid) {
+  const StatPartial* parts = st.d_part.as<StatPartial>();
+  uint32_t nparts = (uint32_t)grid;
+  if (grid > (uint64_t)STAT_REDUCE_SPAN) {
+    const uint32_t groups = (uint32_t)((grid + STAT_REDUCE_SPAN - 1) / STAT_REDUCE_SPAN);
+    hipLaunchKernelGGL(k_stat_reduce<false>, dim3(groups), dim3(STAT_THREADS), 0, h->stream, parts, nparts, st.d_part2.as<StatPartial>(),
+                       (StatTotals*)nullptr);
+    parts = st.d_part2.as<StatPartial>();
+    nparts = groups;
+  }
+  hipLaunchKernelGGL(k_stat_reduce<true>, dim3(1), dim3(STAT_THREADS), 0, h->stream, parts, nparts, (StatPartial*)nullptr,
+                     st.d_tot.as<StatTotals>());
+}
+static int stage_stats_read(ofdm_handle* h, StatState& st, StatTotals* t) {
+  HIPCHK(h, hipSetDevice(h->cfg.device_id));
+  HIPCHK(h, hipMemcpyAsync(t, st.d_tot.p, sizeof(*t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return OFDM_OK;
 }
 

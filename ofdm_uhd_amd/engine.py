@@ -44,6 +44,10 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# the slots of the memory-polynomial stage by the names Engine gives them
+_MEMPOLY_SLOT = {"dpd": _abi.OFDM_MEMPOLY_DPD, "pa": _abi.OFDM_MEMPOLY_PA}
+
+
 def _u32(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
@@ -113,6 +117,8 @@ class Engine(object):
         self.tx_resamp_bank_cfg = None  # the transmit resampler bank's configuration in force (set_tx_resamp_bank), None without one
         self.multipath_cfg = None  # the propagation channel's configuration in force (set_multipath), None without one
         self.cfr_cfg = None  # the crest-factor reduction stage's configuration in force (set_cfr), None without one
+        self.dpd_cfg = None  # the predistorter's configuration in force (set_dpd), None without one
+        self.pa_cfg = None   # the amplifier model's configuration in force (set_pa), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -884,6 +890,89 @@ class Engine(object):
     def cfr_last_ms(self):
         """HIP-event time of k_cfr and its reduction in the last cfr() / cfr_device() (needs prof_enable())."""
         return self._stage_last_ms("cfr")
+
+    # -- memory polynomial: the predistorter (slot dpd, transmit side) and the amplifier model (slot pa, air side) -----
+    # one implementation, two instances (csrc/mempoly.h): ``name`` is "dpd" or "pa"
+    def _mempoly_set(self, name, cfg, kw):
+        if cfg is None and kw:
+            cfg = importlib.import_module(".dpd", __package__).mempoly_cfg(**kw)
+        self._check(self._lib.ofdm_set_mempoly(self._h, _MEMPOLY_SLOT[name], C.byref(cfg) if cfg is not None else None))
+        setattr(self, name + "_cfg", cfg)
+
+    def _mempoly(self, name, iq):
+        assert not self.device_ptrs
+        cfg = getattr(self, name + "_cfg")
+        if cfg is None:
+            raise ValueError("%s() without set_%s()" % (name, name))
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("%s() takes complex64 samples (its 16-bit side is the output)" % name)
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        n = len(iq)
+        sc16 = cfg.out_format == _abi.OFDM_IQ_SC16
+        out = np.zeros((max(n, 1), 2), np.int16) if sc16 else np.zeros(max(n, 1), np.complex64)
+        return out[:self._stage_call("mempoly", _MEMPOLY_SLOT[name], _ptr(iq) if n else None, n, _ptr(out), len(out))]
+
+    def _mempoly_stats(self, name):
+        st = _abi.ofdm_mempoly_stats()
+        self._check(self._lib.ofdm_mempoly_stats(self._h, _MEMPOLY_SLOT[name], C.byref(st)))
+        return st.as_dict()
+
+    def _mempoly_last_ms(self, name):
+        ms = C.c_double(0)
+        self._check(self._lib.ofdm_mempoly_last_ms(self._h, _MEMPOLY_SLOT[name], C.byref(ms)))
+        return ms.value
+
+    def set_dpd(self, cfg=None, **kw):
+        """Configure the predistorter: an ``ofdm_mempoly_cfg`` (dpd.mempoly_cfg) or its keywords (coef=, out_format=,
+        out_scale=, limit=).  ``set_dpd(None)`` with no keywords removes it.  Resets the slot's stream state and
+        statistics; the amplifier model (set_pa) is a separate instance and keeps its own."""
+        self._mempoly_set("dpd", cfg, kw)
+
+    def dpd_reset(self):
+        """Start a new stream: the history and the statistics are zero."""
+        self._check(self._lib.ofdm_mempoly_reset(self._h, _abi.OFDM_MEMPOLY_DPD))
+
+    def dpd(self, iq):
+        """Host mode: the next complex64 samples of the stream -> as many predistorted samples (complex64, or int16 of
+        shape (n, 2) with out_format "sc16"), no delay.  Stateful: any segmentation of a stream gives the same bits."""
+        return self._mempoly("dpd", iq)
+
+    def dpd_device(self, iq_ptr, nin, out_ptr, out_cap):
+        """Device mode: both buffers are device pointers and must not overlap.  Returns the number of outputs written."""
+        return self._stage_device("mempoly", _abi.OFDM_MEMPOLY_DPD, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap))
+
+    def dpd_stats(self):
+        """The statistics since set_dpd() / dpd_reset() as a dict: n, n_over, peak_in, peak_out, sum_in, sum_out
+        (ofdm_mempoly_stats; dpd.report turns them into gain, peak expansion and the share over the limit)."""
+        return self._mempoly_stats("dpd")
+
+    def dpd_last_ms(self):
+        """HIP-event time of k_mempoly and its reduction in the last dpd() / dpd_device() (needs prof_enable())."""
+        return self._mempoly_last_ms("dpd")
+
+    def set_pa(self, cfg=None, **kw):
+        """Configure the amplifier model, the same stage in the other slot: as set_dpd."""
+        self._mempoly_set("pa", cfg, kw)
+
+    def pa_reset(self):
+        """Start a new stream: the history and the statistics are zero."""
+        self._check(self._lib.ofdm_mempoly_reset(self._h, _abi.OFDM_MEMPOLY_PA))
+
+    def pa(self, iq):
+        """Host mode: the next complex64 samples of the stream -> as many samples behind the amplifier: as dpd()."""
+        return self._mempoly("pa", iq)
+
+    def pa_device(self, iq_ptr, nin, out_ptr, out_cap):
+        """Device mode: as dpd_device()."""
+        return self._stage_device("mempoly", _abi.OFDM_MEMPOLY_PA, C.c_void_p(iq_ptr), int(nin), C.c_void_p(out_ptr), int(out_cap))
+
+    def pa_stats(self):
+        """The statistics since set_pa() / pa_reset(): as dpd_stats()."""
+        return self._mempoly_stats("pa")
+
+    def pa_last_ms(self):
+        """HIP-event time of k_mempoly and its reduction in the last pa() / pa_device() (needs prof_enable())."""
+        return self._mempoly_last_ms("pa")
 
     # -- coded links: the two call shapes every codec shares (the counterpart of csrc/engine_codec.inc) ----------------
     # ``head`` is what a call takes ahead of its batch: () or (C.byref(cfg),).

@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from . import cfr as _cfr, config, csi as _csi, ddc as _ddc, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import cfr as _cfr, config, csi as _csi, ddc as _ddc, dpd as _dpd, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -28,9 +28,18 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=False, cfr=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=False, cfr=None, dpd=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
+        @param dpd: digital predistortion, ``dict(coef=table[, limit=])``: the engine's memory-polynomial stage (dpd.py,
+               Engine.dpd) with the (M, K) table ``coef`` (dpd.train / dpd.fit) runs last, behind ``cfr`` where both are
+               given: CFR, then DPD, then the converter.  The stages in front then emit complex64 and this one does the
+               ``iq_format`` store.  ``limit`` is the converter's full scale in the stream's units; the stage counts the
+               samples above it and clamps nothing.  No delay: flush(end=True) / send_pkt(eof=True) starts the stage
+               afresh, ``last_dpd`` holds the figures (dpd.report) of the stream that ended last, or of the running
+               one, and ``set_dpd_coef(coef)`` swaps the table between streams.  A table holds for the transmit
+               amplitude and the peak limit it was trained at: train again after changing either, and give ``cfr=``
+               with it (an amplifier has no inverse past its compression point).  None: nothing new runs
         @param cfr: crest-factor reduction, ``dict(papr_db=7.0, half_width=16[, threshold=][, kind="hann"])``: the
                engine's peak-windowing stage (cfr.py, Engine.cfr) runs last, behind ``duc`` / ``resample`` where there is
                one; those stages then emit complex64 and this one does the ``iq_format`` store.  Peaks are pulled down to
@@ -87,6 +96,10 @@ class ofdm_mod(object):
             raise ValueError("ofdm_mod takes duc= or resample=, not both")
         if sig:
             _sig.coding(fec=fec, ldpc=ldpc, rs=bool(rs))    # (ValueError for what is no coding, before anything is built)
+        if dpd is not None:
+            if "coef" not in dpd or set(dpd) - {"coef", "limit"}:
+                raise ValueError("dpd= takes coef and limit, not %s" % ", ".join(sorted(dpd)))
+            _dpd.mempoly_cfg(dpd["coef"], limit=dpd.get("limit"))   # (ValueError for a bad table, before anything is built)
         self._pad_for_usrp = pad_for_usrp
         self._msgq_limit = msgq_limit
         self._modulation = options.modulation
@@ -106,7 +119,9 @@ class ofdm_mod(object):
         self._duc_live = False       # the wideband stream holds samples whose filter tail is still to come
         occ = self._occupied_tones / float(self._fft_length)
         self._cfr = None if cfr is None else dict(cfr)   # with it, the stage in front stores complex64
-        stage_format, stage_scale = (iq_format, iq_scale) if cfr is None else ("fc32", None)
+        self._dpd = None if dpd is None else dict(dpd)   # with it, cfr= too stores complex64
+        last_format, last_scale = (iq_format, iq_scale) if dpd is None else ("fc32", None)   # of the stage in front of dpd=
+        stage_format, stage_scale = (last_format, last_scale) if cfr is None else ("fc32", None)
         if duc is not None:
             # the 16-bit format, if any, is the wideband side's: the modulator's output (the stage's input) is complex64
             d = dict(duc)
@@ -122,6 +137,12 @@ class ofdm_mod(object):
             self._duc = "tx_resamp"
         elif iqio.check_format(stage_format) != "fc32":
             self._engine.set_tx_iq_format(iq_format, iq_scale)
+        self._dpd_live = False       # the stage has seen samples of a stream that has not ended
+        self._last_dpd = None
+        if self._dpd is not None:
+            coef = self._dpd["coef"]
+            self._dpd = dict(limit=self._dpd.get("limit"), out_format=iqio.check_format(iq_format), out_scale=iq_scale)
+            self.set_dpd_coef(coef)
         self._cfr_live = False       # the stage holds samples that are still to come out
         self._cfr_rms = None         # the level its threshold was set against
         self._last_cfr = None
@@ -138,7 +159,7 @@ class ofdm_mod(object):
             if d:
                 raise ValueError("cfr= takes papr_db, half_width, threshold and kind, not %s" % ", ".join(sorted(d)))
             self._cfr = dict(threshold=thr, papr_db=papr, window=window, level=_cfr.modem_rms(cfg_opts) * gain,
-                             out_format=iqio.check_format(iq_format), out_scale=iq_scale)
+                             out_format=iqio.check_format(last_format), out_scale=last_scale)
             self.set_cfr_amplitude(1.0)
         self._fec = _fec.as_cfg(fec)
         self._ldpc = _ldpc.as_cfg(ldpc)
@@ -191,6 +212,22 @@ class ofdm_mod(object):
         if self._cfr is not None and self._cfr_live:
             return _cfr.report(self._engine.cfr_stats(), self._cfr_rms)
         return self._last_cfr
+
+    def set_dpd_coef(self, coef):
+        """Another predistorter table (dpd=), between streams: the stage starts afresh.  The table holds for the
+        transmit amplitude and peak limit it was trained at."""
+        if self._dpd is None:
+            raise ValueError("set_dpd_coef() needs ofdm_mod(dpd=)")
+        self._engine.set_dpd(_dpd.mempoly_cfg(coef, **self._dpd))
+        self._dpd_live = False
+
+    @property
+    def last_dpd(self):
+        """dpd.report of the predistorter (dpd=): of the stream flush(end=True) ended last, or of the running one.
+        None without the stage or before any sample."""
+        if self._dpd is not None and self._dpd_live:
+            return _dpd.report(self._engine.dpd_stats())
+        return self._last_dpd
 
     # -- packets ------------------------------------------------------------------
     def send_pkt(self, payload='', eof=False, coding=None):
@@ -263,9 +300,10 @@ class ofdm_mod(object):
         """Modulate everything queued so far; returns the samples (also written to the sink).  With a wideband stage
         (duc= / resample=) they are the wideband stream's next samples (with resample= possibly none yet); ``end=True`` then appends the filter's tail (Q zero
         narrowband samples pushed through) and starts the stage afresh.  With cfr= the samples went through the
-        crest-factor reduction stage last and come out half_width samples late; ``end=True`` pushes that many zeros."""
-        end = end and (self._duc is not None or self._cfr is not None) and (
-            self._duc_live or self._cfr_live or bool(self._pending))
+        crest-factor reduction stage last and come out half_width samples late; ``end=True`` pushes that many zeros.
+        With dpd= the predistorter runs behind all of them; it has no tail, ``end=True`` starts it afresh."""
+        end = end and (self._duc is not None or self._cfr is not None or self._dpd is not None) and (
+            self._duc_live or self._cfr_live or self._dpd_live or bool(self._pending))
         if not self._pending and not end:
             return None
         iq = None
@@ -307,6 +345,17 @@ class ofdm_mod(object):
                 eng.cfr_reset()
                 self._cfr_live = False
             iq = np.concatenate(parts) if len(parts) > 1 else parts[0]
+        if self._dpd is not None:
+            eng = self._engine
+            if iq is not None:
+                iq = eng.dpd(iq)
+                self._dpd_live = True
+            if end and self._dpd_live:
+                self._last_dpd = _dpd.report(eng.dpd_stats())
+                eng.dpd_reset()
+                self._dpd_live = False
+            if iq is None:           # (the end of a stream whose samples all went out before: the stage has no tail)
+                return None
         if self._sink is not None:
             self._sink.write(iq)
         return iq

@@ -3,7 +3,7 @@
 the gain stage (gr.multiply_const_cc ``amp``) is folded into the modulator kernel's store."""
 import copy
 
-from . import ofdm, options as _options
+from . import dpd as _dpd, ofdm, options as _options
 
 # flag, group, keyword arguments of the reference's option table (transmit_path.py:72-79)
 _FLAGS = (
@@ -18,7 +18,7 @@ _FLAGS = (
 
 class transmit_path(object):
     def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=None, cfr=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=None, cfr=None, dpd=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
@@ -37,7 +37,10 @@ class transmit_path(object):
         then choose the coding that every packet announces.
         ``cfr``: crest-factor reduction of ofdm_mod, ``dict(papr_db=7.0, half_width=16[, threshold=])``, the last stage;
         None: the options' ``cfr_papr`` / ``cfr_half_width`` (--cfr-papr / --cfr-half-width), no stage where cfr_papr
-        is unset.  The threshold follows the transmit amplitude."""
+        is unset.  The threshold follows the transmit amplitude.
+        ``dpd``: digital predistortion of ofdm_mod, ``dict(coef=table[, limit=])``, behind ``cfr``; None: the table in
+        the .npy file the options' ``dpd`` names (--dpd), no stage where it is unset.  The table does not follow the
+        transmit amplitude: it holds for the amplitude it was trained at."""
         opts = copy.copy(options)
         if rs is None:
             rs = bool(getattr(opts, "rs", None))
@@ -58,6 +61,8 @@ class transmit_path(object):
         if cfr is None and getattr(opts, "cfr_papr", None) is not None:
             hw = getattr(opts, "cfr_half_width", None)
             cfr = dict(papr_db=float(opts.cfr_papr), half_width=16 if hw is None else int(hw))
+        if dpd is None and getattr(opts, "dpd", None):
+            dpd = dict(coef=_dpd.load_coef(opts.dpd))
         self._apply_carrier_map = bool(apply_carrier_map)
         self._cfr = cfr is not None
         self._verbose = bool(getattr(opts, "verbose", False))
@@ -65,7 +70,7 @@ class transmit_path(object):
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
                                      iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc, sig=sig,
-                                     cfr=cfr)
+                                     cfr=cfr, dpd=dpd)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
