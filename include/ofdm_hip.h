@@ -1198,6 +1198,64 @@ int ofdm_mempoly_stats(ofdm_handle *h, uint32_t slot, struct ofdm_mempoly_stats 
  * table is unchanged. */
 int ofdm_mempoly_last_ms(const ofdm_handle *h, uint32_t slot, double *ms);
 
+/* --- spectrum measurement: an averaged-periodogram (Welch) estimator over any complex stream --------------------------
+ * What ofdm_cfr and ofdm_mempoly exist for is what a transmitter emits outside its channel.  This stage measures it: the
+ * power spectrum of a stream, segment by segment, with a float64 average, a max-hold and, where asked for, the
+ * per-segment rows (adjacent-channel leakage, occupied bandwidth and mask margins are host-side figures of the average:
+ * spectrum.py).  It reads its input and changes nothing.
+ * Definition.  F = nfft, S = hop, w[i] = taps[i]; n is the stream index from the last reset (ofdm_set_psd,
+ * ofdm_psd_reset).  Input samples are complex64, or ofdm_sc16 converted by the receive rule (float)int16 * in_scale.
+ * Segment j covers x[j S .. j S + F); after T samples, T < F ? 0 : (T - F) / S + 1 segments are complete, and a call
+ * completes those whose last sample it brought.  State: the samples from the first incomplete segment on, always fewer
+ * than F; calls of 0 samples are included.  Per segment, in float32, every operation rounded once:
+ *   e[i]   = (x[jS + i].re * w[i], x[jS + i].im * w[i])
+ *   X      = fft_F(e)                                         the forward transform of ofdm_sense, same schedule: the
+ *                                                             same inputs give the same bits
+ *   P_j[k] = X[k].re * X[k].re + X[k].im * X[k].im            two products, one addition
+ * P_j is a function of the stream alone: any segmentation of a stream gives bit-identical rows.  Accumulators since the
+ * reset: nseg; sum[k], the float64 sum of P_j[k]; peak[k] = max over j of P_j[k], from 0 (order-independent; a NaN is not
+ * counted, as in ofdm_sense).  The float64 sums are added per thread, per workgroup and then per call in an order fixed
+ * by the call's segment count alone, without float atomics: equal calls give equal sums, and two segmentations differ by
+ * the rounding of float64 additions alone (the rule of ofdm_cfr's statistics).  Bins are in FFT order: bin k is the
+ * frequency k / F cycles per sample for k < F / 2 and (k - F) / F from there on.
+ * Pointers are host or device as the handle was created (nrows and nseg are always host memory).  Like ofdm_cfr, the
+ * call orders itself behind an ofdm_tx_async still in flight and returns after the stream drained.  The kernels take no
+ * id in the OFDM_K_* table (ofdm_psd_last_ms).  Additions only: OFDM_ABI_VERSION stays 6, and with the stage not
+ * configured nothing here launches, allocates or copies.
+ * OFDM_E_INVAL: bad struct_size; an nfft that is not a power of two in [64, OFDM_PSD_MAX_FFT]; a hop of 0 or above nfft;
+ * a tap among the first nfft that is not finite, or all of them zero (entries beyond nfft are not looked at); bad
+ * in_format or in_scale; a complex64 pointer not 8-byte, an ofdm_sc16 or float pointer not 4-byte, a double pointer not
+ * 8-byte aligned; rows overlapping iq_in; ofdm_psd / ofdm_psd_reset / ofdm_psd_count / ofdm_psd_read without a
+ * configuration; a stream past 2^62 samples; a call that completes more than 2^31 - 1 segments (split it).  A refused
+ * configuration leaves the one in force (or none), stream state and accumulators included, as it was; a refused call
+ * moves nothing.
+ * OFDM_E_CAPACITY: rows given and rows_cap below the call's segment count (*nrows is set); the stream state and the
+ * accumulators are then unchanged. */
+#define OFDM_PSD_MAX_FFT 4096
+typedef struct ofdm_psd_cfg {
+  uint32_t struct_size;   /* = sizeof(ofdm_psd_cfg) */
+  uint32_t nfft;          /* F: a power of two, 64..OFDM_PSD_MAX_FFT */
+  uint32_t hop;           /* S: 1..nfft */
+  uint32_t in_format;     /* OFDM_IQ_FC32 | OFDM_IQ_SC16 */
+  float in_scale;         /* OFDM_IQ_SC16 only: finite, > 0; 0 = the default 2^-15 */
+  float taps[OFDM_PSD_MAX_FFT]; /* the window: the first nfft finite and not all zero */
+} ofdm_psd_cfg;
+/* NULL: none (touches no device memory).  Resets the stream state and the accumulators. */
+int ofdm_set_psd(ofdm_handle *h, const ofdm_psd_cfg *cfg);
+/* a new stream: nothing pending, accumulators zero */
+int ofdm_psd_reset(ofdm_handle *h);
+/* segments the next call of nin samples would complete */
+int ofdm_psd_count(ofdm_handle *h, uint64_t nin, uint64_t *nrows);
+/* the next nin samples of the stream.  rows: NULL, or room for rows_cap rows of nfft float32, which receive this call's
+ * P_j in segment order. */
+int ofdm_psd(ofdm_handle *h, const void *iq_in, uint64_t nin, float *rows, uint64_t rows_cap, uint64_t *nrows);
+/* the accumulators since ofdm_set_psd / ofdm_psd_reset: nfft sums, nfft maxima, the segment count; each may be NULL */
+int ofdm_psd_read(ofdm_handle *h, double *sum, float *peak, uint64_t *nseg);
+/* HIP-event time of k_psd and k_psd_reduce in the last ofdm_psd, which must have run with profiling on
+ * (ofdm_prof_enable) and completed a segment; OFDM_E_INVAL otherwise.  As ofdm_cfr_last_ms: the OFDM_K_* table is
+ * unchanged. */
+int ofdm_psd_last_ms(const ofdm_handle *h, double *ms);
+
 /* --- coded links: rate-1/2, K = 7 convolutional code over the payload, Viterbi decoder on the GPU --------------------
  * A forward-error-correcting layer at the payload boundary: ofdm_fec_encode turns payloads into coded blocks that go
  * to ofdm_tx / ofdm_make_packets as payloads; ofdm_fec_decode takes the payloads ofdm_rx delivered (CRC-failed ones

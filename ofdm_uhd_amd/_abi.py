@@ -32,6 +32,7 @@ OFDM_MEMPOLY_MAX_MEMORY = 8
 OFDM_MEMPOLY_MAX_ORDERS = 5
 OFDM_MEMPOLY_DPD, OFDM_MEMPOLY_PA = 0, 1     # the two slots of ofdm_set_mempoly
 OFDM_MEMPOLY_SLOTS = 2
+OFDM_PSD_MAX_FFT = 4096
 OFDM_FEC_MAX_PAYLOAD = 2040
 OFDM_FEC_MAX_CODED = 4090
 OFDM_FEC_RATE_1_2, OFDM_FEC_RATE_2_3, OFDM_FEC_RATE_3_4, OFDM_FEC_RATE_5_6 = 0, 1, 2, 3
@@ -352,6 +353,17 @@ class ofdm_mempoly_stats(C.Structure):    # the header's ``struct ofdm_mempoly_s
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ofdm_psd_cfg(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nfft", C.c_uint32),
+        ("hop", C.c_uint32),
+        ("in_format", C.c_uint32),
+        ("in_scale", C.c_float),
+        ("taps", C.c_float * OFDM_PSD_MAX_FFT),
+    ]
+
+
 class ofdm_fec_cfg(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -419,6 +431,7 @@ EXPORTS = (
     "ofdm_set_multipath", "ofdm_multipath_reset", "ofdm_multipath", "ofdm_multipath_last_ms",
     "ofdm_set_cfr", "ofdm_cfr_reset", "ofdm_cfr", "ofdm_cfr_stats", "ofdm_cfr_last_ms",
     "ofdm_set_mempoly", "ofdm_mempoly_reset", "ofdm_mempoly", "ofdm_mempoly_stats", "ofdm_mempoly_last_ms",
+    "ofdm_set_psd", "ofdm_psd_reset", "ofdm_psd_count", "ofdm_psd", "ofdm_psd_read", "ofdm_psd_last_ms",
     "ofdm_fec_coded_len", "ofdm_fec_payload_len", "ofdm_fec_encode", "ofdm_fec_decode", "ofdm_fec_decode_soft",
     "ofdm_fec_last_ms", "ofdm_fec_coded_len_rate", "ofdm_fec_payload_len_rate", "ofdm_fec_punct_last_ms",
     "ofdm_set_rx_soft", "ofdm_rx_soft", "ofdm_rx_fec_decode_soft", "ofdm_rx_soft_last_ms",
@@ -525,6 +538,12 @@ def _declare(lib):
     lib.ofdm_cfr.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
     lib.ofdm_cfr_stats.argtypes = [H, C.POINTER(ofdm_cfr_stats)]
     lib.ofdm_cfr_last_ms.argtypes = [H, C.POINTER(C.c_double)]
+    lib.ofdm_set_psd.argtypes = [H, C.POINTER(ofdm_psd_cfg)]
+    lib.ofdm_psd_reset.argtypes = [H]
+    lib.ofdm_psd_count.argtypes = [H, C.c_uint64, u64p]
+    lib.ofdm_psd.argtypes = [H, vp, C.c_uint64, vp, C.c_uint64, u64p]
+    lib.ofdm_psd_read.argtypes = [H, vp, vp, u64p]
+    lib.ofdm_psd_last_ms.argtypes = [H, C.POINTER(C.c_double)]
     lib.ofdm_set_mempoly.argtypes = [H, C.c_uint32, C.POINTER(ofdm_mempoly_cfg)]
     lib.ofdm_mempoly_reset.argtypes = [H, C.c_uint32]
     lib.ofdm_mempoly.argtypes = [H, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p]

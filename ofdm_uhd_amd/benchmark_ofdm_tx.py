@@ -11,7 +11,9 @@ import struct
 import sys
 from optparse import OptionParser
 
-from . import dpd, iqio, ofdm, options as _options, transmit_path
+import numpy as np
+
+from . import dpd, iqio, ofdm, options as _options, spectrum, transmit_path
 
 
 def build_payloads(options, data_source=None):
@@ -66,6 +68,16 @@ def make_parser():
                            "table of shape (memory, orders) in this .npy file (dpd.train / dpd.fit), which holds for the "
                            "--tx-amplitude and --cfr-papr it was trained at; gain, peak expansion and the share of "
                            "samples above full scale are printed at the end [default=off]")
+    parser.add_option("", "--psd", default=None, metavar="NFFT[,HOP]",
+                      help="measure the spectrum of what is written, on the GPU: a Welch estimate over segments of NFFT "
+                           "samples (a power of two, 64 to 4096) at hop HOP (NFFT / 2); occupied bandwidth and, behind "
+                           "--duc-interp / --tx-resamp-*, the adjacent-channel leakage ratio are printed at the end "
+                           "[default=off]")
+    parser.add_option("", "--psd-spacing", type="eng_float", default=None, metavar="F",
+                      help="with --psd: distance of the adjacent channels in cycles per sample of the written stream "
+                           "[default=the modem's rate]")
+    parser.add_option("", "--psd-out", default=None, metavar="FILE.npy",
+                      help="with --psd: save the density in ascending frequency [default=off]")
     parser.add_option("", "--fec", action="store_true", default=False,
                       help="coded link: protect every payload (at most 2040 bytes) with the rate-1/2 K=7 convolutional "
                            "code and interleaver, encoded on the GPU; demodulate with benchmark_ofdm_rx --fec "
@@ -114,6 +126,8 @@ def _main_tx_resamp_bank(parser, options):
         parser.error("--tx-resamp-freqs does not combine with --cfr-papr")
     if options.dpd is not None:
         parser.error("--tx-resamp-freqs does not combine with --dpd")
+    if options.psd is not None:
+        parser.error("--tx-resamp-freqs does not combine with --psd")
     if options.tx_resamp_freq:
         parser.error("--tx-resamp-freqs and --tx-resamp-freq are mutually exclusive")
     if not options.tx_resamp_interp and not options.tx_resamp_decim:
@@ -180,8 +194,16 @@ def main(argv=None):
             dpd_stage = dict(coef=dpd.load_coef(options.dpd), limit=full)
         except (OSError, ValueError) as e:
             parser.error("--dpd: %s" % e)
+    if (options.psd_spacing is not None or options.psd_out) and options.psd is None:
+        parser.error("--psd-spacing / --psd-out need --psd")
     try:
-        txpath = transmit_path.transmit_path(options, dpd=dpd_stage)
+        psd_stage = _options.psd_from_options(options)
+        if psd_stage is not None:
+            spectrum.psd_cfg(psd_stage["nfft"], psd_stage["hop"])
+    except ValueError as e:
+        parser.error("--psd: %s" % e)
+    try:
+        txpath = transmit_path.transmit_path(options, dpd=dpd_stage, spectrum=psd_stage)
     except ValueError as e:
         if options.cfr_papr is None:
             raise
@@ -204,6 +226,13 @@ def main(argv=None):
     if r is not None:
         sys.stderr.write("dpd: gain %.2f dB, peak expansion %.2f dB, %.3g of the samples above full scale\n" % (
             r["gain_db"], r["peak_expansion_db"], r["share_over"]))
+    r = txpath.ofdm_tx.last_spectrum
+    if r is not None:
+        aclr = "" if r.get("aclr_db") is None else ", ACLR lower %.2f / upper %.2f dB" % r["aclr_db"]
+        sys.stderr.write("psd: %d segments of %d, power %.4g, occupied bandwidth (99 %%) %.5f%s\n" % (
+            r["nseg"], r["nfft"], r["power"], r["obw"], aclr))
+        if options.psd_out:
+            np.save(options.psd_out, spectrum.ascending(r["density"]))
     return npk
 
 

@@ -34,6 +34,7 @@
 #include "multipath.h"
 #include "cfr.h"
 #include "mempoly.h"
+#include "psd.h"
 #include "fec.h"
 #include "fec_punct.h"
 #include "fec_rel.h"
@@ -138,6 +139,7 @@ struct ofdm_handle {
   MultipathState multipath;  // propagation channel between ofdm_tx and ofdm_rx (multipath.h / engine_multipath.inc)
   CfrState cfr;              // transmit crest-factor reduction, the last stage before a converter (cfr.h / engine_cfr.inc)
   MempolyState mempoly[OFDM_MEMPOLY_SLOTS];  // memory polynomials: the predistorter and the amplifier model (mempoly.h / engine_mempoly.inc)
+  PsdState psd;  // spectrum measurement: Welch estimator over any stream (psd.h / engine_psd.inc)
   FecState fec;  // coded links: convolutional encoder and Viterbi decoder over the payloads (fec.h / engine_fec.inc)
   FecPunctState fec_punct;  // their punctured rates (fec_punct.h)
   FecRelState fec_rel;  // the soft-output decoder: reliabilities out of the inner code (fec_rel.h)
@@ -580,6 +582,7 @@ extern "C" void ofdm_destroy(ofdm_handle* h) {
   h->multipath.release();
   h->cfr.release();
   for (MempolyState& m : h->mempoly) m.release();
+  h->psd.release();
   h->fec.release();
   h->fec_punct.release();
   h->fec_rel.release();
@@ -1030,6 +1033,7 @@ extern "C" int ofdm_channel(ofdm_handle* h, ofdm_c32* iq, uint64_t n, const ofdm
 #include "engine_multipath.inc"
 #include "engine_cfr.inc"
 #include "engine_mempoly.inc"
+#include "engine_psd.inc"
 #include "engine_codec.inc"
 #include "engine_fec.inc"
 #include "engine_soft.inc"

@@ -12,7 +12,8 @@
 // is a stage's own: its configuration checks and messages, its index limits, its output count, its Params and its
 // template dispatch.  engine_multipath.inc, the propagation channel stage, engine_cfr.inc, the crest-factor reduction
 // stage, and engine_mempoly.inc, the memory-polynomial stage, follow them with the transmit single shape; the last two
-// keep statistics (stream_stats.h) through the stage_stats_* steps below.
+// keep statistics (stream_stats.h) through the stage_stats_* steps below.  engine_psd.inc, the spectrum stage, uses the
+// skeleton's arm, reset, enter, time, history-roll and finish steps; it has no sample output and stages its own input.
 
 #define RCCHK(expr)         \
   do {                      \

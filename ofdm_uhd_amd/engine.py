@@ -119,6 +119,7 @@ class Engine(object):
         self.cfr_cfg = None  # the crest-factor reduction stage's configuration in force (set_cfr), None without one
         self.dpd_cfg = None  # the predistorter's configuration in force (set_dpd), None without one
         self.pa_cfg = None   # the amplifier model's configuration in force (set_pa), None without one
+        self.psd_cfg = None  # the spectrum stage's configuration in force (set_psd), None without one
         self.rx_iq_format = self.tx_iq_format = "fc32"
         self.rx_iq_scale, self.tx_iq_scale = iqio.RX_SCALE, iqio.TX_SCALE
 
@@ -973,6 +974,73 @@ class Engine(object):
     def pa_last_ms(self):
         """HIP-event time of k_mempoly and its reduction in the last pa() / pa_device() (needs prof_enable())."""
         return self._mempoly_last_ms("pa")
+
+    # -- spectrum measurement: a Welch estimator over any stream (csrc/psd.h; figures: spectrum.py) --------------------
+    def set_psd(self, cfg=None, **kw):
+        """Configure the spectrum stage: an ``ofdm_psd_cfg`` (spectrum.psd_cfg) or its keywords (nfft=, hop=, window=,
+        in_format=, in_scale=).  ``set_psd(None)`` with no keywords removes it.  Resets the stream state and the
+        accumulators."""
+        self._stage_set("psd", "spectrum.psd_cfg", cfg, kw)
+
+    def psd_reset(self):
+        """Start a new stream: nothing pending, the accumulators zero."""
+        self._check(self._lib.ofdm_psd_reset(self._h))
+
+    def psd_count(self, nin):
+        """Segments the next call of ``nin`` samples would complete."""
+        return self._stage_count("psd", nin)
+
+    def _psd_samples(self, iq):
+        if self.psd_cfg is None:
+            raise ValueError("psd() without set_psd()")
+        if self.psd_cfg.in_format == _abi.OFDM_IQ_SC16:
+            return iqio.as_sc16(iq)
+        if np.asarray(iq).dtype == np.int16:
+            raise ValueError("int16 samples handed to a spectrum stage in fc32 mode (in_format=\"sc16\")")
+        return np.ascontiguousarray(iq, np.complex64).reshape(-1)
+
+    def psd(self, iq, rows=False):
+        """Host mode: the next samples of the stream (complex64, or int16 of shape (n, 2) with in_format "sc16") into
+        the estimator.  Returns the number of segments the call completed, or with ``rows=True`` their float32 power
+        spectra, shape (segments, nfft), FFT order.  Stateful: any segmentation of a stream gives the same rows."""
+        assert not self.device_ptrs
+        iq = self._psd_samples(iq)
+        n = len(iq)
+        if not rows:
+            return self._stage_call("psd", _ptr(iq) if n else None, n, None, 0)
+        nfft = int(self.psd_cfg.nfft)
+        out = np.zeros((max(self.psd_count(n), 1), nfft), np.float32)
+        return out[:self._stage_call("psd", _ptr(iq) if n else None, n, _ptr(out), len(out))]
+
+    def psd_device(self, iq_ptr, nin, rows_ptr=None, rows_cap=0):
+        """Device mode: ``iq_ptr`` is a device pointer in the configured input format, ``rows_ptr`` None or a device
+        buffer of ``rows_cap`` rows of nfft float32 that must not overlap the input.  Returns the segments completed."""
+        return self._stage_device("psd", C.c_void_p(iq_ptr), int(nin), C.c_void_p(rows_ptr) if rows_ptr else None, int(rows_cap))
+
+    def psd_read(self):
+        """The accumulators since set_psd() / psd_reset() as a dict: ``sum`` (float64, nfft), ``peak`` (float32, nfft),
+        both in FFT order, and ``nseg`` (spectrum.report turns them into density, ACLR, occupied bandwidth and mask
+        margin).  In device mode the two arrays are read through the library's own staging: pass device buffers to
+        psd_read_device instead."""
+        if self.psd_cfg is None:
+            raise ValueError("psd_read() without set_psd()")
+        assert not self.device_ptrs
+        nfft = int(self.psd_cfg.nfft)
+        s, p, n = np.zeros(nfft, np.float64), np.zeros(nfft, np.float32), C.c_uint64(0)
+        self._check(self._lib.ofdm_psd_read(self._h, _ptr(s), _ptr(p), C.byref(n)))
+        return {"sum": s, "peak": p, "nseg": n.value}
+
+    def psd_read_device(self, sum_ptr=None, peak_ptr=None):
+        """Device mode: the sums (nfft float64) and maxima (nfft float32) into device buffers; returns ``nseg``."""
+        assert self.device_ptrs
+        n = C.c_uint64(0)
+        self._check(self._lib.ofdm_psd_read(self._h, C.c_void_p(sum_ptr) if sum_ptr else None,
+                                            C.c_void_p(peak_ptr) if peak_ptr else None, C.byref(n)))
+        return n.value
+
+    def psd_last_ms(self):
+        """HIP-event time of k_psd and k_psd_reduce in the last psd() / psd_device() (needs prof_enable())."""
+        return self._stage_last_ms("psd")
 
     # -- coded links: the two call shapes every codec shares (the counterpart of csrc/engine_codec.inc) ----------------
     # ``head`` is what a call takes ahead of its batch: () or (C.byref(cfg),).

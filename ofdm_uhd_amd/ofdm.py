@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from . import cfr as _cfr, config, csi as _csi, ddc as _ddc, dpd as _dpd, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
+from . import cfr as _cfr, config, csi as _csi, ddc as _ddc, dpd as _dpd, duc as _duc, engine, fec as _fec, iqio, ldpc as _ldpc, ofdm_packet_utils, pfb as _pfb, resample as _resample, rs as _rs, sig as _sig, spectrum as _spectrum, tx_resample as _tx_resample  # noqa: F401  (ofdm_packet_utils re-exported like digital.ofdm_packet_utils)
 from .config import known_symbols_4512_3  # noqa: F401  (ofdm.py:310-325)
 
 
@@ -28,9 +28,18 @@ class ofdm_mod(object):
     """
 
     def __init__(self, options, msgq_limit=2, pad_for_usrp=True, device_id=0, iq_format="fc32", iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=False, cfr=None, dpd=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=False, cfr=None, dpd=None, spectrum=None):
         """
         @param options: pass modulation options from higher layers (fft length, occupied tones, etc.)
+        @param spectrum: spectrum measurement, ``dict(nfft=1024[, hop=][, window=][, spacing=][, mask=])``: the engine's
+               Welch estimator (spectrum.py, Engine.psd) reads the stream flush() hands out, behind ``duc`` /
+               ``resample`` / ``cfr`` / ``dpd`` and in the format it is handed out in (an sc16 output is measured as the
+               16-bit samples a converter gets), and changes nothing.  ``last_spectrum`` holds the figures
+               (spectrum.report: density, peak, nseg, obw, aclr_db, mask_margin_db, ...) of the stream flush(end=True)
+               ended last, or of the running one.  The channel's centre and width come from the options and the wideband
+               stage: occupied_tones / fft_length of the modem's rate around the stage's centre frequency; ``spacing``
+               (None: the modem's rate, the raster of the multi-link banks) places the adjacent channels, ``mask`` is
+               spectrum.mask_margin_db's.  None: nothing new runs
         @param dpd: digital predistortion, ``dict(coef=table[, limit=])``: the engine's memory-polynomial stage (dpd.py,
                Engine.dpd) with the (M, K) table ``coef`` (dpd.train / dpd.fit) runs last, behind ``cfr`` where both are
                given: CFR, then DPD, then the converter.  The stages in front then emit complex64 and this one does the
@@ -161,6 +170,26 @@ class ofdm_mod(object):
             self._cfr = dict(threshold=thr, papr_db=papr, window=window, level=_cfr.modem_rms(cfg_opts) * gain,
                              out_format=iqio.check_format(last_format), out_scale=last_scale)
             self.set_cfr_amplitude(1.0)
+        self._spectrum = None        # spectrum=: the channel and what to report of it
+        self._spectrum_live = False  # the estimator has seen samples of a stream that has not ended
+        self._last_spectrum = None
+        if spectrum is not None:
+            d = dict(spectrum)
+            fmt = iqio.check_format(iq_format)
+            in_scale = None if fmt == "fc32" or iq_scale is None else 1.0 / iqio.check_scale(iq_scale, iqio.TX_SCALE)
+            pcfg = _spectrum.psd_cfg(d.pop("nfft", 1024), d.pop("hop", None), d.pop("window", "blackmanharris"),
+                                     in_format=fmt, in_scale=in_scale)
+            center, rate = 0.0, 1.0              # the modem's centre and rate in the stream that is measured
+            if self._duc is not None:
+                wide = getattr(self._engine, self._duc + "_cfg")
+                center = float(wide.center_freq)
+                rate = float(getattr(wide, "decimation", 1)) / float(wide.interpolation)
+            spacing = d.pop("spacing", None)
+            self._spectrum = dict(center=center, bandwidth=occ * rate, spacing=rate if spacing is None else float(spacing),
+                                  mask=d.pop("mask", None))
+            if d:
+                raise ValueError("spectrum= takes nfft, hop, window, spacing and mask, not %s" % ", ".join(sorted(d)))
+            self._engine.set_psd(pcfg)
         self._fec = _fec.as_cfg(fec)
         self._ldpc = _ldpc.as_cfg(ldpc)
         if self._fec is not None and self._ldpc is not None:
@@ -228,6 +257,23 @@ class ofdm_mod(object):
         if self._dpd is not None and self._dpd_live:
             return _dpd.report(self._engine.dpd_stats())
         return self._last_dpd
+
+    def _spectrum_report(self):
+        c = self._spectrum
+        read = self._engine.psd_read()
+        if read["nseg"] == 0:
+            return None
+        # (a channel as wide as the stream, or adjacent channels that wrap onto it, have no ACLR: none is reported)
+        fits = c["spacing"] >= c["bandwidth"] and c["spacing"] + c["bandwidth"] <= 1.0
+        return _spectrum.report(read, self._engine.psd_cfg, c["center"], c["bandwidth"], c["spacing"] if fits else None, c["mask"])
+
+    @property
+    def last_spectrum(self):
+        """spectrum.report of the spectrum measurement (spectrum=): of the stream flush(end=True) ended last, or of the
+        running one.  None without the stage or before a whole segment."""
+        if self._spectrum is not None and self._spectrum_live:
+            return self._spectrum_report()
+        return self._last_spectrum
 
     # -- packets ------------------------------------------------------------------
     def send_pkt(self, payload='', eof=False, coding=None):
@@ -301,9 +347,11 @@ class ofdm_mod(object):
         (duc= / resample=) they are the wideband stream's next samples (with resample= possibly none yet); ``end=True`` then appends the filter's tail (Q zero
         narrowband samples pushed through) and starts the stage afresh.  With cfr= the samples went through the
         crest-factor reduction stage last and come out half_width samples late; ``end=True`` pushes that many zeros.
-        With dpd= the predistorter runs behind all of them; it has no tail, ``end=True`` starts it afresh."""
-        end = end and (self._duc is not None or self._cfr is not None or self._dpd is not None) and (
-            self._duc_live or self._cfr_live or self._dpd_live or bool(self._pending))
+        With dpd= the predistorter runs behind all of them; it has no tail, ``end=True`` starts it afresh.  With
+        spectrum= the estimator reads what is returned; ``end=True`` keeps its figures as ``last_spectrum`` and starts it
+        afresh."""
+        end = end and (self._duc is not None or self._cfr is not None or self._dpd is not None or self._spectrum is not None) and (
+            self._duc_live or self._cfr_live or self._dpd_live or self._spectrum_live or bool(self._pending))
         if not self._pending and not end:
             return None
         iq = None
@@ -354,7 +402,18 @@ class ofdm_mod(object):
                 self._last_dpd = _dpd.report(eng.dpd_stats())
                 eng.dpd_reset()
                 self._dpd_live = False
-            if iq is None:           # (the end of a stream whose samples all went out before: the stage has no tail)
+            if iq is None and self._spectrum is None:   # (the end of a stream whose samples all went out before: the stage has no tail)
+                return None
+        if self._spectrum is not None:
+            eng = self._engine
+            if iq is not None:
+                eng.psd(iq)
+                self._spectrum_live = True
+            if end and self._spectrum_live:
+                self._last_spectrum = self._spectrum_report()
+                eng.psd_reset()
+                self._spectrum_live = False
+            if iq is None:           # (the end of a stream whose samples all went out before: the estimator has no tail)
                 return None
         if self._sink is not None:
             self._sink.write(iq)

@@ -80,6 +80,23 @@ def tx_resamp_from_options(options):
                 center_freq=float(getattr(options, "tx_resamp_freq", 0.0) or 0.0))
 
 
+def psd_from_options(options):
+    """dict(nfft=, hop=[, spacing=]) from --psd "NFFT[,HOP]" and --psd-spacing, None where --psd is unset; ValueError
+    for anything that is not one or two integers."""
+    text = getattr(options, "psd", None)
+    if not text:
+        return None
+    parts = str(text).split(",")
+    if len(parts) not in (1, 2):
+        raise ValueError("--psd takes NFFT or NFFT,HOP")
+    nfft = int(parts[0])
+    out = dict(nfft=nfft, hop=int(parts[1]) if len(parts) == 2 else None)
+    spacing = getattr(options, "psd_spacing", None)
+    if spacing is not None:
+        out["spacing"] = float(spacing)
+    return out
+
+
 def default_options(**overrides):
     """An options object carrying every hot-path flag at the reference's default."""
     v = optparse.Values()

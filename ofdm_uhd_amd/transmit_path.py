@@ -18,7 +18,7 @@ _FLAGS = (
 
 class transmit_path(object):
     def __init__(self, options, device_id=0, apply_carrier_map=False, iq_format=None, iq_scale=None, duc=None,
-                 resample=None, fec=None, rs=None, ldpc=None, sig=None, cfr=None, dpd=None):
+                 resample=None, fec=None, rs=None, ldpc=None, sig=None, cfr=None, dpd=None, spectrum=None):
         """``apply_carrier_map=True`` re-enables what transmit_path.py:67 has commented out: the map
         given to send_pkt really reaches the mapper (and must reach the receiver's frame sink too).
         ``iq_format`` / ``iq_scale``: sample format of the output (ofdm_mod); None: the options' ``iq_format`` /
@@ -40,7 +40,10 @@ class transmit_path(object):
         is unset.  The threshold follows the transmit amplitude.
         ``dpd``: digital predistortion of ofdm_mod, ``dict(coef=table[, limit=])``, behind ``cfr``; None: the table in
         the .npy file the options' ``dpd`` names (--dpd), no stage where it is unset.  The table does not follow the
-        transmit amplitude: it holds for the amplitude it was trained at."""
+        transmit amplitude: it holds for the amplitude it was trained at.
+        ``spectrum``: spectrum measurement of ofdm_mod, ``dict(nfft=[, hop=][, window=][, spacing=][, mask=])``, which
+        reads what the path hands out; None: the options' ``psd`` ("NFFT[,HOP]", --psd) and ``psd_spacing``
+        (--psd-spacing), no measurement where psd is unset.  The figures are ``ofdm_tx.last_spectrum``."""
         opts = copy.copy(options)
         if rs is None:
             rs = bool(getattr(opts, "rs", None))
@@ -63,6 +66,8 @@ class transmit_path(object):
             cfr = dict(papr_db=float(opts.cfr_papr), half_width=16 if hw is None else int(hw))
         if dpd is None and getattr(opts, "dpd", None):
             dpd = dict(coef=_dpd.load_coef(opts.dpd))
+        if spectrum is None and getattr(opts, "psd", None):
+            spectrum = _options.psd_from_options(opts)
         self._apply_carrier_map = bool(apply_carrier_map)
         self._cfr = cfr is not None
         self._verbose = bool(getattr(opts, "verbose", False))
@@ -70,7 +75,7 @@ class transmit_path(object):
         self.carrier_map_old = ""
         self.ofdm_tx = ofdm.ofdm_mod(opts, msgq_limit=4, pad_for_usrp=False, device_id=device_id, iq_format=iq_format,
                                      iq_scale=iq_scale, duc=duc, resample=resample, fec=fec, rs=rs, ldpc=ldpc, sig=sig,
-                                     cfr=cfr, dpd=dpd)
+                                     cfr=cfr, dpd=dpd, spectrum=spectrum)
         self.set_tx_amplitude(opts.tx_amplitude)
         if self._verbose:
             self._print_verbage()
